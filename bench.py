@@ -80,7 +80,12 @@ def parse(argv=None):
     p.add_argument("--no-var-t", action="store_true", help="skip the dataset-shaped run with per-batch prompt lengths (`e2e_var_T`)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-roofline", action="store_true")
-    return p.parse_args(argv)
+    p.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the ids the last timed step returned "
+                                                         "as DIR/<name>.npy (float64), for output-for-output comparison of builds")
+    a = p.parse_args(argv)
+    if a.steps < 1:
+        p.error("--steps must be >= 1")
+    return a
 
 
 # ------------------------------------------------------------------------------------------------ self-launch
@@ -176,7 +181,8 @@ class DryWorkload:
 
 
 def timed(work, a, world, rank, dev, dist, cdev, steps, warmup):
-    """W untimed + exactly K timed steps between barrier + synchronize fences; max over ranks.  -> (seconds, last ids)"""
+    """W untimed + exactly K timed steps between barrier + synchronize fences; max over ranks.  -> (seconds, ids of the last
+    timed step: [B, N_new], or every rank's [world * B, N_new] in rank order when the step gathers them)"""
     import torch
     coll = world > 1 or FORCE_COLLECTIVE      # (OPUS_BENCH_FORCE_COLLECTIVE=1: the N > 1 code path on one rank, tests/test_gpu_rccl.py)
     gathered = [torch.empty((work.B, work.N_new), dtype=torch.long, device=cdev) for _ in range(world)] if coll else None
@@ -216,7 +222,25 @@ def timed(work, a, world, rank, dev, dist, cdev, steps, warmup):
         assert [int(w.item()) for w in who] == list(range(world)), who
         assert len(gathered) == world and torch.equal(gathered[rank].cpu(), out.cpu())
     assert out.shape == (work.B, work.N_new), out.shape
-    return dt, out
+    return dt, (torch.cat([g.cpu() for g in gathered]) if coll else out)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs DIR: {name: tensor} -> DIR/<name>.npy as float64 (token ids are exact in it).  An array over its share of
+    the 64 MB cap is cut to a fixed, seeded sample of its rows (the same rows on every run)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        x = t.detach().cpu().numpy().astype(np.float64)
+        if x.nbytes > share:
+            keep = max(1, share // max(1, x.nbytes // max(1, x.shape[0])))
+            x = x[np.sort(np.random.default_rng(0).choice(x.shape[0], keep, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), x)
+    log(f"dumped {', '.join(sorted(arrays))} to {d}")
 
 
 def two_in_flight(model, cfg, a, rank, lengths, dev, steps, warmup):
@@ -627,7 +651,8 @@ def main():
         main_work = Workload(model, cfg, a, rank, B, lengths, dev)
         c2_work = None if a.no_c2 or B == 1 else Workload(model, cfg, a, rank, 1, [a.residues], dev)
 
-    dt, _ = timed(main_work, a, world, rank, dev, dist, cdev, a.steps, a.warmup)
+    dt, main_ids = timed(main_work, a, world, rank, dev, dist, cdev, a.steps, a.warmup)
+    dumps = {"ids": main_ids.cpu().clone()}      # (host copy now: later passes must not be able to touch it)
     log(f"timed {a.steps} steps at batch {B}: {1e3 * dt / a.steps:.2f} ms/step")
     mixed = a.mixed_lengths
     res = {
@@ -649,7 +674,8 @@ def main():
         res["invalid"] = True
 
     if c2_work is not None:      # configs[1]: batch 1, same rules (every rank runs it so that collectives stay matched)
-        dt2, _ = timed(c2_work, a, world, rank, dev, dist, cdev, a.steps, a.warmup)
+        dt2, c2_ids = timed(c2_work, a, world, rank, dev, dist, cdev, a.steps, a.warmup)
+        dumps["c2_ids"] = c2_ids.cpu().clone()
         log(f"timed {a.steps} steps at batch 1: {1e3 * dt2 / a.steps:.2f} ms/step")
         res["c2"] = {"workload": f"OPUS-PLLM-{a.model} shape: batch 1/GPU, {a.residues}-residue protein, 96 positions, {N_new} new "
                                  f"tokens, greedy (BASELINE configs[1])",
@@ -698,6 +724,9 @@ def main():
         dist.barrier()
     if rank == 0 and world == 1 and not dry and not a.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(cfg, main_work.lengths[0], main_work.n_text, N_new, B)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, dumps)
+        res["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": sorted(dumps)}
     if rank == 0:
         print(json.dumps(res), flush=True)
     if world > 1 or FORCE_COLLECTIVE:

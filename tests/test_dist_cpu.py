@@ -120,3 +120,26 @@ def test_bench_refuses_a_world_size_that_contradicts_gpus():
     assert r.returncode != 0 and "WORLD_SIZE=1" in (r.stderr + r.stdout)
     r = _run_bench(["--gpus", "1"], {"OPUS_BENCH_DRYRUN": "1", "WORLD_SIZE": "2", "RANK": "0", "OPUS_BENCH_BACKEND": "gloo"})
     assert r.returncode != 0 and "WORLD_SIZE=2" in (r.stderr + r.stdout)
+
+
+def test_bench_dump_outputs_dry_run(tmp_path):
+    """--dump-outputs DIR: after the timed steps rank 0 writes the ids the last timed step returned - every rank's, in rank
+    order - as DIR/ids.npy (and DIR/c2_ids.npy for the batch-1 line), float64; the line says what it wrote."""
+    import json
+    import numpy as np
+    out = tmp_path / "dump"
+    r = _run_bench(["--gpus", "2", "--batch", "3", "--steps", "3", "--warmup", "1", "--new-tokens", "4", "--dump-outputs", str(out)],
+                   {"OPUS_BENCH_DRYRUN": "1", "OPUS_BENCH_BACKEND": "gloo"})
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["dumped_outputs"]["arrays"] == ["c2_ids", "ids"]
+    ids, c2 = np.load(out / "ids.npy"), np.load(out / "c2_ids.npy")
+    assert ids.dtype == np.float64 and c2.dtype == np.float64
+    stub = lambda b, rank: np.arange(b * 4).reshape(b, 4) + 1000 * rank           # bench.DryWorkload's ids
+    assert np.array_equal(ids, np.concatenate([stub(3, 0), stub(3, 1)]))
+    assert np.array_equal(c2, np.concatenate([stub(1, 0), stub(1, 1)]))
+
+
+def test_bench_rejects_zero_steps():
+    r = _run_bench(["--gpus", "1", "--steps", "0"], {"OPUS_BENCH_DRYRUN": "1"})
+    assert r.returncode != 0 and "--steps" in r.stderr
