@@ -160,6 +160,24 @@ int opus_llama_prefill(opus_ctx *ctx, const void *d_embeds, const uint8_t *d_mas
 /* Row D3: one decode step for the B rows of the last prefill: tok int32 [B] -> logits fp32 [B,V]. */
 int opus_llama_decode_step(opus_ctx *ctx, const int32_t *d_tok, float *d_logits, void *stream);
 
+/* Teacher-forced scoring (the reference's forward(labels=...), opus_llama.py:41-92): the prefill's layers run on EVERY position
+ * (embeds fp16 [B,T,H], mask u8 [B,T]: right-padded, unpadded or left-padded rows, positions t - first valid slot), then for the
+ * R flat positions d_rows[r] = b T + t (int32, device) the final norm + lm_head give operand-dtype logits and
+ * d_logprob[r] = log_softmax(logits)[d_targets[r]] (fp32; a target < 0 gives 0).  d_logits [R, V] (operand dtype, row r = position
+ * d_rows[r]) or NULL: loss-only, the logits live chunk by chunk in d_scratch (at most 128 MiB of them per chunk).  d_scratch
+ * (device, scratch_bytes) holds the gathered rows (+ the chunk's logits): opus_llama_forward_scratch_bytes says what it takes
+ * (less: smaller chunks).  Overwrites the context's KV cache and leaves it without a prefill: opus_llama_decode_step then fails
+ * with OPUS_ESTATE until the next prefill / generate.  opus_workspace_bytes is unchanged by it. */
+int opus_llama_forward(opus_ctx *ctx, const void *d_embeds, const uint8_t *d_mask, int32_t B, int32_t T, const int32_t *d_rows,
+                       int32_t R, const int32_t *d_targets, float *d_logprob, void *d_logits, void *d_scratch,
+                       int64_t scratch_bytes, void *stream);
+/* Scratch bytes opus_llama_forward wants for R scored rows (with_logits: d_logits is given); -1 on a bad config. */
+int64_t opus_llama_forward_scratch_bytes(const opus_config *cfg, int32_t R, int32_t with_logits);
+/* Diagnostic: the NLL kernel alone.  Per row of operand-dtype logits [R, V] (row-major): d_lse[r] = logsumexp (fp32, d_lse may
+ * be NULL) and d_logprob[r] = l[y] - lse with y = d_targets[r] (y < 0: 0; y >= V: NaN). */
+int opus_debug_xent(opus_ctx *ctx, const void *d_logits, int32_t R, int32_t V, const int32_t *d_targets, float *d_logprob,
+                    float *d_lse, void *stream);
+
 /* Rows G1 (+D1-D4): greedy search of GenerationMixin as driven by opus_llama.py:95-132.
  * next = argmax(last logits); finished rows emit pad_id; a row finishes on any of eos_ids (host
  * array, may be empty); stops when all rows are finished or after max_new steps.

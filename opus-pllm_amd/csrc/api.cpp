@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <map>
 #include <string>
 #include <vector>
@@ -962,7 +963,7 @@ static int lm_head_opt(opus_ctx *c, hipStream_t s, int B) {
                 g.dec_vocab, 1);
 }
 
-static int prefill_opt(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8_t *mask, int B, int T) {
+static int prefill_opt(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8_t *mask, int B, int T, bool all_rows) {
     const opus_config &g = c->cfg;
     const int H = g.dec_dim, M = B * T;
     HIPC(hipMemsetAsync(c->d_cnt, 0, HANDOFF_ERR * sizeof(int32_t), s));
@@ -970,6 +971,7 @@ static int prefill_opt(opus_ctx *c, hipStream_t s, const half_t *embeds, const u
     KL(KC_OTHER, 6.0 * M * H, launch_h2f(embeds, c->d_x, (int64_t)M * H, s));
     KL(KC_OTHER, 10.0 * M * H, launch_add_pos(c->d_x, c->dec_pos, c->d_kstart, nullptr, 0, B, T, H, g.dec_max_pos + 1, s));
     for (int l = 0; l < g.dec_layers; ++l) OPC(opt_layer(c, s, c->dec[l], l, c->d_x, c->d_xn, M, B, T, false));
+    if (all_rows) return OPUS_OK;
     KL(KC_OTHER, 8.0 * B * H, launch_take_last(c->d_x, B, T, H, c->d_xl, s));
     OPC(lm_head_opt(c, s, B));
     OPC(reset_step(c, s, T));
@@ -990,9 +992,15 @@ static int decode_step_opt(opus_ctx *c, hipStream_t s) {
     return OPUS_OK;
 }
 
-static int prefill(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8_t *mask, int B, int T) {
+// all_rows: every position of every row runs through the last layer too, and the final residual stream of all B T rows is left in
+// d_x for opus_llama_forward; no lm_head, and the context is left without a prefill (decode_step fails until the next one).
+static int prefill(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8_t *mask, int B, int T, bool all_rows = false) {
     c->phase = PH_PREFILL;
-    if (c->cfg.dec_arch == 1) return prefill_opt(c, s, embeds, mask, B, T);
+    if (all_rows) {
+        c->prefilled = false;
+        c->cur_B = 0;
+    }
+    if (c->cfg.dec_arch == 1) return prefill_opt(c, s, embeds, mask, B, T, all_rows);
     const opus_config &g = c->cfg;
     const int H = g.dec_dim, F = g.dec_ffn, nh = g.dec_heads, nkv = g.dec_kv_heads, hd = g.dec_head_dim;
     const int QKV = (nh + 2 * nkv) * hd, QD = nh * hd;
@@ -1031,7 +1039,7 @@ static int prefill(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8
         a.B = B; a.T = T; a.heads = nh; a.group = nh / nkv; a.head_dim = hd; a.causal = 1;
         a.scale = 1.0f / sqrtf((float)hd);
         KLF(KC_ATTN_PREFILL, 2.0 * M * (QKV + QD), 2.0 * B * (double)T * T * QD, launch_attn_prefill(a, s));
-        if (l + 1 == g.dec_layers && T > 1 && !g_knobs.misc[7]) {
+        if (l + 1 == g.dec_layers && T > 1 && !all_rows && !g_knobs.misc[7]) {
             // Last layer: its K / V are in the cache for every position, but behind the attention only the LAST position of a row
             // is ever used (lm_head reads that row alone, opus_arch.py -> HF generate keeps the last logits): wo, gate/up and
             // down run on B rows with the decode step's kernels instead of on B T rows (Llama-3-8B, 64 x 96: ~1.85 ms of tiled
@@ -1066,6 +1074,10 @@ static int prefill(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8
         OPC(gemm(c, s, c->d_act, F, L.wd, M, H, F, nullptr, EPI_NONE, c->d_x, c->d_x, H, 1));
         have_stat = c->rq_ln_done != 0;
         if (have_stat) OPC(finalize());
+    }
+    if (all_rows) {
+        c->xh_src = nullptr;
+        return OPUS_OK;
     }
     if (!last_rows_done) {
         KL(KC_OTHER, 8.0 * B * H, launch_take_last(c->d_x, B, T, H, c->d_xl, s));
@@ -1191,6 +1203,93 @@ extern "C" int opus_llama_decode_step(opus_ctx *c, const int32_t *d_tok, float *
     OPC(decode_step(c, s, d_tok));
     if (d_logits)
         HIPC(hipMemcpyAsync(d_logits, c->d_logits, (size_t)c->cur_B * c->cfg.dec_vocab * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return OPUS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ teacher-forced scoring
+// Logits slab of one loss-only chunk: at most this many bytes (well inside the 256 MiB Infinity Cache, so that the NLL kernel
+// may find the GEMM's output there).
+static constexpr int64_t SCORE_SLAB_BYTES = 128ll << 20;
+
+// Rows per chunk of the score phase: all R, or (loss-only) as many as a logits slab holds - whole multiples of 64 from 64 up.
+static int64_t score_chunk_cap(const opus_config &g, int64_t R, bool loss_only) {
+    if (!loss_only) return R;
+    const int64_t cap = SCORE_SLAB_BYTES / ((int64_t)g.dec_vocab * (int64_t)sizeof(half_t));
+    return std::min(R, cap >= 64 ? cap & ~(int64_t)63 : std::max<int64_t>(cap, 1));
+}
+// caller scratch a chunk of n rows needs: the gathered fp32 rows (+ the logits slab when loss-only)
+static int64_t score_chunk_bytes(const opus_config &g, int64_t n, bool loss_only) {
+    return (int64_t)align_up((size_t)n * g.dec_dim * sizeof(float)) +
+           (loss_only ? (int64_t)align_up((size_t)n * g.dec_vocab * sizeof(half_t)) : 0);
+}
+// the chunk the caller's scratch allows (a smaller scratch than opus_llama_forward_scratch_bytes asks for: smaller chunks)
+static int64_t score_chunk_rows(const opus_config &g, int64_t R, bool loss_only, int64_t scratch_bytes) {
+    int64_t n = score_chunk_cap(g, R, loss_only);
+    while (n > 0 && score_chunk_bytes(g, n, loss_only) > scratch_bytes) n = n >= 128 ? (n / 2) & ~(int64_t)63 : n - 1;
+    return n;
+}
+
+// final norm + lm_head over the n fp32 rows in X -> operand-dtype logits [n, V] (row stride V), then the NLL of every row
+static int score_rows(opus_ctx *c, hipStream_t s, const float *X, int n, half_t *logits, const int32_t *targets, float *logprob,
+                      float *lse) {
+    const opus_config &g = c->cfg;
+    const int H = g.dec_dim, V = g.dec_vocab;
+    c->xh_src = nullptr;
+    if (g.dec_arch == 1) {
+        KL(KC_NORM, 6.0 * n * H, launch_layernorm(X, c->dec_lnfw, c->dec_lnfb, g.dec_rms_eps, n, H, c->d_xn, nullptr, s));
+        OPC(gemm(c, s, c->d_xn, H, c->lm_head, n, V, H, nullptr, EPI_NONE, nullptr, logits, V, 0));
+    } else {   // RMSNorm folded into lm_head: fused into the skinny / mid kernels, a weight-less norm into d_xn otherwise
+        OPC(gemm_norm(c, s, X, g.dec_rms_eps, c->d_xn, c->lm_head, n, V, H, EPI_NONE, logits, V, 0));
+    }
+    KL(KC_XENT, 2.0 * n * V + 12.0 * n, launch_xent(logits, V, n, V, targets, logprob, lse, s));
+    return OPUS_OK;
+}
+
+extern "C" int opus_llama_forward(opus_ctx *c, const void *d_embeds, const uint8_t *d_mask, int32_t B, int32_t T,
+                                  const int32_t *d_rows, int32_t R, const int32_t *d_targets, float *d_logprob, void *d_logits,
+                                  void *d_scratch, int64_t scratch_bytes, void *stream) {
+    OPC(need_ready(c));
+    OPC(check_prefill_args(c, d_embeds, d_mask, B, T));
+    if (R < 0 || (int64_t)R > (int64_t)B * T) return fail(OPUS_ESHAPE, "forward: R=%d rows of a %d x %d batch", R, B, T);
+    if (R > 0 && (!d_rows || !d_targets || !d_logprob)) return fail(OPUS_EBADARG, "forward: null rows / targets / logprob");
+    const opus_config &g = c->cfg;
+    const bool loss_only = d_logits == nullptr;
+    const int64_t chunk = R > 0 ? score_chunk_rows(g, R, loss_only, d_scratch ? scratch_bytes : 0) : 0;
+    if (R > 0 && chunk < 1)
+        return fail(OPUS_EBADARG, "forward: scratch of %lld bytes holds no row (opus_llama_forward_scratch_bytes)", (long long)scratch_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    OPC(prefill(c, s, (const half_t *)d_embeds, d_mask, B, T, true));
+    c->phase = PH_SCORE;
+    const int H = g.dec_dim, V = g.dec_vocab;
+    float *rows_f = reinterpret_cast<float *>(d_scratch);
+    half_t *slab = loss_only ? reinterpret_cast<half_t *>((char *)d_scratch + align_up((size_t)chunk * H * sizeof(float))) : nullptr;
+    for (int64_t r0 = 0; r0 < R; r0 += chunk) {
+        const int n = (int)std::min<int64_t>(chunk, R - r0);
+        KL(KC_OTHER, 8.0 * n * H + 4.0 * n, launch_gather_rows(c->d_x, d_rows + r0, n, (int64_t)B * T, H, rows_f, s));
+        half_t *out = loss_only ? slab : reinterpret_cast<half_t *>(d_logits) + r0 * V;
+        OPC(score_rows(c, s, rows_f, n, out, d_targets + r0, d_logprob + r0, nullptr));
+    }
+    return OPUS_OK;
+}
+
+extern "C" int64_t opus_llama_forward_scratch_bytes(const opus_config *cfg, int32_t R, int32_t with_logits) {
+    if (check_cfg(cfg) != OPUS_OK) return -1;
+    if (R < 0) {
+        fail(OPUS_ESHAPE, "forward_scratch_bytes: R=%d", R);
+        return -1;
+    }
+    return R == 0 ? 0 : score_chunk_bytes(*cfg, score_chunk_cap(*cfg, R, !with_logits), !with_logits);
+}
+
+extern "C" int opus_debug_xent(opus_ctx *c, const void *d_logits, int32_t R, int32_t V, const int32_t *d_targets, float *d_logprob,
+                               float *d_lse, void *stream) {
+    if (!c) return fail(OPUS_EBADARG, "ctx is null");
+    if (!d_logits || !d_targets || !d_logprob) return fail(OPUS_EBADARG, "debug_xent: null pointer");
+    if (R < 0 || V < 1) return fail(OPUS_ESHAPE, "debug_xent: R=%d V=%d", R, V);
+    HIPC(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    c->phase = PH_SCORE;
+    KL(KC_XENT, 2.0 * R * V + 12.0 * R, launch_xent((const half_t *)d_logits, V, R, V, d_targets, d_logprob, d_lse, s));
     return OPUS_OK;
 }
 
@@ -1651,8 +1750,8 @@ extern "C" int opus_timing_reset(opus_ctx *c) {
     return OPUS_OK;
 }
 static const char *kclass_names[KC_COUNT] = {"gemm_skinny", "gemm_mid", "gemm_wide", "gemm_ring", "gemm_pp", "gemm_tile", "splitk_reduce",
-                                            "attn_prefill", "attn_decode", "norm", "other", "gemm_stream"};
-static const char *phase_names[PH_COUNT] = {"encode", "project", "splice", "prefill", "decode", "other"};
+                                            "attn_prefill", "attn_decode", "norm", "other", "gemm_stream", "xent"};
+static const char *phase_names[PH_COUNT] = {"encode", "project", "splice", "prefill", "decode", "other", "score"};
 
 extern "C" int opus_timing_get(opus_ctx *c, const char *kernel_class, const char *phase, double *ms, int64_t *launches,
                                double *bytes, double *flops) {

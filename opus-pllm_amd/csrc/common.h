@@ -52,9 +52,9 @@ int skinny_max_m();   // rows up to which the skinny kernel is used (default 4, 
 constexpr int MID_MAX_M = 64;   // (65..128 rows measured faster on the split-K tile kernel)
 // kernel classes of the per-launch timing (opus_timing_get): one per kernel family
 enum KClass { KC_SKINNY = 0, KC_MID, KC_WIDE, KC_RING, KC_PP, KC_TILE, KC_REDUCE, KC_ATTN_PREFILL, KC_ATTN_DECODE, KC_NORM,
-              KC_OTHER, KC_STREAM, KC_COUNT };
+              KC_OTHER, KC_STREAM, KC_XENT, KC_COUNT };
 // phases of the path a launch belongs to (set by the entry points of api.cpp)
-enum Phase { PH_ENCODE = 0, PH_PROJECT, PH_SPLICE, PH_PREFILL, PH_DECODE, PH_OTHER, PH_COUNT };
+enum Phase { PH_ENCODE = 0, PH_PROJECT, PH_SPLICE, PH_PREFILL, PH_DECODE, PH_OTHER, PH_SCORE, PH_COUNT };
 
 // Measurement hook.  While a LaunchEvents record is armed (thread-local, set by api.cpp in timing mode only), the next
 // principal kernel launch is dispatched with hipExtLaunchKernelGGL so that (main0, main1) carry the dispatch's own start /
@@ -285,6 +285,12 @@ hipError_t launch_embed_tokens(const int32_t *tok, const half_t *emb, int B, int
 hipError_t launch_add_pos(float *x, const half_t *pos, const int32_t *kstart, const int32_t *step, int t0, int B, int Tq,
                           int H, int max_idx, hipStream_t s);
 hipError_t launch_take_last(const float *x, int B, int T, int H, float *out, hipStream_t s);
+// score.hip: out[r] = x[rows[r]] (fp32 rows of width H; an index outside [0, n_src) gives a zero row)
+hipError_t launch_gather_rows(const float *x, const int32_t *rows, int R, int64_t n_src, int H, float *out, hipStream_t s);
+// score.hip: per row r of logits [R, V] (row stride ld): lse[r] = logsumexp, logprob[r] = l[targets[r]] - lse[r] (fp32;
+// target < 0: 0, target >= V: NaN; lse may be null)
+hipError_t launch_xent(const half_t *logits, int64_t ld, int R, int V, const int32_t *targets, float *logprob, float *lse,
+                       hipStream_t s);
 hipError_t launch_relu_h(half_t *x, int64_t n, hipStream_t s);
 hipError_t launch_fill_synth(void *dst, int dtype, int64_t rows, int64_t cols, uint64_t seed, float std,
                              float mean, int64_t rb, int64_t rs, int64_t ro, int tiled, uint64_t fold_seed,

@@ -499,6 +499,132 @@ class OpusLlamaForCausalLM:
         emb, mask, _ = self._splice(input_ids, attention_mask, prot, True)
         return self._greedy(emb, mask, int(max_new_tokens), [int(e) for e in eos], int(pad_token_id), sampler)
 
+    # ------------------------------------------------------------------ teacher-forced scoring
+    @torch.no_grad()
+    def forward(self, input_ids: Optional[torch.Tensor] = None, attention_mask: Optional[torch.Tensor] = None,
+                position_ids: Optional[torch.Tensor] = None, past_key_values=None, labels: Optional[torch.Tensor] = None,
+                use_cache: Optional[bool] = None, output_attentions: Optional[bool] = None,
+                output_hidden_states: Optional[bool] = None, seq=None, input_embed: Optional[torch.Tensor] = None,
+                return_dict: Optional[bool] = None, protein_tokens: Optional[torch.Tensor] = None, return_logits: bool = True,
+                **kwargs):
+        """opus_llama.py:41-92 (+ LlamaForCausalLM.forward): with `seq` (or `input_embed` pooled embeddings / `protein_tokens`
+        projected blocks) the proteins are spliced into the prompt in training mode (right padding, IGNORE_INDEX labels on the
+        protein slots); otherwise `input_ids` are embedded (or `inputs_embeds` taken as they are).  Returns a CausalLMOutput:
+        `loss` = HF's causal-LM loss (target of position t is labels[b, t + 1]; -100 ignored; fp32 mean over the counted targets,
+        NaN when none is counted), `logits` [B, T, V] in the operand dtype (None with return_logits=False; values at masked
+        positions are unspecified), `past_key_values` = None; extensions `token_logprobs` fp32 [B, T] (log p(labels[b, t]) at
+        counted targets, 0 elsewhere) and `n_tokens`.
+        Rows are right-padded or unpadded; left-padded rows only with position_ids == cumsum(mask) - 1 on their real slots (what
+        the kernels compute; HF would use arange positions).  Overwrites this context's KV cache: decode_step fails until the next
+        prefill / generate.  Batches above max_batch run in groups of max_batch rows (one loss over all of them)."""
+        if past_key_values is not None:
+            raise NotImplementedError("forward(): `past_key_values` input is not supported (no incremental scoring)")
+        if use_cache:
+            raise NotImplementedError("forward(): use_cache=True is not supported (no cache is returned)")
+        if output_attentions or output_hidden_states:
+            raise NotImplementedError("forward(): output_attentions / output_hidden_states are not supported")
+        inputs_embeds = kwargs.pop("inputs_embeds", None)
+        if kwargs:
+            raise TypeError(f"forward() got unexpected keyword arguments {sorted(kwargs)}")
+        cfg = self.cfg
+        embeds = None
+        if seq is not None or input_embed is not None or protein_tokens is not None:
+            if input_ids is None:
+                raise ValueError("forward() with proteins needs input_ids (the prompt with its <seq> placeholders)")
+            mask_in = attention_mask if attention_mask is not None else torch.ones_like(input_ids, dtype=torch.bool)
+            _, _, mask, _, embeds, labels = self.prepare_inputs_labels_for_multimodal(
+                input_ids, None, mask_in, None, labels, seq if seq is not None else (), input_embed, inference_mode=False,
+                protein_tokens=protein_tokens)
+            position_ids = None                                 # (the splice's rows are right-padded, positions 0..n-1)
+        if embeds is None:
+            if inputs_embeds is not None:
+                if input_ids is not None:
+                    raise ValueError("You cannot specify both input_ids and inputs_embeds at the same time")
+                embeds = inputs_embeds
+            else:
+                if input_ids is None:
+                    raise ValueError("You have to specify either input_ids or inputs_embeds")
+                ids = input_ids.long()
+                if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= cfg.dec_vocab):
+                    raise ValueError(f"input_ids must lie in [0, {cfg.dec_vocab}) without proteins (a <seq> placeholder needs seq=)")
+                embeds = self.model.embed_tokens(ids)
+            mask = attention_mask
+        if embeds.dim() != 3 or embeds.shape[2] != cfg.dec_dim:
+            raise ValueError(f"embeddings must be [B, T, {cfg.dec_dim}], got {tuple(embeds.shape)}")
+        B, T, _ = embeds.shape
+        if T > cfg.max_prompt:
+            raise _cabi.OpusError(-2, f"forward: T={T} positions exceed max_prompt={cfg.max_prompt}")
+        m = np.ones((B, T), dtype=bool) if mask is None else mask.detach().cpu().bool().numpy()
+        if m.shape != (B, T):
+            raise ValueError(f"attention_mask {m.shape} does not match the embeddings' [B, T] = {(B, T)}")
+        _check_forward_mask(m, None if position_ids is None else position_ids.detach().cpu().numpy())
+        lab = None
+        if labels is not None:
+            lab = labels.detach().cpu().long().numpy()
+            if lab.shape != (B, T):
+                raise ValueError(f"labels {lab.shape} do not match the embeddings' [B, T] = {(B, T)}")
+            bad = (lab != IGNORE_INDEX) & ((lab < 0) | (lab >= cfg.dec_vocab))
+            if bad.any():
+                raise ValueError(f"labels must be {IGNORE_INDEX} or lie in [0, {cfg.dec_vocab})")
+            src = np.zeros((B, T), dtype=bool)
+            src[:, :-1] = lab[:, 1:] != IGNORE_INDEX                # counted target of position t: labels[b, t + 1]
+            if (src & ~m).any():
+                b, t = map(int, np.argwhere(src & ~m)[0])
+                raise ValueError(f"labels[{b}, {t + 1}] is counted but its source position {t} is masked out: "
+                                 "its logits are not defined on this path")
+        else:
+            src = np.zeros((B, T), dtype=bool)
+
+        dev, dt = self.device, _cabi.operand_dtype()
+        embeds = embeds.to(dev, dt).contiguous()
+        mask_u8 = torch.from_numpy(m.astype(np.uint8)).to(dev)
+        token_lp = torch.zeros((B, T), dtype=torch.float32, device=dev)
+        logits = torch.empty((B, T, cfg.dec_vocab), dtype=dt, device=dev) if return_logits else None
+        G = cfg.max_batch
+        tgt_all = np.full((B, T), -1, dtype=np.int32)
+        if lab is not None:
+            tgt_all[:, :-1] = np.where(src[:, :-1], lab[:, 1:], -1)
+        cc = _cabi.CConfig.from_config(cfg)
+        R_max = min(B, G) * T if return_logits else max(int(src[g0:g0 + G].sum()) for g0 in range(0, B, G))
+        n_scratch = int(self._lib.opus_llama_forward_scratch_bytes(C.byref(cc), R_max, 1 if return_logits else 0))
+        s = self._enter()
+        with torch.cuda.stream(self._stream):
+            scratch = torch.empty((max(n_scratch, 1),), dtype=torch.uint8, device=dev)
+            keep = []
+            for g0 in range(0, B, G):
+                Bg = min(G, B - g0)
+                if return_logits:
+                    rows = np.arange(Bg * T, dtype=np.int32)
+                    tg = tgt_all[g0:g0 + Bg].reshape(-1)
+                else:
+                    rows = np.flatnonzero(src[g0:g0 + Bg].reshape(-1)).astype(np.int32)
+                    tg = tgt_all[g0:g0 + Bg].reshape(-1)[rows]
+                R = int(rows.size)
+                d_rows = torch.from_numpy(rows).to(dev, non_blocking=True) if R else None
+                d_tg = torch.from_numpy(np.ascontiguousarray(tg)).to(dev, non_blocking=True) if R else None
+                lp = torch.empty((max(R, 1),), dtype=torch.float32, device=dev)
+                _cabi.check(self._lib.opus_llama_forward(
+                    self._ctx, embeds[g0:].data_ptr(), mask_u8[g0:].data_ptr(), Bg, T,
+                    None if d_rows is None else d_rows.data_ptr(), R, None if d_tg is None else d_tg.data_ptr(), lp.data_ptr(),
+                    None if logits is None else logits[g0:].data_ptr(), scratch.data_ptr(), n_scratch, s))
+                if return_logits:
+                    token_lp[g0:g0 + Bg, 1:] = lp.view(Bg, T)[:, :-1]
+                elif R:
+                    flat = token_lp[g0:g0 + Bg].view(-1)                # position t scores the label at t + 1
+                    flat[torch.from_numpy(rows.astype(np.int64) + 1).to(dev)] = lp[:R]
+                keep.append((d_rows, d_tg, lp))
+            n_tokens = int(src.sum())
+            loss = None
+            if lab is not None:
+                loss = -token_lp.sum() / n_tokens if n_tokens else torch.tensor(float("nan"), device=dev)
+        self._leave()
+        out = CausalLMOutput(loss=loss, logits=logits, token_logprobs=token_lp, n_tokens=n_tokens)
+        if return_dict is False:
+            return out.to_tuple()
+        return out
+
+    __call__ = forward
+
     # ------------------------------------------------------------------ parity taps (tests / bench)
     def prefill_logits(self, embeds: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
         B, T, _ = embeds.shape
@@ -591,3 +717,54 @@ def _splice_labels(input_ids, attention_mask, labels, n_tok, T_out, inference_mo
             else:
                 out[b, : len(row)] = torch.tensor(row, dtype=lab.dtype)
     return out
+
+
+def _check_forward_mask(m: np.ndarray, pos: Optional[np.ndarray]) -> None:
+    """The rows forward() can score as HF would: the valid slots of every row are contiguous; a row that starts late (left
+    padding) needs position_ids == cumsum(mask) - 1 on its real slots, which is what the kernels compute (t - first valid slot)
+    and not what HF derives without position_ids (arange).  Given position_ids must equal that on every real slot."""
+    B, T = m.shape
+    for b in range(B):
+        idx = np.flatnonzero(m[b])
+        if idx.size and idx[-1] - idx[0] + 1 != idx.size:
+            raise ValueError(f"attention_mask row {b} has a hole: valid slots must be contiguous (right- or left-padded rows)")
+    want = np.cumsum(m, axis=1) - 1
+    if pos is not None:
+        if pos.shape != (B, T):
+            raise ValueError(f"position_ids {pos.shape} do not match the mask {(B, T)}")
+        if (pos != want)[m].any():
+            raise ValueError("position_ids must equal cumsum(attention_mask) - 1 on the real slots: the kernels derive positions "
+                             "from the mask")
+    elif (m.any(axis=1) & ~m[:, 0]).any():
+        raise ValueError("left-padded rows need position_ids = cumsum(attention_mask) - 1: without them HF uses arange positions "
+                         "and the result would differ; pass position_ids or right-pad the rows")
+
+
+class CausalLMOutput:
+    """What forward() returns, indexed like transformers' CausalLMOutputWithPast: attributes and keys `loss`, `logits`,
+    `past_key_values` (always None here); integer indices / to_tuple() run over the fields that are not None.  Extension fields
+    (attributes only): `token_logprobs` fp32 [B, T] and `n_tokens`."""
+    _fields = ("loss", "logits", "past_key_values")
+
+    def __init__(self, loss=None, logits=None, past_key_values=None, token_logprobs=None, n_tokens=0):
+        self.loss, self.logits, self.past_key_values = loss, logits, past_key_values
+        self.token_logprobs, self.n_tokens = token_logprobs, n_tokens
+
+    def keys(self):
+        return [k for k in self._fields if getattr(self, k) is not None]
+
+    def to_tuple(self):
+        return tuple(getattr(self, k) for k in self.keys())
+
+    def __getitem__(self, k):
+        if isinstance(k, str):
+            if k not in self.keys():
+                raise KeyError(k)
+            return getattr(self, k)
+        return self.to_tuple()[k]
+
+    def __iter__(self):
+        return iter(self.keys())
+
+    def __len__(self):
+        return len(self.keys())
