@@ -173,6 +173,35 @@ int opus_llama_forward(opus_ctx *ctx, const void *d_embeds, const uint8_t *d_mas
                        int64_t scratch_bytes, void *stream);
 /* Scratch bytes opus_llama_forward wants for R scored rows (with_logits: d_logits is given); -1 on a bad config. */
 int64_t opus_llama_forward_scratch_bytes(const opus_config *cfg, int32_t R, int32_t with_logits);
+/* Shared-prefix scoring.  opus_llama_prefix is opus_llama_prefill (same cache, step counter and decode state afterwards:
+ * opus_llama_decode_step continues it) that also copies the final residual rows of every row's LAST position, fp32 [B, H], into
+ * d_last_rows and returns the cache epoch in *epoch.  The last slot of every row must be a real token (left-padded or unpadded
+ * rows).  The prefix stays valid until the next call on this context that prefills or permutes the cache (opus_llama_prefill /
+ * _prefix / _forward, opus_generate_*, opus_kv_reorder, the debug attention entries); decode steps keep it. */
+int opus_llama_prefix(opus_ctx *ctx, const void *d_embeds, const uint8_t *d_mask, int32_t B, int32_t T, float *d_last_logits,
+                      float *d_last_rows, int64_t *epoch, void *stream);
+/* Scores R continuation rows behind the prefix of `epoch` (OPUS_ESTATE when it is stale or from another context).  d_embeds
+ * operand dtype [R, n, H]: row r's token embeddings, right-padded to n positions (1 <= n <= max_prompt, else OPUS_ESHAPE);
+ * h_lens [R] (host): real tokens per row (0 .. n); h_src [R] (host): prefix row of every row (0 .. P - 1, repeats and any order);
+ * d_last_rows fp32 [P, H]: what opus_llama_prefix returned, P = its B.  Token j of row r sits at position Tp - kstart + j of its
+ * prefix row (at most max_prompt + max_new_tokens positions in all, else OPUS_ESHAPE).  Output, compact over the real tokens in
+ * row-major order (row 0's lens[0] tokens, then row 1's ...): d_logprob[k] = log p(d_targets[k] | prefix, earlier tokens of the
+ * row) in fp32; token 0 of a row is scored from the prefix's last position.  Reads the KV cache and writes neither it nor the
+ * decode state: the same prefix can be scored any number of times and decoded afterwards.  Rows run in passes of as many as the
+ * prefill's activation buffers hold positions (max_batch x max_prompt); d_scratch (device) holds
+ * opus_llama_score_scratch_bytes(cfg, R, n) bytes.  Phase "score"; the attention kernel is timed as class "attn_prefill". */
+int opus_llama_score_continuations(opus_ctx *ctx, const void *d_embeds, int32_t R, int32_t n, const int32_t *h_lens,
+                                   const int32_t *h_src, const float *d_last_rows, int32_t P, int64_t epoch,
+                                   const int32_t *d_targets, float *d_logprob, void *d_scratch, int64_t scratch_bytes, void *stream);
+/* Scratch bytes opus_llama_score_continuations needs for R rows of n positions; -1 on a bad config or R < 1, n < 1, n > max_prompt. */
+int64_t opus_llama_score_scratch_bytes(const opus_config *cfg, int32_t R, int32_t n);
+/* attn_prefix_kernel alone, on layer 0 of this context's KV cache: d_k_hist / d_v_hist fp16 [P, kv, Tp, hd] (keys rotated) go to
+ * slots 0 .. Tp - 1, d_kstart int32 [P] (device) is the first visible slot of each prefix row; d_qkv [R n, (heads + 2 kv) hd]: the
+ * continuation rows' q | k | v, q and k rotated; h_src [R] (host) their prefix rows.  Query t of row r attends to slots
+ * kstart[p] .. Tp - 1 of p = h_src[r] and to positions 0 .. t of its own row.  d_out [R n, heads hd].  Leaves the context
+ * without a prefill. */
+int opus_debug_attn_prefix(opus_ctx *ctx, const void *d_qkv, const void *d_k_hist, const void *d_v_hist, const int32_t *d_kstart,
+                           int32_t P, int32_t Tp, int32_t R, int32_t n, const int32_t *h_src, void *d_out, void *stream);
 /* Diagnostic: the NLL kernel alone.  Per row of operand-dtype logits [R, V] (row-major): d_lse[r] = logsumexp (fp32, d_lse may
  * be NULL) and d_logprob[r] = l[y] - lse with y = d_targets[r] (y < 0: 0; y >= V: NaN). */
 int opus_debug_xent(opus_ctx *ctx, const void *d_logits, int32_t R, int32_t V, const int32_t *d_targets, float *d_logprob,

@@ -18,7 +18,7 @@ SRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "lib", "libopus_pllm.so")
 LIB_BF16 = os.path.join(HERE, "lib", "libopus_pllm_bf16.so")      # the same sources with -DOPUS_BF16 (csrc/common.h)
-SOURCES = ["gemm.hip", "gemm_stream.hip", "norm.hip", "elementwise.hip", "attn_prefill.hip", "attn_decode.hip", "beam.hip", "score.hip", "api.cpp"]
+SOURCES = ["gemm.hip", "gemm_stream.hip", "norm.hip", "elementwise.hip", "attn_prefill.hip", "attn_prefix.hip", "attn_decode.hip", "beam.hip", "score.hip", "api.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
@@ -28,6 +28,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-u
 # -fno-honor-nans (prefill attention only): fmaxf otherwise canonicalises every MFMA result first (28 instead of 13 max
 # instructions per 16 scores); the kernel never produces a NaN (masked scores are -inf, the running maximum is guarded).
 EXTRA = {"attn_prefill.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"],
+         "attn_prefix.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"],
          "attn_decode.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 
 

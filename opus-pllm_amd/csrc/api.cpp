@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <atomic>
 #include <map>
 #include <string>
 #include <vector>
@@ -157,6 +158,23 @@ struct opus_ctx {
     char *proj_big = nullptr;
     // beam search (opus_beam_topk / opus_kv_reorder): one layer's K and V cache rows while they are permuted (first use allocates)
     half_t *kv_tmp = nullptr;
+    // cache epoch: a new value (process-wide unique, so that a handle of another context never matches) whenever a call prefills or
+    // permutes the KV cache; opus_llama_prefix hands it out, opus_llama_score_continuations checks it.  h_kstart: the first real
+    // slot of every row of the last opus_llama_prefix (host copy for the continuation rows' positions).
+    int64_t epoch = 0;
+    std::vector<int32_t> h_kstart;
+};
+
+static std::atomic<int64_t> g_epoch{0};
+static void new_epoch(opus_ctx *c) { c->epoch = ++g_epoch; }
+
+// Continuation rows of opus_llama_score_continuations in the prefill's layer loop: B rows of T new positions behind a cached prefix.
+// No mask / kstart upload, no cache write, no decode state: rotary (learned positions for OPT) at Tp - kstart[p] + t through
+// nkst[b] = kstart[p] - Tp, and attn_prefix_kernel instead of the causal prefill attention.
+struct ContRows {
+    const int32_t *nkst;          // [B] device
+    AttnPrefixParams attn;        // layer-independent fields (kc / vc are set per layer)
+    int nblocks;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -922,7 +940,20 @@ static int attn_decode(opus_ctx *c, hipStream_t s, int l, int B, int T, int slab
 //   x = inputs_embeds + pos;  per layer  x += Wo attn(LN1 x) + bo;  x += W2 gelu(W1 LN2 x + b1) + b2;  logits = lm_head LNf x.
 // No rotary: the (cos, sin) table holds (1, 0), so the fused rotate-and-cache kernels only append to the KV cache; the
 // query scale head_dim^-0.5 is applied to the scores in fp32.
-static int opt_layer(opus_ctx *c, hipStream_t s, const DecLayer &L, int l, float *x, half_t *xn, int M, int B, int T, bool decode) {
+static int attn_prefix(opus_ctx *c, hipStream_t s, const ContRows &cr, int l, int M) {
+    const opus_config &g = c->cfg;
+    AttnPrefixParams a = cr.attn;
+    a.kc = c->kc + l * c->cache_sl;
+    a.vc = c->vc + l * c->cache_sl;
+    const int QKV = (g.dec_heads + 2 * g.dec_kv_heads) * g.dec_head_dim, QD = g.dec_heads * g.dec_head_dim;
+    // algorithmic bytes: the rows' projections + output, and every (prefix row, kv head)'s visible cache slots once
+    KLF(KC_ATTN_PREFILL, 2.0 * M * (QKV + QD) + 4.0 * cr.nblocks * g.dec_kv_heads * g.dec_head_dim * a.Tp,
+        4.0 * M * (double)QD * (a.Tp + a.n), launch_attn_prefix(a, cr.nblocks, s));
+    return OPUS_OK;
+}
+
+static int opt_layer(opus_ctx *c, hipStream_t s, const DecLayer &L, int l, float *x, half_t *xn, int M, int B, int T, bool decode,
+                     const ContRows *cont = nullptr) {
     const opus_config &g = c->cfg;
     const int H = g.dec_dim, F = g.dec_ffn, nh = g.dec_heads, nkv = g.dec_kv_heads, hd = g.dec_head_dim;
     const int QKV = (nh + 2 * nkv) * hd, QD = nh * hd;
@@ -930,6 +961,9 @@ static int opt_layer(opus_ctx *c, hipStream_t s, const DecLayer &L, int l, float
     OPC(gemm(c, s, xn, H, L.wqkv, M, QKV, H, L.bqkv, EPI_NONE, nullptr, c->d_qkv, QKV, 0));
     if (decode) {
         OPC(attn_decode(c, s, l, B, T));
+    } else if (cont) {
+        KL(KC_OTHER, 4.0 * M * QKV, launch_dec_rope_cache(c->d_qkv, c->cs_dec, cont->nkst, B, T, nh, nkv, hd, nullptr, nullptr, 0, 0, s));
+        OPC(attn_prefix(c, s, *cont, l, M));
     } else {
         KL(KC_OTHER, 4.0 * M * QKV,
            launch_dec_rope_cache(c->d_qkv, c->cs_dec, c->d_kstart, B, T, nh, nkv, hd, c->kc + l * c->cache_sl,
@@ -963,14 +997,15 @@ static int lm_head_opt(opus_ctx *c, hipStream_t s, int B) {
                 g.dec_vocab, 1);
 }
 
-static int prefill_opt(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8_t *mask, int B, int T, bool all_rows) {
+static int prefill_opt(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8_t *mask, int B, int T, bool all_rows,
+                       const ContRows *cont) {
     const opus_config &g = c->cfg;
     const int H = g.dec_dim, M = B * T;
     HIPC(hipMemsetAsync(c->d_cnt, 0, HANDOFF_ERR * sizeof(int32_t), s));
-    KL(KC_OTHER, 1.0 * M, launch_mask_to_kstart(mask, B, T, c->d_kstart, s));
+    if (!cont) KL(KC_OTHER, 1.0 * M, launch_mask_to_kstart(mask, B, T, c->d_kstart, s));
     KL(KC_OTHER, 6.0 * M * H, launch_h2f(embeds, c->d_x, (int64_t)M * H, s));
-    KL(KC_OTHER, 10.0 * M * H, launch_add_pos(c->d_x, c->dec_pos, c->d_kstart, nullptr, 0, B, T, H, g.dec_max_pos + 1, s));
-    for (int l = 0; l < g.dec_layers; ++l) OPC(opt_layer(c, s, c->dec[l], l, c->d_x, c->d_xn, M, B, T, false));
+    KL(KC_OTHER, 10.0 * M * H, launch_add_pos(c->d_x, c->dec_pos, cont ? cont->nkst : c->d_kstart, nullptr, 0, B, T, H, g.dec_max_pos + 1, s));
+    for (int l = 0; l < g.dec_layers; ++l) OPC(opt_layer(c, s, c->dec[l], l, c->d_x, c->d_xn, M, B, T, false, cont));
     if (all_rows) return OPUS_OK;
     KL(KC_OTHER, 8.0 * B * H, launch_take_last(c->d_x, B, T, H, c->d_xl, s));
     OPC(lm_head_opt(c, s, B));
@@ -994,19 +1029,27 @@ static int decode_step_opt(opus_ctx *c, hipStream_t s) {
 
 // all_rows: every position of every row runs through the last layer too, and the final residual stream of all B T rows is left in
 // d_x for opus_llama_forward; no lm_head, and the context is left without a prefill (decode_step fails until the next one).
-static int prefill(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8_t *mask, int B, int T, bool all_rows = false) {
-    c->phase = PH_PREFILL;
-    if (all_rows) {
-        c->prefilled = false;
-        c->cur_B = 0;
+// cont: the B rows are continuations behind the cached prefix (ContRows; implies all_rows, mask unused): the KV cache, kstart,
+// the step word and the decode state are left as they are.
+static int prefill(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8_t *mask, int B, int T, bool all_rows = false,
+                   const ContRows *cont = nullptr) {
+    c->phase = cont ? PH_SCORE : PH_PREFILL;
+    if (cont) {
+        all_rows = true;
+    } else {
+        new_epoch(c);
+        if (all_rows) {
+            c->prefilled = false;
+            c->cur_B = 0;
+        }
     }
-    if (c->cfg.dec_arch == 1) return prefill_opt(c, s, embeds, mask, B, T, all_rows);
+    if (c->cfg.dec_arch == 1) return prefill_opt(c, s, embeds, mask, B, T, all_rows, cont);
     const opus_config &g = c->cfg;
     const int H = g.dec_dim, F = g.dec_ffn, nh = g.dec_heads, nkv = g.dec_kv_heads, hd = g.dec_head_dim;
     const int QKV = (nh + 2 * nkv) * hd, QD = nh * hd;
     const int M = B * T;
     HIPC(hipMemsetAsync(c->d_cnt, 0, HANDOFF_ERR * sizeof(int32_t), s));       // hand-off words start from zero on every call
-    KL(KC_OTHER, 1.0 * M, launch_mask_to_kstart(mask, B, T, c->d_kstart, s));
+    if (!cont) KL(KC_OTHER, 1.0 * M, launch_mask_to_kstart(mask, B, T, c->d_kstart, s));
     KL(KC_OTHER, 6.0 * M * H, launch_h2f(embeds, c->d_x, (int64_t)M * H, s));
     // RMSNorm fused around the big tiled GEMM, as the encoder's LayerNorm (GemmParams::ln_* with mu = 0): the wo / down epilogue
     // leaves fp16(x) + per-slab sums of squares, the consuming projection scales its rows by rstd in its epilogue
@@ -1027,18 +1070,23 @@ static int prefill(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8
         } else {
             OPC(gemm_norm(c, s, c->d_x, g.dec_rms_eps, c->d_xn, L.wqkv, M, QKV, H, EPI_NONE, c->d_qkv, QKV, 0, L.bqkv));
         }
-        KL(KC_OTHER, 4.0 * M * QKV,
-           launch_dec_rope_cache(c->d_qkv, c->cs_dec, c->d_kstart, B, T, nh, nkv, hd, c->kc + l * c->cache_sl,
-                                 c->vc + l * c->cache_sl, c->cache_sb, c->cache_sh, s));
-        AttnParams a;
-        a.Q = c->d_qkv; a.K = c->d_qkv + QD; a.V = c->d_qkv + QD + nkv * hd;
-        a.q_sb = a.k_sb = a.v_sb = (int64_t)T * QKV;
-        a.q_st = a.k_st = a.v_st = QKV;
-        a.O = c->d_ctx; a.o_sb = (int64_t)T * QD; a.o_st = QD;
-        a.kstart = c->d_kstart; a.kend = nullptr;
-        a.B = B; a.T = T; a.heads = nh; a.group = nh / nkv; a.head_dim = hd; a.causal = 1;
-        a.scale = 1.0f / sqrtf((float)hd);
-        KLF(KC_ATTN_PREFILL, 2.0 * M * (QKV + QD), 2.0 * B * (double)T * T * QD, launch_attn_prefill(a, s));
+        if (cont) {
+            KL(KC_OTHER, 4.0 * M * QKV, launch_dec_rope_cache(c->d_qkv, c->cs_dec, cont->nkst, B, T, nh, nkv, hd, nullptr, nullptr, 0, 0, s));
+            OPC(attn_prefix(c, s, *cont, l, M));
+        } else {
+            KL(KC_OTHER, 4.0 * M * QKV,
+               launch_dec_rope_cache(c->d_qkv, c->cs_dec, c->d_kstart, B, T, nh, nkv, hd, c->kc + l * c->cache_sl,
+                                     c->vc + l * c->cache_sl, c->cache_sb, c->cache_sh, s));
+            AttnParams a;
+            a.Q = c->d_qkv; a.K = c->d_qkv + QD; a.V = c->d_qkv + QD + nkv * hd;
+            a.q_sb = a.k_sb = a.v_sb = (int64_t)T * QKV;
+            a.q_st = a.k_st = a.v_st = QKV;
+            a.O = c->d_ctx; a.o_sb = (int64_t)T * QD; a.o_st = QD;
+            a.kstart = c->d_kstart; a.kend = nullptr;
+            a.B = B; a.T = T; a.heads = nh; a.group = nh / nkv; a.head_dim = hd; a.causal = 1;
+            a.scale = 1.0f / sqrtf((float)hd);
+            KLF(KC_ATTN_PREFILL, 2.0 * M * (QKV + QD), 2.0 * B * (double)T * T * QD, launch_attn_prefill(a, s));
+        }
         if (l + 1 == g.dec_layers && T > 1 && !all_rows && !g_knobs.misc[7]) {
             // Last layer: its K / V are in the cache for every position, but behind the attention only the LAST position of a row
             // is ever used (lm_head reads that row alone, opus_arch.py -> HF generate keeps the last logits): wo, gate/up and
@@ -1290,6 +1338,204 @@ extern "C" int opus_debug_xent(opus_ctx *c, const void *d_logits, int32_t R, int
     hipStream_t s = (hipStream_t)stream;
     c->phase = PH_SCORE;
     KL(KC_XENT, 2.0 * R * V + 12.0 * R, launch_xent((const half_t *)d_logits, V, R, V, d_targets, d_logprob, d_lse, s));
+    return OPUS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ shared-prefix scoring
+// opus_llama_prefix = a prefill that also hands out the final residual rows of every row's last position and the cache epoch;
+// opus_llama_score_continuations runs continuation rows behind that cached prefix (prefill()'s layer loop with ContRows) and
+// scores them: the first token of a continuation from the prefix's last row, token j >= 1 from continuation position j - 1.
+
+// rows the decoder activation buffers hold (carve's Md)
+static int64_t dec_rows_cap(const opus_config &g) {
+    const int64_t B16 = ((int64_t)g.max_batch + 15) & ~(int64_t)15;
+    return std::max<int64_t>((int64_t)g.max_batch * g.max_prompt, B16);
+}
+// continuation rows per pass of the layer loop: as many as the prefill's activation buffers hold positions (not max_batch rows)
+static int64_t prefix_group_rows(const opus_config &g, int64_t R, int n) { return std::min<int64_t>(R, dec_rows_cap(g) / n); }
+// int32 table words of one pass of Rg rows: row offsets per prefix row, row list, position bases, workgroup table, gather index
+static int64_t prefix_table_words(const opus_config &g, int64_t Rg, int n) {
+    const int G = g.dec_heads / g.dec_kv_heads;
+    return (int64_t)g.max_batch + 1 + 2 * Rg + 2 * (int64_t)attn_prefix_max_blocks((int)Rg, g.max_batch, G, n) + Rg * n;
+}
+static int64_t prefix_scratch_bytes(const opus_config &g, int64_t R, int n) {
+    const int64_t Rg = prefix_group_rows(g, R, n);
+    return (int64_t)align_up((size_t)prefix_table_words(g, Rg, n) * sizeof(int32_t)) +
+           score_chunk_bytes(g, score_chunk_cap(g, Rg * n, true), true);
+}
+
+// host tables of one pass: rows src[0 .. Rg) (local row ids) grouped by prefix row, in the layout AttnPrefixParams reads
+struct PrefixTables {
+    std::vector<int32_t> w;
+    int off = 0, list = 0, nkst = 0, blocks = 0, gidx = 0, nblocks = 0;
+};
+static void build_prefix_tables(const opus_config &g, const std::vector<int32_t> &kst, int Tp, const int32_t *src, int Rg, int n,
+                                PrefixTables &t) {
+    const int P = (int)kst.size(), G = g.dec_heads / g.dec_kv_heads;
+    t.off = 0;
+    t.list = P + 1;
+    t.nkst = t.list + Rg;
+    t.blocks = t.nkst + Rg;
+    t.w.assign((size_t)t.blocks, 0);
+    for (int r = 0; r < Rg; ++r) ++t.w[t.off + src[r] + 1];
+    for (int p = 0; p < P; ++p) t.w[t.off + p + 1] += t.w[t.off + p];
+    std::vector<int32_t> fill(t.w.begin() + t.off, t.w.begin() + t.off + P);
+    for (int r = 0; r < Rg; ++r) {
+        t.w[t.list + fill[src[r]]++] = r;
+        t.w[t.nkst + r] = kst[src[r]] - Tp;               // rotary / learned position of new position j: Tp - kstart[p] + j
+    }
+    t.nblocks = attn_prefix_blocks(t.w.data() + t.off, P, G, n, nullptr);
+    t.w.resize((size_t)t.blocks + 2 * t.nblocks);
+    attn_prefix_blocks(t.w.data() + t.off, P, G, n, t.w.data() + t.blocks);
+    t.gidx = (int)t.w.size();
+}
+
+extern "C" int opus_llama_prefix(opus_ctx *c, const void *d_embeds, const uint8_t *d_mask, int32_t B, int32_t T, float *d_last_logits,
+                                 float *d_last_rows, int64_t *epoch, void *stream) {
+    OPC(need_ready(c));
+    OPC(check_prefill_args(c, d_embeds, d_mask, B, T));
+    if (!d_last_rows || !epoch) return fail(OPUS_EBADARG, "prefix: null last rows / epoch");
+    hipStream_t s = (hipStream_t)stream;
+    c->h_kstart.clear();
+    OPC(prefill(c, s, (const half_t *)d_embeds, d_mask, B, T));
+    const opus_config &g = c->cfg;
+    HIPC(hipMemcpyAsync(d_last_rows, c->d_xl, (size_t)B * g.dec_dim * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (d_last_logits)
+        HIPC(hipMemcpyAsync(d_last_logits, c->d_logits, (size_t)B * g.dec_vocab * sizeof(float), hipMemcpyDeviceToDevice, s));
+    std::vector<int32_t> kst(B);
+    HIPC(hipMemcpyAsync(kst.data(), c->d_kstart, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    c->h_kstart = kst;
+    *epoch = c->epoch;
+    return OPUS_OK;
+}
+
+extern "C" int64_t opus_llama_score_scratch_bytes(const opus_config *cfg, int32_t R, int32_t n) {
+    if (check_cfg(cfg) != OPUS_OK) return -1;
+    if (R < 1 || n < 1 || n > cfg->max_prompt) {
+        fail(OPUS_ESHAPE, "score_scratch_bytes: R=%d n=%d (1 <= n <= max_prompt=%d)", R, n, cfg->max_prompt);
+        return -1;
+    }
+    return prefix_scratch_bytes(*cfg, R, n);
+}
+
+extern "C" int opus_llama_score_continuations(opus_ctx *c, const void *d_embeds, int32_t R, int32_t n, const int32_t *h_lens,
+                                              const int32_t *h_src, const float *d_last_rows, int32_t P, int64_t epoch,
+                                              const int32_t *d_targets, float *d_logprob, void *d_scratch, int64_t scratch_bytes,
+                                              void *stream) {
+    OPC(need_ready(c));
+    if (!d_embeds || !h_lens || !h_src || !d_last_rows || !d_targets || !d_logprob || !d_scratch)
+        return fail(OPUS_EBADARG, "score_continuations: null pointer");
+    const opus_config &g = c->cfg;
+    if (R < 1 || n < 1 || n > g.max_prompt)
+        return fail(OPUS_ESHAPE, "score_continuations: R=%d rows of n=%d positions (1 <= n <= max_prompt=%d)", R, n, g.max_prompt);
+    if (!c->prefilled || epoch != c->epoch || (int)c->h_kstart.size() != c->cur_B || P != c->cur_B)
+        return fail(OPUS_ESTATE, "score_continuations: the prefix is not this context's current one (a later call prefilled or "
+                                 "permuted the cache, or the handle belongs to another context)");
+    const int Tp = c->cur_T, ctx_cap = g.max_prompt + g.max_new_tokens;
+    int64_t N = 0;
+    for (int r = 0; r < R; ++r) {
+        if (h_src[r] < 0 || h_src[r] >= P) return fail(OPUS_EBADARG, "score_continuations: prefix row %d of row %d outside [0, %d)", h_src[r], r, P);
+        if (h_lens[r] < 0 || h_lens[r] > n) return fail(OPUS_ESHAPE, "score_continuations: length %d of row %d outside [0, %d]", h_lens[r], r, n);
+        if (Tp - c->h_kstart[h_src[r]] + n > ctx_cap)
+            return fail(OPUS_ESHAPE, "score_continuations: prefix of %d tokens + %d positions exceed the context's %d positions "
+                                     "(max_prompt + max_new_tokens)", Tp - c->h_kstart[h_src[r]], n, ctx_cap);
+        N += h_lens[r];
+    }
+    if (N >= (1ll << 31)) return fail(OPUS_ESHAPE, "score_continuations: %lld scored tokens", (long long)N);
+    const int64_t need = prefix_scratch_bytes(g, R, n);
+    if (scratch_bytes < need)
+        return fail(OPUS_EBADARG, "score_continuations: scratch of %lld bytes, %lld needed (opus_llama_score_scratch_bytes)",
+                    (long long)scratch_bytes, (long long)need);
+    hipStream_t s = (hipStream_t)stream;
+    const int H = g.dec_dim, G = g.dec_heads / g.dec_kv_heads;
+    const int64_t Rg_max = prefix_group_rows(g, R, n);
+    const int64_t chunk = score_chunk_cap(g, Rg_max * n, true);
+    int32_t *tbl = reinterpret_cast<int32_t *>(d_scratch);
+    float *rows_f = reinterpret_cast<float *>((char *)d_scratch + align_up((size_t)prefix_table_words(g, Rg_max, n) * sizeof(int32_t)));
+    half_t *slab = reinterpret_cast<half_t *>((char *)rows_f + align_up((size_t)chunk * H * sizeof(float)));
+    int64_t base = 0;                                               // compact index of the pass's first scored token
+    for (int64_t r0 = 0; r0 < R; r0 += Rg_max) {
+        const int Rg = (int)std::min<int64_t>(Rg_max, R - r0);
+        PrefixTables t;
+        build_prefix_tables(g, c->h_kstart, Tp, h_src + r0, Rg, n, t);
+        if (t.nblocks > attn_prefix_max_blocks(Rg, g.max_batch, G, n)) return fail(OPUS_EHIP, "score_continuations: block table overflow");
+        // scored rows: token 0 of row r from the prefix's last row (gather index -(p) - 1), token j from position j - 1 of the pass
+        int64_t Ng = 0;
+        for (int r = 0; r < Rg; ++r) {
+            const int L = h_lens[r0 + r];
+            if (L > 0) t.w.push_back(-h_src[r0 + r] - 1);
+            for (int j = 1; j < L; ++j) t.w.push_back(r * n + j - 1);
+            Ng += L;
+        }
+        if ((int64_t)t.w.size() > prefix_table_words(g, Rg_max, n)) return fail(OPUS_EHIP, "score_continuations: table overflow");
+        HIPC(hipMemcpyAsync(tbl, t.w.data(), t.w.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        ContRows cr;
+        cr.nkst = tbl + t.nkst;
+        cr.nblocks = t.nblocks;
+        AttnPrefixParams &a = cr.attn;
+        a.kc = a.vc = nullptr; a.cache_sb = c->cache_sb; a.cache_sh = c->cache_sh; a.kstart = c->d_kstart; a.Tp = Tp;
+        a.qkv = c->d_qkv; a.n = n; a.list = tbl + t.list; a.off = tbl + t.off; a.blocks = tbl + t.blocks; a.out = c->d_ctx;
+        a.nh = g.dec_heads; a.nkv = g.dec_kv_heads; a.hd = g.dec_head_dim; a.scale = 1.0f / sqrtf((float)g.dec_head_dim);
+        const half_t *emb = reinterpret_cast<const half_t *>(d_embeds) + r0 * n * (int64_t)H;
+        OPC(prefill(c, s, emb, nullptr, Rg, n, true, &cr));
+        c->phase = PH_SCORE;
+        for (int64_t k0 = 0; k0 < Ng; k0 += chunk) {
+            const int m = (int)std::min<int64_t>(chunk, Ng - k0);
+            KL(KC_OTHER, 8.0 * m * H + 4.0 * m,
+               launch_gather_rows2(c->d_x, (int64_t)Rg * n, d_last_rows, P, tbl + t.gidx + k0, m, H, rows_f, s));
+            OPC(score_rows(c, s, rows_f, m, slab, d_targets + base + k0, d_logprob + base + k0, nullptr));
+        }
+        base += Ng;
+        HIPC(hipStreamSynchronize(s));                              // (the table upload's host buffer is reused by the next pass)
+    }
+    return OPUS_OK;
+}
+
+// attn_prefix_kernel alone, as opus_llama_score_continuations launches it, on layer 0 of this context's KV cache: the prefix
+// d_k_hist / d_v_hist [P, kv heads, Tp, hd] (keys rotated, as the cache holds them) is copied into slots 0 .. Tp - 1 and d_kstart
+// [P] into the context's kstart; d_qkv [R n, (heads + 2 kv) hd]: the continuation rows' projections, q and k already rotated;
+// h_src [R] (host): prefix row of every continuation row.  d_out [R n, heads hd].  Leaves the context without a prefill.
+extern "C" int opus_debug_attn_prefix(opus_ctx *c, const void *d_qkv, const void *d_k_hist, const void *d_v_hist, const int32_t *d_kstart,
+                                      int32_t P, int32_t Tp, int32_t R, int32_t n, const int32_t *h_src, void *d_out, void *stream) {
+    if (!c || !d_qkv || !d_k_hist || !d_v_hist || !d_kstart || !h_src || !d_out) return fail(OPUS_EBADARG, "debug_attn_prefix: null pointer");
+    const opus_config &g = c->cfg;
+    if (P < 1 || P > g.max_batch || Tp < 1 || Tp > g.max_prompt || R < 1 || n < 1)
+        return fail(OPUS_ESHAPE, "debug_attn_prefix: P=%d Tp=%d R=%d n=%d exceed the context (%d, %d)", P, Tp, R, n, g.max_batch, g.max_prompt);
+    for (int r = 0; r < R; ++r)
+        if (h_src[r] < 0 || h_src[r] >= P) return fail(OPUS_EBADARG, "debug_attn_prefix: prefix row %d of row %d outside [0, %d)", h_src[r], r, P);
+    HIPC(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int nkv = g.dec_kv_heads, hd = g.dec_head_dim, G = g.dec_heads / nkv;
+    std::vector<int32_t> kst(P);
+    HIPC(hipMemcpyAsync(kst.data(), d_kstart, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    for (int p = 0; p < P; ++p)
+        if (kst[p] < 0 || kst[p] >= Tp) return fail(OPUS_EBADARG, "debug_attn_prefix: kstart[%d]=%d outside [0, %d)", p, kst[p], Tp);
+    c->prefilled = false;                                     // (the cache no longer belongs to a prefill)
+    new_epoch(c);
+    const size_t pitch = (size_t)c->cache_sh * sizeof(half_t), roww = (size_t)Tp * hd * sizeof(half_t);
+    HIPC(hipMemcpy2DAsync(c->kc, pitch, d_k_hist, roww, roww, (size_t)P * nkv, hipMemcpyDeviceToDevice, s));
+    HIPC(hipMemcpy2DAsync(c->vc, pitch, d_v_hist, roww, roww, (size_t)P * nkv, hipMemcpyDeviceToDevice, s));
+    HIPC(hipMemcpyAsync(c->d_kstart, d_kstart, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    PrefixTables t;
+    build_prefix_tables(g, kst, Tp, h_src, R, n, t);
+    int32_t *d_tbl = nullptr;
+    HIPC(hipMalloc((void **)&d_tbl, t.w.size() * sizeof(int32_t)));
+    hipError_t e = hipMemcpyAsync(d_tbl, t.w.data(), t.w.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
+    AttnPrefixParams a;
+    a.kc = c->kc; a.vc = c->vc; a.cache_sb = c->cache_sb; a.cache_sh = c->cache_sh; a.kstart = c->d_kstart; a.Tp = Tp;
+    a.qkv = (const half_t *)d_qkv; a.n = n; a.list = d_tbl + t.list; a.off = d_tbl + t.off; a.blocks = d_tbl + t.blocks;
+    a.out = (half_t *)d_out; a.nh = g.dec_heads; a.nkv = nkv; a.hd = hd; a.scale = 1.0f / sqrtf((float)hd);
+    c->phase = PH_SCORE;
+    if (e == hipSuccess) {
+        Timed tm(c, s, KC_ATTN_PREFILL, 2.0 * R * n * (double)(G + 2) * nkv * hd * 2 + 4.0 * t.nblocks * nkv * hd * Tp,
+                 4.0 * R * n * (double)G * nkv * hd * (Tp + n));
+        e = launch_attn_prefix(a, t.nblocks, s);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(d_tbl);
+    if (e != hipSuccess) return fail(OPUS_EHIP, "debug_attn_prefix failed: %s", hipGetErrorString(e));
     return OPUS_OK;
 }
 
@@ -1616,6 +1862,7 @@ extern "C" int opus_kv_reorder(opus_ctx *c, const int32_t *d_src_rows, int32_t R
     const size_t row = (size_t)c->cache_sb, layer = row * g.max_batch;
     if (!c->kv_tmp) HIPC(hipMalloc((void **)&c->kv_tmp, 2 * layer * sizeof(half_t)));
     c->phase = PH_DECODE;
+    new_epoch(c);
     // only the filled slots (0 .. T + *step - 1, read from the device step word) of the rows that change place move
     const int nkv = g.dec_kv_heads, hd = g.dec_head_dim, T0 = c->cur_T;
     for (int l = 0; l < g.dec_layers; ++l) {
@@ -1697,6 +1944,7 @@ extern "C" int opus_debug_attn_decode(opus_ctx *c, const void *d_qkv, const void
     if (d_k_new) HIPC(hipMemcpy2DAsync(d_k_new, one, c->kc + (size_t)L * hd, pitch, one, (size_t)B * nkv, hipMemcpyDeviceToDevice, s));
     if (d_v_new) HIPC(hipMemcpy2DAsync(d_v_new, one, c->vc + (size_t)L * hd, pitch, one, (size_t)B * nkv, hipMemcpyDeviceToDevice, s));
     c->prefilled = false;                                     // (the cache no longer belongs to a prefill)
+    new_epoch(c);
     return OPUS_OK;
 }
 

@@ -250,6 +250,27 @@ __device__ __forceinline__ void block_row_rstd(const float *__restrict__ ssq, in
 bool gemm_goes_wide(int M, int N);
 bool gemm_goes_pp(int M, int N);     // would launch_gemm route an fp16-A GEMM of this shape to gemm_pp_kernel (the big tiled kernel)?   // would launch_gemm route an fp16-A GEMM of this shape to gemm_wide_kernel?
 hipError_t launch_attn_prefill(const AttnParams &p, hipStream_t s);
+// attn_prefix.hip: attention of continuation rows over a cached prefix + their own positions (opus_llama_score_continuations).
+// Continuation row r has n positions at rows r n .. r n + n - 1 of qkv ([rows][(nh + 2 nkv) hd], q and k rotated); the rows that
+// belong to prefix row p are list[off[p] .. off[p + 1]).  Keys: cache slots kstart[p] .. Tp - 1 of row p ([P][nkv][slot][hd] at
+// kc / vc with strides cache_sb / cache_sh), then the row's own positions 0 .. t.  blocks: (p, first stacked query) per workgroup
+// (attn_prefix_blocks).  out: [rows][nh hd].
+struct AttnPrefixParams {
+    const half_t *kc, *vc;
+    int64_t cache_sb, cache_sh;
+    const int32_t *kstart;
+    int Tp;
+    const half_t *qkv;
+    int n;
+    const int32_t *list, *off, *blocks;
+    half_t *out;
+    int nh, nkv, hd;
+    float scale;
+};
+// workgroup table of launch_attn_prefix for the row lists off[0 .. P] (blocks = nullptr: count only); returns the block count
+int attn_prefix_blocks(const int32_t *off, int P, int G, int n, int32_t *blocks);
+int attn_prefix_max_blocks(int R, int P, int G, int n);   // an upper bound of that count for R rows over P prefix rows
+hipError_t launch_attn_prefix(const AttnPrefixParams &p, int nblocks, hipStream_t s);
 
 // norm.hip
 hipError_t launch_layernorm(const float *x, const float *w, const float *b, float eps, int64_t rows, int D,
@@ -287,6 +308,9 @@ hipError_t launch_add_pos(float *x, const half_t *pos, const int32_t *kstart, co
 hipError_t launch_take_last(const float *x, int B, int T, int H, float *out, hipStream_t s);
 // score.hip: out[r] = x[rows[r]] (fp32 rows of width H; an index outside [0, n_src) gives a zero row)
 hipError_t launch_gather_rows(const float *x, const int32_t *rows, int R, int64_t n_src, int H, float *out, hipStream_t s);
+// out[r] = rows[r] >= 0 ? x[rows[r]] : y[-rows[r] - 1] (two sources: continuation rows and the prefix's last rows)
+hipError_t launch_gather_rows2(const float *x, int64_t n_x, const float *y, int64_t n_y, const int32_t *rows, int R, int H, float *out,
+                               hipStream_t s);
 // score.hip: per row r of logits [R, V] (row stride ld): lse[r] = logsumexp, logprob[r] = l[targets[r]] - lse[r] (fp32;
 // target < 0: 0, target >= V: NaN; lse may be null)
 hipError_t launch_xent(const half_t *logits, int64_t ld, int R, int V, const int32_t *targets, float *logprob, float *lse,

@@ -112,6 +112,8 @@ hipError_t launch_esm_rope(half_t *qkv, const float *cs, int B, int T, int heads
 
 // Llama prefill (D1, D4): rotary on q and k at position t - kstart[b] (first real token = 0), in place
 // on the fused [B*T, (nh+2nkv)*hd] buffer, then K and V appended to the cache [b][kvh][slot t][hd].
+// kc == nullptr: rotary only, no cache write (continuation rows of opus_llama_score_continuations, whose kstart[b] is the prefix
+// row's first slot minus its length: positions Tp - kstart[p] + t).
 __global__ __launch_bounds__(256) void dec_rope_cache_kernel(half_t *__restrict__ qkv, const float *__restrict__ cs,
                                                              const int32_t *__restrict__ kstart, int T, int nh, int nkv,
                                                              int hd, half_t *__restrict__ kc, half_t *__restrict__ vc,
@@ -129,7 +131,7 @@ __global__ __launch_bounds__(256) void dec_rope_cache_kernel(half_t *__restrict_
     const int64_t ld = (int64_t)(nh + 2 * nkv) * hd;
     half_t *base = qkv + row * ld + (int64_t)hh * hd + v * 8;
     rope8(base, half, cs + ((int64_t)pos * half + v * 8) * 2, 1.0f);
-    if (hh >= nh) {
+    if (hh >= nh && kc) {
         const int kh = hh - nh;
         half_t *kd = kc + b * cache_sb + kh * cache_sh + (int64_t)t * hd + v * 8;
         half_t *vd = vc + b * cache_sb + kh * cache_sh + (int64_t)t * hd + v * 8;

@@ -1,6 +1,7 @@
 // Teacher-forced scoring (opus_llama_forward): the row gather in front of the lm_head over many rows and the log-softmax /
 // NLL reduction behind it.
-//   gather_rows : out[r] = x[rows[r]] for fp32 residual-stream rows (launch_take_last with an index list)
+//   gather_rows : out[r] = x[rows[r]] for fp32 residual-stream rows (launch_take_last with an index list); gather_rows2 the
+//                 same over two sources (opus_llama_score_continuations: continuation rows and the prefix's last rows)
 //   xent        : per row of operand-dtype logits [R, V] and target y: lse = logsumexp(l), logprob = l[y] - lse (fp32)
 #include "common.h"
 
@@ -24,6 +25,24 @@ hipError_t launch_gather_rows(const float *x, const int32_t *rows, int R, int64_
     if (R <= 0) return hipSuccess;
     if (H & 3) return hipErrorInvalidValue;
     hipLaunchKernelGGL(gather_rows_kernel, dim3(R), dim3(256), 0, s, x, rows, n_src, H, out);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void gather_rows2_kernel(const float *__restrict__ x, int64_t n_x, const float *__restrict__ y,
+                                                           int64_t n_y, const int32_t *__restrict__ rows, int H,
+                                                           float *__restrict__ out) {
+    const int r = blockIdx.x;
+    const int64_t i = rows[r];
+    const float *src = i >= 0 ? (i < n_x ? x + i * H : nullptr) : (-i - 1 < n_y ? y + (-i - 1) * H : nullptr);
+    float4 *dst = reinterpret_cast<float4 *>(out + (int64_t)r * H);
+    for (int c = threadIdx.x; c < (H >> 2); c += 256)
+        dst[c] = src ? reinterpret_cast<const float4 *>(src)[c] : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+hipError_t launch_gather_rows2(const float *x, int64_t n_x, const float *y, int64_t n_y, const int32_t *rows, int R, int H, float *out,
+                               hipStream_t s) {
+    if (R <= 0) return hipSuccess;
+    if (H & 3) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gather_rows2_kernel, dim3(R), dim3(256), 0, s, x, n_x, y, n_y, rows, H, out);
     return hipGetLastError();
 }
 

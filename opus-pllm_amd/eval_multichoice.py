@@ -11,6 +11,10 @@ message (with the <seq> placeholder when the item has a sequence) rendered by th
 left-pad -> generate -> decode, cut at the separator -> gather in rank order -> rank 0 extracts the option letters, prints
 the accuracy and saves [{ground_truth, generated}].
 As in eval_ddp.py the gather moves token ids over RCCL instead of pickled strings.
+
+--rank_options (not in the reference): no generation and no regex on free text.  Each batch's prompts are prefilled once
+(cache_prefix) and the four answer texts `The correct answer is A)` .. `D)` are scored behind them (score_continuations); the
+best-scoring text is written as `generated` (so score_multichoice is unchanged) with the four sums as `option_logprobs`.
 """
 from __future__ import annotations
 
@@ -40,6 +44,52 @@ def render_question(item, tokenizer) -> str:
     return conv.get_prompt_eval()
 
 
+OPTIONS = "ABCD"
+
+
+def option_text(letter: str) -> str:
+    """The answer the prompt asks for ("format 'The correct answer is'", prompt.multichoice_prompt)."""
+    return f"The correct answer is {letter})"
+
+
+ANSWER_CUE = "assistant\n"        # what the rendered prompt ends with (the chat template's generation prompt)
+
+
+def _encode(tokenizer, text: str):
+    """Ids of `text` without special tokens (a tokenizer without add_special_tokens: its leading BOS dropped)."""
+    try:
+        return list(tokenizer(text, add_special_tokens=False).input_ids)
+    except TypeError:
+        ids = list(tokenizer(text).input_ids)
+        bos = getattr(tokenizer, "bos_token_id", None)
+        return ids[1:] if ids and bos is not None and ids[0] == bos else ids
+
+
+def option_ids(tokenizer, letter: str):
+    """Token ids of option_text(letter) as they follow the prompt's answer cue: the tokens the cue + answer text adds behind the
+    cue alone (a tokenizer may merge across the boundary; then the answer text on its own)."""
+    cue = _encode(tokenizer, ANSWER_CUE)
+    both = _encode(tokenizer, ANSWER_CUE + option_text(letter))
+    if both[: len(cue)] == cue and len(both) > len(cue):
+        return both[len(cue):]
+    return _encode(tokenizer, option_text(letter))
+
+
+@torch.no_grad()
+def rank_batch(model, tokenizer, batch, dev):
+    """One batch of items -> option log-likelihoods fp32 [B, 4]: the prompts prefilled once, the four answers scored behind them."""
+    prompts = [render_question(q, tokenizer) for q in batch]
+    rows = [opa.tokenizer_seq_token(p, tokenizer, opa.DEFAULT_SEQ_TOKEN_INDEX, return_tensors="pt").to(dev) for p in prompts]
+    ids = opa.left_pad_sequence(rows, padding_value=tokenizer.pad_token_id, batch_first=True)
+    T = ids.shape[1]
+    mask = torch.stack([torch.arange(T, device=dev) >= T - r.numel() for r in rows])      # (left padding)
+    prefix = model.cache_prefix(ids, [q["input"] for q in batch], attention_mask=mask)
+    conts = [torch.tensor(option_ids(tokenizer, L), dtype=torch.long) for L in OPTIONS]
+    B = len(batch)
+    res = model.score_continuations(prefix, conts * B, prefix_rows=torch.arange(B).repeat_interleave(len(OPTIONS)))
+    return res.logprob.view(B, len(OPTIONS)).float()
+
+
 def eval_model(args):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -66,6 +116,8 @@ def eval_model(args):
     dev = torch.device("cuda", local)
     outs = []
     t0 = time.time()
+    if getattr(args, "rank_options", False):
+        return _eval_ranked(args, qs, mine, tokenizer, model, dev, rank, world, t0)
     for i in range(0, len(mine), args.batch_size):
         batch = mine[i:i + args.batch_size]
         prompts = [render_question(q, tokenizer) for q in batch]
@@ -95,7 +147,27 @@ def eval_model(args):
         torch.distributed.destroy_process_group()
 
 
-if __name__ == "__main__":
+def _eval_ranked(args, qs, mine, tokenizer, model, dev, rank, world, t0):
+    scores = [rank_batch(model, tokenizer, mine[i:i + args.batch_size], dev) for i in range(0, len(mine), args.batch_size)]
+    local = torch.cat(scores) if scores else torch.empty((0, len(OPTIONS)), dtype=torch.float32, device=dev)
+    every = odist.all_gather_logits(local)
+    if rank == 0:
+        dt = time.time() - t0
+        lp = every.cpu().tolist()
+        result = [{"ground_truth": q["answer"], "generated": option_text(OPTIONS[max(range(len(OPTIONS)), key=row.__getitem__)]),
+                   "option_logprobs": row} for q, row in zip(qs, lp)]
+        correct, hist = score_multichoice(result)
+        n = len(qs)
+        print(hist)
+        print(f"\n{correct}/{n}:Accuracy: {100.0 * correct / max(n, 1):.2f}%")
+        print(f"entries/sec: {n / dt}, time elapsed: {dt}")
+        with open(args.save_path, "w") as f:
+            json.dump(result, f)
+    if world > 1:
+        torch.distributed.destroy_process_group()
+
+
+def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser()
     p.add_argument("--model-base-path", type=str, default="synthetic:c1_tiny")
     p.add_argument("--opus-pllm-weights-path", type=str, default="synthetic")
@@ -111,4 +183,10 @@ if __name__ == "__main__":
     p.add_argument("--batch_size", type=int, default=8)              # hard-coded 8 in the reference (:100)
     p.add_argument("--max_residues", type=int, default=1024)
     p.add_argument("--max_prompt", type=int, default=384)
-    eval_model(p.parse_args())
+    p.add_argument("--rank_options", action="store_true",
+                   help="rank the four answers by log-likelihood behind one cached prompt instead of generating")
+    return p
+
+
+if __name__ == "__main__":
+    eval_model(build_parser().parse_args())

@@ -625,6 +625,114 @@ class OpusLlamaForCausalLM:
 
     __call__ = forward
 
+    # ------------------------------------------------------------------ shared-prefix scoring
+    @torch.no_grad()
+    def cache_prefix(self, input_ids: torch.Tensor, seq=None, attention_mask: Optional[torch.Tensor] = None,
+                     seq_embedding=None, protein_tokens: Optional[torch.Tensor] = None) -> "OpusPrefix":
+        """Prefills a prompt batch once and returns a handle that score_continuations() ranks continuations against.  The inputs
+        are prepared exactly as generate() prepares them (inference-mode splice with `seq` / `seq_embedding` / `protein_tokens`;
+        left-padded or unpadded rows): it IS a prefill, decode_logits() continues it as after prefill_logits().  The last slot of
+        every row must be a real token (ValueError otherwise).  The handle is valid until the next call on this context that
+        prefills or permutes the cache (cache_prefix, generate, forward, prefill_logits, beam search); decode steps keep it."""
+        if input_ids is None:
+            raise ValueError("cache_prefix() needs input ids")
+        if attention_mask is not None and not bool(attention_mask.detach().bool()[:, -1].all()):
+            raise ValueError("cache_prefix(): the last slot of every row must be a real token (left-pad the prompts)")
+        if seq is not None or seq_embedding is not None or protein_tokens is not None:
+            _, _, mask, _, embeds, _ = self.prepare_inputs_labels_for_multimodal(
+                input_ids, None, attention_mask if attention_mask is not None else torch.ones_like(input_ids, dtype=torch.bool),
+                None, None, seq if seq is not None else (), seq_embedding, inference_mode=True, protein_tokens=protein_tokens)
+        else:
+            dummy = torch.zeros((input_ids.shape[0], self.cfg.n_prot_tokens, self.cfg.dec_dim), dtype=_cabi.operand_dtype(),
+                                device=self.device)
+            embeds, mask, _ = self._splice(input_ids, attention_mask, dummy, True)
+        mask = mask.to(self.device).to(torch.uint8).contiguous()
+        if not bool(mask[:, -1].all()):
+            raise ValueError("cache_prefix(): the last slot of every row must be a real token")
+        B, T, H = embeds.shape
+        embeds = embeds.to(self.device, _cabi.operand_dtype()).contiguous()
+        s = self._enter()
+        with torch.cuda.stream(self._stream):
+            last = torch.empty((B, H), dtype=torch.float32, device=self.device)
+            epoch = C.c_int64(0)
+            _cabi.check(self._lib.opus_llama_prefix(self._ctx, embeds.data_ptr(), mask.data_ptr(), B, T, None, last.data_ptr(),
+                                                    C.byref(epoch), s))
+        self._leave()
+        return OpusPrefix(self, epoch.value, last, mask.sum(dim=1).cpu())
+
+    @torch.no_grad()
+    def score_continuations(self, prefix: "OpusPrefix", continuations, prefix_rows=None,
+                            attention_mask: Optional[torch.Tensor] = None) -> "ContinuationScores":
+        """Teacher-forced log-probabilities of continuations behind a cached prefix, without prefilling the prompt again.
+        `continuations`: a list of 1-D id sequences (ragged) or a right-padded LongTensor [R, n] with `attention_mask`.
+        `prefix_rows` [R]: the prefix row each continuation follows (repeats and any order; default: the identity when R equals
+        the prefix's row count).  Returns token_logprobs fp32 [R, n] = log p(c_j | prefix, c_<j) (0 at padding; c_0 is scored
+        from the prefix's last position), logprob [R] (row sums) and n_tokens [R].  Writes neither the KV cache nor the decode
+        state.  A stale handle or one of another context raises OpusError -6; n > max_prompt raises -2."""
+        cfg = self.cfg
+        if not isinstance(prefix, OpusPrefix):
+            raise TypeError("score_continuations() needs the OpusPrefix that cache_prefix() returned")
+        if isinstance(continuations, torch.Tensor):
+            ids = continuations.detach().cpu().long()
+            if ids.dim() != 2:
+                raise ValueError("continuations as a tensor must be [R, n] (right-padded)")
+            m = torch.ones_like(ids, dtype=torch.bool) if attention_mask is None else attention_mask.detach().cpu().bool()
+            if m.shape != ids.shape:
+                raise ValueError(f"attention_mask {tuple(m.shape)} does not match the continuations {tuple(ids.shape)}")
+            lens = m.sum(dim=1)
+            if (m != (torch.arange(ids.shape[1])[None, :] < lens[:, None])).any():
+                raise ValueError("continuations must be right-padded: the mask of a row is ones, then zeros")
+            ids = ids.masked_fill(~m, 0)
+        else:
+            rows = [torch.as_tensor(c, dtype=torch.long).reshape(-1).cpu() for c in continuations]
+            lens = torch.tensor([r.numel() for r in rows], dtype=torch.long)
+            ids = torch.zeros((len(rows), max([1] + lens.tolist())), dtype=torch.long)
+            for i, r in enumerate(rows):
+                ids[i, : r.numel()] = r
+            m = torch.arange(ids.shape[1])[None, :] < lens[:, None]
+        R, n = ids.shape
+        if R < 1:
+            raise ValueError("score_continuations() needs at least one continuation")
+        if n > cfg.max_prompt:
+            raise _cabi.OpusError(-2, f"score_continuations: continuations of {n} positions exceed max_prompt={cfg.max_prompt}")
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= cfg.dec_vocab):
+            raise ValueError(f"continuation ids must lie in [0, {cfg.dec_vocab})")
+        if prefix_rows is None:
+            if R != prefix.rows:
+                raise ValueError(f"{R} continuations for {prefix.rows} prefix rows: pass prefix_rows")
+            src = np.arange(R, dtype=np.int32)
+        else:
+            src = np.asarray(torch.as_tensor(prefix_rows).cpu(), dtype=np.int64).reshape(-1)
+            if src.shape[0] != R:
+                raise ValueError(f"prefix_rows has {src.shape[0]} entries for {R} continuations")
+            if src.size and (src.min() < 0 or src.max() >= prefix.rows):
+                raise ValueError(f"prefix_rows must lie in [0, {prefix.rows})")
+            src = src.astype(np.int32)
+        dev = self.device
+        lens_np = lens.numpy().astype(np.int32)
+        tgt = ids[m].to(torch.int32)                                       # compact: row-major over the real tokens
+        N = int(tgt.numel())
+        cc = _cabi.CConfig.from_config(cfg)
+        n_scratch = int(self._lib.opus_llama_score_scratch_bytes(C.byref(cc), R, n))
+        if n_scratch < 0:
+            raise _cabi.OpusError(-2, f"score_continuations: R={R} n={n}")
+        embeds = self.model.embed_tokens(ids.to(dev)).to(_cabi.operand_dtype()).contiguous()
+        s = self._enter()
+        with torch.cuda.stream(self._stream):
+            scratch = torch.empty((n_scratch,), dtype=torch.uint8, device=dev)
+            d_tgt = tgt.to(dev, non_blocking=True) if N else torch.zeros((1,), dtype=torch.int32, device=dev)
+            lp = torch.zeros((max(N, 1),), dtype=torch.float32, device=dev)
+            h_lens = (C.c_int32 * R)(*lens_np.tolist())
+            h_src = (C.c_int32 * R)(*src.tolist())
+            _cabi.check(self._lib.opus_llama_score_continuations(
+                self._ctx, embeds.data_ptr(), R, n, h_lens, h_src, prefix._last_rows.data_ptr(), prefix.rows, prefix._epoch,
+                d_tgt.data_ptr(), lp.data_ptr(), scratch.data_ptr(), n_scratch, s))
+            token_lp = torch.zeros((R, n), dtype=torch.float32, device=dev)
+            token_lp[m.to(dev)] = lp[:N]
+            logprob = token_lp.sum(dim=1)
+        self._leave()
+        return ContinuationScores(token_lp, logprob, lens.to(dev))
+
     # ------------------------------------------------------------------ parity taps (tests / bench)
     def prefill_logits(self, embeds: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
         B, T, _ = embeds.shape
@@ -738,6 +846,24 @@ def _check_forward_mask(m: np.ndarray, pos: Optional[np.ndarray]) -> None:
     elif (m.any(axis=1) & ~m[:, 0]).any():
         raise ValueError("left-padded rows need position_ids = cumsum(attention_mask) - 1: without them HF uses arange positions "
                          "and the result would differ; pass position_ids or right-pad the rows")
+
+
+class OpusPrefix:
+    """What cache_prefix() returns: a prompt batch prefilled into its context's KV cache.  `rows` prompts, `lengths` [rows] their
+    real token counts; the final residual row of every prompt's last position (fp32 [rows, hidden]) scores a continuation's first
+    token.  Valid until the next call on the context that prefills or permutes its cache (the epoch check of the native side)."""
+
+    def __init__(self, owner, epoch: int, last_rows: torch.Tensor, lengths: torch.Tensor):
+        self._owner, self._epoch, self._last_rows = owner, int(epoch), last_rows
+        self.rows = int(last_rows.shape[0])
+        self.lengths = lengths
+
+
+class ContinuationScores:
+    """What score_continuations() returns: token_logprobs fp32 [R, n] (0 at padding), logprob fp32 [R] (row sums), n_tokens [R]."""
+
+    def __init__(self, token_logprobs: torch.Tensor, logprob: torch.Tensor, n_tokens: torch.Tensor):
+        self.token_logprobs, self.logprob, self.n_tokens = token_logprobs, logprob, n_tokens
 
 
 class CausalLMOutput:
