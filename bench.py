@@ -9,8 +9,14 @@ Headline workload (`value`, every N): the per-GPU shard of BASELINE.json configs
 of 512 residues per GPU (batch 512 over 8 GPUs), 89-id prompt with one <seq> (96 decoder positions), 32 new tokens, greedy,
 fp16.  Every rank runs that shard on its own proteins with a full weight replica (weak scaling), exactly the reference's
 replica parallelism (eval/run_opus_ddp.py:77-79,138), so the N = 1 line is one shard and the 1 -> 8 curve is the configs[3]
-curve.  The latency configuration configs[1] (batch 1, one 512-residue protein; round 1's headline) is measured in the same
-process with the same rules and reported under "c2" in the same JSON line.
+curve.
+
+A plain run does only what that figure needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints the
+line.  Everything else the script measures runs only with --full, in the same process after the headline: the latency
+configuration configs[1] (batch 1, one 512-residue protein; round 1's headline, "c2"), the product entry point (`e2e`,
+`e2e_var_T`), two batches in flight, the roofline pass, the projector stage, the N > 1 rank diagnostics and the CPU
+baseline; the --no-* options leave parts of it out.  --dump-outputs writes the batch-1 ids as well, so a plain run that is
+given it also runs (and reports) the batch-1 steps.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself
 (python -m torch.distributed.run, rendezvous on 127.0.0.1) before anything touches a GPU; under a launcher it reads
@@ -74,6 +80,9 @@ def parse(argv=None):
     p.add_argument("--bucket", type=int, default=256, help="residues per length bucket with --mixed-lengths --padded-encoder")
     p.add_argument("--padded-encoder", action="store_true", help="A/B aid: the padded (length-bucketed) encoder of rounds 1-3 "
                                                                  "instead of the token-packed one")
+    p.add_argument("--full", action="store_true", help="after the headline, also run everything else the script measures (c2, e2e, "
+                                                        "e2e_var_T, two_in_flight, roofline, projector stage, rank diagnostics, "
+                                                        "CPU baseline); the --no-* options below leave parts of it out")
     p.add_argument("--no-c2", action="store_true", help="skip the batch-1 latency configuration (configs[1])")
     p.add_argument("--no-inflight", action="store_true", help="skip the two-batches-in-flight measurement (`two_in_flight`)")
     p.add_argument("--no-e2e", action="store_true", help="skip the strings-in -> ids-out measurement through model.generate (`e2e`)")
@@ -631,9 +640,10 @@ def main():
     cdev = dev if (backend == "nccl" and not dry) else torch.device("cpu")     # where collectives run
 
     B, N_new = a.batch, a.new_tokens
+    with_c2 = (a.full or bool(a.dump_outputs)) and not a.no_c2 and B != 1      # --dump-outputs writes c2_ids too
     if dry:
         main_work = DryWorkload(B, N_new, rank)
-        c2_work = None if a.no_c2 or B == 1 else DryWorkload(1, N_new, rank)
+        c2_work = DryWorkload(1, N_new, rank) if with_c2 else None
         cfg = model = None
     else:
         import opus_pllm_amd as opa
@@ -649,7 +659,7 @@ def main():
         torch.cuda.synchronize(dev)
         log(f"weights {weights.nbytes() / 1e9:.1f} GB resident")
         main_work = Workload(model, cfg, a, rank, B, lengths, dev)
-        c2_work = None if a.no_c2 or B == 1 else Workload(model, cfg, a, rank, 1, [a.residues], dev)
+        c2_work = Workload(model, cfg, a, rank, 1, [a.residues], dev) if with_c2 else None
 
     dt, main_ids = timed(main_work, a, world, rank, dev, dist, cdev, a.steps, a.warmup)
     dumps = {"ids": main_ids.cpu().clone()}      # (host copy now: later passes must not be able to touch it)
@@ -682,7 +692,7 @@ def main():
                      "value": world * a.steps / dt2, "unit": "proteins/s", "generated_tokens_per_sec": world * N_new * a.steps / dt2,
                      "ms_per_step": 1e3 * dt2 / a.steps, "steps": a.steps, "warmup": a.warmup}
 
-    if not dry and not a.no_e2e and world == 1:
+    if a.full and not dry and not a.no_e2e and world == 1:
         # the product call on strings + host prompt ids, same K / W, same fences: tokeniser, bucketing and H2D copies included
         e2e_work = E2EWorkload(main_work, cfg, rank)
         ref_ids = main_work.run()
@@ -696,16 +706,16 @@ def main():
                               "bucketing, host->device copies, encode, projectors, splice, prefill, decode, ids back as a LongTensor; "
                               "what the reference's entries/sec loop times per batch minus its text (de)tokeniser"}
 
-    if not dry and not a.no_var_t and world == 1 and B >= 8:
+    if a.full and not dry and not a.no_var_t and world == 1 and B >= 8:
         res["e2e_var_T"] = e2e_var_T(model, cfg, a, rank, main_work.lengths, dev)
         log(f"e2e_var_T: {res['e2e_var_T']['var_T']['ms_per_batch']:.2f} ms/batch (fixed T {res['e2e_var_T']['fixed_T']['ms_per_batch']:.2f}, "
             f"per-batch recapture {res['e2e_var_T']['var_T_recapture']['ms_per_batch']:.2f})")
 
-    if not dry and not a.no_inflight and world == 1 and a.steps >= 2:
+    if a.full and not dry and not a.no_inflight and world == 1 and a.steps >= 2:
         res["two_in_flight"] = two_in_flight(model, cfg, a, rank, main_work.lengths, dev, a.steps, a.warmup)
         log(f"two batches in flight: {res['two_in_flight']['ms_per_step']:.2f} ms/step")
 
-    if not dry and not a.no_roofline:
+    if a.full and not dry and not a.no_roofline:
         # every rank runs the (collective-free) measurement pass, rank 0 reports it
         r_main = roofline(model, main_work, dev)
         r_c2 = roofline(model, c2_work, dev) if c2_work is not None else None
@@ -717,12 +727,14 @@ def main():
             if r_proj is not None:
                 res["projector_stage"] = r_proj
     if world > 1 or FORCE_COLLECTIVE:
-        diag = rank_diagnostics(main_work, world, rank, dev, dist, cdev)
+        if a.full:
+            diag = rank_diagnostics(main_work, world, rank, dev, dist, cdev)
+            if rank == 0:
+                res["ranks"] = diag
         if rank == 0:
-            res["ranks"] = diag
             res["collective_backend"] = backend
         dist.barrier()
-    if rank == 0 and world == 1 and not dry and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not dry and not a.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(cfg, main_work.lengths[0], main_work.n_text, N_new, B)
     if rank == 0 and a.dump_outputs:
         dump_outputs(a.dump_outputs, dumps)

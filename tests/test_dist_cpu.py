@@ -85,7 +85,7 @@ def test_bench_gpus2_starts_two_ranks_by_itself():
     census - and rank 0 prints ONE line with n_gpus = 2.  OPUS_BENCH_DRYRUN replaces the model by a stub (no GPU in this
     container): what is covered is the launch / collective plumbing that deadlocked in round 1's review."""
     import json
-    r = _run_bench(["--gpus", "2", "--batch", "3", "--steps", "2", "--warmup", "1", "--new-tokens", "4"],
+    r = _run_bench(["--gpus", "2", "--batch", "3", "--steps", "2", "--warmup", "1", "--new-tokens", "4", "--full"],
                    {"OPUS_BENCH_DRYRUN": "1", "OPUS_BENCH_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -103,7 +103,7 @@ def test_bench_gpus8_plumbing_dry_run():
     """The driver's N = 8 line, plumbing only (8 CPU ranks, gloo, stub workload): self-launch, rendezvous, the sequence of
     collectives of both workloads, the per-rank diagnostics and ONE JSON line with n_gpus = 8."""
     import json
-    r = _run_bench(["--gpus", "8", "--batch", "2", "--steps", "2", "--warmup", "1", "--new-tokens", "3"],
+    r = _run_bench(["--gpus", "8", "--batch", "2", "--steps", "2", "--warmup", "1", "--new-tokens", "3", "--full"],
                    {"OPUS_BENCH_DRYRUN": "1", "OPUS_BENCH_BACKEND": "gloo"}, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -113,6 +113,21 @@ def test_bench_gpus8_plumbing_dry_run():
     assert abs(d["value"] - 8 * 2 * 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
     assert d["ranks"]["rank_census"] == list(range(8))
     assert set(d["ranks"]["path_ms_per_rank"]) == {"min", "median", "max", "slowest_rank"}
+
+
+def test_bench_plain_run_measures_the_headline_only():
+    """Without --full a run times the headline steps and prints their line: no batch-1 sub-run and no rank diagnostics
+    (--full and the tests above have them)."""
+    import json
+    r = _run_bench(["--gpus", "2", "--batch", "3", "--steps", "2", "--warmup", "1", "--new-tokens", "4"],
+                   {"OPUS_BENCH_DRYRUN": "1", "OPUS_BENCH_BACKEND": "gloo"})
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["steps"] == 2 and d["warmup"] == 1 and d["collective_backend"] == "gloo"
+    assert abs(d["value"] - 2 * 3 * 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
+    assert "c2" not in d and "ranks" not in d and "batch 1" not in r.stderr, d
 
 
 def test_bench_refuses_a_world_size_that_contradicts_gpus():

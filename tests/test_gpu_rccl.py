@@ -33,7 +33,7 @@ def test_bench_timed_region_through_rccl_collectives():
     """bench.py at N = 1 with the collective path forced: the same statements rank 0 of the driver's 8-GPU run executes (a small
     model: what is exercised is the plumbing, not the kernels)."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--model", "c1_tiny", "--batch", "4",
-           "--residues", "64", "--new-tokens", "8", "--no-c2", "--no-inflight", "--no-e2e", "--no-var-t", "--no-cpu-baseline", "--no-roofline"]
+           "--residues", "64", "--new-tokens", "8", "--full", "--no-c2", "--no-inflight", "--no-e2e", "--no-var-t", "--no-cpu-baseline", "--no-roofline"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=_env(OPUS_BENCH_FORCE_COLLECTIVE="1"), timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

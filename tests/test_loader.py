@@ -292,16 +292,16 @@ def test_two_stage_eval_loop_projects_the_shard_once(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_gpus2_on_one_gpu_with_gloo():
-    """`python bench.py --gpus 2` with no launcher and OPUS_BENCH_BACKEND=gloo on a one-GPU box: two ranks share the card,
-    run the real path (C1-size model), gather their ids, and rank 0 prints one line with n_gpus = 2, a roofline block and the
-    batch-1 sub-run.  (Round 1's script ran a single rank here and would have deadlocked under a real launcher.)"""
+    """`python bench.py --gpus 2 --full` with no launcher and OPUS_BENCH_BACKEND=gloo on a one-GPU box: two ranks share the
+    card, run the real path (C1-size model), gather their ids, and rank 0 prints one line with n_gpus = 2, a roofline block and
+    the batch-1 sub-run.  (Round 1's script ran a single rank here and would have deadlocked under a real launcher.)"""
     import subprocess
     import sys
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["OPUS_BENCH_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(here, "bench.py"), "--gpus", "2", "--model", "c1_tiny", "--batch", "4",
-                        "--residues", "96", "--new-tokens", "8", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+                        "--residues", "96", "--new-tokens", "8", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -310,6 +310,28 @@ def test_bench_gpus2_on_one_gpu_with_gloo():
     assert d["n_gpus"] == 2 and d["config"]["batch_per_gpu"] == 4 and "invalid" not in d
     assert d["value"] > 0 and d["c2"]["value"] > 0
     assert d["roofline"]["frac"] > 0 and set(d["roofline"]["phases"]) >= {"encode", "project", "prefill", "decode"}
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_on_the_gpu(tmp_path):
+    """`python bench.py` without --full on the real path (C1-size model): the headline line alone - none of the measurements
+    --full adds - and --dump-outputs still writes the ids of both workloads (the batch-1 steps run for that)."""
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(here, "bench.py"), "--gpus", "1", "--model", "c1_tiny", "--batch", "8",
+                        "--residues", "96", "--new-tokens", "8", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["steps"] == 3 and d["warmup"] == 1 and "invalid" not in d
+    assert not set(d) & {"e2e", "e2e_var_T", "two_in_flight", "roofline", "projector_stage", "cpu_baseline", "ranks"}, sorted(d)
+    assert d["c2"]["steps"] == 3 and d["dumped_outputs"]["arrays"] == ["c2_ids", "ids"]
+    assert np.load(out / "ids.npy").shape == (8, 8) and np.load(out / "c2_ids.npy").shape == (1, 8)
 
 
 def test_opt_and_qwen_state_dict_mappings_roundtrip():

@@ -11,7 +11,7 @@ show() { python3 -c "
 import json,sys
 d=json.load(open(sys.argv[1])); r=d['roofline']
 print(sys.argv[2], 'ms/step', round(d['ms_per_step'],2), 'decode', round(r['phases']['decode']['kernel_ms'],1), {k:round(v,1) for k,v in r['kernel_ms_per_step'].items() if k in ('gemm_stream','gemm_wide','attn_decode')})" $1 "$2"; }
-B="--no-c2 --no-inflight --no-cpu-baseline --no-e2e --no-var-t"
+B="--full --no-c2 --no-inflight --no-cpu-baseline --no-e2e --no-var-t"
 echo "== parity of the forced plans (stream GEMM tests)" 
 for v in 1 2; do OPUS_KNOB_MISC1=$v python3 -m pytest tests/test_gpu_batch64.py -q -m gpu -k "stream_gemm or decode_step_agrees" 2>&1 | tail -1; done
 echo "== isolated narrow GEMMs, 64 rows (tools/bench_gemm.py narrow)"

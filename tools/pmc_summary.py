@@ -9,7 +9,7 @@ Write pass: --pmc WRITE_SIZE                                 (KiB, exact for 16-
 gfx950 correction (MI355X_MICROARCH.md "HBM"): the read-request counter tallies the 128-B requests of a
 wide coalesced stream at 64 B, i.e. FETCH_SIZE reads exactly half of the bytes -> bytes = requests * 128
 for the non-32B requests.
-With bench.json (the line of `bench.py --steps 1 --warmup 0 --no-c2`, whose roofline block lists the ALGORITHMIC bytes of
+With bench.json (the line of `bench.py --full --steps 1 --warmup 0 --no-c2`, whose roofline block lists the ALGORITHMIC bytes of
 every kernel class: weights once + activations + outputs, api.cpp gemm_any / attn_decode) the summary also gives, per
 kernel class, counter bytes / algorithmic bytes - the over-fetch beyond L2 that a reader otherwise works out by hand.
 """
