@@ -202,6 +202,24 @@ int64_t opus_llama_score_scratch_bytes(const opus_config *cfg, int32_t R, int32_
  * without a prefill. */
 int opus_debug_attn_prefix(opus_ctx *ctx, const void *d_qkv, const void *d_k_hist, const void *d_v_hist, const int32_t *d_kstart,
                            int32_t P, int32_t Tp, int32_t R, int32_t n, const int32_t *h_src, void *d_out, void *stream);
+/* ESM-2 contact maps (EsmContactPredictionHead / fair-esm return_contacts=True) beside the per-residue states, on the token-packed
+ * encoder: the same arguments and pooled output as opus_esm2_encode_packed, then d_contacts fp32 receives protein b's [n_b, n_b]
+ * map (n_b = cu[b + 1] - cu[b] - 2 residues, row-major) at element offset sum_{b' < b} n_{b'}^2.  Needs the optional weights
+ * "enc.contact.weight" fp32 [enc_layers * enc_heads] (channel l * enc_heads + h) and "enc.contact.bias" fp32 [1] (OPUS_ESTATE
+ * names the missing one).  d_scratch (256-byte aligned) holds opus_esm2_contacts_scratch_bytes(cfg, h_cu, B) bytes: the context's
+ * workspace does not grow.  opus_esm2_last_hidden afterwards returns every residue row.  Phase "encode", kernel class "contact". */
+int opus_esm2_contacts_packed(opus_ctx *ctx, const int32_t *d_tokens, const int32_t *h_cu, int32_t B, float *d_pooled, float *d_contacts,
+                              void *d_scratch, int64_t scratch_bytes, void *stream);
+/* Scratch bytes of opus_esm2_contacts_packed for these proteins (about 4 sum n^2 + 4 sum n * layers * heads); -1 on bad arguments. */
+int64_t opus_esm2_contacts_scratch_bytes(const opus_config *cfg, const int32_t *h_cu, int32_t B);
+/* Diagnostic: one layer's contact accumulation alone.  d_q / d_k: operand-dtype rows of stride ld elements, head h at column
+ * h * head_dim (q already scaled, both rotated), token-packed proteins h_cu[B + 1] (host, at least 2 tokens each).  Over the
+ * interior positions (tokens 1 .. n_b) of P_h = softmax over all of the protein's keys of q k^T: d_A [sum n_b^2] =
+ * sum_h d_w[h] P_h (packed as in opus_esm2_contacts_packed), d_rows / d_cols [sum n_b][heads] the interior row / column sums of
+ * P_h (protein b's rows from cu[b] - 2 b).  d_scratch: 256 + 4 (B + 1) + 4 heads sum_b ceil(n_b / 64) n_b bytes or more. */
+int opus_debug_contacts(opus_ctx *ctx, const void *d_q, const void *d_k, int64_t ld, const int32_t *h_cu, int32_t B, int32_t heads,
+                        int32_t head_dim, const float *d_w, float *d_A, float *d_rows, float *d_cols, void *d_scratch,
+                        int64_t scratch_bytes, void *stream);
 /* Diagnostic: the NLL kernel alone.  Per row of operand-dtype logits [R, V] (row-major): d_lse[r] = logsumexp (fp32, d_lse may
  * be NULL) and d_logprob[r] = l[y] - lse with y = d_targets[r] (y < 0: 0; y >= V: NaN). */
 int opus_debug_xent(opus_ctx *ctx, const void *d_logits, int32_t R, int32_t V, const int32_t *d_targets, float *d_logprob,
@@ -332,7 +350,9 @@ int64_t opus_stat(opus_ctx *ctx, const char *name);
  * hipGraph) every kernel launch of the path is recorded with its own dispatch start / end events on the launch stream
  * (hipExtLaunchKernelGGL - the interval rocprofv3 --kernel-trace reports), its kernel class, the phase of the path it
  * belongs to, and its ALGORITHMIC bytes and FLOPs.  opus_timing_get sums the records since the last reset that match
- * kernel_class and phase ("*" = any); opus_timing_names returns "class,class,...;phase,phase,..." . */
+ * kernel_class and phase ("*" = any); opus_timing_names returns "class,class,...;phase,phase,..." .  Classes and phases are
+ * addressed by name, never by position.  Order of the lists: phases are append-only ("score" last); among the classes "xent"
+ * stays the last entry, as published since opus_llama_forward, and a class added later ("contact") is listed in front of it. */
 int opus_timing_enable(opus_ctx *ctx, int32_t on);
 int opus_timing_reset(opus_ctx *ctx);
 int opus_timing_get(opus_ctx *ctx, const char *kernel_class, const char *phase, double *ms, int64_t *launches, double *bytes,

@@ -10,7 +10,9 @@ the canonical tensor names of synth.py and handed to DeviceWeights (fuse, LoRA-m
   4. CSTP encoding adapter  <adapter>/modality_encoder/modality_encoding_adapter.ckpt, Lightning ckpt holding
                             protein_projection.linear.{weight,bias} (protein_projector/builder.py:15-25)
 plus the ESM-2 checkpoint the reference pulls from the fair_esm hub cache (cstp_v3/modelling.py:21),
-looked up in $OPUS_ESM2_CKPT or ~/.cache/torch/hub/checkpoints/esm2_t33_650M_UR50D.pt.
+looked up in $OPUS_ESM2_CKPT or ~/.cache/torch/hub/checkpoints/esm2_t33_650M_UR50D.pt, and its contact regression (optional:
+get_amino_acid_embeddings(return_contacts=True)) from $OPUS_ESM2_CONTACT_CKPT, the checkpoint itself, or fair-esm's sibling file
+<checkpoint stem>-contact-regression.pt (load_esm2_contact_head).
 No network access is attempted: a missing artefact raises FileNotFoundError naming it.
 
 Offline / benchmark use: model_base_path = "synthetic:<preset>" (llama3_8b, vicuna_13b, c1_tiny, micro)
@@ -195,6 +197,21 @@ def canonical_from_esm2(sd: Dict[str, torch.Tensor], cfg: OpusConfig) -> Dict[st
     return out
 
 
+def contact_head_from_esm2(sd: Dict[str, torch.Tensor]) -> Optional[Dict[str, torch.Tensor]]:
+    """fair_esm ESM2 state dict -> the contact regression (contact_head.regression, fp32 weight [layers * heads], bias [1]) under
+    the canonical names enc.contact.{weight,bias}, or None when the checkpoint has no contact head."""
+    def strip(k):
+        for p in ("encoder.sentence_encoder.", "encoder.", "sentence_encoder."):
+            if k.startswith(p):
+                return k[len(p):]
+        return k
+    sd = {strip(k): v for k, v in sd.items()}
+    w, b = sd.get("contact_head.regression.weight"), sd.get("contact_head.regression.bias")
+    if w is None or b is None:
+        return None
+    return {"enc.contact.weight": w.float().reshape(-1), "enc.contact.bias": b.float().reshape(1)}
+
+
 def canonical_from_cstp(ckpt: dict) -> Dict[str, torch.Tensor]:
     sd = ckpt.get("state_dict", ckpt)
     return {"proj.weight": sd["protein_projection.linear.weight"], "proj.bias": sd["protein_projection.linear.bias"]}
@@ -248,6 +265,37 @@ def _esm2_ckpt_path() -> str:
         raise FileNotFoundError(f"ESM-2 checkpoint not found at {p}: set OPUS_ESM2_CKPT (the reference downloads it through "
                                 "esm.pretrained.esm2_t33_650M_UR50D(), cstp_v3/modelling.py:21; no download is attempted here)")
     return p
+
+
+def esm2_contact_ckpt_path(ckpt_path: str) -> Optional[str]:
+    """Where the contact regression of the ESM-2 checkpoint `ckpt_path` lives, if anywhere: the file OPUS_ESM2_CONTACT_CKPT names,
+    else fair-esm's sibling file <checkpoint stem>-contact-regression.pt (fair-esm's pretrained loaders fetch and keep it beside the
+    model file - the hub cache holds esm2_t33_650M_UR50D.pt and esm2_t33_650M_UR50D-contact-regression.pt - and merge its 'model'
+    entry into the state dict at load time), else None."""
+    p = os.environ.get("OPUS_ESM2_CONTACT_CKPT")
+    if p:
+        if not os.path.exists(p):
+            raise FileNotFoundError(f"OPUS_ESM2_CONTACT_CKPT={p} does not exist")
+        return p
+    sib = os.path.splitext(ckpt_path)[0] + "-contact-regression.pt"
+    return sib if os.path.exists(sib) else None
+
+
+def load_esm2_contact_head(ckpt_path: str, esm_sd: Dict[str, torch.Tensor]) -> Optional[Dict[str, torch.Tensor]]:
+    """The contact head for the ESM-2 checkpoint at `ckpt_path` (state dict `esm_sd`), as fair-esm assembles it: the file
+    OPUS_ESM2_CONTACT_CKPT names when set, else the checkpoint's own contact_head.regression.*, else the sibling
+    <stem>-contact-regression.pt; None when there is none (get_amino_acid_embeddings(return_contacts=True) then raises).  A
+    regression file without the two tensors raises ValueError."""
+    explicit = bool(os.environ.get("OPUS_ESM2_CONTACT_CKPT"))
+    head = None if explicit else contact_head_from_esm2(esm_sd)
+    if head is None:
+        p = esm2_contact_ckpt_path(ckpt_path)
+        if p is not None:
+            reg = torch.load(p, map_location="cpu", weights_only=False)
+            head = contact_head_from_esm2(reg.get("model", reg))
+            if head is None:
+                raise ValueError(f"{p} holds no contact_head.regression.{{weight,bias}}")
+    return head
 
 
 # ------------------------------------------------------------------------------------------------ entry point
@@ -340,8 +388,12 @@ def load_pretrained_model(model_base_path, adapter_path, model_name, load_8bit=F
     elif cstp_path is not None:
         raise ValueError("cstp_path must be the path of modality_encoding_adapter.ckpt, or None for the identity protein "
                          "projector (the reference's default `True` is a placeholder its own loader cannot open)")
-    esm = torch.load(_esm2_ckpt_path(), map_location="cpu", weights_only=False)
+    esm_path = _esm2_ckpt_path()
+    esm = torch.load(esm_path, map_location="cpu", weights_only=False)
     canon.update(canonical_from_esm2(esm.get("model", esm), cfg))
+    head = load_esm2_contact_head(esm_path, esm.get("model", esm))
+    if head is not None:
+        canon.update(head)          # (bound beside the fused tensors: get_amino_acid_embeddings(return_contacts=True))
     weights = DeviceWeights.from_canonical(cfg, canon, device, lora=lora)
     eos = resolve_eos_token_id(hf_cfg, tokenizer.eos_token_id, model_base_path)
     model = OpusLlamaForCausalLM(cfg, weights, device, eos_token_id=eos, pad_token_id=tokenizer.pad_token_id)

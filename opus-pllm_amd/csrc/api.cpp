@@ -657,8 +657,33 @@ extern "C" int opus_tile_weight(const void *d_src, void *d_dst, int64_t N, int64
 // offsets, T the longest protein - the GEMMs multiply no padding and a batch of mixed lengths is ONE set of large launches
 // instead of one per length bucket; positions come from a row -> position table (written by the embedding kernel), the attention
 // takes its rows from cu.
+// Contact maps riding along the packed encoder (opus_esm2_contacts_packed): the regression head and the caller-scratch buffers
+// (contact.hip's layouts), n_max = the longest protein's interior length.
+struct ContactRun {
+    const float *w, *bias;
+    float *A, *vec, *part, *sw, *out;
+    int n_max;
+};
+
+static int contact_layer(opus_ctx *c, hipStream_t s, const ContactRun &ct, int l, int B) {
+    const opus_config &g = c->cfg;
+    const int D = g.enc_dim, nh = g.enc_heads, hd = D / nh, C = g.enc_layers * nh;
+    ContactParams p;
+    p.Q = c->e_qkv; p.K = c->e_qkv + D; p.ld = 3 * D; p.cu = c->e_cu; p.B = B; p.heads = nh; p.w = ct.w + l * nh;
+    p.A = ct.A; p.accumulate = l > 0; p.rows = ct.vec; p.vld = C; p.c0 = l * nh; p.part = ct.part;
+    double n2 = 0.0, nt = 0.0;                                       // (interior n^2, all-key T n per protein)
+    for (int b = 0; b < B; ++b) {
+        const double n = c->h_cu[b + 1] - c->h_cu[b] - 2, t = n + 2;
+        if (n > 0) { n2 += n * n; nt += n * t; }
+    }
+    // two Q K^T passes over every head; bytes: the A tile read-modify-write + Q / K once
+    KLF(KC_CONTACT, 8.0 * n2 + 4.0 * (c->h_cu[B]) * D, 2.0 * 2.0 * nt * hd * nh, launch_esm_contact_accum(p, hd, ct.n_max, s));
+    KL(KC_CONTACT, 4.0 * n2 / 64.0 * nh * 2.0, launch_esm_contact_colsum(ct.part, c->e_cu, B, nh, ct.n_max, ct.vec, C, l * nh, 1, s));
+    return OPUS_OK;
+}
+
 static int esm2_encode_rows(opus_ctx *c, hipStream_t s, const int32_t *d_tokens, const int32_t *d_lens, const int32_t *d_cu, int B, int T,
-                            int M, float *d_pooled) {
+                            int M, float *d_pooled, const ContactRun *ct = nullptr) {
     const opus_config &g = c->cfg;
     c->phase = PH_ENCODE;
     const int D = g.enc_dim, F = g.enc_ffn, nh = g.enc_heads, hd = D / nh;
@@ -700,6 +725,7 @@ static int esm2_encode_rows(opus_ctx *c, hipStream_t s, const int32_t *d_tokens,
             if (packed) KL(KC_OTHER, 8.0 * M * D, launch_esm_rope(c->e_qkv, c->cs_enc, 1, M, nh, hd, 1.0f / sqrtf((float)hd), s, c->e_pos));
             else KL(KC_OTHER, 8.0 * M * D, launch_esm_rope(c->e_qkv, c->cs_enc, B, T, nh, hd, 1.0f / sqrtf((float)hd), s));
         }
+        if (ct) OPC(contact_layer(c, s, *ct, l, B));                 // (e_qkv: q scaled and rotated, k rotated, every token row)
         AttnParams a;
         a.Q = c->e_qkv; a.K = c->e_qkv + D; a.V = c->e_qkv + 2 * D;
         a.q_sb = a.k_sb = a.v_sb = packed ? 0 : (int64_t)T * 3 * D;
@@ -726,6 +752,14 @@ static int esm2_encode_rows(opus_ctx *c, hipStream_t s, const int32_t *d_tokens,
     KL(KC_NORM, 8.0 * M * D, launch_layernorm(c->e_x, c->enc_lnfw, c->enc_lnfb, g.enc_ln_eps, M, D, nullptr, c->e_hid, s));
     if (packed) KL(KC_OTHER, 4.0 * M * D, launch_masked_mean_packed(c->e_hid, d_cu, B, D, d_pooled, s));
     else KL(KC_OTHER, 4.0 * M * D, launch_masked_mean(c->e_hid, d_lens, B, T, D, d_pooled, s));
+    if (ct) {
+        const int C = g.enc_layers * nh;
+        double n2 = 0.0, ni = 0.0;
+        for (int b = 0; b < B; ++b) { const double n = c->h_cu[b + 1] - c->h_cu[b] - 2; n2 += n * n; ni += n; }
+        KL(KC_CONTACT, 4.0 * ni * C, launch_esm_contact_scale(ct->vec, d_cu, B, C, ct->w, ct->sw, s));
+        KLF(KC_CONTACT, 12.0 * n2 + 8.0 * ni * C * cdiv((int64_t)ct->n_max, 64), 2.0 * n2 * C,
+            launch_esm_contact_finish(ct->A, ct->vec, ct->sw, d_cu, B, C, ct->n_max, ct->bias, ct->out, s));
+    }
     return OPUS_OK;
 }
 
@@ -759,6 +793,105 @@ extern "C" int opus_esm2_encode_packed(opus_ctx *c, const int32_t *d_tokens, con
     c->h_cu.assign(h_cu, h_cu + B + 1);                              // (host copy: per-protein FLOP accounting of the timing records)
     HIPC(launch_upload_i32(h_cu, B + 1, c->e_cu, s));                 // through the kernel arguments: no host buffer outlives the call
     return esm2_encode_rows(c, s, d_tokens, nullptr, c->e_cu, B, Tmax, (int)M, d_pooled);
+}
+
+// ------------------------------------------------------------------------------------------------ contact maps
+// Caller scratch of opus_esm2_contacts_packed (contact.hip layouts): A [sum n^2] | vec [sum n][C] | part [H sum cdiv(n, 64) n] |
+// sw [B][C] fp32, each 256-byte aligned.  n = tokens - 2 per protein.
+struct ContactScratch {
+    int64_t a, vec, part, sw, total;
+    int n_max;
+};
+static ContactScratch contact_scratch(const opus_config &g, const int32_t *h_cu, int B) {
+    ContactScratch z{};
+    const int64_t C = (int64_t)g.enc_layers * g.enc_heads;
+    int64_t n2 = 0, ni = 0, pq = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t n = std::max<int64_t>(h_cu[b + 1] - h_cu[b] - 2, 0);
+        n2 += n * n; ni += n; pq += (n + 63) / 64 * n;
+        z.n_max = std::max<int>(z.n_max, (int)n);
+    }
+    z.a = 0;
+    z.vec = z.a + (int64_t)align_up((size_t)n2 * 4);
+    z.part = z.vec + (int64_t)align_up((size_t)(ni * C) * 4);
+    z.sw = z.part + (int64_t)align_up((size_t)(pq * g.enc_heads) * 4);
+    z.total = z.sw + (int64_t)align_up((size_t)(B * C) * 4);
+    return z;
+}
+
+static int check_packed_cu(const opus_config &g, const int32_t *h_cu, int B, const char *who) {
+    if (B < 1 || B > g.max_batch) return fail(OPUS_ESHAPE, "%s: B=%d exceeds max_batch=%d", who, B, g.max_batch);
+    if (h_cu[0] != 0) return fail(OPUS_EBADARG, "%s: cu[0] must be 0", who);
+    for (int b = 0; b < B; ++b) {
+        const int t = h_cu[b + 1] - h_cu[b];
+        if (t < 2 || t > g.max_enc_tokens)
+            return fail(OPUS_ESHAPE, "%s: protein %d has %d tokens (2 .. max_enc_tokens=%d)", who, b, t, g.max_enc_tokens);
+    }
+    if (h_cu[B] > (int64_t)g.max_batch * g.max_enc_tokens) return fail(OPUS_ESHAPE, "%s: %d tokens exceed the workspace", who, h_cu[B]);
+    return OPUS_OK;
+}
+
+extern "C" int64_t opus_esm2_contacts_scratch_bytes(const opus_config *cfg, const int32_t *h_cu, int32_t B) {
+    if (!cfg || !h_cu || check_cfg(cfg) != OPUS_OK || check_packed_cu(*cfg, h_cu, B, "esm2_contacts_scratch_bytes") != OPUS_OK) return -1;
+    return contact_scratch(*cfg, h_cu, B).total;
+}
+
+extern "C" int opus_esm2_contacts_packed(opus_ctx *c, const int32_t *d_tokens, const int32_t *h_cu, int32_t B, float *d_pooled,
+                                         float *d_contacts, void *d_scratch, int64_t scratch_bytes, void *stream) {
+    OPC(need_ready(c));
+    if (!d_tokens || !h_cu || !d_pooled || !d_contacts || !d_scratch) return fail(OPUS_EBADARG, "esm2_contacts_packed: null pointer");
+    const opus_config &g = c->cfg;
+    OPC(check_packed_cu(g, h_cu, B, "esm2_contacts_packed"));
+    const int64_t C = (int64_t)g.enc_layers * g.enc_heads;
+    ContactRun ct;
+    GW("enc.contact.weight", OPUS_F32, (std::vector<int64_t>{C}), ct.w);
+    GW("enc.contact.bias", OPUS_F32, (std::vector<int64_t>{1}), ct.bias);
+    const ContactScratch z = contact_scratch(g, h_cu, B);
+    if (scratch_bytes < z.total)
+        return fail(OPUS_ESHAPE, "esm2_contacts_packed: scratch of %lld bytes, %lld needed", (long long)scratch_bytes, (long long)z.total);
+    if (((uintptr_t)d_scratch) & 255) return fail(OPUS_EBADARG, "esm2_contacts_packed: scratch must be 256-byte aligned");
+    char *base = (char *)d_scratch;
+    ct.A = (float *)(base + z.a); ct.vec = (float *)(base + z.vec); ct.part = (float *)(base + z.part); ct.sw = (float *)(base + z.sw);
+    ct.out = d_contacts;
+    ct.n_max = z.n_max;
+    int Tmax = 0;
+    for (int b = 0; b < B; ++b) Tmax = std::max(Tmax, h_cu[b + 1] - h_cu[b]);
+    hipStream_t s = (hipStream_t)stream;
+    c->h_cu.assign(h_cu, h_cu + B + 1);
+    HIPC(launch_upload_i32(h_cu, B + 1, c->e_cu, s));
+    return esm2_encode_rows(c, s, d_tokens, nullptr, c->e_cu, B, Tmax, h_cu[B], d_pooled, &ct);
+}
+
+extern "C" int opus_debug_contacts(opus_ctx *c, const void *d_q, const void *d_k, int64_t ld, const int32_t *h_cu, int32_t B,
+                                   int32_t heads, int32_t head_dim, const float *d_w, float *d_A, float *d_rows, float *d_cols,
+                                   void *d_scratch, int64_t scratch_bytes, void *stream) {
+    if (!c || !d_q || !d_k || !h_cu || !d_w || !d_A || !d_rows || !d_cols || !d_scratch) return fail(OPUS_EBADARG, "debug_contacts: null pointer");
+    if (B < 1 || B > 4096 || heads < 1 || (head_dim != 16 && head_dim != 32 && head_dim != 64 && head_dim != 128) || ld < (int64_t)heads * head_dim ||
+        (ld & 7) || (((uintptr_t)d_q | (uintptr_t)d_k) & 15))
+        return fail(OPUS_ESHAPE, "debug_contacts: B=%d heads=%d head_dim=%d ld=%lld", B, heads, head_dim, (long long)ld);
+    if (contact_accum_lds(heads) > 160 * 1024) return fail(OPUS_ESHAPE, "debug_contacts: %d heads exceed the workgroup's LDS", heads);
+    if (h_cu[0] != 0) return fail(OPUS_EBADARG, "debug_contacts: cu[0] must be 0");
+    int64_t pq = 0;
+    int n_max = 0;
+    for (int b = 0; b < B; ++b) {
+        const int t = h_cu[b + 1] - h_cu[b];
+        if (t < 2) return fail(OPUS_ESHAPE, "debug_contacts: protein %d has %d tokens (at least 2)", b, t);
+        pq += (int64_t)(t - 2 + 63) / 64 * (t - 2);
+        n_max = std::max(n_max, t - 2);
+    }
+    const int64_t need = (int64_t)align_up((size_t)(B + 1) * 4) + pq * heads * 4;
+    if (scratch_bytes < need) return fail(OPUS_ESHAPE, "debug_contacts: scratch of %lld bytes, %lld needed", (long long)scratch_bytes, (long long)need);
+    HIPC(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    int32_t *d_cu = (int32_t *)d_scratch;
+    float *part = (float *)((char *)d_scratch + align_up((size_t)(B + 1) * 4));
+    HIPC(launch_upload_i32(h_cu, B + 1, d_cu, s));
+    ContactParams p;
+    p.Q = (const half_t *)d_q; p.K = (const half_t *)d_k; p.ld = ld; p.cu = d_cu; p.B = B; p.heads = heads; p.w = d_w;
+    p.A = d_A; p.accumulate = 0; p.rows = d_rows; p.vld = heads; p.c0 = 0; p.part = part;
+    HIPC(launch_esm_contact_accum(p, head_dim, n_max, s));
+    HIPC(launch_esm_contact_colsum(part, d_cu, B, heads, n_max, d_cols, heads, 0, 0, s));
+    return OPUS_OK;
 }
 
 extern "C" int opus_esm2_last_hidden(opus_ctx *c, float *d_out, int32_t B, int32_t T, void *stream) {
@@ -1998,7 +2131,7 @@ extern "C" int opus_timing_reset(opus_ctx *c) {
     return OPUS_OK;
 }
 static const char *kclass_names[KC_COUNT] = {"gemm_skinny", "gemm_mid", "gemm_wide", "gemm_ring", "gemm_pp", "gemm_tile", "splitk_reduce",
-                                            "attn_prefill", "attn_decode", "norm", "other", "gemm_stream", "xent"};
+                                            "attn_prefill", "attn_decode", "norm", "other", "gemm_stream", "contact", "xent"};
 static const char *phase_names[PH_COUNT] = {"encode", "project", "splice", "prefill", "decode", "other", "score"};
 
 extern "C" int opus_timing_get(opus_ctx *c, const char *kernel_class, const char *phase, double *ms, int64_t *launches,

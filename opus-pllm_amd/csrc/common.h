@@ -52,7 +52,9 @@ int skinny_max_m();   // rows up to which the skinny kernel is used (default 4, 
 constexpr int MID_MAX_M = 64;   // (65..128 rows measured faster on the split-K tile kernel)
 // kernel classes of the per-launch timing (opus_timing_get): one per kernel family
 enum KClass { KC_SKINNY = 0, KC_MID, KC_WIDE, KC_RING, KC_PP, KC_TILE, KC_REDUCE, KC_ATTN_PREFILL, KC_ATTN_DECODE, KC_NORM,
-              KC_OTHER, KC_STREAM, KC_XENT, KC_COUNT };
+              KC_OTHER, KC_STREAM, KC_CONTACT, KC_XENT, KC_COUNT };
+// Ordering rule of the published class list (opus_timing_names, include/opus_pllm.h): "xent" stays its last entry, as published
+// since opus_llama_forward, and a class added later goes in front of it.  Classes are looked up by name, never by index.
 // phases of the path a launch belongs to (set by the entry points of api.cpp)
 enum Phase { PH_ENCODE = 0, PH_PROJECT, PH_SPLICE, PH_PREFILL, PH_DECODE, PH_OTHER, PH_SCORE, PH_COUNT };
 
@@ -271,6 +273,32 @@ struct AttnPrefixParams {
 int attn_prefix_blocks(const int32_t *off, int P, int G, int n, int32_t *blocks);
 int attn_prefix_max_blocks(int R, int P, int G, int n);   // an upper bound of that count for R rows over P prefix rows
 hipError_t launch_attn_prefix(const AttnPrefixParams &p, int nblocks, hipStream_t s);
+
+// contact.hip: ESM-2 contact maps (opus_esm2_contacts_packed).  One layer's accumulation over token-packed proteins cu[B + 1]
+// (rows <cls> residues <eos>): Q / K rows of stride ld (head h at column h hd; q scaled and both rotated as the attention takes
+// them); A[sum n_b^2] (+)= sum_h w[h] P_h over the interior positions, rows[(cu[b] - 2 b + i) vld + c0 + h] = interior row sums
+// of P_h, part = the column-sum partials that launch_esm_contact_colsum reduces into the same layout (add: += instead of =).
+struct ContactParams {
+    const half_t *Q, *K;
+    int64_t ld;
+    const int32_t *cu;
+    int B, heads;
+    const float *w;
+    float *A;
+    int accumulate;
+    float *rows;
+    int64_t vld;
+    int c0;
+    float *part;
+};
+size_t contact_accum_lds(int heads);
+hipError_t launch_esm_contact_accum(const ContactParams &p, int head_dim, int max_n, hipStream_t s);   // max_n: longest n_b
+hipError_t launch_esm_contact_colsum(const float *part, const int32_t *cu, int B, int heads, int max_n, float *vec, int64_t vld, int c0,
+                                     int add, hipStream_t s);
+// sw[b][c] = w[c] / sum_i vec[i][c] over protein b's rows; then out = sigmoid(bias + A + A^T - sum_c sw_c a_c a_c^T) (vec [.][C] = a)
+hipError_t launch_esm_contact_scale(const float *vec, const int32_t *cu, int B, int C, const float *w, float *sw, hipStream_t s);
+hipError_t launch_esm_contact_finish(const float *A, const float *vec, const float *sw, const int32_t *cu, int B, int C, int max_n,
+                                     const float *bias, float *out, hipStream_t s);
 
 // norm.hip
 hipError_t launch_layernorm(const float *x, const float *w, const float *b, float eps, int64_t rows, int D,

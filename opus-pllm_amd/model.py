@@ -33,6 +33,16 @@ class _ProteinEncoderHandle:
     def get_protein_seq_embeddings(self, data: Sequence[str]) -> torch.Tensor:
         return self._owner._encode(list(data))
 
+    def get_amino_acid_embeddings(self, data, return_contacts: bool = False):
+        """ProteinSeqEmbeddingExtractor.get_amino_acid_embeddings (cstp_v3/modelling.py:61-77): data = [(label, sequence)] (or
+        plain sequences) -> list of fp32 [n_i, enc_dim] per-residue last-layer states (rows 1 .. len_i - 2 of
+        representations[enc_layers], as the reference slices them at :75) on the model's device; with return_contacts=True
+        (embeddings, contacts), contacts a list of fp32 [n_i, n_i] maps equal to fair-esm's results["contacts"][i, :n_i, :n_i].
+        The reference feeds CPU tokens to the model it moved to the GPU (:35 vs :68), so its call as written fails with a device
+        mismatch; this is the intended behaviour."""
+        seqs = [d[1] if isinstance(d, (tuple, list)) else d for d in data]
+        return self._owner._amino_acid_embeddings(seqs, return_contacts)
+
 
 class _InnerModel:
     """What get_model() returns (OpusLlamaModel in the reference): embed_tokens + module handles."""
@@ -137,6 +147,67 @@ class OpusLlamaForCausalLM:
             self._last_enc_shape = (1, int(cu[-1]))
         self._leave()
         return out
+
+    # caller scratch of one contacts call (opus_esm2_contacts_scratch_bytes): proteins are grouped so that a group stays under this
+    # many bytes (a single protein may exceed it alone: 4000 residues at the ESM-2 650M shape need about 64 MB of map + 21 MB of
+    # per-channel vectors + the column partials)
+    CONTACT_SCRATCH_BUDGET = 1 << 30
+
+    def _amino_acid_embeddings(self, seqs: List[str], return_contacts: bool = False):
+        cfg = self.cfg
+        cc = _cabi.CConfig.from_config(cfg)
+        embs: List[torch.Tensor] = []
+        maps: List[torch.Tensor] = []
+        n = len(seqs)
+        i0 = 0
+        s = self._enter()
+        try:
+            while i0 < n:
+                i1 = min(n, i0 + cfg.max_batch)
+                toks, cu = batch_convert_packed(seqs[i0:i1])
+                longest = int((cu[1:] - cu[:-1]).max())
+                if longest > cfg.max_enc_tokens:
+                    raise _cabi.OpusError(-2, f"protein of {longest - 2} residues exceeds max_enc_tokens={cfg.max_enc_tokens}")
+                if return_contacts:
+                    while True:         # shrink the group until its scratch fits the budget (or it is one protein)
+                        B = len(cu) - 1
+                        cu_arr = (C.c_int32 * (B + 1))(*[int(v) for v in cu])
+                        need = int(self._lib.opus_esm2_contacts_scratch_bytes(C.byref(cc), cu_arr, B))
+                        if need <= self.CONTACT_SCRATCH_BUDGET or B == 1:
+                            break
+                        i1 = i0 + max(1, B // 2)
+                        toks, cu = batch_convert_packed(seqs[i0:i1])
+                B = len(cu) - 1
+                cu_arr = (C.c_int32 * (B + 1))(*[int(v) for v in cu])
+                M = int(cu[-1])
+                pooled = torch.empty((B, cfg.enc_dim), dtype=torch.float32, device=self.device)
+                hidden = torch.empty((M, cfg.enc_dim), dtype=torch.float32, device=self.device)
+                if return_contacts:
+                    nres = (cu[1:] - cu[:-1] - 2).astype(np.int64)
+                    out = torch.empty((max(1, int((nres * nres).sum())),), dtype=torch.float32, device=self.device)
+                    scratch = torch.empty((max(need, 256),), dtype=torch.uint8, device=self.device)
+                with torch.cuda.stream(self._stream):
+                    d_tok = torch.from_numpy(toks).to(self.device, non_blocking=True)
+                    if return_contacts:
+                        _cabi.check(self._lib.opus_esm2_contacts_packed(self._ctx, d_tok.data_ptr(), cu_arr, B, pooled.data_ptr(),
+                                                                        out.data_ptr(), scratch.data_ptr(), need, s))
+                        off = 0
+                        for nb in nres.tolist():
+                            maps.append(out[off:off + nb * nb].view(nb, nb))
+                            off += nb * nb
+                    else:
+                        _cabi.check(self._lib.opus_esm2_encode_packed(self._ctx, d_tok.data_ptr(), cu_arr, B, pooled.data_ptr(), s))
+                    _cabi.check(self._lib.opus_esm2_last_hidden(self._ctx, hidden.data_ptr(), 1, M, s))
+                    for b in range(B):
+                        embs.append(hidden[int(cu[b]) + 1:int(cu[b + 1]) - 1])
+                    self._last_enc_shape = (1, M)
+                    if return_contacts:
+                        scratch.record_stream(self._stream)
+                    d_tok.record_stream(self._stream)
+                i0 = i1
+        finally:
+            self._leave()
+        return (embs, maps) if return_contacts else embs
 
     def _encode_padded(self, seqs: List[str], bucket: int = 256) -> torch.Tensor:
         """list[str] -> pooled fp32 [B, enc_dim].  Mixed lengths are processed in length buckets

@@ -162,6 +162,23 @@ def param_count(cfg: OpusConfig) -> int:
     return sum(int(np.prod(s)) for _, s, _, _ in canonical_spec(cfg))
 
 
+def contact_head_std(cfg: OpusConfig) -> float:
+    """Weight scale of the synthetic contact regression: 12 / sqrt(channels).  The interior attention probabilities of the
+    synthetic encoder are close to uniform (about 1 / n each), so their symmetrised, APC-corrected maps deviate from zero by
+    a fraction of 1 / n; a weight of O(1 / sqrt(C)) would leave every logit within a few hundredths of the bias (a flat map that
+    any two implementations agree on).  This scale spreads the logits over roughly +-1 at the micro and ESM-2 650M shapes."""
+    return 12.0 / math.sqrt(cfg.enc_layers * cfg.enc_heads)
+
+
+def contact_head(cfg: OpusConfig, seed: int = 0) -> Dict[str, np.ndarray]:
+    """The synthetic contact head: enc.contact.weight fp32 [enc_layers * enc_heads] (channel l * enc_heads + h) and
+    enc.contact.bias fp32 [1], each from its own stream (tensor_seed of its name).  Kept out of canonical_spec: the head is
+    optional, and param_count / the loaders enumerate that list."""
+    C = cfg.enc_layers * cfg.enc_heads
+    return {"enc.contact.weight": hash_normal(tensor_seed("enc.contact.weight", seed), 0, C, contact_head_std(cfg)),
+            "enc.contact.bias": hash_normal(tensor_seed("enc.contact.bias", seed), 0, 1, 0.5)}
+
+
 # ---------------------------------------------------------------------------------------------
 # synthetic inputs (SURVEY 8d "Synthetic inputs")
 RESIDUES = "ACDEFGHIKLMNPQRSTVWY"

@@ -160,6 +160,21 @@ class DeviceWeights:
         self.cfg = cfg
         self.device = device
         self.tensors: Dict[str, torch.Tensor] = {}
+        # optional tensors bound beside the fused ones (the ESM-2 contact head: enc.contact.weight fp32 [enc_layers * enc_heads],
+        # enc.contact.bias fp32 [1]); opus_weights_ready does not need them
+        self.extra: Dict[str, torch.Tensor] = {}
+
+    CONTACT_NAMES = ("enc.contact.weight", "enc.contact.bias")
+
+    def set_contact_head(self, weight, bias) -> None:
+        """Bind the contact regression (canonical names enc.contact.{weight,bias}) at the next bind()."""
+        C = self.cfg.enc_layers * self.cfg.enc_heads
+        w = torch.as_tensor(np.asarray(weight) if not torch.is_tensor(weight) else weight).float().reshape(-1)
+        b = torch.as_tensor(np.asarray(bias) if not torch.is_tensor(bias) else bias).float().reshape(-1)
+        if w.numel() != C or b.numel() != 1:
+            raise ValueError(f"contact head: weight [{C}] and bias [1] expected, got {tuple(w.shape)} and {tuple(b.shape)}")
+        self.extra["enc.contact.weight"] = w.to(self.device).contiguous()
+        self.extra["enc.contact.bias"] = b.to(self.device).contiguous()
 
     # -- construction -------------------------------------------------------------------------
     def _alloc(self, f: Fused) -> torch.Tensor:
@@ -208,6 +223,8 @@ class DeviceWeights:
                 if f.tiled:
                     self.tensors[f.name] = tile_weight(t)
             self._derive(spec, None, None, folded_vec)
+            if all(k in canon for k in self.CONTACT_NAMES):
+                self.set_contact_head(canon["enc.contact.weight"], canon["enc.contact.bias"])
             torch.cuda.synchronize(self.device)
         return self
 
@@ -226,8 +243,9 @@ class DeviceWeights:
                 raise ValueError(f.derive)
 
     @classmethod
-    def synthetic(cls, cfg: OpusConfig, seed: int, device, stream: int = 0) -> "DeviceWeights":
-        """Fill the fused tensors on the GPU with the deterministic synthetic model (synth.py twin)."""
+    def synthetic(cls, cfg: OpusConfig, seed: int, device, stream: int = 0, contact_head: bool = False) -> "DeviceWeights":
+        """Fill the fused tensors on the GPU with the deterministic synthetic model (synth.py twin); contact_head: also the
+        synthetic contact regression (synth.contact_head)."""
         self = cls(cfg, torch.device(device))
         lib = _cabi.lib()
         if not stream:      # the fills and _derive's torch ops on ONE stream: torch's current one (not the null stream beside it)
@@ -268,12 +286,15 @@ class DeviceWeights:
                                                     p.rows, p.cols, synth.tensor_seed(p.canon, seed), std, mean,
                                                     p.rb, p.rs, p.ro, 1 if f.tiled else 0, fseed, fstd, fmean, stream))
             self._derive(fspec, unfolded, vector)
+            if contact_head:
+                head = synth.contact_head(cfg, seed)
+                self.set_contact_head(head["enc.contact.weight"], head["enc.contact.bias"])
         return self
 
     # -- binding ---------------------------------------------------------------------------------
     def bind(self, ctx) -> None:
         lib = _cabi.lib()
-        for name, t in self.tensors.items():
+        for name, t in list(self.tensors.items()) + list(self.extra.items()):
             shape = (C.c_int64 * t.dim())(*t.shape)
             _cabi.check(lib.opus_bind_weight(ctx, name.encode(), t.data_ptr(),
                                              _cabi.OPUS_F16 if t.dtype == _cabi.operand_dtype() else _cabi.OPUS_F32,
@@ -281,4 +302,4 @@ class DeviceWeights:
         _cabi.check(lib.opus_weights_ready(ctx))
 
     def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self.tensors.values())
+        return sum(t.numel() * t.element_size() for t in list(self.tensors.values()) + list(self.extra.values()))

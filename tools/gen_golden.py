@@ -630,10 +630,38 @@ def main():
     print("C1 chain")
     c1 = opa.c1_tiny()
     gold_c1(c1, synth.canonical_weights(c1, seed=0))
+    print("contacts (micro)"); gold_contacts(cfg, w, seqs)
     with open(os.path.join(GOLD, "MANIFEST.json"), "w") as f:
         json.dump(dict(generator="tools/gen_golden.py", weights_seed=0, torch=torch.__version__,
                        transformers=__import__("transformers").__version__,
                        reference="/root/reference (Fanchuana/OPUS-PLLM @ 2026-05-29)"), f, indent=1)
+
+
+
+def gold_contacts(cfg, w, seqs):
+    """contacts_micro.npz: HF EsmModel on the synthetic micro weights with the synthetic contact head (synth.contact_head) -
+    predict_contacts (get_amino_acid_embeddings(return_contacts=True), cstp_v3/modelling.py:61-77) and the last hidden state
+    on the esm_micro sequences plus an empty and a one-residue protein."""
+    from opus_pllm_amd.alphabet import batch_convert
+    seqs = list(seqs) + ["", synth.synth_protein(1, 9)]
+    hf = build_hf_esm(cfg, w)
+    head = synth.contact_head(cfg, 0)
+    with torch.no_grad():
+        hf.contact_head.regression.weight.copy_(torch.from_numpy(head["enc.contact.weight"]).reshape(1, -1))
+        hf.contact_head.regression.bias.copy_(torch.from_numpy(head["enc.contact.bias"]).reshape(1))
+    toks, lens = batch_convert(seqs)
+    t = torch.from_numpy(toks).long()
+    mask = (t != 1).long()
+    with torch.no_grad():
+        contacts = hf.predict_contacts(t, mask)
+        last = hf(input_ids=t, attention_mask=mask).last_hidden_state
+    logit = torch.logit(contacts.double().clamp(1e-12, 1 - 1e-12))
+    vals = torch.cat([logit[i, :len(s), :len(s)].reshape(-1) for i, s in enumerate(seqs) if len(s) > 1])
+    save("contacts_micro", tokens=toks, lens=lens, contacts=contacts.numpy().astype(np.float32),
+         last_hidden=last.numpy().astype(np.float32), logit_std=np.array(float(vals.std()), np.float64),
+         weight=head["enc.contact.weight"], bias=head["enc.contact.bias"])
+    with open(os.path.join(GOLD, "contacts_micro.seqs.json"), "w") as f:
+        json.dump(seqs, f)
 
 
 if __name__ == "__main__":
