@@ -251,6 +251,26 @@ int opus_generate_sample(opus_ctx *ctx, const void *d_embeds, const uint8_t *d_m
 int opus_debug_sample(opus_ctx *ctx, const float *d_logits, int32_t B, float temperature, float top_p, uint64_t seed,
                       int32_t step, int32_t *d_tokens, void *stream);
 
+/* generate(return_dict_in_generate=True, output_*=True): opus_generate_greedy (temperature == 0; top_p and seed unused) or
+ * opus_generate_sample (temperature > 0) that also returns, per generated step, what the caller asks for (NULL = off; caller
+ * memory, fp32):
+ *   d_token_logprobs [B, max_new]: log p(chosen token) under the model's distribution (temperature 1, no filters); 0 for a row
+ *     that finished before the step (its EOS / last stop-sequence token still counts).  The log-sum-exp is fused into the
+ *     arg-max pass over the logits.
+ *   d_scores [max_new, B, dec_vocab]: HF's processed scores - greedy: the logits; sampling: logits / temperature where the draw's
+ *     top-k / top-p filters kept the token (the draw's own keep test), -inf elsewhere.
+ *   d_logits [max_new, B, dec_vocab]: the raw logits.
+ * Steps at and past *n_out hold nothing defined.  The output addresses reach the captured decode step through a small device
+ * descriptor written before the loop: each call may pass fresh buffers without a new graph; which outputs are on is part of the
+ * graph's identity.  All three NULL: exactly opus_generate_greedy / _sample (same launches, same graph). */
+int opus_generate_scored(opus_ctx *ctx, const void *d_embeds, const uint8_t *d_mask, int32_t B, int32_t T, int32_t max_new,
+                         const int32_t *eos_ids, int32_t n_eos, int32_t pad_id, float temperature, float top_p, uint64_t seed,
+                         int32_t *d_out_ids, int32_t *n_out, float *d_token_logprobs, float *d_scores, float *d_logits,
+                         void *stream);
+/* Diagnostic: opus_generate_scored's fused arg-max / log-sum-exp pass on fp32 logits [B, V] (B <= max_batch, any V >= 1; rows
+ * need no alignment): d_idx [B] the arg-max (lowest index among ties, bitwise what the greedy step picks), d_lse [B]. */
+int opus_debug_argmax_lse(opus_ctx *ctx, const float *d_logits, int32_t B, int32_t V, int32_t *d_idx, float *d_lse, void *stream);
+
 /* Diagnostic entry points (kernel-level parity tests and micro-benchmarks; not part of the path's
  * drop-in surface).  opus_debug_gemm: C[M,Nout] = epi(A[M,K] W[N,K]^T + bias) (+ residual fp32);
  * epi 0 none, 1 erf-GELU, 2 silu(gate)*up with W rows in [16 gate | 16 up] groups (Nout = N/2).

@@ -114,6 +114,7 @@ struct opus_ctx {
         int B = -1, maxnew = -1, pad = 0, neos = -1;
         const int32_t *out = nullptr;
         float temp = 0.f, top_p = 1.f;
+        int outs = 0;                    // GEN_* flags of opus_generate_scored (the addresses come from the descriptor)
         uint64_t used = 0;
     };
     static constexpr int MAX_GRAPHS = 4;
@@ -122,6 +123,13 @@ struct opus_ctx {
     int64_t graph_instantiations = 0;    // opus_stat("graph_instantiations")
     int64_t graph_replays = 0;
     int64_t decode_steps = 0;            // decode steps enqueued by opus_generate_* (eager or from a graph)
+    // opus_generate_scored's outputs: a separate small allocation (first use), not the workspace - the descriptor of the call's
+    // output addresses (h_gen, copied to d_gen before the loop), the part sums of the fused log-sum-exp and the draw's thresholds
+    char *gen_mem = nullptr;
+    GenOutDesc *d_gen = nullptr;
+    GenOutDesc h_gen{};
+    float *d_gpsum = nullptr, *d_gthr = nullptr;
+    int gen_outs = 0;                    // GEN_* flags of the running call (0: the plain step)
     // row-scale fusion (GemmParams::xh_out / row_ssq): one-shot request for the next gemm() and its outcome
     half_t *rq_xh = nullptr;
     int rq_done = 0;
@@ -386,6 +394,7 @@ extern "C" int opus_ctx_destroy(opus_ctx *c) {
     if (c->ws) (void)hipFree(c->ws);
     if (c->proj_big) (void)hipFree(c->proj_big);
     if (c->kv_tmp) (void)hipFree(c->kv_tmp);
+    if (c->gen_mem) (void)hipFree(c->gen_mem);
     if (c->h_nunf) (void)hipHostFree(c->h_nunf);
     for (auto &e : c->poll_ev) if (e) (void)hipEventDestroy(e);
     delete c;
@@ -1672,22 +1681,52 @@ extern "C" int opus_debug_attn_prefix(opus_ctx *c, const void *d_qkv, const void
     return OPUS_OK;
 }
 
-// next token per row: argmax (greedy) or temperature / top-p sampling, then the GenerationMixin bookkeeping
+// opus_generate_scored's outputs (opus_ctx::gen_outs)
+enum { GEN_LOGPROBS = 1, GEN_SCORES = 2, GEN_LOGITS = 4 };
+
+static int ensure_gen_mem(opus_ctx *c) {
+    if (c->gen_mem) return OPUS_OK;
+    const size_t B = c->cfg.max_batch;
+    const size_t o_ps = align_up(sizeof(GenOutDesc)), o_thr = o_ps + align_up(APART * B * sizeof(float));
+    HIPC(hipMalloc((void **)&c->gen_mem, o_thr + align_up(B * sizeof(float))));
+    c->d_gen = reinterpret_cast<GenOutDesc *>(c->gen_mem);
+    c->d_gpsum = reinterpret_cast<float *>(c->gen_mem + o_ps);
+    c->d_gthr = reinterpret_cast<float *>(c->gen_mem + o_thr);
+    return OPUS_OK;
+}
+
+// next token per row: argmax (greedy) or temperature / top-p sampling, then the GenerationMixin bookkeeping.  With gen_outs set
+// (opus_generate_scored): the first pass also sums the parts' exponentials and the step kernel writes the chosen token's
+// log-probability (GEN_LOGPROBS), and / or the score writer copies the step's logits out (GEN_SCORES / GEN_LOGITS).
 static int argmax(opus_ctx *c, hipStream_t s, int max_new, int n_eos, int pad_id, int32_t *d_out) {
     c->phase = PH_DECODE;
     const opus_config &g = c->cfg;
     const int32_t *chosen = nullptr;
+    const bool lp = c->gen_outs & GEN_LOGPROBS, sc = c->gen_outs & (GEN_SCORES | GEN_LOGITS);
     if (c->samp_temp > 0.f) {
         KL(KC_OTHER, 4.0 * 4 * c->cur_B * g.dec_vocab,
            launch_sample_select(c->d_logits, c->cur_B, g.dec_vocab, c->samp_temp, c->samp_top_p, c->samp_top_k, c->d_seed, c->d_step,
-                                c->d_pval, c->d_pidx, c->d_probs, c->d_cand_i, c->d_cand_n, c->d_zpart, c->d_spart, c->d_chosen, nullptr, s));
+                                c->d_pval, c->d_pidx, c->d_probs, c->d_cand_i, c->d_cand_n, c->d_zpart, c->d_spart, c->d_chosen, nullptr,
+                                lp ? c->d_gpsum : nullptr, sc ? c->d_gthr : nullptr, s));
         chosen = c->d_chosen;
+    } else if (lp) {
+        KL(KC_OTHER, 4.0 * c->cur_B * g.dec_vocab,
+           launch_argmax_lse_partial(c->d_logits, c->cur_B, g.dec_vocab, c->d_pval, c->d_pidx, c->d_gpsum, s));
     } else {
         KL(KC_OTHER, 4.0 * c->cur_B * g.dec_vocab, launch_argmax_partial(c->d_logits, c->cur_B, g.dec_vocab, c->d_pval, c->d_pidx, s));
     }
-    KL(KC_OTHER, 512.0 * c->cur_B,
-       launch_argmax_step(c->d_pval, c->d_pidx, chosen, c->cur_B, c->d_eos, n_eos, pad_id, c->d_fin, d_out, max_new, c->d_step,
-                          c->d_next, c->d_nunf, c->d_stop, c->n_stop, s));
+    if (sc)
+        KL(KC_OTHER, 4.0 * c->cur_B * g.dec_vocab * (1 + ((c->gen_outs & GEN_SCORES) ? 1 : 0) + ((c->gen_outs & GEN_LOGITS) ? 1 : 0)),
+           launch_gen_scores(c->d_logits, c->cur_B, g.dec_vocab, c->d_gen, c->d_step, max_new, c->samp_temp, c->samp_top_p, c->d_pval,
+                             c->samp_temp > 0.f ? c->d_gthr : nullptr, s));
+    if (lp)
+        KL(KC_OTHER, 512.0 * c->cur_B + 8.0 * c->cur_B,
+           launch_argmax_lse_step(c->d_pval, c->d_pidx, c->d_gpsum, chosen, c->cur_B, c->d_eos, n_eos, pad_id, c->d_fin, d_out, max_new,
+                                  c->d_step, c->d_next, c->d_nunf, c->d_stop, c->n_stop, c->d_logits, g.dec_vocab, c->d_gen, s));
+    else
+        KL(KC_OTHER, 512.0 * c->cur_B,
+           launch_argmax_step(c->d_pval, c->d_pidx, chosen, c->cur_B, c->d_eos, n_eos, pad_id, c->d_fin, d_out, max_new, c->d_step,
+                              c->d_next, c->d_nunf, c->d_stop, c->n_stop, s));
     return OPUS_OK;
 }
 
@@ -1700,7 +1739,7 @@ static int greedy_body(opus_ctx *c, hipStream_t s, int max_new, int n_eos, int p
 
 static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mask, int32_t B, int32_t T, int32_t max_new,
                          const int32_t *eos_ids, int32_t n_eos, int32_t pad_id, float temperature, float top_p, uint64_t seed,
-                         int32_t *d_out_ids, int32_t *n_out, void *stream) {
+                         int32_t *d_out_ids, int32_t *n_out, void *stream, const GenOutDesc *outs = nullptr) {
     OPC(need_ready(c));
     if (temperature < 0.f || top_p <= 0.f || top_p > 1.f) return fail(OPUS_EBADARG, "generate: temperature >= 0 and 0 < top_p <= 1");
     c->samp_temp = temperature;
@@ -1714,16 +1753,27 @@ static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mas
     const opus_config &g = c->cfg;
     if (n_eos) HIPC(hipMemcpyAsync(c->d_eos, eos_ids, n_eos * sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIPC(hipMemcpyAsync(c->d_seed, &seed, sizeof(seed), hipMemcpyHostToDevice, s));
+    int gen_outs = 0;
+    if (outs) {
+        gen_outs = (outs->token_lp ? GEN_LOGPROBS : 0) | (outs->scores ? GEN_SCORES : 0) | (outs->logits ? GEN_LOGITS : 0);
+        if (gen_outs) {
+            OPC(ensure_gen_mem(c));
+            c->h_gen = *outs;                // (a member: the source outlives the asynchronous copy)
+            HIPC(hipMemcpyAsync(c->d_gen, &c->h_gen, sizeof(GenOutDesc), hipMemcpyHostToDevice, s));
+        }
+    }
     HIPC(hipMemsetAsync(c->d_fin, 0, B * sizeof(int32_t), s));
     HIPC(hipMemsetAsync(c->d_nunf, 0, (size_t)max_new * sizeof(int32_t), s));
     OPC(prefill(c, s, (const half_t *)d_embeds, d_mask, B, T));
+    c->gen_outs = gen_outs;              // (the prefill's own launches are the same either way)
+    struct GenOutsReset { opus_ctx *c; ~GenOutsReset() { c->gen_outs = 0; } } gen_outs_reset{c};
 
     // OPUS_NO_GRAPH=1: eager launches (rocprofv3 --pmc cannot collect counters through graph replays)
     const bool use_graph = s != nullptr && !c->timing && !getenv("OPUS_NO_GRAPH");
     auto find_graph = [&]() -> opus_ctx::GraphEntry * {
         for (auto &e : c->graphs)
             if (e.exec && e.B == B && e.maxnew == max_new && e.pad == pad_id && e.neos == n_eos && e.out == d_out_ids &&
-                e.temp == temperature && e.top_p == top_p) return &e;
+                e.temp == temperature && e.top_p == top_p && e.outs == gen_outs) return &e;
         return nullptr;
     };
     opus_ctx::GraphEntry *ge = use_graph ? find_graph() : nullptr;
@@ -1753,6 +1803,7 @@ static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mas
                 if (ee != hipSuccess) return fail(OPUS_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(ee));
                 ++c->graph_instantiations;
                 e.B = B; e.maxnew = max_new; e.pad = pad_id; e.neos = n_eos; e.temp = temperature; e.top_p = top_p; e.out = d_out_ids;
+                e.outs = gen_outs;
                 if ((int)c->graphs.size() >= opus_ctx::MAX_GRAPHS) {           // least recently used out
                     size_t v = 0;
                     for (size_t k = 1; k < c->graphs.size(); ++k) if (c->graphs[k].used < c->graphs[v].used) v = k;
@@ -1816,6 +1867,37 @@ extern "C" int opus_generate_sample(opus_ctx *c, const void *d_embeds, const uin
                          stream);
 }
 
+/* opus_generate_greedy (temperature == 0) / opus_generate_sample (temperature > 0) with per-step outputs, each optional (NULL =
+   off): d_token_logprobs fp32 [B, max_new] (log-probability of the chosen token under the model's distribution; 0 after a row
+   has finished), d_scores fp32 [max_new, B, V] (greedy: the logits; sampling: logits / T, -inf where the draw's top-k / top-p
+   filters removed the token), d_logits fp32 [max_new, B, V] (the raw logits).  Steps past *n_out are not defined.  All NULL: the
+   plain call, the same launches and graph. */
+extern "C" int opus_generate_scored(opus_ctx *c, const void *d_embeds, const uint8_t *d_mask, int32_t B, int32_t T, int32_t max_new,
+                                    const int32_t *eos_ids, int32_t n_eos, int32_t pad_id, float temperature, float top_p,
+                                    uint64_t seed, int32_t *d_out_ids, int32_t *n_out, float *d_token_logprobs, float *d_scores,
+                                    float *d_logits, void *stream) {
+    if (!c) return fail(OPUS_EBADARG, "ctx is null");
+    if (!(temperature >= 0.f)) return fail(OPUS_EBADARG, "generate_scored: temperature must be >= 0 (0 = greedy)");
+    const GenOutDesc outs{d_token_logprobs, d_scores, d_logits, nullptr};
+    return generate_impl(c, d_embeds, d_mask, B, T, max_new, eos_ids, n_eos, pad_id, temperature, temperature > 0.f ? top_p : 1.f,
+                         temperature > 0.f ? seed : 0, d_out_ids, n_out, stream, &outs);
+}
+
+/* Diagnostic: the fused arg-max / log-sum-exp pass of opus_generate_scored on fp32 logits [B, V] (B <= max_batch, any V >= 1):
+   d_idx [B] (the arg-max argmax_partial gives: lowest index among ties), d_lse [B]. */
+extern "C" int opus_debug_argmax_lse(opus_ctx *c, const float *d_logits, int32_t B, int32_t V, int32_t *d_idx, float *d_lse,
+                                     void *stream) {
+    if (!c || !d_logits || !d_idx || !d_lse) return fail(OPUS_EBADARG, "debug_argmax_lse: null pointer");
+    if (B < 1 || B > c->cfg.max_batch || V < 1) return fail(OPUS_ESHAPE, "debug_argmax_lse: B=%d (max_batch %d) V=%d", B, c->cfg.max_batch, V);
+    HIPC(hipSetDevice(c->device));
+    OPC(ensure_gen_mem(c));
+    hipStream_t s = (hipStream_t)stream;
+    c->phase = PH_OTHER;
+    KL(KC_OTHER, 4.0 * B * V, launch_argmax_lse_partial(d_logits, B, V, c->d_pval, c->d_pidx, c->d_gpsum, s));
+    KL(KC_OTHER, 512.0 * B, launch_argmax_lse_final(c->d_pval, c->d_pidx, c->d_gpsum, B, d_idx, d_lse, s));
+    return OPUS_OK;
+}
+
 /* Diagnostic: one draw per row from fp32 logits [B,V] with the sampling head (step counter = `step`). */
 extern "C" int opus_debug_sample(opus_ctx *c, const float *d_logits, int32_t B, float temperature, float top_p, uint64_t seed,
                                  int32_t step, int32_t *d_tokens, void *stream) {
@@ -1826,7 +1908,7 @@ extern "C" int opus_debug_sample(opus_ctx *c, const float *d_logits, int32_t B, 
     HIPC(hipMemcpyAsync(c->d_seed, &seed, sizeof(seed), hipMemcpyHostToDevice, s));
     HIPC(hipMemcpyAsync(c->d_plan, &step, sizeof(step), hipMemcpyHostToDevice, s));
     HIPC(launch_sample_select(d_logits, B, c->cfg.dec_vocab, temperature, top_p, c->samp_top_k, c->d_seed, c->d_plan, c->d_pval, c->d_pidx,
-                              c->d_probs, c->d_cand_i, c->d_cand_n, c->d_zpart, c->d_spart, d_tokens, nullptr, s));
+                              c->d_probs, c->d_cand_i, c->d_cand_n, c->d_zpart, c->d_spart, d_tokens, nullptr, nullptr, nullptr, s));
     HIPC(hipStreamSynchronize(s));   // seed / step are host temporaries
     return OPUS_OK;
 }
@@ -1965,7 +2047,7 @@ extern "C" int opus_beam_sample_topk(opus_ctx *c, const float *d_logits, const f
     const int top_k = c->samp_top_k > 0 && c->samp_top_k < min_keep ? min_keep : c->samp_top_k;    // TopKLogitsWarper: max(top_k, min_tokens_to_keep)
     KL(KC_OTHER, 4.0 * 4 * R * V,
        launch_sample_select(lg, R, V, temperature, top_p, top_k, nullptr, nullptr, c->d_pval, c->d_pidx, c->d_probs, c->d_cand_i,
-                            c->d_cand_n, c->d_zpart, c->d_spart, nullptr, c->d_bthr, s));
+                            c->d_cand_n, c->d_zpart, c->d_spart, nullptr, c->d_bthr, nullptr, nullptr, s));
     // (the candidate lists of the nucleus search are consumed: their buffers hold the rows' min_keep best logits next)
     KL(KC_OTHER, 12.0 * R * V,
        launch_beam_sample(lg, d_run_scores, B, K, V, M, temperature, c->d_pval, c->d_bthr, min_keep, c->d_probs, c->d_cand_i, seed, step,

@@ -356,10 +356,13 @@ hipError_t launch_splice_plan(const int64_t *ids, const uint8_t *mask, int B, in
 hipError_t launch_splice_fill(const int64_t *ids, const uint8_t *mask, int B, int Tt, const half_t *prot,
                               int n_tok, int H, int V, const half_t *emb, const int32_t *plan, int Tout,
                               int left_pad, half_t *out, uint8_t *mask_out, int32_t *pos_out, hipStream_t s);
-// (thr_out != nullptr: no draw; the rows' keep thresholds on p = exp(l / T - max / T) are written there - beam-sample)
+// (thr_out != nullptr: no draw; the rows' keep thresholds on p = exp(l / T - max / T) are written there - beam-sample.
+//  psum != nullptr: the first pass is argmax_lse_partial (part sums for the log-sum-exp); thr_keep != nullptr: the draw also
+//  exports its keep thresholds there)
 hipError_t launch_sample_select(const float *logits, int B, int V, float temperature, float top_p, int top_k, const uint64_t *seed,
                                 const int32_t *step, float *pmax, int32_t *pidx, float *cand_p, int32_t *cand_i,
-                                int32_t *cand_n, float *zpart, float *spart, int32_t *chosen, float *thr_out, hipStream_t s);
+                                int32_t *cand_n, float *zpart, float *spart, int32_t *chosen, float *thr_out, float *psum,
+                                float *thr_keep, hipStream_t s);
 constexpr int APART = 64;     // parts a logits row is cut into by argmax_partial / sample_stage1 (pmax[row * APART + part])
 __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
     x += 0x9E3779B97F4A7C15ull;
@@ -371,6 +374,26 @@ hipError_t launch_argmax_step(const float *pval, const int32_t *pidx, const int3
                               int32_t *finished, int32_t *out_ids, int max_new, const int32_t *step,
                               int32_t *next_tok, int32_t *n_unfinished, const int32_t *stop, int n_stop, hipStream_t s);
 hipError_t launch_step_advance(int32_t *step, hipStream_t s);
+// generate()'s optional outputs, read by the captured step from device memory (opus_generate_scored writes the descriptor before
+// its loop): token_lp [B, max_new], scores / logits [max_new, B, V], fp32, rows and steps indexed by the device step word; null = off
+struct GenOutDesc {
+    float *token_lp;
+    float *scores;
+    float *logits;
+    float *unused;
+};
+// argmax_partial + each part's sum of exp(l - part max) (psum [B, APART])
+hipError_t launch_argmax_lse_partial(const float *logits, int B, int V, float *pval, int32_t *pidx, float *psum, hipStream_t s);
+// argmax_step + out->token_lp[b, step] = logits[b, tok] - logsumexp(logits[b]) (0 for rows finished before the step)
+hipError_t launch_argmax_lse_step(const float *pval, const int32_t *pidx, const float *psum, const int32_t *chosen, int B,
+                                  const int32_t *eos, int n_eos, int pad_id, int32_t *finished, int32_t *out_ids, int max_new,
+                                  const int32_t *step, int32_t *next_tok, int32_t *n_unfinished, const int32_t *stop, int n_stop,
+                                  const float *logits, int V, const GenOutDesc *out, hipStream_t s);
+hipError_t launch_argmax_lse_final(const float *pval, const int32_t *pidx, const float *psum, int B, int32_t *idx, float *lse,
+                                   hipStream_t s);
+// out->scores / out->logits at the step (thr != nullptr: sampling - l / T where the draw kept the token, -inf elsewhere)
+hipError_t launch_gen_scores(const float *logits, int B, int V, const GenOutDesc *out, const int32_t *step, int max_new,
+                             float temperature, float top_p, const float *pmax, const float *thr, hipStream_t s);
 // beam.hip: best M of the K V continuations per batch row (log_softmax + running scores), cache rows of the surviving beams
 hipError_t launch_beam_topk(const float *logits, const float *run, int B, int K, int V, int M, float *lse, float *out_s,
                             int32_t *out_i, hipStream_t s);

@@ -524,30 +524,112 @@ hipError_t launch_argmax_partial(const float *logits, int B, int V, float *pval,
     return hipGetLastError();
 }
 
+// Stage 1 with the part's log-sum-exp (generate()'s output_token_logprobs): the same (max, lowest index) per part, bitwise - the
+// same loops and comparisons - plus psum = sum over the part of exp(l - part max).  The logits are read once: each thread keeps a
+// running sum against its running maximum (one exponential per value, the sum rescaled when the maximum grows), and the block
+// tree combines (max, sum) pairs.  -inf entries add nothing; a part with no finite value leaves (-inf, 0).
+__global__ __launch_bounds__(256) void argmax_lse_partial_kernel(const float *__restrict__ logits, int V, float *__restrict__ pval,
+                                                                 int32_t *__restrict__ pidx, float *__restrict__ psum) {
+    __shared__ float s_v[256];
+    __shared__ int s_i[256];
+    __shared__ float s_s[256];
+    const int b = blockIdx.y, part = blockIdx.x;
+    const float *row = logits + (int64_t)b * V;
+    const int per = ((V + APART - 1) / APART + 3) & ~3;
+    // (hi >= lo: a part past the row's end is empty.  argmax_partial's tail loop re-reads the last < 4 values there - harmless
+    //  for a maximum, not for a sum)
+    const int lo = part * per, hi = (lo + per < V ? lo + per : (lo < V ? V : lo));
+    float bv = -INFINITY, bs = 0.f;
+    int bi = 0x7fffffff;
+    auto acc = [&](float v) {                 // (before bv moves to v)
+        if (v > bv) bs = bs * __expf(bv - v) + 1.f;
+        else if (v > -INFINITY) bs += __expf(v - bv);
+    };
+    if ((((uintptr_t)row) & 15) == 0) {
+        for (int i = lo + threadIdx.x * 4; i + 3 < hi; i += 1024) {
+            const float4 v = *reinterpret_cast<const float4 *>(row + i);
+            acc(v.x); if (v.x > bv) { bv = v.x; bi = i; }
+            acc(v.y); if (v.y > bv) { bv = v.y; bi = i + 1; }
+            acc(v.z); if (v.z > bv) { bv = v.z; bi = i + 2; }
+            acc(v.w); if (v.w > bv) { bv = v.w; bi = i + 3; }
+        }
+        for (int i = lo + ((hi - lo) & ~3) + threadIdx.x; i < hi; i += 256) {
+            const float v = row[i];
+            acc(v);
+            if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
+        }
+    } else {
+        for (int i = lo + threadIdx.x; i < hi; i += 256) {
+            const float v = row[i];
+            acc(v);
+            if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
+        }
+    }
+    s_v[threadIdx.x] = bv;
+    s_i[threadIdx.x] = bi;
+    s_s[threadIdx.x] = bs;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) {
+            const float v = s_v[threadIdx.x + o], m = s_v[threadIdx.x];
+            const int i = s_i[threadIdx.x + o];
+            const float M = fmaxf(m, v);
+            s_s[threadIdx.x] = M == -INFINITY ? 0.f : s_s[threadIdx.x] * __expf(m - M) + s_s[threadIdx.x + o] * __expf(v - M);
+            if (v > m || (v == m && i < s_i[threadIdx.x])) {
+                s_v[threadIdx.x] = v;
+                s_i[threadIdx.x] = i;
+            }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        pval[b * APART + part] = s_v[0];
+        pidx[b * APART + part] = s_i[0];
+        psum[b * APART + part] = s_s[0];
+    }
+}
+
+// One wave, lane p holding part p's (max mp, sum sp) and M the row maximum: lse = M + log(sum_p sp exp(mp - M)), the parts summed
+// in a fixed butterfly order (every lane returns the same value).
+__device__ __forceinline__ float parts_lse(float mp, float sp, float M) {
+    float e = mp > -INFINITY ? sp * __expf(mp - M) : 0.f;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o, 64);
+    return M + logf(e);
+}
+
 // Stage 2: one wave per row combines the partials (lowest index wins ties, as torch.argmax), then the
 // GenerationMixin bookkeeping: finished rows emit pad_id; a row finishes when it emits an EOS id.
-__global__ __launch_bounds__(64) void argmax_step_kernel(const float *__restrict__ pval, const int32_t *__restrict__ pidx,
-                                                         const int32_t *__restrict__ chosen,
-                                                         const int32_t *__restrict__ eos, int n_eos, int pad_id,
-                                                         int32_t *__restrict__ finished, int32_t *__restrict__ out_ids,
-                                                         int max_new, const int32_t *__restrict__ step,
-                                                         int32_t *__restrict__ next_tok, int32_t *__restrict__ n_unf,
-                                                         const int32_t *__restrict__ stop, int n_stop) {
+// LP (argmax_lse_step_kernel): also the row's log-sum-exp from argmax_lse_partial's part sums, and the chosen token's
+// log-probability l[tok] - lse into out->token_lp[b, step] (0 for a row that had finished before this step).
+template <bool LP>
+__device__ __forceinline__ void argmax_step_body(const float *__restrict__ pval, const int32_t *__restrict__ pidx,
+                                                 const int32_t *__restrict__ chosen, const int32_t *__restrict__ eos, int n_eos,
+                                                 int pad_id, int32_t *__restrict__ finished, int32_t *__restrict__ out_ids,
+                                                 int max_new, const int32_t *__restrict__ step, int32_t *__restrict__ next_tok,
+                                                 int32_t *__restrict__ n_unf, const int32_t *__restrict__ stop, int n_stop,
+                                                 const float *__restrict__ logits, int V, const float *__restrict__ psum,
+                                                 const GenOutDesc *__restrict__ out) {
     const int b = blockIdx.x, lane = threadIdx.x;
     float bv = pval[b * APART + lane];
     int bi = pidx[b * APART + lane];
+    const float mp = bv, sp = LP ? psum[b * APART + lane] : 0.f;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float v = __shfl_xor(bv, o, 64);
         const int i = __shfl_xor(bi, o, 64);
         if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
     }
+    const float lse = LP ? parts_lse(mp, sp, bv) : 0.f;
     if (chosen) bi = chosen[b];               // sampling: the token was drawn by sample_select_kernel
     if (lane == 0) {
         const int st = *step;
         int fin = finished[b];
         int tok = fin ? pad_id : (bi == 0x7fffffff ? 0 : bi);
         if (st < max_new) out_ids[(int64_t)b * max_new + st] = tok;
+        if (LP && st < max_new)
+            out->token_lp[(int64_t)b * max_new + st] =
+                fin ? 0.f : ((unsigned)tok < (unsigned)V ? logits[(int64_t)b * V + tok] - lse : NAN);
         if (!fin)
             for (int e = 0; e < n_eos; ++e) fin |= (tok == eos[e]);
         // opt-in stop sequence (the ids of "###", which the reference cuts at after decoding: run_opus_ddp.py:19-27): a row
@@ -562,11 +644,122 @@ __global__ __launch_bounds__(64) void argmax_step_kernel(const float *__restrict
         if (!fin && st < max_new) atomicAdd(&n_unf[st], 1);
     }
 }
+__global__ __launch_bounds__(64) void argmax_step_kernel(const float *__restrict__ pval, const int32_t *__restrict__ pidx,
+                                                         const int32_t *__restrict__ chosen,
+                                                         const int32_t *__restrict__ eos, int n_eos, int pad_id,
+                                                         int32_t *__restrict__ finished, int32_t *__restrict__ out_ids,
+                                                         int max_new, const int32_t *__restrict__ step,
+                                                         int32_t *__restrict__ next_tok, int32_t *__restrict__ n_unf,
+                                                         const int32_t *__restrict__ stop, int n_stop) {
+    argmax_step_body<false>(pval, pidx, chosen, eos, n_eos, pad_id, finished, out_ids, max_new, step, next_tok, n_unf, stop, n_stop,
+                            nullptr, 0, nullptr, nullptr);
+}
+__global__ __launch_bounds__(64) void argmax_lse_step_kernel(const float *__restrict__ pval, const int32_t *__restrict__ pidx,
+                                                             const int32_t *__restrict__ chosen,
+                                                             const int32_t *__restrict__ eos, int n_eos, int pad_id,
+                                                             int32_t *__restrict__ finished, int32_t *__restrict__ out_ids,
+                                                             int max_new, const int32_t *__restrict__ step,
+                                                             int32_t *__restrict__ next_tok, int32_t *__restrict__ n_unf,
+                                                             const int32_t *__restrict__ stop, int n_stop,
+                                                             const float *__restrict__ logits, int V, const float *__restrict__ psum,
+                                                             const GenOutDesc *__restrict__ out) {
+    argmax_step_body<true>(pval, pidx, chosen, eos, n_eos, pad_id, finished, out_ids, max_new, step, next_tok, n_unf, stop, n_stop,
+                           logits, V, psum, out);
+}
 hipError_t launch_argmax_step(const float *pval, const int32_t *pidx, const int32_t *chosen, int B, const int32_t *eos,
                               int n_eos, int pad_id, int32_t *finished, int32_t *out_ids, int max_new, const int32_t *step,
                               int32_t *next_tok, int32_t *n_unfinished, const int32_t *stop, int n_stop, hipStream_t s) {
     hipLaunchKernelGGL(argmax_step_kernel, dim3(B), dim3(64), 0, s, pval, pidx, chosen, eos, n_eos, pad_id, finished, out_ids,
                        max_new, step, next_tok, n_unfinished, stop, n_stop);
+    return hipGetLastError();
+}
+hipError_t launch_argmax_lse_partial(const float *logits, int B, int V, float *pval, int32_t *pidx, float *psum, hipStream_t s) {
+    hipLaunchKernelGGL(argmax_lse_partial_kernel, dim3(APART, B), dim3(256), 0, s, logits, V, pval, pidx, psum);
+    return hipGetLastError();
+}
+hipError_t launch_argmax_lse_step(const float *pval, const int32_t *pidx, const float *psum, const int32_t *chosen, int B,
+                                  const int32_t *eos, int n_eos, int pad_id, int32_t *finished, int32_t *out_ids, int max_new,
+                                  const int32_t *step, int32_t *next_tok, int32_t *n_unfinished, const int32_t *stop, int n_stop,
+                                  const float *logits, int V, const GenOutDesc *out, hipStream_t s) {
+    hipLaunchKernelGGL(argmax_lse_step_kernel, dim3(B), dim3(64), 0, s, pval, pidx, chosen, eos, n_eos, pad_id, finished, out_ids,
+                       max_new, step, next_tok, n_unfinished, stop, n_stop, logits, V, psum, out);
+    return hipGetLastError();
+}
+
+// opus_debug_argmax_lse: the row's arg-max (argmax_step's combine) and log-sum-exp from argmax_lse_partial's parts.
+__global__ __launch_bounds__(64) void argmax_lse_final_kernel(const float *__restrict__ pval, const int32_t *__restrict__ pidx,
+                                                              const float *__restrict__ psum, int32_t *__restrict__ idx,
+                                                              float *__restrict__ lse) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    float bv = pval[b * APART + lane];
+    int bi = pidx[b * APART + lane];
+    const float mp = bv, sp = psum[b * APART + lane];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float v = __shfl_xor(bv, o, 64);
+        const int i = __shfl_xor(bi, o, 64);
+        if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
+    }
+    const float l = parts_lse(mp, sp, bv);
+    if (lane == 0) {
+        idx[b] = bi;
+        lse[b] = l;
+    }
+}
+hipError_t launch_argmax_lse_final(const float *pval, const int32_t *pidx, const float *psum, int B, int32_t *idx, float *lse,
+                                   hipStream_t s) {
+    hipLaunchKernelGGL(argmax_lse_final_kernel, dim3(B), dim3(64), 0, s, pval, pidx, psum, idx, lse);
+    return hipGetLastError();
+}
+
+// generate()'s output_scores / output_logits: the step's logits row b into out->scores[step, b] / out->logits[step, b] (fp32,
+// [max_new, B, V]; a null pointer is skipped).  thr != nullptr (sampling): scores hold HF's processed scores, l / T where the draw
+// kept the token and -inf elsewhere.  "Kept" is the draw's own test, not a second filter: stage 1's p = exp(l / T - max / T) (the
+// same fma and exponential as sample_stage1_kernel), above stage 1's candidate bound (1 - top_p) / V and above the threshold
+// sample_stage2 exported (thr[b]).  Grid (chunks of GS_CHUNK values, B); float4 when every row is 16-byte aligned.
+constexpr int GS_CHUNK = 4096;
+__global__ __launch_bounds__(256) void gen_scores_kernel(const float *__restrict__ logits, int V, const GenOutDesc *__restrict__ out,
+                                                         const int32_t *__restrict__ step, int max_new, float inv_temp, float top_p,
+                                                         const float *__restrict__ pmax, const float *__restrict__ thr) {
+    const int b = blockIdx.y, B = gridDim.y;
+    const int st = *step;
+    if (st >= max_new) return;
+    float *sc = out->scores, *lg = out->logits;
+    const int64_t o = ((int64_t)st * B + b) * V;
+    const float *row = logits + (int64_t)b * V;
+    float gmax = 0.f, t = 0.f, cand = 0.f;
+    if (thr) {
+        gmax = pmax[b * APART];
+        for (int k = 1; k < APART; ++k) gmax = fmaxf(gmax, pmax[b * APART + k]);
+        gmax *= inv_temp;
+        t = thr[b];
+        cand = (1.0f - top_p) / (float)V;
+    }
+    auto proc = [&](float l) -> float {
+        if (!thr) return l;
+        const float p = __expf(__builtin_fmaf(l, inv_temp, -gmax));
+        return (p > cand && p > t) ? l * inv_temp : -INFINITY;
+    };
+    const int lo = blockIdx.x * GS_CHUNK, hi = (lo + GS_CHUNK < V ? lo + GS_CHUNK : V);
+    const bool vec = (V & 3) == 0 && ((((uintptr_t)logits) | (uintptr_t)sc | (uintptr_t)lg) & 15) == 0;
+    if (vec) {
+        for (int i = lo + threadIdx.x * 4; i < hi; i += 1024) {
+            const float4 v = *reinterpret_cast<const float4 *>(row + i);
+            if (lg) *reinterpret_cast<float4 *>(lg + o + i) = v;
+            if (sc) *reinterpret_cast<float4 *>(sc + o + i) = make_float4(proc(v.x), proc(v.y), proc(v.z), proc(v.w));
+        }
+    } else {
+        for (int i = lo + threadIdx.x; i < hi; i += 256) {
+            const float v = row[i];
+            if (lg) lg[o + i] = v;
+            if (sc) sc[o + i] = proc(v);
+        }
+    }
+}
+hipError_t launch_gen_scores(const float *logits, int B, int V, const GenOutDesc *out, const int32_t *step, int max_new,
+                             float temperature, float top_p, const float *pmax, const float *thr, hipStream_t s) {
+    hipLaunchKernelGGL(gen_scores_kernel, dim3((V + GS_CHUNK - 1) / GS_CHUNK, B), dim3(256), 0, s, logits, V, out, step, max_new,
+                       thr ? 1.0f / temperature : 1.0f, top_p, pmax, thr);
     return hipGetLastError();
 }
 
@@ -694,11 +887,13 @@ __global__ __launch_bounds__(256) void sample_stage1_kernel(const float *__restr
 constexpr int SAMPLE_LDS_CAP = 6144;
 // thr_out != nullptr: no draw - the row's keep threshold (a token is kept iff its p = exp(l / T - max / T) exceeds it) is written
 // there instead (beam-sample: beam.hip draws M continuations per batch row from the K filtered rows jointly).
+// thr_keep != nullptr: the draw's threshold is exported there as well (generate()'s output_scores: gen_scores_kernel).
 __global__ __launch_bounds__(256) void sample_stage2_kernel(int V, float top_p, int top_k, const uint64_t *__restrict__ seed_p,
                                                             const int32_t *__restrict__ step, const float *__restrict__ cand_p,
                                                             const int32_t *__restrict__ cand_i, const int32_t *__restrict__ cand_n,
                                                             const float *__restrict__ zpart, const float *__restrict__ spart,
-                                                            int32_t *__restrict__ chosen, float *__restrict__ thr_out) {
+                                                            int32_t *__restrict__ chosen, float *__restrict__ thr_out,
+                                                            float *__restrict__ thr_keep) {
     __shared__ float scratch[4];
     __shared__ float s_pref[257];
     __shared__ float s_wtot[4];
@@ -814,6 +1009,7 @@ __global__ __launch_bounds__(256) void sample_stage2_kernel(int V, float top_p, 
             if (tid == 0) thr_out[b] = lo_e;
             return;
         }
+        if (thr_keep && tid == 0) thr_keep[b] = lo_e;
         draw(lo_e);
         return;
     }
@@ -855,17 +1051,20 @@ __global__ __launch_bounds__(256) void sample_stage2_kernel(int V, float top_p, 
         if (tid == 0) thr_out[b] = lo;
         return;
     }
+    if (thr_keep && tid == 0) thr_keep[b] = lo;
     draw(lo);
 }
 
 hipError_t launch_sample_select(const float *logits, int B, int V, float temperature, float top_p, int top_k, const uint64_t *seed,
                                 const int32_t *step, float *pmax, int32_t *pidx, float *cand_p, int32_t *cand_i,
-                                int32_t *cand_n, float *zpart, float *spart, int32_t *chosen, float *thr_out, hipStream_t s) {
-    hipLaunchKernelGGL(argmax_partial_kernel, dim3(APART, B), dim3(256), 0, s, logits, V, pmax, pidx);
+                                int32_t *cand_n, float *zpart, float *spart, int32_t *chosen, float *thr_out, float *psum,
+                                float *thr_keep, hipStream_t s) {
+    if (psum) hipLaunchKernelGGL(argmax_lse_partial_kernel, dim3(APART, B), dim3(256), 0, s, logits, V, pmax, pidx, psum);
+    else hipLaunchKernelGGL(argmax_partial_kernel, dim3(APART, B), dim3(256), 0, s, logits, V, pmax, pidx);
     hipLaunchKernelGGL(sample_stage1_kernel, dim3(APART, B), dim3(256), 0, s, logits, V, 1.0f / temperature, top_p, pmax, cand_p,
                        cand_i, cand_n, zpart, spart);
     hipLaunchKernelGGL(sample_stage2_kernel, dim3(B), dim3(256), 0, s, V, top_p, top_k, seed, step, cand_p, cand_i, cand_n, zpart,
-                       spart, chosen, thr_out);
+                       spart, chosen, thr_out, thr_keep);
     return hipGetLastError();
 }
 

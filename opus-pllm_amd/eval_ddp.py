@@ -30,13 +30,15 @@ from opus_pllm_amd.prompt import after_process_output, build_prompt, max_new_tok
 
 
 def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperature=0.0, top_p=0.7, num_beams=1,
-             use_input_embed=False, device=None, logits_out=None, stop_sequence=None, inflight=1):
+             use_input_embed=False, device=None, logits_out=None, stop_sequence=None, inflight=1, logprobs_out=None):
     """The batch loop of run_opus_ddp.py:88-134 over this rank's items -> [n, max_new] new ids (rows padded with eos).
 
     use_input_embed (two-stage pipeline): the `input_embed` vectors of the WHOLE shard go through the modality
     projectors once, at M = len(items) (model.project_dataset), and the decode batches consume the stored protein tokens;
     without it every batch encodes and projects its own proteins, as the reference does.
     logits_out (a list, --dump_logits): receives the fp32 [b, V] logits of each batch's last decode step (model.last_logits).
+    logprobs_out (a list, --save_logprobs): receives ([n, max_new] fp32 token log-probabilities, 0 after a row's end, [n] counted
+    positions) - generate(return_dict_in_generate=True, output_token_logprobs=True).
     inflight (--inflight): batches in flight on this GPU.  The reference's loop is strictly sequential; with n > 1, n contexts
     that share the model's weights (model.new_context()) take the batches round-robin from n host threads - batches are
     independent, results come back in input order and are the same ids as with one context: greedy ids because the kernels are
@@ -49,6 +51,7 @@ def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperatu
     starts = list(range(0, len(items), batch_size))
     outs = [None] * len(starts)
     last = [None] * len(starts)
+    lps = [None] * len(starts)
     # one sampler seed per batch, drawn in input order before any worker thread starts (generate() would otherwise draw it from
     # the global generator at call time: with two threads racing, which batch got which seed depended on thread scheduling)
     seeds = [int(torch.randint(0, 2 ** 62, (1,)).item()) for _ in starts] if temperature > 0 else [None] * len(starts)
@@ -61,11 +64,18 @@ def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperatu
         ids = opa.left_pad_sequence(ids, padding_value=tokenizer.pad_token_id, batch_first=True)
         mask = ids != tokenizer.pad_token_id
         extra = {} if prot_all is None else {"protein_tokens": prot_all[i:i + len(batch)]}
+        if logprobs_out is not None:
+            extra.update(return_dict_in_generate=True, output_token_logprobs=True)
         with torch.inference_mode():
             out = m.generate(ids, [q["input"] for q in batch], attention_mask=mask, pad_token_id=tokenizer.eos_token_id,
                              do_sample=temperature > 0, temperature=temperature, top_p=top_p,
                              num_beams=num_beams, max_new_tokens=max_new, use_cache=True, stop_sequence=stop_sequence,
                              seed=seeds[j], **extra)
+        if logprobs_out is not None:
+            lp = torch.zeros((out.sequences.shape[0], max_new), dtype=torch.float32, device=dev)
+            lp[:, : out.token_logprobs.shape[1]] = out.token_logprobs
+            lps[j] = (lp, out.n_tokens)
+            out = out.sequences
         if logits_out is not None:
             last[j] = m.last_logits(len(batch))
         full = torch.full((out.shape[0], max_new), tokenizer.eos_token_id, dtype=torch.long, device=dev)
@@ -99,6 +109,8 @@ def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperatu
             raise errs[0]
     if logits_out is not None:
         logits_out.extend(last)
+    if logprobs_out is not None:
+        logprobs_out.extend(lps)
     return torch.cat(outs) if outs else torch.empty((0, max_new), dtype=torch.long, device=dev)
 
 
@@ -139,10 +151,16 @@ def eval_model(args):
     dev = torch.device("cuda", local)
     t0 = time.time()
     logits = [] if args.dump_logits else None
+    lps = [] if args.save_logprobs else None
     local_ids = annotate(model, tokenizer, mine, args.input_path, args.batch_size, max_new, args.temperature, args.top_p,
                          args.num_beams, args.use_input_embed, dev, logits,
-                         tokenizer.encode("###", add_special_tokens=False) if args.stop_at_hashes else None, inflight=args.inflight)
+                         tokenizer.encode("###", add_special_tokens=False) if args.stop_at_hashes else None, inflight=args.inflight,
+                         logprobs_out=lps)
     all_ids = odist.all_gather_ids(local_ids, tokenizer.eos_token_id)
+    if lps is not None:         # [n, max_new] log-probabilities and [n] counted positions, in rank order
+        loc_lp = torch.cat([x[0] for x in lps]) if lps else torch.empty((0, max_new), dtype=torch.float32, device=dev)
+        loc_n = torch.cat([x[1] for x in lps]).view(-1, 1) if lps else torch.empty((0, 1), dtype=torch.long, device=dev)
+        all_lp, all_n = odist.all_gather_logits(loc_lp).cpu(), odist.all_gather_ids(loc_n, 0).view(-1).cpu()
     if logits is not None:      # parity dump: last-step fp32 logits of every item, gathered in rank order over RCCL
         loc = torch.cat(logits) if logits else torch.empty((0, model.cfg.dec_vocab), dtype=torch.float32, device=dev)
         all_logits = odist.all_gather_logits(loc)
@@ -152,6 +170,11 @@ def eval_model(args):
         dt = time.time() - t0
         texts = [after_process_output(t) for t in tokenizer.batch_decode(all_ids, skip_special_tokens=True)]
         result = [{"ground_truth": q["output"], "generated": t} for q, t in zip(qs, texts)]
+        if lps is not None:     # over the row's counted tokens (its EOS / "###" included)
+            for k, r in enumerate(result):
+                row = all_lp[k, : int(all_n[k])]
+                r["logprob"] = float(row.double().sum())
+                r["token_logprobs"] = [float(v) for v in row]
         print(f"entries/sec: {n / dt}, time elapsed: {dt}")
         with open(args.save_path, "w") as f:
             json.dump(result, f)
@@ -184,6 +207,9 @@ if __name__ == "__main__":
     p.add_argument("--inflight", type=int, default=2,
                    help="batches in flight per GPU (contexts sharing the weights, one host thread each): with 2, one batch's kernels "
                         "fill the other's launch gaps and ramps (+10 %% throughput at batch 64; same ids)")
+    p.add_argument("--save_logprobs", action="store_true",
+                   help="each saved item also gets `logprob` and `token_logprobs`: the log-probabilities of its generated tokens "
+                        "(greedy or sampling; computed on the GPU in the decode loop)")
     p.add_argument("--dump_logits", type=str, default=None,
                    help="parity dump: save the fp32 last-step logits of every item ([n, V], input order) to this .pt file")
     eval_model(p.parse_args())

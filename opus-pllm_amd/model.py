@@ -369,8 +369,25 @@ class OpusLlamaForCausalLM:
 
     # ------------------------------------------------------------------ rows G0, G1, D1-D4
     @torch.no_grad()
-    def generate(self, inputs: Optional[torch.Tensor] = None, seq=None, seq_embedding=None, **kwargs) -> torch.LongTensor:
-        """opus_llama.py:95-132 + GenerationMixin greedy search: returns ONLY the new ids [B, n_new]."""
+    def generate(self, inputs: Optional[torch.Tensor] = None, seq=None, seq_embedding=None, **kwargs):
+        """opus_llama.py:95-132 + GenerationMixin greedy search: returns ONLY the new ids [B, n_new].
+
+        return_dict_in_generate=True returns a GenerateDecoderOnlyOutput (greedy, sampling) or a GenerateBeamDecoderOnlyOutput
+        (num_beams > 1: `sequences`, `sequences_scores`) instead, `sequences` holding those same ids.  Without it the output_*
+        flags are ignored, as in transformers.  Greedy and sampling only:
+          output_scores: `scores`, one fp32 [B, V] device tensor per step - HF's processed scores (greedy: the logits; sampling:
+            logits / temperature, -inf where top-k / top-p removed the token - the set the draw used);
+          output_logits: `logits`, the raw fp32 logits per step (greedy: the same tensors as `scores`);
+          output_token_logprobs (extension): `token_logprobs` fp32 [B, n] (log-probability of the chosen token under the
+            model's distribution, 0 after a row finished; its EOS / last stop-sequence token counts), `logprob` [B] (row
+            sums), `n_tokens` [B] (positions counted) - no [B, V] tensor is kept per step."""
+        return_dict = bool(kwargs.pop("return_dict_in_generate", False))
+        want = {k: bool(kwargs.pop(k, False)) for k in ("output_scores", "output_logits", "output_token_logprobs",
+                                                         "output_attentions", "output_hidden_states")}
+        if return_dict:
+            for k in ("output_attentions", "output_hidden_states"):
+                if want[k]:
+                    raise NotImplementedError(f"generate({k}=True) is not supported: the decode path keeps no per-layer tensors")
         kwargs.pop("position_ids", None)
         protein_tokens = kwargs.pop("protein_tokens", None)
         attention_mask = kwargs.pop("attention_mask", None)
@@ -383,6 +400,9 @@ class OpusLlamaForCausalLM:
         seed = kwargs.pop("seed", None)
         num_beams = kwargs.pop("num_beams", 1)
         num_beams = 1 if num_beams is None else int(num_beams)
+        if return_dict and num_beams > 1 and (want["output_scores"] or want["output_logits"] or want["output_token_logprobs"]):
+            raise NotImplementedError("with num_beams > 1, return_dict_in_generate returns `sequences` and `sequences_scores` only: "
+                                      "output_scores / output_logits / output_token_logprobs are built for greedy and sampling")
         max_new = int(kwargs.pop("max_new_tokens", 32))
         kwargs.pop("use_cache", None)
         self.set_stop_sequence(kwargs.pop("stop_sequence", None))          # extension (opt-in "###" early stop), see below
@@ -416,8 +436,37 @@ class OpusLlamaForCausalLM:
                                 device=self.device)
             embeds, mask, _ = self._splice(inputs, attention_mask, dummy, True)
         if num_beams > 1:
-            return self._beam_search(embeds, mask, max_new, eos, beam_pad, num_beams, sampler)
-        return self._greedy(embeds, mask, max_new, eos, int(pad_id), sampler)
+            ids = self._beam_search(embeds, mask, max_new, eos, beam_pad, num_beams, sampler)
+            if not return_dict:
+                return ids
+            return GenerateBeamDecoderOnlyOutput(sequences=ids, sequences_scores=self.last_beam_scores.to(self.device))
+        if not return_dict:
+            return self._greedy(embeds, mask, max_new, eos, int(pad_id), sampler)
+        return self._greedy(embeds, mask, max_new, eos, int(pad_id), sampler,
+                            outputs=(want["output_token_logprobs"], want["output_scores"], want["output_logits"]))
+
+    def compute_transition_scores(self, sequences: torch.Tensor, scores, beam_indices: Optional[torch.Tensor] = None,
+                                  normalize_logits: bool = False) -> torch.Tensor:
+        """transformers' GenerationMixin.compute_transition_scores: the score of each generated token, [B, n].  `sequences`
+        holds the new ids only (what generate() returns here); `scores` is out.scores or out.logits; normalize_logits=True
+        applies a log-softmax over the vocabulary first (on out.logits: the token log-probabilities)."""
+        V = scores[0].shape[-1]
+        if beam_indices is None:
+            beam_indices = torch.arange(scores[0].shape[0]).view(-1, 1).to(sequences.device)
+            beam_indices = beam_indices.expand(-1, len(scores))
+        stacked = torch.stack(scores).reshape(len(scores), -1).transpose(0, 1)
+        if normalize_logits:
+            stacked = torch.nn.functional.log_softmax(stacked.reshape(-1, V, stacked.shape[-1]), dim=1)
+            stacked = stacked.reshape(-1, stacked.shape[-1])
+        beam_mask = beam_indices < 0
+        max_len = (1 - beam_mask.long()).sum(-1).max()
+        beam_indices = beam_indices.clone()[:, :max_len]
+        beam_mask = beam_mask[:, :max_len]
+        beam_indices[beam_mask] = 0
+        indices = sequences[:, sequences.shape[-1] - max_len:] + beam_indices * V
+        out = stacked.gather(0, indices)
+        out[beam_mask] = 0
+        return out
 
     # TopKLogitsWarper of the sampling paths.  The reference pins transformers 4.46.3 (requirements.txt:20), whose
     # GenerationConfig.top_k defaults to 50 whenever it samples (transformers >= 5 defaults to None); the reference's drivers never
@@ -506,8 +555,10 @@ class OpusLlamaForCausalLM:
         _cabi.check(self._lib.opus_set_stop_sequence(self._ctx, arr, len(ids)))
         self._stop_ids = ids
 
-    def _greedy(self, embeds, mask, max_new, eos, pad_id, sampler=None) -> torch.Tensor:
+    def _greedy(self, embeds, mask, max_new, eos, pad_id, sampler=None, outputs=None):
+        """outputs = (token_logprobs, scores, logits) flags: a GenerateDecoderOnlyOutput instead of the ids."""
         B, T, _ = embeds.shape
+        V = self.cfg.dec_vocab
         embeds = embeds.contiguous()
         mask = mask.to(torch.uint8).contiguous()
         s = self._enter()
@@ -522,7 +573,20 @@ class OpusLlamaForCausalLM:
             eos_arr = (C.c_int32 * max(1, len(eos)))(*eos)
             if sampler is not None:
                 self._set_top_k(sampler[3] if len(sampler) > 3 else self.default_top_k)
-            if sampler is None:
+            if outputs is not None:
+                want_lp, want_sc, want_lg = outputs
+                # fresh caller-owned tensors every call: their addresses reach the captured step through a device descriptor
+                lp = torch.zeros((B, max_new), dtype=torch.float32, device=self.device) if want_lp else None
+                sc = torch.empty((max_new, B, V), dtype=torch.float32, device=self.device) if want_sc else None
+                lg = torch.empty((max_new, B, V), dtype=torch.float32, device=self.device) if want_lg else None
+                if sampler is None and sc is not None and lg is not None:
+                    lg = None                                   # greedy: the processed scores are the logits - one tensor
+                t, p, sd = (sampler[0], sampler[1], sampler[2]) if sampler is not None else (0.0, 1.0, 0)
+                ptr = lambda x: None if x is None else x.data_ptr()                          # noqa: E731
+                _cabi.check(self._lib.opus_generate_scored(self._ctx, embeds.data_ptr(), mask.data_ptr(), B, T, max_new,
+                                                           eos_arr, len(eos), pad_id, t, p, sd, out.data_ptr(), C.byref(n_out),
+                                                           ptr(lp), ptr(sc), ptr(lg), s))
+            elif sampler is None:
                 _cabi.check(self._lib.opus_generate_greedy(self._ctx, embeds.data_ptr(), mask.data_ptr(), B, T, max_new,
                                                            eos_arr, len(eos), pad_id, out.data_ptr(), C.byref(n_out), s))
             else:
@@ -530,7 +594,20 @@ class OpusLlamaForCausalLM:
                                                            eos_arr, len(eos), pad_id, sampler[0], sampler[1], sampler[2],
                                                            out.data_ptr(), C.byref(n_out), s))
         self._leave()
-        return out[:, : n_out.value].long()              # (a copy: the id buffer is reused by the next call)
+        n = n_out.value
+        ids = out[:, :n].long()                          # (a copy: the id buffer is reused by the next call)
+        if outputs is None:
+            return ids
+        res = GenerateDecoderOnlyOutput(sequences=ids)
+        if want_sc:
+            res.scores = tuple(sc[k] for k in range(n))
+        if want_lg:
+            res.logits = res.scores if lg is None else tuple(lg[k] for k in range(n))
+        if want_lp:
+            res.token_logprobs = lp[:, :n]
+            res.logprob = res.token_logprobs.sum(dim=1)
+            res.n_tokens = counted_tokens(ids, eos, getattr(self, "_stop_ids", []))
+        return res
 
     def generate_from_tokens(self, d_tokens, d_lens, input_ids: torch.Tensor,
                              attention_mask: Optional[torch.Tensor], max_new_tokens: int, eos: Sequence[int] = (),
@@ -935,6 +1012,79 @@ class ContinuationScores:
 
     def __init__(self, token_logprobs: torch.Tensor, logprob: torch.Tensor, n_tokens: torch.Tensor):
         self.token_logprobs, self.logprob, self.n_tokens = token_logprobs, logprob, n_tokens
+
+
+def counted_tokens(ids: torch.Tensor, eos: Sequence[int], stop: Sequence[int] = ()) -> torch.Tensor:
+    """Positions of each row of new ids [B, n] up to and including the token that finished it - an EOS id, or the last id of the
+    stop sequence - or all n (int64 [B], on the device of `ids`): the positions generate()'s token_logprobs count."""
+    B, n = ids.shape
+    if n == 0:
+        return torch.zeros(B, dtype=torch.int64, device=ids.device)
+    done = torch.zeros((B, n), dtype=torch.bool, device=ids.device)
+    if len(eos):
+        done |= torch.isin(ids, torch.tensor(list(eos), dtype=ids.dtype, device=ids.device))
+    k = len(stop)
+    if k and n >= k:
+        win = ids.unfold(1, k, 1)                                       # [B, n - k + 1, k]: ids t - k + 1 .. t
+        done[:, k - 1:] |= (win == torch.tensor(list(stop), dtype=ids.dtype, device=ids.device)).all(-1)
+    pos = torch.arange(1, n + 1, device=ids.device).expand(B, n)
+    return torch.where(done, pos, torch.full_like(pos, n)).min(dim=1).values
+
+
+class _FieldsOutput:
+    """Indexed like transformers' ModelOutput: attributes and keys are the fields in `_fields`; keys(), integer indices,
+    iteration and to_tuple() run over the fields that are not None.  Other attributes are extensions (attributes only)."""
+    _fields: tuple = ()
+
+    def keys(self):
+        return [k for k in self._fields if getattr(self, k) is not None]
+
+    def to_tuple(self):
+        return tuple(getattr(self, k) for k in self.keys())
+
+    def __getitem__(self, k):
+        if isinstance(k, str):
+            if k not in self.keys():
+                raise KeyError(k)
+            return getattr(self, k)
+        return self.to_tuple()[k]
+
+    def __contains__(self, k):
+        return k in self.keys()
+
+    def __iter__(self):
+        return iter(self.keys())
+
+    def __len__(self):
+        return len(self.keys())
+
+
+class GenerateDecoderOnlyOutput(_FieldsOutput):
+    """generate(return_dict_in_generate=True) for greedy and sampling, as transformers' class of that name: `sequences` (the
+    new ids [B, n]), `scores` / `logits` (tuples of n fp32 [B, V] tensors, or None); `attentions`, `hidden_states` and
+    `past_key_values` stay None.  Extension fields (output_token_logprobs=True; attributes only): `token_logprobs` fp32 [B, n],
+    `logprob` fp32 [B], `n_tokens` [B]."""
+    _fields = ("sequences", "scores", "logits", "attentions", "hidden_states", "past_key_values")
+
+    def __init__(self, sequences=None, scores=None, logits=None, attentions=None, hidden_states=None, past_key_values=None,
+                 token_logprobs=None, logprob=None, n_tokens=None):
+        self.sequences, self.scores, self.logits = sequences, scores, logits
+        self.attentions, self.hidden_states, self.past_key_values = attentions, hidden_states, past_key_values
+        self.token_logprobs, self.logprob, self.n_tokens = token_logprobs, logprob, n_tokens
+
+
+class GenerateBeamDecoderOnlyOutput(_FieldsOutput):
+    """generate(return_dict_in_generate=True, num_beams > 1), as transformers' class of that name: `sequences` (the best
+    hypothesis of every row, new ids [B, n]) and `sequences_scores` fp32 [B] (its length-normalised log-probability, the value
+    last_beam_scores holds); the per-step fields stay None."""
+    _fields = ("sequences", "sequences_scores", "scores", "logits", "beam_indices", "attentions", "hidden_states",
+               "past_key_values")
+
+    def __init__(self, sequences=None, sequences_scores=None, scores=None, logits=None, beam_indices=None, attentions=None,
+                 hidden_states=None, past_key_values=None):
+        self.sequences, self.sequences_scores, self.scores, self.logits = sequences, sequences_scores, scores, logits
+        self.beam_indices, self.attentions, self.hidden_states, self.past_key_values = (beam_indices, attentions, hidden_states,
+                                                                                         past_key_values)
 
 
 class CausalLMOutput:
