@@ -138,7 +138,9 @@ __global__ __launch_bounds__(256) void beam_sample_kernel(const float *__restric
             if (!(p > th) && !(l >= lm)) continue;
             const float a = (l - off) * inv_temp + add;
             const uint64_t h = splitmix64(h0 + 0xD1B54A32D192ED03ull * (uint64_t)(v + 1));
-            const float u = ((float)(h >> 40) + 0.5f) * (1.0f / 16777216.0f);      // (0, 1)
+            // (0, 1) on a 23-bit grid: k + 0.5 with k < 2^23 is exact in fp32.  (With 24 bits, k + 0.5 rounds to even from 2^23 on and
+            //  k = 2^24 - 1 gave u = 1: an infinite key that drew its token first whatever its weight.)
+            const float u = ((float)(h >> 41) + 0.5f) * (1.0f / 8388608.0f);
             const float key = a - __logf(-__logf(u));
             const int id = k * V + v;
             if (key > bk[BEAM_MAXM - 1] || (key == bk[BEAM_MAXM - 1] && id < bi[BEAM_MAXM - 1])) {

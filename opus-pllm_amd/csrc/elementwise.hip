@@ -792,7 +792,9 @@ __device__ __forceinline__ float block_max256(float v, float *scratch) {
 }
 
 // inclusive prefix sums over the 256 threads of a workgroup: wave scans by shuffles + the four wave totals through LDS (two
-// barriers instead of a 256-step serial walk by one thread).  Fixed order: reproducible; non-decreasing for non-negative inputs.
+// barriers instead of a 256-step serial walk by one thread).  Fixed order: reproducible.  Exact, hence non-decreasing, for ints;
+// NOT for fp32: every thread sums its prefix in its own association, so a thread that adds 0 can still land an ulp above or below
+// its neighbour (the draw below makes its interval bounds monotone with block_incl_max256).
 template <class T>
 __device__ __forceinline__ T block_incl_scan256(T v, T *sw) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -808,6 +810,21 @@ __device__ __forceinline__ T block_incl_scan256(T v, T *sw) {
     T base = 0;
     for (int w = 0; w < wave; ++w) base += sw[w];
     return base + x;
+}
+// inclusive prefix maximum over the 256 threads (the same shape; max is exact, so the result is non-decreasing)
+__device__ __forceinline__ float block_incl_max256(float v, float *sw) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float y = __shfl_up(x, o, 64);
+        if (lane >= o) x = fmaxf(x, y);
+    }
+    __syncthreads();
+    if (lane == 63) sw[wave] = x;
+    __syncthreads();
+    for (int w = 0; w < wave; ++w) x = fmaxf(x, sw[w]);
+    return x;
 }
 
 // Stage 1 (APART workgroups per row, after argmax_partial has left the per-part maxima): p_i = exp(l_i/T - max),
@@ -936,7 +953,10 @@ __global__ __launch_bounds__(256) void sample_stage2_kernel(int V, float top_p, 
             mine += p > lo ? p : 0.f;
         }
         const float incl = block_incl_scan256<float>(mine, s_wtot);
-        s_pref[tid + 1] = incl;                      // (the intervals [s_pref[t], s_pref[t + 1]) partition [0, total) exactly)
+        // the fp32 scan is not monotone (see there): the interval bounds are the running MAXIMUM of the scan over the threads that
+        // hold kept mass, so a thread without kept mass owns an empty interval and the intervals [s_pref[t], s_pref[t + 1])
+        // partition [0, total) - exactly one thread owns the target (u < 1: u * total rounds below total)
+        s_pref[tid + 1] = block_incl_max256(mine > 0.f ? incl : 0.f, s_wtot);
         if (tid == 0) s_pref[0] = 0.f;
         __syncthreads();
         const float total = s_pref[256];
@@ -954,7 +974,7 @@ __global__ __launch_bounds__(256) void sample_stage2_kernel(int V, float top_p, 
                     if (target < run) { pick = id; break; }
                 }
             }
-            chosen[b] = pick >= 0 ? pick : last_kept;
+            if (last_kept >= 0) chosen[b] = pick >= 0 ? pick : last_kept;   // (the walk's own rounding may end short of target)
         }
     };
     if (in_lds)
