@@ -271,6 +271,32 @@ int opus_generate_scored(opus_ctx *ctx, const void *d_embeds, const uint8_t *d_m
  * need no alignment): d_idx [B] the arg-max (lowest index among ties, bitwise what the greedy step picks), d_lse [B]. */
 int opus_debug_argmax_lse(opus_ctx *ctx, const float *d_logits, int32_t B, int32_t V, int32_t *d_idx, float *d_lse, void *stream);
 
+/* generate()'s logits processors, transformers' semantics and order (GenerationMixin._get_logits_processor): the repetition
+ * penalty, no_repeat_ngram_size, bad_words_ids, then min_new_tokens; under sampling the temperature / top-k / top-p warpers follow.
+ * The setting applies to the opus_generate_greedy / _sample / _scored calls of this context that follow (not to beam search),
+ * until it is set again; all defaults (1.0, 0, 0, no entries) clear it, and the calls are then exactly those without processors.
+ *   repetition_penalty p > 0 (1: off): every DISTINCT id of the row's history is changed once, s < 0 ? s * p : s / p (fp32).
+ *   no_repeat_ngram_size n >= 0 (0: off): with t >= n - 1 ids generated, the id that followed each earlier occurrence of the last
+ *     n - 1 ids is -inf.
+ *   min_new_tokens m >= 0 (0: off): the call's EOS ids are -inf while fewer than m ids have been generated (no EOS ids: no-op).
+ *   bad words (HOST arrays): entry e = bad_ids[bad_offsets[e] .. bad_offsets[e + 1]), n_bad + 1 offsets from 0.  A single id is
+ *     -inf at every step unless it is one of the call's EOS ids (transformers drops such entries); the last id of a longer entry
+ *     is -inf when the history is at least as long as the entry and ends with its other ids.  Ids lie in [0, dec_vocab).
+ * The history is the ids generated so far, never the prompt (the reference generates from inputs_embeds); a finished row's
+ * history holds its pad ids.  Capacities: at most 256 bad-word entries of 1 to 8 ids, 1024 ids in all; max_new <= 2048.
+ * With processors on, opus_generate_scored's d_scores hold the processed scores; d_logits and d_token_logprobs stay raw (the
+ * log-probability under the unprocessed distribution).  Only "on / off" is part of the captured step's identity: new values
+ * need no new graph.  Returns OPUS_EBADARG for a value out of range or over a capacity. */
+int opus_set_logits_processors(opus_ctx *ctx, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_new_tokens,
+                               const int32_t *bad_ids, const int32_t *bad_offsets, int32_t n_bad);
+/* Diagnostic: the processor kernel alone, in place on fp32 logits [B, V] (any B >= 1, V >= 1): row b's history is
+ * d_hist[b * hist_stride + 0 .. hist_len) (device; hist_len <= 2048), eos_ids a HOST array (at most 64), the setting as above
+ * (bad ids bounded by V).  Ordered on `stream`. */
+int opus_debug_logits_process(opus_ctx *ctx, float *d_logits, int32_t B, int32_t V, const int32_t *d_hist, int32_t hist_stride,
+                              int32_t hist_len, const int32_t *eos_ids, int32_t n_eos, float repetition_penalty,
+                              int32_t no_repeat_ngram_size, int32_t min_new_tokens, const int32_t *bad_ids,
+                              const int32_t *bad_offsets, int32_t n_bad, void *stream);
+
 /* Diagnostic entry points (kernel-level parity tests and micro-benchmarks; not part of the path's
  * drop-in surface).  opus_debug_gemm: C[M,Nout] = epi(A[M,K] W[N,K]^T + bias) (+ residual fp32);
  * epi 0 none, 1 erf-GELU, 2 silu(gate)*up with W rows in [16 gate | 16 up] groups (Nout = N/2).
@@ -372,7 +398,8 @@ int64_t opus_stat(opus_ctx *ctx, const char *name);
  * belongs to, and its ALGORITHMIC bytes and FLOPs.  opus_timing_get sums the records since the last reset that match
  * kernel_class and phase ("*" = any); opus_timing_names returns "class,class,...;phase,phase,..." .  Classes and phases are
  * addressed by name, never by position.  Order of the lists: phases are append-only ("score" last); among the classes "xent"
- * stays the last entry, as published since opus_llama_forward, and a class added later ("contact") is listed in front of it. */
+ * stays the last entry, as published since opus_llama_forward, and a class added later ("contact", "logitproc") is listed in front
+ * of it. */
 int opus_timing_enable(opus_ctx *ctx, int32_t on);
 int opus_timing_reset(opus_ctx *ctx);
 int opus_timing_get(opus_ctx *ctx, const char *kernel_class, const char *phase, double *ms, int64_t *launches, double *bytes,

@@ -120,6 +120,11 @@ SIGNATURES = {
     "opus_generate_scored": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32,
                                        C.c_float, C.c_float, C.c_uint64, _P, C.POINTER(C.c_int32), _P, _P, _P, _P]),
     "opus_debug_argmax_lse": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    "opus_set_logits_processors": (C.c_int, [_P, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                             C.c_int32]),
+    "opus_debug_logits_process": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                            C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32,
+                                            _P]),
     "opus_debug_gemm_rowscale": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                            C.c_float, C.POINTER(C.c_int32), _P]),
 }

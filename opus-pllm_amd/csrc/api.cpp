@@ -115,6 +115,7 @@ struct opus_ctx {
         const int32_t *out = nullptr;
         float temp = 0.f, top_p = 1.f;
         int outs = 0;                    // GEN_* flags of opus_generate_scored (the addresses come from the descriptor)
+        bool lproc = false;              // logits processors on (their values come from the descriptor d_lproc)
         uint64_t used = 0;
     };
     static constexpr int MAX_GRAPHS = 4;
@@ -130,6 +131,17 @@ struct opus_ctx {
     GenOutDesc h_gen{};
     float *d_gpsum = nullptr, *d_gthr = nullptr;
     int gen_outs = 0;                    // GEN_* flags of the running call (0: the plain step)
+    // logits processors (opus_set_logits_processors): the host setting, uploaded in stream order by every generate call, and a
+    // separate allocation made on first use - the device descriptor, the step word of opus_debug_logits_process, the output
+    // descriptors split into raw (before the processors) and processed (after), the raw rows' log-sum-exp and the raw logits of the
+    // history positions [max_batch, max_new_tokens]
+    bool lproc_on = false;
+    LogitsProcDesc h_lproc{1.0f, 0, 0, 0, {}, {}};
+    char *lproc_mem = nullptr;
+    LogitsProcDesc *d_lproc = nullptr;
+    int32_t *d_lstep = nullptr, *d_ridx = nullptr;
+    GenOutDesc *d_gen_raw = nullptr, *d_gen_proc = nullptr;
+    float *d_rlse = nullptr, *d_rawh = nullptr;
     // row-scale fusion (GemmParams::xh_out / row_ssq): one-shot request for the next gemm() and its outcome
     half_t *rq_xh = nullptr;
     int rq_done = 0;
@@ -395,6 +407,7 @@ extern "C" int opus_ctx_destroy(opus_ctx *c) {
     if (c->proj_big) (void)hipFree(c->proj_big);
     if (c->kv_tmp) (void)hipFree(c->kv_tmp);
     if (c->gen_mem) (void)hipFree(c->gen_mem);
+    if (c->lproc_mem) (void)hipFree(c->lproc_mem);
     if (c->h_nunf) (void)hipHostFree(c->h_nunf);
     for (auto &e : c->poll_ev) if (e) (void)hipEventDestroy(e);
     delete c;
@@ -1695,31 +1708,92 @@ static int ensure_gen_mem(opus_ctx *c) {
     return OPUS_OK;
 }
 
+static int ensure_lproc_mem(opus_ctx *c) {
+    if (c->lproc_mem) return OPUS_OK;
+    const size_t B = c->cfg.max_batch, N = c->cfg.max_new_tokens;
+    const size_t o_st = align_up(sizeof(LogitsProcDesc)), o_gr = o_st + align_up(B * sizeof(int32_t)),
+                 o_gp = o_gr + align_up(sizeof(GenOutDesc)), o_ls = o_gp + align_up(sizeof(GenOutDesc)),
+                 o_rh = o_ls + align_up(B * sizeof(float));
+    HIPC(hipMalloc((void **)&c->lproc_mem, o_rh + align_up(B * N * sizeof(float))));
+    c->d_lproc = reinterpret_cast<LogitsProcDesc *>(c->lproc_mem);
+    c->d_ridx = reinterpret_cast<int32_t *>(c->lproc_mem + o_st);
+    c->d_lstep = c->d_ridx;                               // (opus_debug_logits_process only: no generate call in flight uses both)
+    c->d_gen_raw = reinterpret_cast<GenOutDesc *>(c->lproc_mem + o_gr);
+    c->d_gen_proc = reinterpret_cast<GenOutDesc *>(c->lproc_mem + o_gp);
+    c->d_rlse = reinterpret_cast<float *>(c->lproc_mem + o_ls);
+    c->d_rawh = reinterpret_cast<float *>(c->lproc_mem + o_rh);
+    return OPUS_OK;
+}
+
+// the setting's words through the kernel arguments (stream order, no host buffer outlives the call): the header and the used
+// offsets, then the used ids
+static int upload_lproc(opus_ctx *c, const LogitsProcDesc &h, hipStream_t s) {
+    const int32_t *w = reinterpret_cast<const int32_t *>(&h);
+    const int head = (int)(offsetof(LogitsProcDesc, bad_off) / sizeof(int32_t)) + h.n_bad + 1;
+    int32_t *dw = reinterpret_cast<int32_t *>(c->d_lproc);
+    HIPC(launch_upload_i32(w, head, dw, s));
+    const int n_ids = h.bad_off[h.n_bad];
+    const int o_ids = (int)(offsetof(LogitsProcDesc, bad_ids) / sizeof(int32_t));
+    if (n_ids) HIPC(launch_upload_i32(w + o_ids, n_ids, dw + o_ids, s));
+    return OPUS_OK;
+}
+
+static int upload_gen_desc(const GenOutDesc &h, GenOutDesc *d, hipStream_t s) {
+    HIPC(launch_upload_i32(reinterpret_cast<const int32_t *>(&h), (int)(sizeof(GenOutDesc) / sizeof(int32_t)),
+                           reinterpret_cast<int32_t *>(d), s));
+    return OPUS_OK;
+}
+
 // next token per row: argmax (greedy) or temperature / top-p sampling, then the GenerationMixin bookkeeping.  With gen_outs set
 // (opus_generate_scored): the first pass also sums the parts' exponentials and the step kernel writes the chosen token's
 // log-probability (GEN_LOGPROBS), and / or the score writer copies the step's logits out (GEN_SCORES / GEN_LOGITS).
+//
+// Logits processors on (c->lproc_on): the processor kernel edits d_logits in place first, reading the history from d_out and the
+// setting from d_lproc.  The raw outputs are taken before it: the raw logits (GEN_LOGITS, through the raw half of the split output
+// descriptor) and the raw rows' log-sum-exp (GEN_LOGPROBS: one more pass over the logits); the kernel records the raw logit of every
+// history position, where the step kernel finds the chosen token's raw logit if a penalty changed it.  The selection, the scores
+// and the bookkeeping then run on the processed logits.
 static int argmax(opus_ctx *c, hipStream_t s, int max_new, int n_eos, int pad_id, int32_t *d_out) {
     c->phase = PH_DECODE;
     const opus_config &g = c->cfg;
     const int32_t *chosen = nullptr;
+    const bool proc = c->lproc_on;
     const bool lp = c->gen_outs & GEN_LOGPROBS, sc = c->gen_outs & (GEN_SCORES | GEN_LOGITS);
+    const size_t BV = (size_t)c->cur_B * g.dec_vocab;
+    if (proc) {
+        if (c->gen_outs & GEN_LOGITS)
+            KL(KC_OTHER, 8.0 * BV, launch_gen_scores(c->d_logits, c->cur_B, g.dec_vocab, c->d_gen_raw, c->d_step, max_new, 0.f, 1.f,
+                                                     nullptr, nullptr, s));
+        if (lp) {
+            KL(KC_OTHER, 4.0 * BV, launch_argmax_lse_partial(c->d_logits, c->cur_B, g.dec_vocab, c->d_pval, c->d_pidx, c->d_gpsum, s));
+            KL(KC_OTHER, 512.0 * c->cur_B, launch_argmax_lse_final(c->d_pval, c->d_pidx, c->d_gpsum, c->cur_B, c->d_ridx, c->d_rlse, s));
+        }
+        KL(KC_LOGITPROC, 12.0 * c->cur_B * max_new,
+           launch_logits_proc(c->d_logits, c->cur_B, g.dec_vocab, d_out, max_new, c->d_step, max_new, c->d_eos, n_eos, c->d_lproc,
+                              lp ? c->d_rawh : nullptr, s));
+    }
     if (c->samp_temp > 0.f) {
         KL(KC_OTHER, 4.0 * 4 * c->cur_B * g.dec_vocab,
            launch_sample_select(c->d_logits, c->cur_B, g.dec_vocab, c->samp_temp, c->samp_top_p, c->samp_top_k, c->d_seed, c->d_step,
                                 c->d_pval, c->d_pidx, c->d_probs, c->d_cand_i, c->d_cand_n, c->d_zpart, c->d_spart, c->d_chosen, nullptr,
-                                lp ? c->d_gpsum : nullptr, sc ? c->d_gthr : nullptr, s));
+                                lp && !proc ? c->d_gpsum : nullptr, sc ? c->d_gthr : nullptr, s));
         chosen = c->d_chosen;
-    } else if (lp) {
+    } else if (lp && !proc) {
         KL(KC_OTHER, 4.0 * c->cur_B * g.dec_vocab,
            launch_argmax_lse_partial(c->d_logits, c->cur_B, g.dec_vocab, c->d_pval, c->d_pidx, c->d_gpsum, s));
     } else {
         KL(KC_OTHER, 4.0 * c->cur_B * g.dec_vocab, launch_argmax_partial(c->d_logits, c->cur_B, g.dec_vocab, c->d_pval, c->d_pidx, s));
     }
-    if (sc)
-        KL(KC_OTHER, 4.0 * c->cur_B * g.dec_vocab * (1 + ((c->gen_outs & GEN_SCORES) ? 1 : 0) + ((c->gen_outs & GEN_LOGITS) ? 1 : 0)),
-           launch_gen_scores(c->d_logits, c->cur_B, g.dec_vocab, c->d_gen, c->d_step, max_new, c->samp_temp, c->samp_top_p, c->d_pval,
-                             c->samp_temp > 0.f ? c->d_gthr : nullptr, s));
-    if (lp)
+    if (proc ? (c->gen_outs & GEN_SCORES) != 0 : sc)
+        KL(KC_OTHER, 4.0 * c->cur_B * g.dec_vocab * (1 + ((c->gen_outs & GEN_SCORES) ? 1 : 0) + ((c->gen_outs & GEN_LOGITS) && !proc ? 1 : 0)),
+           launch_gen_scores(c->d_logits, c->cur_B, g.dec_vocab, proc ? c->d_gen_proc : c->d_gen, c->d_step, max_new, c->samp_temp,
+                             c->samp_top_p, c->d_pval, c->samp_temp > 0.f ? c->d_gthr : nullptr, s));
+    if (lp && proc)
+        KL(KC_OTHER, 512.0 * c->cur_B + 8.0 * c->cur_B * max_new,
+           launch_argmax_rawlp_step(c->d_pval, c->d_pidx, c->d_rlse, c->d_rawh, chosen, c->cur_B, c->d_eos, n_eos, pad_id, c->d_fin, d_out,
+                                    max_new, c->d_step, c->d_next, c->d_nunf, c->d_stop, c->n_stop, c->d_logits, g.dec_vocab,
+                                    c->d_gen_proc, s));
+    else if (lp)
         KL(KC_OTHER, 512.0 * c->cur_B + 8.0 * c->cur_B,
            launch_argmax_lse_step(c->d_pval, c->d_pidx, c->d_gpsum, chosen, c->cur_B, c->d_eos, n_eos, pad_id, c->d_fin, d_out, max_new,
                                   c->d_step, c->d_next, c->d_nunf, c->d_stop, c->n_stop, c->d_logits, g.dec_vocab, c->d_gen, s));
@@ -1762,6 +1836,16 @@ static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mas
             HIPC(hipMemcpyAsync(c->d_gen, &c->h_gen, sizeof(GenOutDesc), hipMemcpyHostToDevice, s));
         }
     }
+    if (c->lproc_on) {
+        if (max_new > LP_MAX_HIST)
+            return fail(OPUS_ESHAPE, "generate: logits processors keep a history of at most %d ids (max_new=%d)", LP_MAX_HIST, max_new);
+        OPC(ensure_lproc_mem(c));
+        OPC(upload_lproc(c, c->h_lproc, s));
+        if (gen_outs) {                      // raw logits before the processors, the rest after them
+            OPC(upload_gen_desc(GenOutDesc{nullptr, nullptr, outs->logits, nullptr}, c->d_gen_raw, s));
+            OPC(upload_gen_desc(GenOutDesc{outs->token_lp, outs->scores, nullptr, nullptr}, c->d_gen_proc, s));
+        }
+    }
     HIPC(hipMemsetAsync(c->d_fin, 0, B * sizeof(int32_t), s));
     HIPC(hipMemsetAsync(c->d_nunf, 0, (size_t)max_new * sizeof(int32_t), s));
     OPC(prefill(c, s, (const half_t *)d_embeds, d_mask, B, T));
@@ -1773,7 +1857,7 @@ static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mas
     auto find_graph = [&]() -> opus_ctx::GraphEntry * {
         for (auto &e : c->graphs)
             if (e.exec && e.B == B && e.maxnew == max_new && e.pad == pad_id && e.neos == n_eos && e.out == d_out_ids &&
-                e.temp == temperature && e.top_p == top_p && e.outs == gen_outs) return &e;
+                e.temp == temperature && e.top_p == top_p && e.outs == gen_outs && e.lproc == c->lproc_on) return &e;
         return nullptr;
     };
     opus_ctx::GraphEntry *ge = use_graph ? find_graph() : nullptr;
@@ -1804,6 +1888,7 @@ static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mas
                 ++c->graph_instantiations;
                 e.B = B; e.maxnew = max_new; e.pad = pad_id; e.neos = n_eos; e.temp = temperature; e.top_p = top_p; e.out = d_out_ids;
                 e.outs = gen_outs;
+                e.lproc = c->lproc_on;
                 if ((int)c->graphs.size() >= opus_ctx::MAX_GRAPHS) {           // least recently used out
                     size_t v = 0;
                     for (size_t k = 1; k < c->graphs.size(); ++k) if (c->graphs[k].used < c->graphs[v].used) v = k;
@@ -1850,6 +1935,67 @@ extern "C" int opus_set_stop_sequence(opus_ctx *c, const int32_t *ids, int32_t n
     if (n) HIPC(hipMemcpy(c->d_stop, ids, n * sizeof(int32_t), hipMemcpyHostToDevice));
     c->n_stop = n;
     drop_graphs(c);                                                               // the captured step holds n_stop
+    return OPUS_OK;
+}
+
+// A logits-processor setting from host values (opus_set_logits_processors / opus_debug_logits_process): checked against the
+// capacities; V > 0 also bounds the ids.
+static int make_lproc(LogitsProcDesc &d, float penalty, int32_t ngram, int32_t min_new, const int32_t *bad_ids, const int32_t *bad_off,
+                      int32_t n_bad, int V, const char *who) {
+    if (!(penalty > 0.f) || !(penalty < INFINITY)) return fail(OPUS_EBADARG, "%s: repetition_penalty must be a positive float", who);
+    if (ngram < 0) return fail(OPUS_EBADARG, "%s: no_repeat_ngram_size must be >= 0", who);
+    if (min_new < 0) return fail(OPUS_EBADARG, "%s: min_new_tokens must be >= 0", who);
+    if (n_bad < 0 || n_bad > LP_MAX_BAD) return fail(OPUS_EBADARG, "%s: %d bad-word entries (at most %d)", who, n_bad, LP_MAX_BAD);
+    if (n_bad > 0 && (!bad_ids || !bad_off)) return fail(OPUS_EBADARG, "%s: null bad-word table", who);
+    if (n_bad > 0 && bad_off[0] != 0) return fail(OPUS_EBADARG, "%s: bad_offsets[0] must be 0", who);
+    for (int e = 0; e < n_bad; ++e) {
+        const int L = bad_off[e + 1] - bad_off[e];
+        if (L < 1 || L > LP_MAX_BAD_LEN) return fail(OPUS_EBADARG, "%s: bad-word entry %d has %d ids (1 to %d)", who, e, L, LP_MAX_BAD_LEN);
+    }
+    const int n_ids = n_bad > 0 ? bad_off[n_bad] : 0;
+    if (n_ids > LP_MAX_BAD_IDS) return fail(OPUS_EBADARG, "%s: %d bad-word ids (at most %d in all)", who, n_ids, LP_MAX_BAD_IDS);
+    for (int i = 0; i < n_ids; ++i)
+        if (bad_ids[i] < 0 || (V > 0 && bad_ids[i] >= V)) return fail(OPUS_EBADARG, "%s: bad-word id %d outside [0, %d)", who, bad_ids[i], V);
+    d = LogitsProcDesc{penalty, ngram, min_new, n_bad, {}, {}};
+    for (int e = 0; e <= n_bad; ++e) d.bad_off[e] = n_bad > 0 ? bad_off[e] : 0;
+    for (int i = 0; i < n_ids; ++i) d.bad_ids[i] = bad_ids[i];
+    return OPUS_OK;
+}
+
+// generate()'s logits processors for the calls that follow (see include/opus_pllm.h).  Only "on / off" enters the captured step's
+// identity: the values travel in the device descriptor every call uploads, so a new penalty needs no new graph.
+extern "C" int opus_set_logits_processors(opus_ctx *c, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_new_tokens,
+                                          const int32_t *bad_ids, const int32_t *bad_offsets, int32_t n_bad) {
+    if (!c) return fail(OPUS_EBADARG, "ctx is null");
+    LogitsProcDesc d;
+    OPC(make_lproc(d, repetition_penalty, no_repeat_ngram_size, min_new_tokens, bad_ids, bad_offsets, n_bad, c->cfg.dec_vocab,
+                   "set_logits_processors"));
+    c->h_lproc = d;
+    c->lproc_on = d.penalty != 1.0f || d.ngram > 0 || d.min_new > 0 || d.n_bad > 0;
+    return OPUS_OK;
+}
+
+/* Diagnostic: the processor kernel alone on caller memory - fp32 logits [B, V] edited in place, history d_hist [B, hist_stride]
+   of hist_len ids per row, host EOS ids, the setting as opus_set_logits_processors takes it. */
+extern "C" int opus_debug_logits_process(opus_ctx *c, float *d_logits, int32_t B, int32_t V, const int32_t *d_hist, int32_t hist_stride,
+                                         int32_t hist_len, const int32_t *eos_ids, int32_t n_eos, float repetition_penalty,
+                                         int32_t no_repeat_ngram_size, int32_t min_new_tokens, const int32_t *bad_ids,
+                                         const int32_t *bad_offsets, int32_t n_bad, void *stream) {
+    if (!c || !d_logits || (hist_len > 0 && !d_hist) || (n_eos > 0 && !eos_ids)) return fail(OPUS_EBADARG, "debug_logits_process: null pointer");
+    if (B < 1 || V < 1 || hist_len < 0 || hist_len > LP_MAX_HIST || hist_stride < hist_len || n_eos < 0 || n_eos > 64)
+        return fail(OPUS_ESHAPE, "debug_logits_process: B=%d V=%d history %d (stride %d, at most %d) n_eos=%d", B, V, hist_len,
+                    hist_stride, LP_MAX_HIST, n_eos);
+    LogitsProcDesc d;
+    OPC(make_lproc(d, repetition_penalty, no_repeat_ngram_size, min_new_tokens, bad_ids, bad_offsets, n_bad, V, "debug_logits_process"));
+    HIPC(hipSetDevice(c->device));
+    OPC(ensure_lproc_mem(c));
+    hipStream_t s = (hipStream_t)stream;
+    c->phase = PH_OTHER;
+    OPC(upload_lproc(c, d, s));
+    if (n_eos) HIPC(launch_upload_i32(eos_ids, n_eos, c->d_eos, s));
+    HIPC(launch_upload_i32(&hist_len, 1, c->d_lstep, s));
+    KL(KC_LOGITPROC, 12.0 * B * hist_len, launch_logits_proc(d_logits, B, V, d_hist, hist_stride, c->d_lstep, hist_len, c->d_eos, n_eos,
+                                                             c->d_lproc, nullptr, s));
     return OPUS_OK;
 }
 
@@ -2213,7 +2359,8 @@ extern "C" int opus_timing_reset(opus_ctx *c) {
     return OPUS_OK;
 }
 static const char *kclass_names[KC_COUNT] = {"gemm_skinny", "gemm_mid", "gemm_wide", "gemm_ring", "gemm_pp", "gemm_tile", "splitk_reduce",
-                                            "attn_prefill", "attn_decode", "norm", "other", "gemm_stream", "contact", "xent"};
+                                            "attn_prefill", "attn_decode", "norm", "other", "gemm_stream", "contact", "logitproc",
+                                            "xent"};
 static const char *phase_names[PH_COUNT] = {"encode", "project", "splice", "prefill", "decode", "other", "score"};
 
 extern "C" int opus_timing_get(opus_ctx *c, const char *kernel_class, const char *phase, double *ms, int64_t *launches,

@@ -52,7 +52,7 @@ int skinny_max_m();   // rows up to which the skinny kernel is used (default 4, 
 constexpr int MID_MAX_M = 64;   // (65..128 rows measured faster on the split-K tile kernel)
 // kernel classes of the per-launch timing (opus_timing_get): one per kernel family
 enum KClass { KC_SKINNY = 0, KC_MID, KC_WIDE, KC_RING, KC_PP, KC_TILE, KC_REDUCE, KC_ATTN_PREFILL, KC_ATTN_DECODE, KC_NORM,
-              KC_OTHER, KC_STREAM, KC_CONTACT, KC_XENT, KC_COUNT };
+              KC_OTHER, KC_STREAM, KC_CONTACT, KC_LOGITPROC, KC_XENT, KC_COUNT };
 // Ordering rule of the published class list (opus_timing_names, include/opus_pllm.h): "xent" stays its last entry, as published
 // since opus_llama_forward, and a class added later goes in front of it.  Classes are looked up by name, never by index.
 // phases of the path a launch belongs to (set by the entry points of api.cpp)
@@ -391,9 +391,33 @@ hipError_t launch_argmax_lse_step(const float *pval, const int32_t *pidx, const 
                                   const float *logits, int V, const GenOutDesc *out, hipStream_t s);
 hipError_t launch_argmax_lse_final(const float *pval, const int32_t *pidx, const float *psum, int B, int32_t *idx, float *lse,
                                    hipStream_t s);
+// argmax_step + out->token_lp[b, step] = raw - lse[b] when logits processors edited the logits in place (opus_ctx::lproc_on):
+// lse [B] is the raw rows' log-sum-exp (taken before the processors ran); raw = raw_hist[b, i] at the first history position i that
+// holds the chosen token (logits_proc_kernel recorded the raw value there), else logits[b, tok] (a logit no processor touched)
+hipError_t launch_argmax_rawlp_step(const float *pval, const int32_t *pidx, const float *lse, const float *raw_hist,
+                                    const int32_t *chosen, int B, const int32_t *eos, int n_eos, int pad_id, int32_t *finished,
+                                    int32_t *out_ids, int max_new, const int32_t *step, int32_t *next_tok, int32_t *n_unfinished,
+                                    const int32_t *stop, int n_stop, const float *logits, int V, const GenOutDesc *out,
+                                    hipStream_t s);
 // out->scores / out->logits at the step (thr != nullptr: sampling - l / T where the draw kept the token, -inf elsewhere)
 hipError_t launch_gen_scores(const float *logits, int B, int V, const GenOutDesc *out, const int32_t *step, int max_new,
                              float temperature, float top_p, const float *pmax, const float *thr, hipStream_t s);
+// logits_proc.hip: generate()'s logits processors (opus_set_logits_processors), read by the captured step from device memory.
+// Capacities (include/opus_pllm.h): LP_MAX_BAD bad-word entries of at most LP_MAX_BAD_LEN ids, LP_MAX_BAD_IDS ids in all; a
+// history of at most LP_MAX_HIST ids.
+constexpr int LP_MAX_BAD = 256, LP_MAX_BAD_LEN = 8, LP_MAX_BAD_IDS = 1024, LP_MAX_HIST = 2048;
+struct LogitsProcDesc {
+    float penalty;                     // repetition_penalty (1: off)
+    int32_t ngram;                     // no_repeat_ngram_size (0: off)
+    int32_t min_new;                   // EOS ids are -inf while fewer ids have been generated (0: off)
+    int32_t n_bad;                     // bad-word entries: entry e = bad_ids[bad_off[e] .. bad_off[e + 1])
+    int32_t bad_off[LP_MAX_BAD + 1];
+    int32_t bad_ids[LP_MAX_BAD_IDS];
+};
+// in place on logits [B, V] (row stride V): the history of row b is hist[b * ld + 0 .. *step) (clamped to max_hist <= LP_MAX_HIST);
+// raw_hist (optional) [B, ld] receives the raw logit of every history position
+hipError_t launch_logits_proc(float *logits, int B, int V, const int32_t *hist, int64_t ld, const int32_t *step, int max_hist,
+                              const int32_t *eos, int n_eos, const LogitsProcDesc *desc, float *raw_hist, hipStream_t s);
 // beam.hip: best M of the K V continuations per batch row (log_softmax + running scores), cache rows of the surviving beams
 hipError_t launch_beam_topk(const float *logits, const float *run, int B, int K, int V, int M, float *lse, float *out_s,
                             int32_t *out_i, hipStream_t s);

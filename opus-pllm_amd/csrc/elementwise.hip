@@ -602,34 +602,52 @@ __device__ __forceinline__ float parts_lse(float mp, float sp, float M) {
 // GenerationMixin bookkeeping: finished rows emit pad_id; a row finishes when it emits an EOS id.
 // LP (argmax_lse_step_kernel): also the row's log-sum-exp from argmax_lse_partial's part sums, and the chosen token's
 // log-probability l[tok] - lse into out->token_lp[b, step] (0 for a row that had finished before this step).
-template <bool LP>
+// LP == 2 (argmax_rawlp_step_kernel, logits processors on): the logits hold the processed values, so the log-sum-exp comes from
+// lse_in[b] (the raw row's, taken before the processors ran) and the chosen token's raw logit from raw_hist when the token is in
+// the row's history (the only logits a processor changes and that can still be chosen: a ban is -inf).
+template <int LP>
 __device__ __forceinline__ void argmax_step_body(const float *__restrict__ pval, const int32_t *__restrict__ pidx,
                                                  const int32_t *__restrict__ chosen, const int32_t *__restrict__ eos, int n_eos,
                                                  int pad_id, int32_t *__restrict__ finished, int32_t *__restrict__ out_ids,
                                                  int max_new, const int32_t *__restrict__ step, int32_t *__restrict__ next_tok,
                                                  int32_t *__restrict__ n_unf, const int32_t *__restrict__ stop, int n_stop,
                                                  const float *__restrict__ logits, int V, const float *__restrict__ psum,
-                                                 const GenOutDesc *__restrict__ out) {
+                                                 const GenOutDesc *__restrict__ out, const float *__restrict__ lse_in = nullptr,
+                                                 const float *__restrict__ raw_hist = nullptr) {
     const int b = blockIdx.x, lane = threadIdx.x;
     float bv = pval[b * APART + lane];
     int bi = pidx[b * APART + lane];
-    const float mp = bv, sp = LP ? psum[b * APART + lane] : 0.f;
+    const float mp = bv, sp = LP == 1 ? psum[b * APART + lane] : 0.f;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float v = __shfl_xor(bv, o, 64);
         const int i = __shfl_xor(bi, o, 64);
         if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
     }
-    const float lse = LP ? parts_lse(mp, sp, bv) : 0.f;
+    float lse = LP == 1 ? parts_lse(mp, sp, bv) : 0.f;
     if (chosen) bi = chosen[b];               // sampling: the token was drawn by sample_select_kernel
+    float raw_tok = 0.f;
+    if (LP == 2) {                            // the chosen token's raw logit: its first history position, if any (all lanes)
+        const int st = *step, n = st < max_new ? st : max_new;
+        const int tok = finished[b] ? pad_id : (bi == 0x7fffffff ? 0 : bi);
+        int first = 0x7fffffff;
+        for (int i = lane; i < n; i += 64)
+            if (out_ids[(int64_t)b * max_new + i] == tok) { first = i; break; }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o, 64));
+        lse = lse_in[b];
+        raw_tok = first != 0x7fffffff ? raw_hist[(int64_t)b * max_new + first]
+                                      : ((unsigned)tok < (unsigned)V ? logits[(int64_t)b * V + tok] : NAN);
+    }
     if (lane == 0) {
         const int st = *step;
         int fin = finished[b];
         int tok = fin ? pad_id : (bi == 0x7fffffff ? 0 : bi);
         if (st < max_new) out_ids[(int64_t)b * max_new + st] = tok;
-        if (LP && st < max_new)
+        if (LP == 1 && st < max_new)
             out->token_lp[(int64_t)b * max_new + st] =
                 fin ? 0.f : ((unsigned)tok < (unsigned)V ? logits[(int64_t)b * V + tok] - lse : NAN);
+        if (LP == 2 && st < max_new) out->token_lp[(int64_t)b * max_new + st] = fin ? 0.f : raw_tok - lse;
         if (!fin)
             for (int e = 0; e < n_eos; ++e) fin |= (tok == eos[e]);
         // opt-in stop sequence (the ids of "###", which the reference cuts at after decoding: run_opus_ddp.py:19-27): a row
@@ -651,7 +669,7 @@ __global__ __launch_bounds__(64) void argmax_step_kernel(const float *__restrict
                                                          int max_new, const int32_t *__restrict__ step,
                                                          int32_t *__restrict__ next_tok, int32_t *__restrict__ n_unf,
                                                          const int32_t *__restrict__ stop, int n_stop) {
-    argmax_step_body<false>(pval, pidx, chosen, eos, n_eos, pad_id, finished, out_ids, max_new, step, next_tok, n_unf, stop, n_stop,
+    argmax_step_body<0>(pval, pidx, chosen, eos, n_eos, pad_id, finished, out_ids, max_new, step, next_tok, n_unf, stop, n_stop,
                             nullptr, 0, nullptr, nullptr);
 }
 __global__ __launch_bounds__(64) void argmax_lse_step_kernel(const float *__restrict__ pval, const int32_t *__restrict__ pidx,
@@ -663,8 +681,29 @@ __global__ __launch_bounds__(64) void argmax_lse_step_kernel(const float *__rest
                                                              const int32_t *__restrict__ stop, int n_stop,
                                                              const float *__restrict__ logits, int V, const float *__restrict__ psum,
                                                              const GenOutDesc *__restrict__ out) {
-    argmax_step_body<true>(pval, pidx, chosen, eos, n_eos, pad_id, finished, out_ids, max_new, step, next_tok, n_unf, stop, n_stop,
+    argmax_step_body<1>(pval, pidx, chosen, eos, n_eos, pad_id, finished, out_ids, max_new, step, next_tok, n_unf, stop, n_stop,
                            logits, V, psum, out);
+}
+__global__ __launch_bounds__(64) void argmax_rawlp_step_kernel(const float *__restrict__ pval, const int32_t *__restrict__ pidx,
+                                                               const int32_t *__restrict__ chosen,
+                                                               const int32_t *__restrict__ eos, int n_eos, int pad_id,
+                                                               int32_t *__restrict__ finished, int32_t *__restrict__ out_ids,
+                                                               int max_new, const int32_t *__restrict__ step,
+                                                               int32_t *__restrict__ next_tok, int32_t *__restrict__ n_unf,
+                                                               const int32_t *__restrict__ stop, int n_stop,
+                                                               const float *__restrict__ logits, int V, const GenOutDesc *__restrict__ out,
+                                                               const float *__restrict__ lse, const float *__restrict__ raw_hist) {
+    argmax_step_body<2>(pval, pidx, chosen, eos, n_eos, pad_id, finished, out_ids, max_new, step, next_tok, n_unf, stop, n_stop,
+                        logits, V, nullptr, out, lse, raw_hist);
+}
+hipError_t launch_argmax_rawlp_step(const float *pval, const int32_t *pidx, const float *lse, const float *raw_hist,
+                                    const int32_t *chosen, int B, const int32_t *eos, int n_eos, int pad_id, int32_t *finished,
+                                    int32_t *out_ids, int max_new, const int32_t *step, int32_t *next_tok, int32_t *n_unfinished,
+                                    const int32_t *stop, int n_stop, const float *logits, int V, const GenOutDesc *out,
+                                    hipStream_t s) {
+    hipLaunchKernelGGL(argmax_rawlp_step_kernel, dim3(B), dim3(64), 0, s, pval, pidx, chosen, eos, n_eos, pad_id, finished, out_ids,
+                       max_new, step, next_tok, n_unfinished, stop, n_stop, logits, V, out, lse, raw_hist);
+    return hipGetLastError();
 }
 hipError_t launch_argmax_step(const float *pval, const int32_t *pidx, const int32_t *chosen, int B, const int32_t *eos,
                               int n_eos, int pad_id, int32_t *finished, int32_t *out_ids, int max_new, const int32_t *step,

@@ -26,11 +26,13 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import opus_pllm_amd as opa                                                    # noqa: E402
 from opus_pllm_amd import dist as odist                                        # noqa: E402
 from opus_pllm_amd.builder import load_pretrained_model, return_cstp_path      # noqa: E402
-from opus_pllm_amd.prompt import after_process_output, build_prompt, max_new_tokens_for   # noqa: E402
+from opus_pllm_amd.prompt import (add_logits_processor_args, after_process_output, build_prompt,  # noqa: E402
+                                  logits_processor_kwargs, max_new_tokens_for)
 
 
 def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperature=0.0, top_p=0.7, num_beams=1,
-             use_input_embed=False, device=None, logits_out=None, stop_sequence=None, inflight=1, logprobs_out=None):
+             use_input_embed=False, device=None, logits_out=None, stop_sequence=None, inflight=1, logprobs_out=None,
+             processors=None):
     """The batch loop of run_opus_ddp.py:88-134 over this rank's items -> [n, max_new] new ids (rows padded with eos).
 
     use_input_embed (two-stage pipeline): the `input_embed` vectors of the WHOLE shard go through the modality
@@ -43,7 +45,8 @@ def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperatu
     that share the model's weights (model.new_context()) take the batches round-robin from n host threads - batches are
     independent, results come back in input order and are the same ids as with one context: greedy ids because the kernels are
     the same, sampled ids because every batch's sampler seed is drawn HERE, in input order, from torch's global generator
-    (torch.manual_seed reproduces a run whatever `inflight` is) and handed to generate(seed=...)."""
+    (torch.manual_seed reproduces a run whatever `inflight` is) and handed to generate(seed=...).
+    processors (--repetition_penalty / --no_repeat_ngram_size / --min_new_tokens): generate() keywords of its logits processors."""
     dev = device or model.device
     prot_all = None
     if use_input_embed and items:
@@ -64,6 +67,7 @@ def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperatu
         ids = opa.left_pad_sequence(ids, padding_value=tokenizer.pad_token_id, batch_first=True)
         mask = ids != tokenizer.pad_token_id
         extra = {} if prot_all is None else {"protein_tokens": prot_all[i:i + len(batch)]}
+        extra.update(processors or {})
         if logprobs_out is not None:
             extra.update(return_dict_in_generate=True, output_token_logprobs=True)
         with torch.inference_mode():
@@ -155,7 +159,7 @@ def eval_model(args):
     local_ids = annotate(model, tokenizer, mine, args.input_path, args.batch_size, max_new, args.temperature, args.top_p,
                          args.num_beams, args.use_input_embed, dev, logits,
                          tokenizer.encode("###", add_special_tokens=False) if args.stop_at_hashes else None, inflight=args.inflight,
-                         logprobs_out=lps)
+                         logprobs_out=lps, processors=logits_processor_kwargs(args))
     all_ids = odist.all_gather_ids(local_ids, tokenizer.eos_token_id)
     if lps is not None:         # [n, max_new] log-probabilities and [n] counted positions, in rank order
         loc_lp = torch.cat([x[0] for x in lps]) if lps else torch.empty((0, max_new), dtype=torch.float32, device=dev)
@@ -212,4 +216,5 @@ if __name__ == "__main__":
                         "(greedy or sampling; computed on the GPU in the decode loop)")
     p.add_argument("--dump_logits", type=str, default=None,
                    help="parity dump: save the fp32 last-step logits of every item ([n, V], input order) to this .pt file")
+    add_logits_processor_args(p)
     eval_model(p.parse_args())

@@ -31,7 +31,8 @@ import opus_pllm_amd as opa                                                    #
 from opus_pllm_amd import conversation as conversation_lib                     # noqa: E402
 from opus_pllm_amd import dist as odist                                        # noqa: E402
 from opus_pllm_amd.builder import load_pretrained_model, return_cstp_path      # noqa: E402
-from opus_pllm_amd.prompt import after_process_output, multichoice_prompt, score_multichoice   # noqa: E402
+from opus_pllm_amd.prompt import (add_logits_processor_args, after_process_output, logits_processor_kwargs,  # noqa: E402
+                                  multichoice_prompt, score_multichoice)
 
 
 def render_question(item, tokenizer) -> str:
@@ -127,7 +128,8 @@ def eval_model(args):
         with torch.inference_mode():
             out = model.generate(ids, [q["input"] for q in batch], attention_mask=mask, pad_token_id=tokenizer.eos_token_id,
                                  seq_embedding=None, do_sample=args.temperature > 0, temperature=args.temperature,
-                                 top_p=args.top_p, num_beams=args.num_beams, max_new_tokens=args.max_new_tokens, use_cache=True)
+                                 top_p=args.top_p, num_beams=args.num_beams, max_new_tokens=args.max_new_tokens, use_cache=True,
+                                 **logits_processor_kwargs(args))
         full = torch.full((out.shape[0], args.max_new_tokens), tokenizer.eos_token_id, dtype=torch.long, device=dev)
         full[:, : out.shape[1]] = out
         outs.append(full)
@@ -185,6 +187,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--max_prompt", type=int, default=384)
     p.add_argument("--rank_options", action="store_true",
                    help="rank the four answers by log-likelihood behind one cached prompt instead of generating")
+    add_logits_processor_args(p)
     return p
 
 

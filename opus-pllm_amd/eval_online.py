@@ -19,7 +19,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import opus_pllm_amd as opa                                                    # noqa: E402
 from opus_pllm_amd.builder import load_pretrained_model, return_cstp_path      # noqa: E402
 from opus_pllm_amd.conversation import conv_vicuna_v0                          # noqa: E402
-from opus_pllm_amd.prompt import is_protein_sequence, online_cut, online_prompt   # noqa: E402
+from opus_pllm_amd.prompt import (add_logits_processor_args, is_protein_sequence, logits_processor_kwargs,  # noqa: E402
+                                  online_cut, online_prompt)
 
 
 def answer_once(model, tokenizer, instruction: str, seq: str, args, conv=conv_vicuna_v0):
@@ -34,7 +35,8 @@ def answer_once(model, tokenizer, instruction: str, seq: str, args, conv=conv_vi
     with torch.inference_mode():
         out = model.generate(input_ids, seq, attention_mask=None, pad_token_id=tokenizer.eos_token_id, seq_embedding=None,
                              do_sample=args.temperature > 0, temperature=args.temperature, top_p=args.top_p,
-                             num_beams=args.num_beams, max_new_tokens=args.max_new_tokens, use_cache=True)
+                             num_beams=args.num_beams, max_new_tokens=args.max_new_tokens, use_cache=True,
+                             **logits_processor_kwargs(args))
     text = tokenizer.batch_decode(out, skip_special_tokens=True)[0]
     return shown, seq, online_cut(text, conv.sep)
 
@@ -79,4 +81,5 @@ if __name__ == "__main__":
     p.add_argument("--load-8bit", action="store_true")
     p.add_argument("--max_residues", type=int, default=1024)
     p.add_argument("--max_prompt", type=int, default=256)
+    add_logits_processor_args(p)
     eval_model(p.parse_args())

@@ -380,7 +380,11 @@ class OpusLlamaForCausalLM:
           output_logits: `logits`, the raw fp32 logits per step (greedy: the same tensors as `scores`);
           output_token_logprobs (extension): `token_logprobs` fp32 [B, n] (log-probability of the chosen token under the
             model's distribution, 0 after a row finished; its EOS / last stop-sequence token counts), `logprob` [B] (row
-            sums), `n_tokens` [B] (positions counted) - no [B, V] tensor is kept per step."""
+            sums), `n_tokens` [B] (positions counted) - no [B, V] tensor is kept per step.
+        Logits processors (greedy and sampling; transformers' semantics and order, before the sampling warpers):
+        repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_length / min_new_tokens (see _logits_processors).  They see
+        only the ids generated so far, never the prompt, as the reference's generate from inputs_embeds does.  With any of them on,
+        `scores` hold the processed scores while `logits` and `token_logprobs` stay raw; num_beams > 1 raises."""
         return_dict = bool(kwargs.pop("return_dict_in_generate", False))
         want = {k: bool(kwargs.pop(k, False)) for k in ("output_scores", "output_logits", "output_token_logprobs",
                                                          "output_attentions", "output_hidden_states")}
@@ -409,6 +413,12 @@ class OpusLlamaForCausalLM:
         pad_id = kwargs.pop("pad_token_id", self.generation_config.pad_token_id)
         eos = kwargs.pop("eos_token_id", self.generation_config.eos_token_id)
         eos = [] if eos is None else ([int(eos)] if isinstance(eos, int) else [int(e) for e in eos])
+        vocab = getattr(getattr(self, "cfg", None), "dec_vocab", None)
+        lproc = _logits_processors(kwargs, eos, vocab)
+        if num_beams > 1 and lproc is not None:
+            raise NotImplementedError("repetition_penalty / no_repeat_ngram_size / bad_words_ids / min_length / min_new_tokens are "
+                                      "built for greedy and sampling, not for num_beams > 1 (transformers applies them to the "
+                                      "beams' log-softmax scores)")
         sampler = None
         if do_sample:       # HF: temperature defaults to 1.0, top_p to 1.0; draws keyed by (seed, row, step)
             t = 1.0 if temperature is None else float(temperature)
@@ -435,6 +445,12 @@ class OpusLlamaForCausalLM:
             dummy = torch.zeros((inputs.shape[0], self.cfg.n_prot_tokens, self.cfg.dec_dim), dtype=_cabi.operand_dtype(),
                                 device=self.device)
             embeds, mask, _ = self._splice(inputs, attention_mask, dummy, True)
+        if lproc is not None:                  # min_length counts the spliced prompt (transformers' _prepare_generated_length)
+            pen, ngram, min_new, min_len, bad = lproc
+            if min_new is None:
+                min_new = max((min_len or 0) - int(embeds.shape[1]), 0)
+            lproc = (pen, ngram, min_new, bad)
+        self._set_logits_processors(lproc)
         if num_beams > 1:
             ids = self._beam_search(embeds, mask, max_new, eos, beam_pad, num_beams, sampler)
             if not return_dict:
@@ -555,6 +571,24 @@ class OpusLlamaForCausalLM:
         _cabi.check(self._lib.opus_set_stop_sequence(self._ctx, arr, len(ids)))
         self._stop_ids = ids
 
+    def _set_logits_processors(self, setting) -> None:
+        """setting = (repetition_penalty, no_repeat_ngram_size, min_new_tokens, bad_words_ids tuple) or None (off), applied to
+        this context's following generate calls; an unchanged setting costs nothing."""
+        if setting is not None and setting == (1.0, 0, 0, ()):
+            setting = None
+        if setting == getattr(self, "_lproc", None):
+            return
+        if setting is None:
+            _cabi.check(self._lib.opus_set_logits_processors(self._ctx, 1.0, 0, 0, None, None, 0))
+        else:
+            pen, ngram, min_new, bad = setting
+            flat = [t for w in bad for t in w]
+            offs = np.cumsum([0] + [len(w) for w in bad]).tolist()
+            ids = (C.c_int32 * max(1, len(flat)))(*flat)
+            off = (C.c_int32 * len(offs))(*offs)
+            _cabi.check(self._lib.opus_set_logits_processors(self._ctx, float(pen), int(ngram), int(min_new), ids, off, len(bad)))
+        self._lproc = setting
+
     def _greedy(self, embeds, mask, max_new, eos, pad_id, sampler=None, outputs=None):
         """outputs = (token_logprobs, scores, logits) flags: a GenerateDecoderOnlyOutput instead of the ids."""
         B, T, _ = embeds.shape
@@ -579,7 +613,7 @@ class OpusLlamaForCausalLM:
                 lp = torch.zeros((B, max_new), dtype=torch.float32, device=self.device) if want_lp else None
                 sc = torch.empty((max_new, B, V), dtype=torch.float32, device=self.device) if want_sc else None
                 lg = torch.empty((max_new, B, V), dtype=torch.float32, device=self.device) if want_lg else None
-                if sampler is None and sc is not None and lg is not None:
+                if sampler is None and sc is not None and lg is not None and getattr(self, "_lproc", None) is None:
                     lg = None                                   # greedy: the processed scores are the logits - one tensor
                 t, p, sd = (sampler[0], sampler[1], sampler[2]) if sampler is not None else (0.0, 1.0, 0)
                 ptr = lambda x: None if x is None else x.data_ptr()                          # noqa: E731
@@ -620,6 +654,7 @@ class OpusLlamaForCausalLM:
         int64 device tensor with the batch rows of bucket k), as encode_seq2embedding buckets strings."""
         cfg = self.cfg
         B = input_ids.shape[0]
+        self._set_logits_processors(None)       # (a previous generate()'s processors do not carry over; no-op when off)
         if bucket_rows == "packed":      # d_tokens: packed int32 [M] on the device; d_lens: the HOST row offsets cu [B + 1]
             s = self._enter()
             with torch.cuda.stream(self._stream):
@@ -1012,6 +1047,55 @@ class ContinuationScores:
 
     def __init__(self, token_logprobs: torch.Tensor, logprob: torch.Tensor, n_tokens: torch.Tensor):
         self.token_logprobs, self.logprob, self.n_tokens = token_logprobs, logprob, n_tokens
+
+
+# capacities of the processor kernel (include/opus_pllm.h, opus_set_logits_processors)
+LP_MAX_BAD, LP_MAX_BAD_LEN, LP_MAX_BAD_IDS = 256, 8, 1024
+
+
+def _logits_processors(kwargs: dict, eos: Sequence[int], vocab: Optional[int]):
+    """Pops generate()'s logits-processor options from kwargs and checks them as transformers does (ValueError), plus the
+    kernel's capacities.  Returns None when every option is off, else (repetition_penalty, no_repeat_ngram_size,
+    min_new_tokens or None, min_length or None, bad_words_ids as a tuple of tuples).  Off: repetition_penalty None / 1.0,
+    no_repeat_ngram_size None / 0 (transformers' defaults), no bad words, min_length / min_new_tokens None / 0 - and both are
+    no-ops without EOS ids (transformers builds no processor then).  min_new_tokens wins over min_length."""
+    pen = kwargs.pop("repetition_penalty", None)
+    ngram = kwargs.pop("no_repeat_ngram_size", None)
+    bad = kwargs.pop("bad_words_ids", None)
+    min_new = kwargs.pop("min_new_tokens", None)
+    min_len = kwargs.pop("min_length", None)
+    if pen is not None:
+        if isinstance(pen, bool) or not isinstance(pen, (int, float)) or not float(pen) > 0 or float(pen) == float("inf"):
+            raise ValueError(f"`repetition_penalty` has to be a strictly positive float, but is {pen}")
+        pen = float(pen)
+    if ngram is not None:
+        if isinstance(ngram, bool) or not isinstance(ngram, (int, np.integer)) or ngram < 0:
+            raise ValueError(f"`no_repeat_ngram_size` has to be a strictly positive integer, but is {ngram}")
+        ngram = int(ngram)
+    for name, v in (("min_new_tokens", min_new), ("min_length", min_len)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0):
+            raise ValueError(f"`{name}` has to be a non-negative integer, but is {v}")
+    if bad is not None:
+        if not isinstance(bad, (list, tuple)) or len(bad) == 0:
+            raise ValueError(f"`bad_words_ids` has to be a non-empty list, but is {bad}.")
+        if any(not isinstance(w, (list, tuple)) or len(w) == 0 for w in bad):
+            raise ValueError(f"`bad_words_ids` has to be a list of non-empty lists, but is {bad}.")
+        for w in bad:
+            for t in w:
+                if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or t < 0 or (vocab is not None and t >= vocab):
+                    raise ValueError(f"`bad_words_ids` holds ids in [0, {vocab if vocab is not None else 'V'}), but is {bad}.")
+        if len(bad) > LP_MAX_BAD:
+            raise ValueError(f"`bad_words_ids` has {len(bad)} entries: at most {LP_MAX_BAD} are built")
+        if max(len(w) for w in bad) > LP_MAX_BAD_LEN:
+            raise ValueError(f"a `bad_words_ids` entry has {max(len(w) for w in bad)} ids: at most {LP_MAX_BAD_LEN} are built")
+        if sum(len(w) for w in bad) > LP_MAX_BAD_IDS:
+            raise ValueError(f"`bad_words_ids` holds {sum(len(w) for w in bad)} ids: at most {LP_MAX_BAD_IDS} in all are built")
+        bad = tuple(tuple(int(t) for t in w) for w in bad)
+    if not eos:
+        min_new = min_len = None
+    if (pen is None or pen == 1.0) and not ngram and bad is None and not min_new and not min_len:
+        return None
+    return (1.0 if pen is None else pen, ngram or 0, min_new, min_len, bad or ())
 
 
 def counted_tokens(ids: torch.Tensor, eos: Sequence[int], stop: Sequence[int] = ()) -> torch.Tensor:

@@ -114,3 +114,19 @@ def online_cut(outputs: str, sep: str = "###") -> str:
     outputs = outputs.strip()
     idx = outputs.find(sep, 2)
     return (outputs if idx < 0 else outputs[:idx]).strip()
+
+
+def add_logits_processor_args(p) -> None:
+    """The drivers' generate() logits processors (transformers' options; all off by default, as in the reference's drivers)."""
+    p.add_argument("--repetition_penalty", type=float, default=None,
+                   help="penalise every id the row has generated (s / p, or s * p for s < 0); 1.0 / unset: off")
+    p.add_argument("--no_repeat_ngram_size", type=int, default=None,
+                   help="never repeat an n-gram of the generated ids; 0 / unset: off")
+    p.add_argument("--min_new_tokens", type=int, default=None,
+                   help="EOS is banned until this many ids have been generated; unset: off")
+
+
+def logits_processor_kwargs(args) -> dict:
+    """generate() keywords of add_logits_processor_args' options (unset ones are left out)."""
+    names = ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens")
+    return {k: getattr(args, k) for k in names if getattr(args, k, None) is not None}
