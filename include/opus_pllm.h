@@ -297,6 +297,31 @@ int opus_debug_logits_process(opus_ctx *ctx, float *d_logits, int32_t B, int32_t
                               int32_t no_repeat_ngram_size, int32_t min_new_tokens, const int32_t *bad_ids,
                               const int32_t *bad_offsets, int32_t n_bad, void *stream);
 
+/* Constrained decoding: generate(prefix_allowed_tokens_fn=TokenTrie), transformers' PrefixConstrainedLogitsProcessor with a
+ * deterministic token automaton instead of a Python callback.  It applies to the opus_generate_greedy / _sample / _scored calls
+ * of this context that follow (not to beam search) until it is set again; n_states = 0 turns it off, and the calls are then
+ * exactly those without it.  Behind min_new_tokens, in front of the sampling warpers.
+ *   The table (HOST arrays, copied to a device allocation the context owns, outside the workspace; the call returns when the
+ *   arrays are the caller's again): state s allows the ids edge_tok[edge_off[s] .. edge_off[s + 1]) (ascending within a state;
+ *   n_states + 1 offsets from 0 to n_edges) and moves to edge_next[e] on edge e; a state with completing[s] != 0 allows the
+ *   n_end end ids (1 to 64) too.  State 0 is the end state (no edges, completing): a row goes there on an end id and on any id
+ *   its state did not allow (a finished row's pads), and may then only emit end ids.  Every other state allows something.
+ *   start: n_start = 1 (every row starts there) or one start state per row (n_start = the batch of the generate calls).
+ * Per step and row the kernel takes one transition on the id generated last (no walk over the history) and stores -inf to every
+ * logit outside the allowed set; allowed logits are not touched.  d_scores of opus_generate_scored hold the masked scores,
+ * d_logits and d_token_logprobs stay raw.  Only "on / off" is part of the captured step's identity: another table, other start
+ * states need no new graph.  Returns OPUS_EBADARG for a table that is not well formed (offsets, ids outside [0, dec_vocab),
+ * targets, order, a state that allows nothing). */
+int opus_set_token_constraint(opus_ctx *ctx, int32_t n_states, const int32_t *edge_off, const int32_t *edge_tok,
+                              const int32_t *edge_next, int32_t n_edges, const uint8_t *completing, const int32_t *end_ids,
+                              int32_t n_end, const int32_t *start, int32_t n_start, void *stream);
+/* Diagnostic: the constraint kernel alone, in place on fp32 logits [B, V] (B <= max_batch, any V >= 1 above the table's ids; rows
+ * need no alignment), against the table set last: row b's history is d_hist[b * hist_stride + 0 .. hist_len) (device).  The rows'
+ * states are brought to the end of the history by the kernel's own transition, one launch per id, and copied to d_state_out [B]
+ * (device, optional).  Ordered on `stream`. */
+int opus_debug_token_constraint(opus_ctx *ctx, float *d_logits, int32_t B, int32_t V, const int32_t *d_hist, int32_t hist_stride,
+                                int32_t hist_len, int32_t *d_state_out, void *stream);
+
 /* Diagnostic entry points (kernel-level parity tests and micro-benchmarks; not part of the path's
  * drop-in surface).  opus_debug_gemm: C[M,Nout] = epi(A[M,K] W[N,K]^T + bias) (+ residual fp32);
  * epi 0 none, 1 erf-GELU, 2 silu(gate)*up with W rows in [16 gate | 16 up] groups (Nout = N/2).
@@ -398,8 +423,8 @@ int64_t opus_stat(opus_ctx *ctx, const char *name);
  * belongs to, and its ALGORITHMIC bytes and FLOPs.  opus_timing_get sums the records since the last reset that match
  * kernel_class and phase ("*" = any); opus_timing_names returns "class,class,...;phase,phase,..." .  Classes and phases are
  * addressed by name, never by position.  Order of the lists: phases are append-only ("score" last); among the classes "xent"
- * stays the last entry, as published since opus_llama_forward, and a class added later ("contact", "logitproc") is listed in front
- * of it. */
+ * stays the last entry, as published since opus_llama_forward, and a class added later ("contact", "constraint", "logitproc") is
+ * listed in front of it ("logitproc" keeps its place next to "xent"). */
 int opus_timing_enable(opus_ctx *ctx, int32_t on);
 int opus_timing_reset(opus_ctx *ctx);
 int opus_timing_get(opus_ctx *ctx, const char *kernel_class, const char *phase, double *ms, int64_t *launches, double *bytes,

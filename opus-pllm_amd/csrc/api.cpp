@@ -116,6 +116,7 @@ struct opus_ctx {
         float temp = 0.f, top_p = 1.f;
         int outs = 0;                    // GEN_* flags of opus_generate_scored (the addresses come from the descriptor)
         bool lproc = false;              // logits processors on (their values come from the descriptor d_lproc)
+        bool cons = false;               // token constraint on (its table comes from the descriptor d_cons)
         uint64_t used = 0;
     };
     static constexpr int MAX_GRAPHS = 4;
@@ -142,6 +143,15 @@ struct opus_ctx {
     int32_t *d_lstep = nullptr, *d_ridx = nullptr;
     GenOutDesc *d_gen_raw = nullptr, *d_gen_proc = nullptr;
     float *d_rlse = nullptr, *d_rawh = nullptr;
+    // token constraint (opus_set_token_constraint): the automaton's table in an allocation of its own, grown on use (cons_tab), and
+    // a small fixed one made on first use (cons_mem) - the device descriptor the captured step reads, the rows' state words
+    // [2, max_batch] (double-buffered by the step's parity) and the step word of opus_debug_token_constraint
+    bool cons_on = false;
+    char *cons_tab = nullptr, *cons_mem = nullptr;
+    size_t cons_tab_bytes = 0;
+    TokenConstraintDesc *d_cons = nullptr;
+    int32_t *d_cstate = nullptr, *d_cstep = nullptr;
+    int32_t cons_n_start = 0, cons_max_id = -1;
     // row-scale fusion (GemmParams::xh_out / row_ssq): one-shot request for the next gemm() and its outcome
     half_t *rq_xh = nullptr;
     int rq_done = 0;
@@ -408,6 +418,8 @@ extern "C" int opus_ctx_destroy(opus_ctx *c) {
     if (c->kv_tmp) (void)hipFree(c->kv_tmp);
     if (c->gen_mem) (void)hipFree(c->gen_mem);
     if (c->lproc_mem) (void)hipFree(c->lproc_mem);
+    if (c->cons_tab) (void)hipFree(c->cons_tab);
+    if (c->cons_mem) (void)hipFree(c->cons_mem);
     if (c->h_nunf) (void)hipHostFree(c->h_nunf);
     for (auto &e : c->poll_ev) if (e) (void)hipEventDestroy(e);
     delete c;
@@ -1757,7 +1769,7 @@ static int argmax(opus_ctx *c, hipStream_t s, int max_new, int n_eos, int pad_id
     c->phase = PH_DECODE;
     const opus_config &g = c->cfg;
     const int32_t *chosen = nullptr;
-    const bool proc = c->lproc_on;
+    const bool proc = c->lproc_on || c->cons_on;            // the logits are edited in place: raw outputs first
     const bool lp = c->gen_outs & GEN_LOGPROBS, sc = c->gen_outs & (GEN_SCORES | GEN_LOGITS);
     const size_t BV = (size_t)c->cur_B * g.dec_vocab;
     if (proc) {
@@ -1768,9 +1780,13 @@ static int argmax(opus_ctx *c, hipStream_t s, int max_new, int n_eos, int pad_id
             KL(KC_OTHER, 4.0 * BV, launch_argmax_lse_partial(c->d_logits, c->cur_B, g.dec_vocab, c->d_pval, c->d_pidx, c->d_gpsum, s));
             KL(KC_OTHER, 512.0 * c->cur_B, launch_argmax_lse_final(c->d_pval, c->d_pidx, c->d_gpsum, c->cur_B, c->d_ridx, c->d_rlse, s));
         }
-        KL(KC_LOGITPROC, 12.0 * c->cur_B * max_new,
-           launch_logits_proc(c->d_logits, c->cur_B, g.dec_vocab, d_out, max_new, c->d_step, max_new, c->d_eos, n_eos, c->d_lproc,
-                              lp ? c->d_rawh : nullptr, s));
+        if (c->lproc_on)
+            KL(KC_LOGITPROC, 12.0 * c->cur_B * max_new,
+               launch_logits_proc(c->d_logits, c->cur_B, g.dec_vocab, d_out, max_new, c->d_step, max_new, c->d_eos, n_eos, c->d_lproc,
+                                  lp ? c->d_rawh : nullptr, s));
+        if (c->cons_on)                      // behind min_new_tokens, in front of the warpers (transformers' order)
+            KL(KC_CONSTRAINT, 4.0 * BV,
+               launch_token_constraint(c->d_logits, c->cur_B, g.dec_vocab, d_out, max_new, c->d_step, max_new, c->d_cons, s));
     }
     if (c->samp_temp > 0.f) {
         KL(KC_OTHER, 4.0 * 4 * c->cur_B * g.dec_vocab,
@@ -1790,7 +1806,7 @@ static int argmax(opus_ctx *c, hipStream_t s, int max_new, int n_eos, int pad_id
                              c->samp_top_p, c->d_pval, c->samp_temp > 0.f ? c->d_gthr : nullptr, s));
     if (lp && proc)
         KL(KC_OTHER, 512.0 * c->cur_B + 8.0 * c->cur_B * max_new,
-           launch_argmax_rawlp_step(c->d_pval, c->d_pidx, c->d_rlse, c->d_rawh, chosen, c->cur_B, c->d_eos, n_eos, pad_id, c->d_fin, d_out,
+           launch_argmax_rawlp_step(c->d_pval, c->d_pidx, c->d_rlse, c->lproc_on ? c->d_rawh : nullptr, chosen, c->cur_B, c->d_eos, n_eos, pad_id, c->d_fin, d_out,
                                     max_new, c->d_step, c->d_next, c->d_nunf, c->d_stop, c->n_stop, c->d_logits, g.dec_vocab,
                                     c->d_gen_proc, s));
     else if (lp)
@@ -1836,11 +1852,13 @@ static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mas
             HIPC(hipMemcpyAsync(c->d_gen, &c->h_gen, sizeof(GenOutDesc), hipMemcpyHostToDevice, s));
         }
     }
-    if (c->lproc_on) {
-        if (max_new > LP_MAX_HIST)
+    if (c->cons_on && c->cons_n_start != 1 && c->cons_n_start != B)
+        return fail(OPUS_ESHAPE, "generate: the token constraint has %d per-row start states, the batch %d rows", c->cons_n_start, B);
+    if (c->lproc_on || c->cons_on) {
+        if (c->lproc_on && max_new > LP_MAX_HIST)
             return fail(OPUS_ESHAPE, "generate: logits processors keep a history of at most %d ids (max_new=%d)", LP_MAX_HIST, max_new);
         OPC(ensure_lproc_mem(c));
-        OPC(upload_lproc(c, c->h_lproc, s));
+        if (c->lproc_on) OPC(upload_lproc(c, c->h_lproc, s));
         if (gen_outs) {                      // raw logits before the processors, the rest after them
             OPC(upload_gen_desc(GenOutDesc{nullptr, nullptr, outs->logits, nullptr}, c->d_gen_raw, s));
             OPC(upload_gen_desc(GenOutDesc{outs->token_lp, outs->scores, nullptr, nullptr}, c->d_gen_proc, s));
@@ -1857,7 +1875,7 @@ static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mas
     auto find_graph = [&]() -> opus_ctx::GraphEntry * {
         for (auto &e : c->graphs)
             if (e.exec && e.B == B && e.maxnew == max_new && e.pad == pad_id && e.neos == n_eos && e.out == d_out_ids &&
-                e.temp == temperature && e.top_p == top_p && e.outs == gen_outs && e.lproc == c->lproc_on) return &e;
+                e.temp == temperature && e.top_p == top_p && e.outs == gen_outs && e.lproc == c->lproc_on && e.cons == c->cons_on) return &e;
         return nullptr;
     };
     opus_ctx::GraphEntry *ge = use_graph ? find_graph() : nullptr;
@@ -1889,6 +1907,7 @@ static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mas
                 e.B = B; e.maxnew = max_new; e.pad = pad_id; e.neos = n_eos; e.temp = temperature; e.top_p = top_p; e.out = d_out_ids;
                 e.outs = gen_outs;
                 e.lproc = c->lproc_on;
+                e.cons = c->cons_on;
                 if ((int)c->graphs.size() >= opus_ctx::MAX_GRAPHS) {           // least recently used out
                     size_t v = 0;
                     for (size_t k = 1; k < c->graphs.size(); ++k) if (c->graphs[k].used < c->graphs[v].used) v = k;
@@ -1996,6 +2015,127 @@ extern "C" int opus_debug_logits_process(opus_ctx *c, float *d_logits, int32_t B
     HIPC(launch_upload_i32(&hist_len, 1, c->d_lstep, s));
     KL(KC_LOGITPROC, 12.0 * B * hist_len, launch_logits_proc(d_logits, B, V, d_hist, hist_stride, c->d_lstep, hist_len, c->d_eos, n_eos,
                                                              c->d_lproc, nullptr, s));
+    return OPUS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ constrained decoding
+static int ensure_cons_mem(opus_ctx *c) {
+    if (c->cons_mem) return OPUS_OK;
+    const size_t o_st = align_up(sizeof(TokenConstraintDesc)), o_sp = o_st + align_up(2 * (size_t)c->cfg.max_batch * sizeof(int32_t));
+    HIPC(hipMalloc((void **)&c->cons_mem, o_sp + align_up(sizeof(int32_t))));
+    c->d_cons = reinterpret_cast<TokenConstraintDesc *>(c->cons_mem);
+    c->d_cstate = reinterpret_cast<int32_t *>(c->cons_mem + o_st);
+    c->d_cstep = reinterpret_cast<int32_t *>(c->cons_mem + o_sp);
+    return OPUS_OK;
+}
+
+// The token automaton generate() is constrained to, for the calls of this context that follow (see include/opus_pllm.h).  The
+// table is checked on the host, then copied to a device allocation the context owns; only "on / off" enters the captured step's
+// identity - the table's addresses and sizes travel in a device descriptor, so another table needs no new graph.
+extern "C" int opus_set_token_constraint(opus_ctx *c, int32_t n_states, const int32_t *edge_off, const int32_t *edge_tok,
+                                         const int32_t *edge_next, int32_t n_edges, const uint8_t *completing, const int32_t *end_ids,
+                                         int32_t n_end, const int32_t *start, int32_t n_start, void *stream) {
+    const char *who = "set_token_constraint";
+    if (!c) return fail(OPUS_EBADARG, "ctx is null");
+    if (n_states == 0) {                     // off (the table stays allocated for the next one)
+        c->cons_on = false;
+        return OPUS_OK;
+    }
+    const int V = c->cfg.dec_vocab;
+    if (n_states < 1 || n_edges < 0 || !edge_off || !completing || !end_ids || !start || (n_edges > 0 && (!edge_tok || !edge_next)))
+        return fail(OPUS_EBADARG, "%s: null table or negative size", who);
+    if (n_end < 1 || n_end > TC_MAX_END) return fail(OPUS_EBADARG, "%s: %d end ids (1 to %d)", who, n_end, TC_MAX_END);
+    if (n_start < 1 || n_start > c->cfg.max_batch)
+        return fail(OPUS_EBADARG, "%s: %d start states (1, or one per row up to max_batch=%d)", who, n_start, c->cfg.max_batch);
+    if (V > TC_MAX_VOCAB) return fail(OPUS_ESHAPE, "%s: vocabulary %d above the kernel's %d", who, V, TC_MAX_VOCAB);
+    if (edge_off[0] != 0 || edge_off[n_states] != n_edges) return fail(OPUS_EBADARG, "%s: edge_off must run from 0 to n_edges", who);
+    if (edge_off[1] != 0 || !completing[0]) return fail(OPUS_EBADARG, "%s: state 0 is the end state (no edges, completing)", who);
+    int32_t max_id = -1;
+    for (int s = 0; s < n_states; ++s) {
+        const int e0 = edge_off[s], e1 = edge_off[s + 1];
+        if (e1 < e0 || e1 > n_edges) return fail(OPUS_EBADARG, "%s: edge_off not monotone at state %d", who, s);
+        for (int e = e0; e < e1; ++e) {
+            if (edge_tok[e] < 0 || edge_tok[e] >= V) return fail(OPUS_EBADARG, "%s: id %d outside [0, %d)", who, edge_tok[e], V);
+            if (e > e0 && edge_tok[e] <= edge_tok[e - 1]) return fail(OPUS_EBADARG, "%s: ids of state %d not ascending", who, s);
+            if (edge_next[e] < 0 || edge_next[e] >= n_states) return fail(OPUS_EBADARG, "%s: target %d outside [0, %d)", who, edge_next[e], n_states);
+        }
+        if (e1 > e0 && edge_tok[e1 - 1] > max_id) max_id = edge_tok[e1 - 1];
+        if (e1 == e0 && !completing[s]) return fail(OPUS_EBADARG, "%s: state %d allows nothing", who, s);
+    }
+    for (int k = 0; k < n_end; ++k) {
+        if (end_ids[k] < 0 || end_ids[k] >= V) return fail(OPUS_EBADARG, "%s: end id %d outside [0, %d)", who, end_ids[k], V);
+        if (end_ids[k] > max_id) max_id = end_ids[k];
+    }
+    for (int k = 0; k < n_start; ++k)
+        if (start[k] < 0 || start[k] >= n_states) return fail(OPUS_EBADARG, "%s: start state %d outside [0, %d)", who, start[k], n_states);
+
+    HIPC(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    OPC(ensure_cons_mem(c));
+    const size_t o_tok = align_up((size_t)(n_states + 1) * 4), o_nxt = o_tok + align_up((size_t)n_edges * 4),
+                 o_end = o_nxt + align_up((size_t)n_edges * 4), o_sta = o_end + align_up((size_t)n_end * 4),
+                 o_cmp = o_sta + align_up((size_t)n_start * 4), total = o_cmp + align_up((size_t)n_states);
+    HIPC(hipStreamSynchronize(s));           // a call in flight may still read the table that is replaced
+    if (total > c->cons_tab_bytes) {
+        if (c->cons_tab) HIPC(hipFree(c->cons_tab));
+        c->cons_tab = nullptr;
+        c->cons_tab_bytes = 0;
+        c->cons_on = false;
+        HIPC(hipMalloc((void **)&c->cons_tab, total));
+        c->cons_tab_bytes = total;
+    }
+    char *t = c->cons_tab;
+    HIPC(hipMemcpyAsync(t, edge_off, (size_t)(n_states + 1) * 4, hipMemcpyHostToDevice, s));
+    if (n_edges) {
+        HIPC(hipMemcpyAsync(t + o_tok, edge_tok, (size_t)n_edges * 4, hipMemcpyHostToDevice, s));
+        HIPC(hipMemcpyAsync(t + o_nxt, edge_next, (size_t)n_edges * 4, hipMemcpyHostToDevice, s));
+    }
+    HIPC(hipMemcpyAsync(t + o_end, end_ids, (size_t)n_end * 4, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(t + o_sta, start, (size_t)n_start * 4, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(t + o_cmp, completing, (size_t)n_states, hipMemcpyHostToDevice, s));
+    TokenConstraintDesc h{};
+    h.edge_off = reinterpret_cast<const int32_t *>(t);
+    h.edge_tok = reinterpret_cast<const int32_t *>(t + o_tok);
+    h.edge_next = reinterpret_cast<const int32_t *>(t + o_nxt);
+    h.completing = reinterpret_cast<const uint8_t *>(t + o_cmp);
+    h.end_ids = reinterpret_cast<const int32_t *>(t + o_end);
+    h.start = reinterpret_cast<const int32_t *>(t + o_sta);
+    h.state = c->d_cstate;
+    h.n_states = n_states; h.n_end = n_end; h.n_start = n_start; h.state_stride = c->cfg.max_batch;
+    HIPC(launch_upload_i32(reinterpret_cast<const int32_t *>(&h), (int)(sizeof(h) / sizeof(int32_t)),
+                           reinterpret_cast<int32_t *>(c->d_cons), s));
+    HIPC(hipStreamSynchronize(s));           // the host arrays are the caller's again
+    c->cons_n_start = n_start;
+    c->cons_max_id = max_id;
+    c->cons_on = true;
+    return OPUS_OK;
+}
+
+/* Diagnostic: the constraint kernel alone on caller memory - fp32 logits [B, V] masked in place for rows whose history is
+   d_hist[b * hist_stride + 0 .. hist_len), against the table of the last opus_set_token_constraint.  The state words are
+   brought to the history's end by the product kernel's own transition, one launch per id (the kernel never walks a history),
+   and copied to d_state_out [B] (optional). */
+extern "C" int opus_debug_token_constraint(opus_ctx *c, float *d_logits, int32_t B, int32_t V, const int32_t *d_hist,
+                                           int32_t hist_stride, int32_t hist_len, int32_t *d_state_out, void *stream) {
+    if (!c || !d_logits || (hist_len > 0 && !d_hist)) return fail(OPUS_EBADARG, "debug_token_constraint: null pointer");
+    if (!c->cons_on) return fail(OPUS_ESTATE, "debug_token_constraint: no table set (opus_set_token_constraint)");
+    if (B < 1 || B > c->cfg.max_batch || V < 1 || V > TC_MAX_VOCAB || hist_len < 0 || hist_stride < hist_len)
+        return fail(OPUS_ESHAPE, "debug_token_constraint: B=%d (max_batch %d) V=%d history %d (stride %d)", B, c->cfg.max_batch, V,
+                    hist_len, hist_stride);
+    if (c->cons_max_id >= V) return fail(OPUS_ESHAPE, "debug_token_constraint: the table holds id %d, V=%d", c->cons_max_id, V);
+    if (c->cons_n_start != 1 && c->cons_n_start != B)
+        return fail(OPUS_ESHAPE, "debug_token_constraint: %d per-row start states, %d rows", c->cons_n_start, B);
+    HIPC(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    c->phase = PH_OTHER;
+    for (int32_t t = 0; t < hist_len; ++t) {
+        HIPC(launch_upload_i32(&t, 1, c->d_cstep, s));
+        HIPC(launch_token_constraint(nullptr, B, V, d_hist, hist_stride, c->d_cstep, hist_len, c->d_cons, s));
+    }
+    HIPC(launch_upload_i32(&hist_len, 1, c->d_cstep, s));
+    KL(KC_CONSTRAINT, 4.0 * B * V, launch_token_constraint(d_logits, B, V, d_hist, hist_stride, c->d_cstep, hist_len, c->d_cons, s));
+    if (d_state_out)                         // (the state words are double-buffered by the step's parity)
+        HIPC(hipMemcpyAsync(d_state_out, c->d_cstate + (hist_len & 1) * c->cfg.max_batch, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     return OPUS_OK;
 }
 
@@ -2359,7 +2499,7 @@ extern "C" int opus_timing_reset(opus_ctx *c) {
     return OPUS_OK;
 }
 static const char *kclass_names[KC_COUNT] = {"gemm_skinny", "gemm_mid", "gemm_wide", "gemm_ring", "gemm_pp", "gemm_tile", "splitk_reduce",
-                                            "attn_prefill", "attn_decode", "norm", "other", "gemm_stream", "contact", "logitproc",
+                                            "attn_prefill", "attn_decode", "norm", "other", "gemm_stream", "contact", "constraint", "logitproc",
                                             "xent"};
 static const char *phase_names[PH_COUNT] = {"encode", "project", "splice", "prefill", "decode", "other", "score"};
 

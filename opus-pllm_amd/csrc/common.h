@@ -52,7 +52,7 @@ int skinny_max_m();   // rows up to which the skinny kernel is used (default 4, 
 constexpr int MID_MAX_M = 64;   // (65..128 rows measured faster on the split-K tile kernel)
 // kernel classes of the per-launch timing (opus_timing_get): one per kernel family
 enum KClass { KC_SKINNY = 0, KC_MID, KC_WIDE, KC_RING, KC_PP, KC_TILE, KC_REDUCE, KC_ATTN_PREFILL, KC_ATTN_DECODE, KC_NORM,
-              KC_OTHER, KC_STREAM, KC_CONTACT, KC_LOGITPROC, KC_XENT, KC_COUNT };
+              KC_OTHER, KC_STREAM, KC_CONTACT, KC_CONSTRAINT, KC_LOGITPROC, KC_XENT, KC_COUNT };
 // Ordering rule of the published class list (opus_timing_names, include/opus_pllm.h): "xent" stays its last entry, as published
 // since opus_llama_forward, and a class added later goes in front of it.  Classes are looked up by name, never by index.
 // phases of the path a launch belongs to (set by the entry points of api.cpp)
@@ -418,6 +418,23 @@ struct LogitsProcDesc {
 // raw_hist (optional) [B, ld] receives the raw logit of every history position
 hipError_t launch_logits_proc(float *logits, int B, int V, const int32_t *hist, int64_t ld, const int32_t *step, int max_hist,
                               const int32_t *eos, int n_eos, const LogitsProcDesc *desc, float *raw_hist, hipStream_t s);
+// constraint.hip: constrained decoding (opus_set_token_constraint).  The automaton's table and the per-row state words live in
+// device memory; the captured step reaches them through this descriptor, so another table needs no new graph.
+constexpr int TC_MAX_VOCAB = 1 << 18, TC_MAX_END = 64;     // the allowed set is a V-bit map in LDS (32 KB at the cap)
+struct TokenConstraintDesc {
+    const int32_t *edge_off;           // [n_states + 1] state s owns the edges edge_off[s] .. edge_off[s + 1)
+    const int32_t *edge_tok;           // [n_edges] ids, ascending within a state
+    const int32_t *edge_next;          // [n_edges] target states
+    const uint8_t *completing;         // [n_states] the end ids are allowed too
+    const int32_t *end_ids;            // [n_end]
+    const int32_t *start;              // [n_start] start state of every row (n_start == 1: shared)
+    int32_t *state;                    // [2, state_stride] the rows' states, double-buffered by the parity of the step
+    int32_t n_states, n_end, n_start, state_stride;
+};
+// in place on logits [B, V] (row stride V): one transition per row on hist[b * ld + *step - 1] (the start state at *step == 0),
+// then -inf outside the state's allowed set.  logits == nullptr: the transition only.
+hipError_t launch_token_constraint(float *logits, int B, int V, const int32_t *hist, int64_t ld, const int32_t *step, int max_hist,
+                                   const TokenConstraintDesc *desc, hipStream_t s);
 // beam.hip: best M of the K V continuations per batch row (log_softmax + running scores), cache rows of the surviving beams
 hipError_t launch_beam_topk(const float *logits, const float *run, int B, int K, int V, int M, float *lse, float *out_s,
                             int32_t *out_i, hipStream_t s);

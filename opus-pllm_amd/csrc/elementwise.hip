@@ -631,8 +631,9 @@ __device__ __forceinline__ void argmax_step_body(const float *__restrict__ pval,
         const int st = *step, n = st < max_new ? st : max_new;
         const int tok = finished[b] ? pad_id : (bi == 0x7fffffff ? 0 : bi);
         int first = 0x7fffffff;
-        for (int i = lane; i < n; i += 64)
-            if (out_ids[(int64_t)b * max_new + i] == tok) { first = i; break; }
+        if (raw_hist)                         // (nullptr: no processor changes a logit that can be chosen - the constraint alone)
+            for (int i = lane; i < n; i += 64)
+                if (out_ids[(int64_t)b * max_new + i] == tok) { first = i; break; }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o, 64));
         lse = lse_in[b];

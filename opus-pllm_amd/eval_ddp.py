@@ -26,8 +26,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import opus_pllm_amd as opa                                                    # noqa: E402
 from opus_pllm_amd import dist as odist                                        # noqa: E402
 from opus_pllm_amd.builder import load_pretrained_model, return_cstp_path      # noqa: E402
-from opus_pllm_amd.prompt import (add_logits_processor_args, after_process_output, build_prompt,  # noqa: E402
-                                  logits_processor_kwargs, max_new_tokens_for)
+from opus_pllm_amd.prompt import (add_constraint_args, add_logits_processor_args, after_process_output,  # noqa: E402
+                                  build_prompt, logits_processor_kwargs, max_new_tokens_for, token_constraint)
 
 
 def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperature=0.0, top_p=0.7, num_beams=1,
@@ -46,7 +46,8 @@ def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperatu
     independent, results come back in input order and are the same ids as with one context: greedy ids because the kernels are
     the same, sampled ids because every batch's sampler seed is drawn HERE, in input order, from torch's global generator
     (torch.manual_seed reproduces a run whatever `inflight` is) and handed to generate(seed=...).
-    processors (--repetition_penalty / --no_repeat_ngram_size / --min_new_tokens): generate() keywords of its logits processors."""
+    processors (--repetition_penalty / --no_repeat_ngram_size / --min_new_tokens, --allowed_terms): generate() keywords of its
+    logits processors and of the token constraint (prefix_allowed_tokens_fn: one TokenTrie, built once, for every batch)."""
     dev = device or model.device
     prot_all = None
     if use_input_embed and items:
@@ -155,11 +156,15 @@ def eval_model(args):
     dev = torch.device("cuda", local)
     t0 = time.time()
     logits = [] if args.dump_logits else None
+    proc_kw = logits_processor_kwargs(args)
+    trie = token_constraint(args, tokenizer)          # --allowed_terms: built once, uploaded once per context
+    if trie is not None:
+        proc_kw["prefix_allowed_tokens_fn"] = trie
     lps = [] if args.save_logprobs else None
     local_ids = annotate(model, tokenizer, mine, args.input_path, args.batch_size, max_new, args.temperature, args.top_p,
                          args.num_beams, args.use_input_embed, dev, logits,
                          tokenizer.encode("###", add_special_tokens=False) if args.stop_at_hashes else None, inflight=args.inflight,
-                         logprobs_out=lps, processors=logits_processor_kwargs(args))
+                         logprobs_out=lps, processors=proc_kw)
     all_ids = odist.all_gather_ids(local_ids, tokenizer.eos_token_id)
     if lps is not None:         # [n, max_new] log-probabilities and [n] counted positions, in rank order
         loc_lp = torch.cat([x[0] for x in lps]) if lps else torch.empty((0, max_new), dtype=torch.float32, device=dev)
@@ -217,4 +222,5 @@ if __name__ == "__main__":
     p.add_argument("--dump_logits", type=str, default=None,
                    help="parity dump: save the fp32 last-step logits of every item ([n, V], input order) to this .pt file")
     add_logits_processor_args(p)
+    add_constraint_args(p)
     eval_model(p.parse_args())

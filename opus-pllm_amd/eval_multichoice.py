@@ -76,6 +76,19 @@ def option_ids(tokenizer, letter: str):
     return _encode(tokenizer, option_text(letter))
 
 
+def option_tries(tokenizer, batch, cache=None):
+    """--constrained: TokenTrie.per_row over the batch, each item's trie holding the answer texts of ITS options (option_text of as
+    many letters as the item has options), ended by the tokenizer's EOS id.  `cache` (a dict) keeps one trie per option count."""
+    cache = {} if cache is None else cache
+    tries = []
+    for q in batch:
+        n = max(1, min(len(q["options"]), len(OPTIONS)))
+        if n not in cache:
+            cache[n] = opa.TokenTrie([option_ids(tokenizer, L) for L in OPTIONS[:n]], end_token_id=tokenizer.eos_token_id)
+        tries.append(cache[n])
+    return opa.TokenTrie.per_row(tries)
+
+
 @torch.no_grad()
 def rank_batch(model, tokenizer, batch, dev):
     """One batch of items -> option log-likelihoods fp32 [B, 4]: the prompts prefilled once, the four answers scored behind them."""
@@ -119,8 +132,12 @@ def eval_model(args):
     t0 = time.time()
     if getattr(args, "rank_options", False):
         return _eval_ranked(args, qs, mine, tokenizer, model, dev, rank, world, t0)
+    tries = {}
     for i in range(0, len(mine), args.batch_size):
         batch = mine[i:i + args.batch_size]
+        extra = logits_processor_kwargs(args)
+        if getattr(args, "constrained", False):       # the answer is one of the item's own option texts, then EOS
+            extra.update(prefix_allowed_tokens_fn=option_tries(tokenizer, batch, tries), eos_token_id=tokenizer.eos_token_id)
         prompts = [render_question(q, tokenizer) for q in batch]
         ids = [opa.tokenizer_seq_token(p, tokenizer, opa.DEFAULT_SEQ_TOKEN_INDEX, return_tensors="pt").to(dev) for p in prompts]
         ids = opa.left_pad_sequence(ids, padding_value=tokenizer.pad_token_id, batch_first=True)
@@ -129,7 +146,7 @@ def eval_model(args):
             out = model.generate(ids, [q["input"] for q in batch], attention_mask=mask, pad_token_id=tokenizer.eos_token_id,
                                  seq_embedding=None, do_sample=args.temperature > 0, temperature=args.temperature,
                                  top_p=args.top_p, num_beams=args.num_beams, max_new_tokens=args.max_new_tokens, use_cache=True,
-                                 **logits_processor_kwargs(args))
+                                 **extra)
         full = torch.full((out.shape[0], args.max_new_tokens), tokenizer.eos_token_id, dtype=torch.long, device=dev)
         full[:, : out.shape[1]] = out
         outs.append(full)
@@ -187,6 +204,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--max_prompt", type=int, default=384)
     p.add_argument("--rank_options", action="store_true",
                    help="rank the four answers by log-likelihood behind one cached prompt instead of generating")
+    p.add_argument("--constrained", action="store_true",
+                   help="generate under a token trie of each item's option texts (always a valid answer) instead of free text")
     add_logits_processor_args(p)
     return p
 

@@ -19,12 +19,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import opus_pllm_amd as opa                                                    # noqa: E402
 from opus_pllm_amd.builder import load_pretrained_model, return_cstp_path      # noqa: E402
 from opus_pllm_amd.conversation import conv_vicuna_v0                          # noqa: E402
-from opus_pllm_amd.prompt import (add_logits_processor_args, is_protein_sequence, logits_processor_kwargs,  # noqa: E402
-                                  online_cut, online_prompt)
+from opus_pllm_amd.prompt import (add_constraint_args, add_logits_processor_args, is_protein_sequence,  # noqa: E402
+                                  logits_processor_kwargs, online_cut, online_prompt, token_constraint)
 
 
-def answer_once(model, tokenizer, instruction: str, seq: str, args, conv=conv_vicuna_v0):
-    """-> (instruction as shown, sequence or None, reply text)."""
+def answer_once(model, tokenizer, instruction: str, seq: str, args, conv=conv_vicuna_v0, constraint=None):
+    """-> (instruction as shown, sequence or None, reply text).  constraint: the TokenTrie of --allowed_terms, if any."""
     dev = model.device
     prompt, shown = online_prompt(instruction, bool(seq), conv)
     if not seq:
@@ -36,7 +36,8 @@ def answer_once(model, tokenizer, instruction: str, seq: str, args, conv=conv_vi
         out = model.generate(input_ids, seq, attention_mask=None, pad_token_id=tokenizer.eos_token_id, seq_embedding=None,
                              do_sample=args.temperature > 0, temperature=args.temperature, top_p=args.top_p,
                              num_beams=args.num_beams, max_new_tokens=args.max_new_tokens, use_cache=True,
-                             **logits_processor_kwargs(args))
+                             **logits_processor_kwargs(args),
+                             **({} if constraint is None else dict(prefix_allowed_tokens_fn=constraint)))
     text = tokenizer.batch_decode(out, skip_special_tokens=True)[0]
     return shown, seq, online_cut(text, conv.sep)
 
@@ -49,6 +50,7 @@ def eval_model(args):
                                                 cstp_path=cstp_path, device="cuda:0", max_batch=max(1, args.num_beams),
                                                 max_enc_tokens=args.max_residues + 2, max_prompt=args.max_prompt,
                                                 max_new_tokens=max(args.max_new_tokens, 1))
+    constraint = token_constraint(args, tokenizer)
     while True:
         try:
             instruction = input("Enter your instruction: ")
@@ -60,7 +62,7 @@ def eval_model(args):
                 print("Invalid sequence!")
         except EOFError:
             return
-        shown, seq, reply = answer_once(model, tokenizer, instruction, seq, args)
+        shown, seq, reply = answer_once(model, tokenizer, instruction, seq, args, constraint=constraint)
         print("----------------------------")
         print(f"Instruction: {shown}")
         print(f"Sequence: {seq}")
@@ -82,4 +84,5 @@ if __name__ == "__main__":
     p.add_argument("--max_residues", type=int, default=1024)
     p.add_argument("--max_prompt", type=int, default=256)
     add_logits_processor_args(p)
+    add_constraint_args(p)
     eval_model(p.parse_args())

@@ -384,7 +384,11 @@ class OpusLlamaForCausalLM:
         Logits processors (greedy and sampling; transformers' semantics and order, before the sampling warpers):
         repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_length / min_new_tokens (see _logits_processors).  They see
         only the ids generated so far, never the prompt, as the reference's generate from inputs_embeds does.  With any of them on,
-        `scores` hold the processed scores while `logits` and `token_logprobs` stay raw; num_beams > 1 raises."""
+        `scores` hold the processed scores while `logits` and `token_logprobs` stay raw; num_beams > 1 raises.
+        Constrained decoding (greedy and sampling): prefix_allowed_tokens_fn=TokenTrie(...) / TokenTrie.per_row([...])
+        (constraint.py) - transformers' PrefixConstrainedLogitsProcessor as a device automaton, behind min_new_tokens and in front
+        of the warpers; `scores` are -inf outside the allowed set, `logits` and `token_logprobs` stay raw.  Any other callable
+        raises NotImplementedError (a Python callback cannot run inside the captured decode step), and so does num_beams > 1."""
         return_dict = bool(kwargs.pop("return_dict_in_generate", False))
         want = {k: bool(kwargs.pop(k, False)) for k in ("output_scores", "output_logits", "output_token_logprobs",
                                                          "output_attentions", "output_hidden_states")}
@@ -419,6 +423,20 @@ class OpusLlamaForCausalLM:
             raise NotImplementedError("repetition_penalty / no_repeat_ngram_size / bad_words_ids / min_length / min_new_tokens are "
                                       "built for greedy and sampling, not for num_beams > 1 (transformers applies them to the "
                                       "beams' log-softmax scores)")
+        constraint = kwargs.pop("prefix_allowed_tokens_fn", None)
+        if constraint is not None:
+            from .constraint import is_constraint
+            if not is_constraint(constraint):
+                raise NotImplementedError("prefix_allowed_tokens_fn has to be a TokenTrie (or TokenTrie.per_row(...)): an arbitrary "
+                                          "Python callback cannot run inside the captured decode step, and there is no host fallback")
+            if num_beams > 1:
+                raise NotImplementedError("prefix_allowed_tokens_fn is built for greedy and sampling, not for num_beams > 1 "
+                                          "(transformers applies it to the beams' log-softmax scores)")
+            if inputs is not None and constraint.n_rows() is not None and constraint.n_rows() != inputs.shape[0]:
+                raise ValueError(f"TokenTrie.per_row holds {constraint.n_rows()} tries, the batch {inputs.shape[0]} rows")
+            table = constraint.compiled()
+            if vocab is not None and (table.min_id() < 0 or table.max_id() >= vocab):
+                raise ValueError(f"the TokenTrie holds ids outside [0, {vocab}) (from {table.min_id()} to {table.max_id()})")
         sampler = None
         if do_sample:       # HF: temperature defaults to 1.0, top_p to 1.0; draws keyed by (seed, row, step)
             t = 1.0 if temperature is None else float(temperature)
@@ -451,6 +469,7 @@ class OpusLlamaForCausalLM:
                 min_new = max((min_len or 0) - int(embeds.shape[1]), 0)
             lproc = (pen, ngram, min_new, bad)
         self._set_logits_processors(lproc)
+        self._set_token_constraint(constraint)
         if num_beams > 1:
             ids = self._beam_search(embeds, mask, max_new, eos, beam_pad, num_beams, sampler)
             if not return_dict:
@@ -589,6 +608,25 @@ class OpusLlamaForCausalLM:
             _cabi.check(self._lib.opus_set_logits_processors(self._ctx, float(pen), int(ngram), int(min_new), ids, off, len(bad)))
         self._lproc = setting
 
+    def _set_token_constraint(self, constraint) -> None:
+        """constraint: a TokenTrie / TokenTrie.per_row object or None (off), applied to this context's following generate calls.
+        The table is uploaded only when the object differs from the one this context holds; None when none is held costs nothing."""
+        if constraint is getattr(self, "_constraint", None):
+            return
+        s = self._enter()
+        try:
+            if constraint is None:
+                _cabi.check(self._lib.opus_set_token_constraint(self._ctx, 0, None, None, None, 0, None, None, 0, None, 0, s))
+            else:
+                t = constraint.compiled()
+                p = lambda a: a.ctypes.data if a.size else None                              # noqa: E731
+                _cabi.check(self._lib.opus_set_token_constraint(self._ctx, t.n_states, p(t.edge_off), p(t.edge_tok), p(t.edge_next),
+                                                                t.n_edges, p(t.completing), p(t.end_ids), len(t.end_ids),
+                                                                p(t.start), len(t.start), s))
+        finally:
+            self._leave()
+        self._constraint = constraint
+
     def _greedy(self, embeds, mask, max_new, eos, pad_id, sampler=None, outputs=None):
         """outputs = (token_logprobs, scores, logits) flags: a GenerateDecoderOnlyOutput instead of the ids."""
         B, T, _ = embeds.shape
@@ -613,7 +651,8 @@ class OpusLlamaForCausalLM:
                 lp = torch.zeros((B, max_new), dtype=torch.float32, device=self.device) if want_lp else None
                 sc = torch.empty((max_new, B, V), dtype=torch.float32, device=self.device) if want_sc else None
                 lg = torch.empty((max_new, B, V), dtype=torch.float32, device=self.device) if want_lg else None
-                if sampler is None and sc is not None and lg is not None and getattr(self, "_lproc", None) is None:
+                if (sampler is None and sc is not None and lg is not None and getattr(self, "_lproc", None) is None
+                        and getattr(self, "_constraint", None) is None):
                     lg = None                                   # greedy: the processed scores are the logits - one tensor
                 t, p, sd = (sampler[0], sampler[1], sampler[2]) if sampler is not None else (0.0, 1.0, 0)
                 ptr = lambda x: None if x is None else x.data_ptr()                          # noqa: E731
@@ -655,6 +694,7 @@ class OpusLlamaForCausalLM:
         cfg = self.cfg
         B = input_ids.shape[0]
         self._set_logits_processors(None)       # (a previous generate()'s processors do not carry over; no-op when off)
+        self._set_token_constraint(None)
         if bucket_rows == "packed":      # d_tokens: packed int32 [M] on the device; d_lens: the HOST row offsets cu [B + 1]
             s = self._enter()
             with torch.cuda.stream(self._stream):

@@ -130,3 +130,27 @@ def logits_processor_kwargs(args) -> dict:
     """generate() keywords of add_logits_processor_args' options (unset ones are left out)."""
     names = ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens")
     return {k: getattr(args, k) for k in names if getattr(args, k, None) is not None}
+
+
+def add_constraint_args(p) -> None:
+    """The drivers' constrained decoding: answers from a closed vocabulary (generate(prefix_allowed_tokens_fn=TokenTrie))."""
+    p.add_argument("--allowed_terms", type=str, default=None,
+                   help="file with one allowed answer per line (a GO term, an EC number, a keyword): the output is one of them")
+    p.add_argument("--allowed_separator", type=str, default=None,
+                   help="with --allowed_terms: the text between two answers of a list (e.g. '; '); unset: exactly one answer")
+    p.add_argument("--allowed_prefix", type=str, default="",
+                   help="with --allowed_terms: text put in front of every answer before tokenising (most tokenisers encode a "
+                        "word differently behind a space)")
+
+
+def token_constraint(args, tokenizer):
+    """The TokenTrie of add_constraint_args' options, built once at start (None when --allowed_terms is unset).  Its end id is
+    the tokenizer's EOS id, which the drivers also pass as pad / eos."""
+    path = getattr(args, "allowed_terms", None)
+    if not path:
+        return None
+    from .constraint import TokenTrie
+    with open(path) as f:
+        terms = [line.rstrip("\n") for line in f if line.strip()]
+    return TokenTrie.from_strings(tokenizer, terms, end_token_id=tokenizer.eos_token_id,
+                                  separator=getattr(args, "allowed_separator", None), prefix=getattr(args, "allowed_prefix", "") or "")
