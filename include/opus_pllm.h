@@ -202,6 +202,47 @@ int64_t opus_llama_score_scratch_bytes(const opus_config *cfg, int32_t R, int32_
  * without a prefill. */
 int opus_debug_attn_prefix(opus_ctx *ctx, const void *d_qkv, const void *d_k_hist, const void *d_v_hist, const int32_t *d_kstart,
                            int32_t P, int32_t Tp, int32_t R, int32_t n, const int32_t *h_src, void *d_out, void *stream);
+/* Trie scoring: exact log-probabilities of every member of a token trie behind the prefix of `epoch`, one tree pass (the planner
+ * is opus-pllm_amd/constraint.py plan_trie_score; OpusLlamaForCausalLM.score_trie drives it).  One call = one pass of `rows` trie
+ * nodes (0 <= rows <= opus_llama_dec_rows_cap), each ONE new position: d_embeds operand dtype [rows, H]; host tables h_src (prefix
+ * row), h_par (parent row in this pass, -1 for a child of the root; otherwise an EARLIER row of the same prefix row one level up)
+ * and h_depth (1 .. opus_llama_tree_max_depth(), else OPUS_ESHAPE).  A row at depth d sits at position Tp - kstart + d - 1 of its
+ * prefix row (at most max_prompt + max_new_tokens positions in all, else OPUS_ESHAPE) and attends to the prefix row's cache slots,
+ * its ancestors and itself (attn_tree_kernel).  Scoring: h_score_src [n_score] lists the rows whose logits are needed - a row
+ * of the pass, or -(p) - 1 for the last position of prefix row p (d_last_rows fp32 [P, H] of opus_llama_prefix); the lm_head runs
+ * once per entry.  Edge e (h_edge_row ascending indices into that list, h_edge_tok, h_edge_slot) writes
+ * d_node_lp[slot] = log_softmax(logits(row))[tok]; stop entry k (h_stop_row ascending, h_stop_set, h_stop_slot) writes
+ * d_stop_lp[slot] = log sum over the ids h_stop_ids[h_stop_off[set] .. h_stop_off[set + 1]) of softmax(logits(row))[id].  Slots lie
+ * in [0, n_slots); a slot no entry names is left as it was.  Every table is checked on the host (OPUS_EBADARG).  Reads the KV
+ * cache and writes neither it nor the decode state (OPUS_ESTATE on a stale or foreign epoch); fixed summation orders, no float
+ * atomics: the same inputs give bitwise the same outputs.  d_scratch holds opus_llama_score_tree_scratch_bytes(...) bytes; the
+ * context's workspace does not grow.  Returns after the stream has finished.  Phase "score". */
+int opus_llama_score_tree(opus_ctx *ctx, const void *d_embeds, int32_t rows, const int32_t *h_src, const int32_t *h_par,
+                          const int32_t *h_depth, int32_t n_score, const int32_t *h_score_src, int32_t n_edges,
+                          const int32_t *h_edge_row, const int32_t *h_edge_tok, const int32_t *h_edge_slot, int32_t n_stops,
+                          const int32_t *h_stop_row, const int32_t *h_stop_set, const int32_t *h_stop_slot, int32_t n_stop_ids,
+                          const int32_t *h_stop_ids, int32_t n_stop_sets, const int32_t *h_stop_off, const float *d_last_rows,
+                          int32_t P, int64_t epoch, float *d_node_lp, float *d_stop_lp, int64_t n_slots, void *d_scratch,
+                          int64_t scratch_bytes, void *stream);
+/* Scratch bytes of one opus_llama_score_tree pass; -1 on a bad config, a negative count or rows above opus_llama_dec_rows_cap. */
+int64_t opus_llama_score_tree_scratch_bytes(const opus_config *cfg, int32_t rows, int32_t n_score, int32_t n_edges, int32_t n_stops,
+                                            int32_t n_stop_ids, int32_t n_stop_sets);
+/* Positions the decoder's activation buffers hold: the rows of one pass of opus_llama_score_tree / _score_continuations
+ * (max(max_batch x max_prompt, max_batch rounded up to 16)); -1 on a bad config. */
+int64_t opus_llama_dec_rows_cap(const opus_config *cfg);
+/* Deepest trie node opus_llama_score_tree takes (64). */
+int32_t opus_llama_tree_max_depth(void);
+/* member_lp[p, m] = the sum of d_node_lp[p, v] over the path of node d_member_node[d_trie[p], m], added in fp32 from the root to
+ * the leaf (-inf where that node is < 0).  d_par / d_depth int32 [tries, ld_nodes] (node 0 = the root), d_node_lp fp32
+ * [P, ld_nodes], d_member_node int32 [tries, M], d_trie int32 [P], d_member_lp fp32 [P, M]; all device. */
+int opus_trie_path_sums(opus_ctx *ctx, const float *d_node_lp, const int32_t *d_trie, const int32_t *d_par, const int32_t *d_depth,
+                        const int32_t *d_member_node, int32_t P, int32_t M, int32_t ld_nodes, float *d_member_lp, void *stream);
+/* attn_tree_kernel alone, on layer 0 of this context's KV cache: the arguments of opus_debug_attn_prefix with one position per row
+ * (d_qkv [R, (heads + 2 kv) hd]) and the host tables h_par / h_depth [R] of opus_llama_score_tree.  Row r attends to slots
+ * kstart[p] .. Tp - 1 of p = h_src[r], to its ancestors and to itself.  d_out [R, heads hd].  Leaves the context without a prefill. */
+int opus_debug_attn_tree(opus_ctx *ctx, const void *d_qkv, const void *d_k_hist, const void *d_v_hist, const int32_t *d_kstart,
+                         int32_t P, int32_t Tp, int32_t R, const int32_t *h_src, const int32_t *h_par, const int32_t *h_depth,
+                         void *d_out, void *stream);
 /* ESM-2 contact maps (EsmContactPredictionHead / fair-esm return_contacts=True) beside the per-residue states, on the token-packed
  * encoder: the same arguments and pooled output as opus_esm2_encode_packed, then d_contacts fp32 receives protein b's [n_b, n_b]
  * map (n_b = cu[b + 1] - cu[b] - 2 residues, row-major) at element offset sum_{b' < b} n_{b'}^2.  Needs the optional weights

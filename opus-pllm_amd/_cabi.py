@@ -112,6 +112,14 @@ SIGNATURES = {
                                                  C.c_int64, _P]),
     "opus_llama_score_scratch_bytes": (C.c_int64, [C.POINTER(CConfig), C.c_int32, C.c_int32]),
     "opus_debug_attn_prefix": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "opus_llama_score_tree": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P,
+                                        C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P]),
+    "opus_llama_score_tree_scratch_bytes": (C.c_int64, [C.POINTER(CConfig), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                        C.c_int32]),
+    "opus_llama_dec_rows_cap": (C.c_int64, [C.POINTER(CConfig)]),
+    "opus_llama_tree_max_depth": (C.c_int32, []),
+    "opus_trie_path_sums": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "opus_debug_attn_tree": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     "opus_debug_xent": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "opus_esm2_contacts_packed": (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.c_int32, _P, _P, _P, C.c_int64, _P]),
     "opus_esm2_contacts_scratch_bytes": (C.c_int64, [C.POINTER(CConfig), C.POINTER(C.c_int32), C.c_int32]),

@@ -17,7 +17,11 @@ Semantics, walking `sent` from the row's root:
   * after an end id, and after any id that was not allowed (a finished row's pads), the allowed ids are the end ids - never an
     empty list.
 Rows finish at an end id only if the caller passes the same ids as generate()'s `eos_token_id`.  A row whose every allowed id was
-banned by another processor (min_new_tokens larger than its shortest member, a bad word) is the caller's error."""
+banned by another processor (min_new_tokens larger than its shortest member, a bad word) is the caller's error.
+
+The same object is what OpusLlamaForCausalLM.score_trie(prefix, trie) scores: exact log-probabilities of EVERY member behind a
+cached prompt in one tree pass.  For that a trie numbers its members (`member_ids`, `member_nodes`, `input_member`,
+`member_strings`) and `plan_trie_score` cuts the tries of a prompt batch into passes of the decoder's layer loop (pure numpy)."""
 from __future__ import annotations
 
 from typing import List, Optional, Sequence, Union
@@ -106,6 +110,16 @@ class TokenTrie:
         # the trie: children[n] = {id: node}, complete[n]; node 0 is the root
         self.children: List[dict] = [{}]
         self.complete: List[bool] = [False]
+        # for score_trie(): node_tok / node_par / node_depth per node (root: -1, -1, 0); the distinct members in order of first
+        # insertion (member_ids, their end nodes member_nodes) and the member index of every sequence passed in (input_member)
+        self.node_tok: List[int] = [-1]
+        self.node_par: List[int] = [-1]
+        self.node_depth: List[int] = [0]
+        self.member_ids: List[List[int]] = []
+        self.member_nodes: List[int] = []
+        self.input_member: List[int] = []
+        self.member_strings: Optional[List[str]] = None
+        member_of_node: dict = {}
         n_members = 0
         for seq in sequences:
             ids = _as_ids(seq)
@@ -123,8 +137,16 @@ class TokenTrie:
                     self.children[node][t] = nxt
                     self.children.append({})
                     self.complete.append(False)
+                    self.node_tok.append(t)
+                    self.node_par.append(node)
+                    self.node_depth.append(self.node_depth[node] + 1)
                 node = nxt
             self.complete[node] = True
+            if node not in member_of_node:
+                member_of_node[node] = len(self.member_ids)
+                self.member_ids.append(ids)
+                self.member_nodes.append(node)
+            self.input_member.append(member_of_node[node])
             n_members += 1
         if n_members == 0:
             raise ValueError("TokenTrie needs at least one member")
@@ -134,6 +156,8 @@ class TokenTrie:
                 if done and first in self.children[n]:
                     raise ValueError(f"ambiguous separator: its first id {first} also continues a member that is complete there")
         self._compiled: Optional[CompiledConstraint] = None
+        self._preorder = None
+        self._score_plans: dict = {}          # score_trie()'s plans by (prefix rows, include_stop, rows per pass)
 
     # ------------------------------------------------------------------ construction helpers
     @classmethod
@@ -143,7 +167,12 @@ class TokenTrie:
         not "nucleus"): pass the text that precedes the answer in the prompt's continuation, usually " " or ""."""
         members = [_encode(tokenizer, prefix + s) for s in strings]
         sep = None if separator is None else _encode(tokenizer, separator)
-        return cls(members, end_token_id=end_token_id, separator=sep)
+        trie = cls(members, end_token_id=end_token_id, separator=sep)
+        first = {}
+        for s, m in zip(strings, trie.input_member):
+            first.setdefault(m, s)
+        trie.member_strings = [first[m] for m in range(len(trie.member_ids))]
+        return trie
 
     @staticmethod
     def per_row(tries: Sequence["TokenTrie"]) -> "PerRowTokenTrie":
@@ -223,6 +252,33 @@ class TokenTrie:
     def n_rows(self) -> Optional[int]:
         return None
 
+    # ------------------------------------------------------------------ score_trie()
+    @property
+    def n_nodes(self) -> int:
+        """Nodes below the root."""
+        return len(self.children) - 1
+
+    @property
+    def max_depth(self) -> int:
+        return max(self.node_depth)
+
+    def stop_ids(self) -> List[int]:
+        """What a completing state allows besides the children: the end ids, then the separator's first id."""
+        return list(self.end_ids) + ([self.separator[0]] if self.separator is not None else [])
+
+    def preorder(self) -> np.ndarray:
+        """Nodes >= 1 in depth-first preorder, children in ascending id."""
+        if self._preorder is None:
+            out, stack = [], [0]
+            while stack:
+                v = stack.pop()
+                if v:
+                    out.append(v)
+                kids = self.children[v]
+                stack.extend(kids[t] for t in sorted(kids, reverse=True))
+            self._preorder = np.asarray(out, dtype=np.int32)
+        return self._preorder
+
 
 class PerRowTokenTrie:
     """TokenTrie.per_row: one table, one start state per row.  Every trie has the same end ids."""
@@ -236,6 +292,7 @@ class PerRowTokenTrie:
         self.tries = tries
         self.end_ids = tries[0].end_ids
         self._compiled: Optional[CompiledConstraint] = None
+        self._score_plans: dict = {}
 
     def __call__(self, batch_id, sent) -> List[int]:
         return self.tries[int(batch_id)].allowed_after(sent)
@@ -270,6 +327,140 @@ def _compile(tries: Sequence[TokenTrie], which: Sequence[int]) -> CompiledConstr
     if off[-1] >= 2 ** 31 or len(counts) >= 2 ** 31:
         raise ValueError("the constraint's table does not fit 32-bit indices")
     return CompiledConstraint(off, toks, nxts, comp, tries[0].end_ids, [roots[w] for w in which])
+
+
+# ---------------------------------------------------------------------------------------------------- score_trie(): the plan
+TRIE_MAX_DEPTH = 64           # deepest member score_trie() takes (opus_llama_tree_max_depth() of the library says the same)
+
+
+class TriePass:
+    """One pass of the decoder's layer loop.  Per row (arrays of length `rows`): tok, prow (prefix row), parent (row of this pass,
+    -1 = the prompt's last position), depth, node, scored (False: an ancestor of the pass's first node, re-computed so that its
+    descendants can attend to it, scored in an earlier pass).  score_src: the rows that go through the lm_head - a row of the pass,
+    or -(p) - 1 for prefix row p's last position.  Edges (edge_row ascending indices into score_src, edge_tok, edge_slot) and stop
+    entries (stop_row ascending, stop_set, stop_slot); slot = p (N + 1) + node."""
+
+    def __init__(self):
+        self.tok, self.prow, self.parent, self.depth, self.node, self.scored = [], [], [], [], [], []
+        self.score_src, self.edge_row, self.edge_tok, self.edge_slot = [], [], [], []
+        self.stop_row, self.stop_set, self.stop_slot = [], [], []
+
+    @property
+    def rows(self) -> int:
+        return len(self.tok)
+
+    def _freeze(self):
+        for k, v in vars(self).items():
+            setattr(self, k, np.asarray(v, dtype=bool if k == "scored" else np.int32))
+        return self
+
+
+class TriePlan:
+    """plan_trie_score's result: passes; P, N (most nodes below a root), M (most members); tries (the distinct tries) and
+    trie_of_row [P]; n_nodes / n_members [P]; rows_evaluated (all passes, re-computed chains included) and evaluated_nodes (without
+    them); stop_ids / stop_off (one id set per distinct trie); node_par / node_depth [tries, N + 1] and member_node [tries, M]
+    (-1 beyond a trie's own count) for the path sums."""
+
+
+def plan_trie_score(tries: Sequence[TokenTrie], include_stop: bool, rows_cap: int) -> TriePlan:
+    """The passes that score tries[p] behind prefix row p (the same object for rows that share a trie).
+
+    Evaluated nodes: without a stop term the nodes >= 1 that have a child (a leaf's token is scored from its parent's logits and
+    nobody attends to a leaf), with it every node >= 1.  Order: prefix row by prefix row, each trie in preorder (children in
+    ascending id).  A pass is a run of that order of at most rows_cap rows, the ancestors of its first node included: in preorder
+    every other parent lies inside the run.  Passes may mix prefix rows.  A root's edges (scored from the prompt's last position)
+    go with the pass that begins its prefix row and cost no row."""
+    tries = list(tries)
+    if not tries or any(not isinstance(t, TokenTrie) for t in tries):
+        raise TypeError("plan_trie_score takes a non-empty list of TokenTrie objects")
+    deepest = max(t.max_depth for t in tries)
+    if deepest > TRIE_MAX_DEPTH:
+        raise ValueError(f"a member of {deepest} ids: score_trie() takes tries up to depth {TRIE_MAX_DEPTH}")
+    if rows_cap < deepest:
+        raise ValueError(f"rows_cap={rows_cap} cannot hold a chain of depth {deepest}")
+    plan = TriePlan()
+    distinct, index = [], {}
+    for t in tries:
+        if id(t) not in index:
+            index[id(t)] = len(distinct)
+            distinct.append(t)
+    P, N, M = len(tries), max(t.n_nodes for t in tries), max(len(t.member_ids) for t in tries)
+    plan.P, plan.N, plan.M, plan.include_stop = P, N, M, bool(include_stop)
+    plan.tries = distinct
+    plan.trie_of_row = np.asarray([index[id(t)] for t in tries], dtype=np.int32)
+    plan.n_nodes = np.asarray([t.n_nodes for t in tries], dtype=np.int64)
+    plan.n_members = np.asarray([len(t.member_ids) for t in tries], dtype=np.int64)
+    plan.node_par = np.full((len(distinct), N + 1), -1, dtype=np.int32)
+    plan.node_depth = np.zeros((len(distinct), N + 1), dtype=np.int32)
+    plan.member_node = np.full((len(distinct), M), -1, dtype=np.int32)
+    off, ids = [0], []
+    for k, t in enumerate(distinct):
+        plan.node_par[k, : t.n_nodes + 1] = t.node_par
+        plan.node_depth[k, : t.n_nodes + 1] = t.node_depth
+        plan.member_node[k, : len(t.member_nodes)] = t.member_nodes
+        ids += t.stop_ids()
+        off.append(len(ids))
+    plan.stop_ids = np.asarray(ids, dtype=np.int32)
+    plan.stop_off = np.asarray(off, dtype=np.int32)
+
+    passes, cur, row_of = [], TriePass(), {}
+    evaluated = 0
+
+    def close():
+        nonlocal cur, row_of
+        if cur.rows or len(cur.score_src):
+            passes.append(cur._freeze())
+        cur, row_of = TriePass(), {}
+
+    def add_row(t, p, v, scored):
+        row_of[v] = cur.rows
+        cur.tok.append(t.node_tok[v])
+        cur.prow.append(p)
+        cur.parent.append(-1 if t.node_par[v] == 0 else row_of[t.node_par[v]])
+        cur.depth.append(t.node_depth[v])
+        cur.node.append(v)
+        cur.scored.append(scored)
+
+    def add_edges(t, p, v, src):
+        """Node v's logits (source `src`) score its children and, in a completing state with a stop term, the stop ids."""
+        kids = t.children[v]
+        stop = include_stop and t.complete[v]
+        if not kids and not stop:
+            return
+        k = len(cur.score_src)
+        cur.score_src.append(src)
+        for tok in sorted(kids):
+            cur.edge_row.append(k)
+            cur.edge_tok.append(tok)
+            cur.edge_slot.append(p * (N + 1) + kids[tok])
+        if stop:
+            cur.stop_row.append(k)
+            cur.stop_set.append(index[id(t)])
+            cur.stop_slot.append(p * (N + 1) + v)
+
+    for p, t in enumerate(tries):
+        row_of = {}                                            # (rows of another prefix row are no parents of this one's)
+        add_edges(t, p, 0, -p - 1)
+        for v in t.preorder().tolist():
+            if not include_stop and not t.children[v]:
+                continue
+            if cur.rows >= rows_cap:
+                close()
+            if t.node_par[v] != 0 and t.node_par[v] not in row_of:      # a fresh pass in the middle of a trie: the chain first
+                chain, a = [], t.node_par[v]
+                while a != 0:
+                    chain.append(a)
+                    a = t.node_par[a]
+                for a in reversed(chain):
+                    add_row(t, p, a, False)
+            add_row(t, p, v, True)
+            add_edges(t, p, v, cur.rows - 1)
+            evaluated += 1
+    close()
+    plan.passes = passes
+    plan.evaluated_nodes = evaluated
+    plan.rows_evaluated = int(sum(ps.rows for ps in passes))
+    return plan
 
 
 def is_constraint(obj) -> bool:

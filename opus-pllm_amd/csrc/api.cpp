@@ -200,7 +200,8 @@ static void new_epoch(opus_ctx *c) { c->epoch = ++g_epoch; }
 
 // Continuation rows of opus_llama_score_continuations in the prefill's layer loop: B rows of T new positions behind a cached prefix.
 // No mask / kstart upload, no cache write, no decode state: rotary (learned positions for OPT) at Tp - kstart[p] + t through
-// nkst[b] = kstart[p] - Tp, and attn_prefix_kernel instead of the causal prefill attention.
+// nkst[b] = kstart[p] - Tp, and attn_prefix_kernel instead of the causal prefill attention.  opus_llama_score_tree runs trie nodes
+// the same way: T = 1, nkst[b] = kstart[p] - Tp - (depth - 1), and attn.par set selects attn_tree_kernel.
 struct ContRows {
     const int32_t *nkst;          // [B] device
     AttnPrefixParams attn;        // layer-independent fields (kc / vc are set per layer)
@@ -1115,7 +1116,7 @@ static int attn_prefix(opus_ctx *c, hipStream_t s, const ContRows &cr, int l, in
     const int QKV = (g.dec_heads + 2 * g.dec_kv_heads) * g.dec_head_dim, QD = g.dec_heads * g.dec_head_dim;
     // algorithmic bytes: the rows' projections + output, and every (prefix row, kv head)'s visible cache slots once
     KLF(KC_ATTN_PREFILL, 2.0 * M * (QKV + QD) + 4.0 * cr.nblocks * g.dec_kv_heads * g.dec_head_dim * a.Tp,
-        4.0 * M * (double)QD * (a.Tp + a.n), launch_attn_prefix(a, cr.nblocks, s));
+        4.0 * M * (double)QD * (a.Tp + a.n), a.par ? launch_attn_tree(a, cr.nblocks, s) : launch_attn_prefix(a, cr.nblocks, s));
     return OPUS_OK;
 }
 
@@ -1703,6 +1704,231 @@ extern "C" int opus_debug_attn_prefix(opus_ctx *c, const void *d_qkv, const void
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     (void)hipFree(d_tbl);
     if (e != hipSuccess) return fail(OPUS_EHIP, "debug_attn_prefix failed: %s", hipGetErrorString(e));
+    return OPUS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ trie scoring
+// opus_llama_score_tree = one pass of a token trie's nodes behind the cached prefix: every row is one new position (a node) that
+// attends to its prefix row's cache slots and to its own ancestors in the pass (attn_tree_kernel).  The planning (which nodes,
+// which order, which pass) is the caller's (opus-pllm_amd/constraint.py, plan_trie_score); this entry checks every table it is
+// given before anything reaches a kernel.
+enum { TREE_MAX_DEPTH = 64 };
+
+extern "C" int64_t opus_llama_dec_rows_cap(const opus_config *cfg) {
+    if (check_cfg(cfg) != OPUS_OK) return -1;
+    return dec_rows_cap(*cfg);
+}
+extern "C" int32_t opus_llama_tree_max_depth(void) { return TREE_MAX_DEPTH; }
+
+// scored rows per lm_head chunk: the slab's cap, and never more rows than the activation buffers hold (the scored list of a full
+// pass is up to max_batch entries longer than the pass: the prefix rows' last positions)
+static int64_t tree_chunk(const opus_config &g, int64_t n_score) {
+    return score_chunk_cap(g, std::min<int64_t>(std::max<int64_t>(n_score, 1), dec_rows_cap(g)), true);
+}
+static int64_t tree_table_words(const opus_config &g, int64_t rows, int64_t n_score, int64_t n_edges, int64_t n_stops, int64_t n_ids,
+                                int64_t n_sets) {
+    const int G = g.dec_heads / g.dec_kv_heads;
+    return (int64_t)g.max_batch + 1 + 3 * rows + 2 * (int64_t)attn_prefix_max_blocks((int)rows, g.max_batch, G, 1) + n_score +
+           3 * n_edges + 3 * n_stops + n_ids + n_sets + 1 + tree_chunk(g, n_score);
+}
+static int64_t tree_scratch_bytes(const opus_config &g, int64_t rows, int64_t n_score, int64_t n_edges, int64_t n_stops, int64_t n_ids,
+                                  int64_t n_sets) {
+    const int64_t chunk = tree_chunk(g, n_score);
+    return (int64_t)align_up((size_t)tree_table_words(g, rows, n_score, n_edges, n_stops, n_ids, n_sets) * sizeof(int32_t)) +
+           score_chunk_bytes(g, chunk, true) + 2 * (int64_t)align_up((size_t)chunk * sizeof(float));
+}
+
+extern "C" int64_t opus_llama_score_tree_scratch_bytes(const opus_config *cfg, int32_t rows, int32_t n_score, int32_t n_edges,
+                                                       int32_t n_stops, int32_t n_stop_ids, int32_t n_stop_sets) {
+    if (check_cfg(cfg) != OPUS_OK) return -1;
+    if (rows < 0 || rows > dec_rows_cap(*cfg) || n_score < 0 || n_edges < 0 || n_stops < 0 || n_stop_ids < 0 || n_stop_sets < 0) {
+        fail(OPUS_ESHAPE, "score_tree_scratch_bytes: rows=%d (0 .. %lld) scored=%d edges=%d stops=%d ids=%d sets=%d", rows,
+             (long long)dec_rows_cap(*cfg), n_score, n_edges, n_stops, n_stop_ids, n_stop_sets);
+        return -1;
+    }
+    return tree_scratch_bytes(*cfg, rows, n_score, n_edges, n_stops, n_stop_ids, n_stop_sets);
+}
+
+// the rows' tables of one pass: every parent earlier in the pass, in the same prefix row, one level up
+static int check_tree_rows(const char *who, int rows, int P, const int32_t *h_src, const int32_t *h_par, const int32_t *h_depth) {
+    for (int r = 0; r < rows; ++r) {
+        if (h_src[r] < 0 || h_src[r] >= P) return fail(OPUS_EBADARG, "%s: prefix row %d of row %d outside [0, %d)", who, h_src[r], r, P);
+        if (h_depth[r] < 1 || h_depth[r] > TREE_MAX_DEPTH)
+            return fail(OPUS_ESHAPE, "%s: depth %d of row %d outside [1, %d]", who, h_depth[r], r, (int)TREE_MAX_DEPTH);
+        const int pa = h_par[r];
+        if (h_depth[r] == 1 ? pa != -1 : (pa < 0 || pa >= r || h_src[pa] != h_src[r] || h_depth[pa] != h_depth[r] - 1))
+            return fail(OPUS_EBADARG, "%s: parent %d of row %d (depth %d) is not an earlier row of its prefix row one level up", who, pa,
+                        r, h_depth[r]);
+    }
+    return OPUS_OK;
+}
+
+extern "C" int opus_llama_score_tree(opus_ctx *c, const void *d_embeds, int32_t rows, const int32_t *h_src, const int32_t *h_par,
+                                     const int32_t *h_depth, int32_t n_score, const int32_t *h_score_src, int32_t n_edges,
+                                     const int32_t *h_edge_row, const int32_t *h_edge_tok, const int32_t *h_edge_slot, int32_t n_stops,
+                                     const int32_t *h_stop_row, const int32_t *h_stop_set, const int32_t *h_stop_slot,
+                                     int32_t n_stop_ids, const int32_t *h_stop_ids, int32_t n_stop_sets, const int32_t *h_stop_off,
+                                     const float *d_last_rows, int32_t P, int64_t epoch, float *d_node_lp, float *d_stop_lp,
+                                     int64_t n_slots, void *d_scratch, int64_t scratch_bytes, void *stream) {
+    OPC(need_ready(c));
+    const opus_config &g = c->cfg;
+    if (rows < 0 || rows > dec_rows_cap(g) || n_score < 0 || n_edges < 0 || n_stops < 0 || n_stop_ids < 0 || n_stop_sets < 0 || n_slots < 1)
+        return fail(OPUS_ESHAPE, "score_tree: rows=%d (0 .. %lld) scored=%d edges=%d stops=%d ids=%d sets=%d slots=%lld", rows,
+                    (long long)dec_rows_cap(g), n_score, n_edges, n_stops, n_stop_ids, n_stop_sets, (long long)n_slots);
+    if (!d_last_rows || !d_node_lp || !d_scratch || (rows && (!d_embeds || !h_src || !h_par || !h_depth)) || (n_score && !h_score_src) ||
+        (n_edges && (!h_edge_row || !h_edge_tok || !h_edge_slot)) ||
+        (n_stops && (!h_stop_row || !h_stop_set || !h_stop_slot || !h_stop_ids || !h_stop_off || !d_stop_lp)))
+        return fail(OPUS_EBADARG, "score_tree: null pointer");
+    if (!c->prefilled || epoch != c->epoch || (int)c->h_kstart.size() != c->cur_B || P != c->cur_B)
+        return fail(OPUS_ESTATE, "score_tree: the prefix is not this context's current one (a later call prefilled or permuted the "
+                                 "cache, or the handle belongs to another context)");
+    const int Tp = c->cur_T, ctx_cap = g.max_prompt + g.max_new_tokens, V = g.dec_vocab, H = g.dec_dim;
+    OPC(check_tree_rows("score_tree", rows, P, h_src, h_par, h_depth));
+    for (int r = 0; r < rows; ++r)
+        if (Tp - c->h_kstart[h_src[r]] + h_depth[r] > ctx_cap)
+            return fail(OPUS_ESHAPE, "score_tree: prefix of %d tokens + depth %d exceed the context's %d positions (max_prompt + "
+                                     "max_new_tokens)", Tp - c->h_kstart[h_src[r]], h_depth[r], ctx_cap);
+    for (int k = 0; k < n_score; ++k)
+        if (h_score_src[k] >= rows || h_score_src[k] < -P)
+            return fail(OPUS_EBADARG, "score_tree: scored source %d of entry %d outside [-%d, %d)", h_score_src[k], k, P, rows);
+    for (int e = 0; e < n_edges; ++e)
+        if (h_edge_row[e] < (e ? h_edge_row[e - 1] : 0) || h_edge_row[e] >= n_score || h_edge_tok[e] < 0 || h_edge_tok[e] >= V ||
+            h_edge_slot[e] < 0 || h_edge_slot[e] >= n_slots)
+            return fail(OPUS_EBADARG, "score_tree: edge %d (scored row %d, id %d, slot %d): rows ascending below %d, ids below %d, "
+                                      "slots below %lld", e, h_edge_row[e], h_edge_tok[e], h_edge_slot[e], n_score, V, (long long)n_slots);
+    if (n_stops) {
+        if (n_stop_sets < 1 || h_stop_off[0] != 0 || h_stop_off[n_stop_sets] != n_stop_ids)
+            return fail(OPUS_EBADARG, "score_tree: stop sets: offsets must run from 0 to %d", n_stop_ids);
+        for (int k = 0; k < n_stop_sets; ++k)
+            if (h_stop_off[k + 1] <= h_stop_off[k]) return fail(OPUS_EBADARG, "score_tree: stop set %d is empty or out of order", k);
+        for (int k = 0; k < n_stop_ids; ++k)
+            if (h_stop_ids[k] < 0 || h_stop_ids[k] >= V) return fail(OPUS_EBADARG, "score_tree: stop id %d outside [0, %d)", h_stop_ids[k], V);
+        for (int k = 0; k < n_stops; ++k)
+            if (h_stop_row[k] < (k ? h_stop_row[k - 1] : 0) || h_stop_row[k] >= n_score || h_stop_set[k] < 0 ||
+                h_stop_set[k] >= n_stop_sets || h_stop_slot[k] < 0 || h_stop_slot[k] >= n_slots)
+                return fail(OPUS_EBADARG, "score_tree: stop entry %d (scored row %d, set %d, slot %d)", k, h_stop_row[k], h_stop_set[k],
+                            h_stop_slot[k]);
+    }
+    const int64_t need = tree_scratch_bytes(g, rows, n_score, n_edges, n_stops, n_stop_ids, n_stop_sets);
+    if (scratch_bytes < need)
+        return fail(OPUS_EBADARG, "score_tree: scratch of %lld bytes, %lld needed (opus_llama_score_tree_scratch_bytes)",
+                    (long long)scratch_bytes, (long long)need);
+    hipStream_t s = (hipStream_t)stream;
+    const int G = g.dec_heads / g.dec_kv_heads;
+    const int64_t chunk = tree_chunk(g, n_score);
+    PrefixTables t;
+    build_prefix_tables(g, c->h_kstart, Tp, h_src, rows, 1, t);
+    if (t.nblocks > attn_prefix_max_blocks(rows, g.max_batch, G, 1)) return fail(OPUS_EHIP, "score_tree: block table overflow");
+    for (int r = 0; r < rows; ++r) t.w[t.nkst + r] -= h_depth[r] - 1;      // position of a node at depth d: Tp - kstart[p] + d - 1
+    auto put = [&](const int32_t *src, int64_t n) {
+        const int at = (int)t.w.size();
+        if (n > 0) t.w.insert(t.w.end(), src, src + n);
+        return at;
+    };
+    const int o_par = put(h_par, rows), o_src = put(h_score_src, n_score);
+    const int o_er = put(h_edge_row, n_edges), o_et = put(h_edge_tok, n_edges), o_es = put(h_edge_slot, n_edges);
+    const int o_sr = put(h_stop_row, n_stops), o_ss = put(h_stop_set, n_stops), o_sl = put(h_stop_slot, n_stops);
+    const int o_ids = put(h_stop_ids, n_stops ? n_stop_ids : 0), o_off = put(h_stop_off, n_stops ? n_stop_sets + 1 : 0);
+    const int o_neg = (int)t.w.size();
+    t.w.insert(t.w.end(), (size_t)chunk, -1);                                // xent's targets: none counted, the lse is what is used
+    const int64_t words = tree_table_words(g, rows, n_score, n_edges, n_stops, n_stop_ids, n_stop_sets);
+    if ((int64_t)t.w.size() > words) return fail(OPUS_EHIP, "score_tree: table overflow");
+    int32_t *tbl = reinterpret_cast<int32_t *>(d_scratch);
+    float *rows_f = reinterpret_cast<float *>((char *)d_scratch + align_up((size_t)words * sizeof(int32_t)));
+    half_t *slab = reinterpret_cast<half_t *>((char *)rows_f + align_up((size_t)chunk * H * sizeof(float)));
+    float *lse = reinterpret_cast<float *>((char *)slab + align_up((size_t)chunk * V * sizeof(half_t)));
+    float *lp_none = reinterpret_cast<float *>((char *)lse + align_up((size_t)chunk * sizeof(float)));
+    HIPC(hipMemcpyAsync(tbl, t.w.data(), t.w.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (rows > 0) {
+        ContRows cr;
+        cr.nkst = tbl + t.nkst;
+        cr.nblocks = t.nblocks;
+        AttnPrefixParams &a = cr.attn;
+        a.kc = a.vc = nullptr; a.cache_sb = c->cache_sb; a.cache_sh = c->cache_sh; a.kstart = c->d_kstart; a.Tp = Tp;
+        a.qkv = c->d_qkv; a.n = 1; a.list = tbl + t.list; a.off = tbl + t.off; a.blocks = tbl + t.blocks; a.out = c->d_ctx;
+        a.nh = g.dec_heads; a.nkv = g.dec_kv_heads; a.hd = g.dec_head_dim; a.scale = 1.0f / sqrtf((float)g.dec_head_dim);
+        a.par = tbl + o_par;
+        OPC(prefill(c, s, reinterpret_cast<const half_t *>(d_embeds), nullptr, rows, 1, true, &cr));
+    }
+    c->phase = PH_SCORE;
+    int e0 = 0, k0s = 0;
+    for (int64_t k0 = 0; k0 < n_score; k0 += chunk) {
+        const int m = (int)std::min<int64_t>(chunk, n_score - k0);
+        int e1 = e0, k1s = k0s;
+        while (e1 < n_edges && h_edge_row[e1] < k0 + m) ++e1;
+        while (k1s < n_stops && h_stop_row[k1s] < k0 + m) ++k1s;
+        KL(KC_OTHER, 8.0 * m * H + 4.0 * m, launch_gather_rows2(c->d_x, rows, d_last_rows, P, tbl + o_src + k0, m, H, rows_f, s));
+        OPC(score_rows(c, s, rows_f, m, slab, tbl + o_neg, lp_none, lse));
+        KL(KC_XENT, 14.0 * (e1 - e0) + 16.0 * (k1s - k0s),
+           launch_tree_edges(slab, V, lse, (int)k0, tbl + o_er + e0, tbl + o_et + e0, tbl + o_es + e0, e1 - e0, d_node_lp,
+                             tbl + o_sr + k0s, tbl + o_ss + k0s, tbl + o_sl + k0s, k1s - k0s, tbl + o_ids, tbl + o_off, d_stop_lp, s));
+        e0 = e1;
+        k0s = k1s;
+    }
+    HIPC(hipStreamSynchronize(s));                                          // (the host tables are the caller's: they may go away)
+    return OPUS_OK;
+}
+
+extern "C" int opus_trie_path_sums(opus_ctx *c, const float *d_node_lp, const int32_t *d_trie, const int32_t *d_par,
+                                   const int32_t *d_depth, const int32_t *d_member_node, int32_t P, int32_t M, int32_t ld_nodes,
+                                   float *d_member_lp, void *stream) {
+    if (!c) return fail(OPUS_EBADARG, "ctx is null");
+    if (!d_node_lp || !d_trie || !d_par || !d_depth || !d_member_node || !d_member_lp) return fail(OPUS_EBADARG, "trie_path_sums: null pointer");
+    if (P < 1 || M < 1 || ld_nodes < 2) return fail(OPUS_ESHAPE, "trie_path_sums: P=%d M=%d nodes=%d", P, M, ld_nodes);
+    HIPC(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    c->phase = PH_SCORE;
+    KL(KC_OTHER, 12.0 * P * M, launch_tree_path_sums(d_node_lp, d_trie, d_par, d_depth, d_member_node, P, M, ld_nodes, d_member_lp, s));
+    return OPUS_OK;
+}
+
+// attn_tree_kernel alone, as opus_llama_score_tree launches it, on layer 0 of this context's KV cache: the arguments of
+// opus_debug_attn_prefix with one position per row (d_qkv [R, (heads + 2 kv) hd]) and h_par / h_depth [R] (host): the parent row
+// of every row (-1 at depth 1; an earlier row of the same prefix row one level up).  d_out [R, heads hd].
+extern "C" int opus_debug_attn_tree(opus_ctx *c, const void *d_qkv, const void *d_k_hist, const void *d_v_hist, const int32_t *d_kstart,
+                                    int32_t P, int32_t Tp, int32_t R, const int32_t *h_src, const int32_t *h_par, const int32_t *h_depth,
+                                    void *d_out, void *stream) {
+    if (!c || !d_qkv || !d_k_hist || !d_v_hist || !d_kstart || !h_src || !h_par || !h_depth || !d_out)
+        return fail(OPUS_EBADARG, "debug_attn_tree: null pointer");
+    const opus_config &g = c->cfg;
+    if (P < 1 || P > g.max_batch || Tp < 1 || Tp > g.max_prompt || R < 1)
+        return fail(OPUS_ESHAPE, "debug_attn_tree: P=%d Tp=%d R=%d exceed the context (%d, %d)", P, Tp, R, g.max_batch, g.max_prompt);
+    OPC(check_tree_rows("debug_attn_tree", R, P, h_src, h_par, h_depth));
+    HIPC(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int nkv = g.dec_kv_heads, hd = g.dec_head_dim, G = g.dec_heads / nkv;
+    std::vector<int32_t> kst(P);
+    HIPC(hipMemcpyAsync(kst.data(), d_kstart, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    for (int p = 0; p < P; ++p)
+        if (kst[p] < 0 || kst[p] >= Tp) return fail(OPUS_EBADARG, "debug_attn_tree: kstart[%d]=%d outside [0, %d)", p, kst[p], Tp);
+    c->prefilled = false;                                     // (the cache no longer belongs to a prefill)
+    new_epoch(c);
+    const size_t pitch = (size_t)c->cache_sh * sizeof(half_t), roww = (size_t)Tp * hd * sizeof(half_t);
+    HIPC(hipMemcpy2DAsync(c->kc, pitch, d_k_hist, roww, roww, (size_t)P * nkv, hipMemcpyDeviceToDevice, s));
+    HIPC(hipMemcpy2DAsync(c->vc, pitch, d_v_hist, roww, roww, (size_t)P * nkv, hipMemcpyDeviceToDevice, s));
+    HIPC(hipMemcpyAsync(c->d_kstart, d_kstart, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    PrefixTables t;
+    build_prefix_tables(g, kst, Tp, h_src, R, 1, t);
+    const int o_par = (int)t.w.size();
+    t.w.insert(t.w.end(), h_par, h_par + R);
+    int32_t *d_tbl = nullptr;
+    HIPC(hipMalloc((void **)&d_tbl, t.w.size() * sizeof(int32_t)));
+    hipError_t e = hipMemcpyAsync(d_tbl, t.w.data(), t.w.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
+    AttnPrefixParams a;
+    a.kc = c->kc; a.vc = c->vc; a.cache_sb = c->cache_sb; a.cache_sh = c->cache_sh; a.kstart = c->d_kstart; a.Tp = Tp;
+    a.qkv = (const half_t *)d_qkv; a.n = 1; a.list = d_tbl + t.list; a.off = d_tbl + t.off; a.blocks = d_tbl + t.blocks;
+    a.out = (half_t *)d_out; a.nh = g.dec_heads; a.nkv = nkv; a.hd = hd; a.scale = 1.0f / sqrtf((float)hd);
+    a.par = d_tbl + o_par;
+    c->phase = PH_SCORE;
+    if (e == hipSuccess) {
+        Timed tm(c, s, KC_ATTN_PREFILL, 2.0 * R * (double)(G + 2) * nkv * hd * 2 + 4.0 * t.nblocks * nkv * hd * Tp,
+                 4.0 * R * (double)G * nkv * hd * (Tp + 1));
+        e = launch_attn_tree(a, t.nblocks, s);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(d_tbl);
+    if (e != hipSuccess) return fail(OPUS_EHIP, "debug_attn_tree failed: %s", hipGetErrorString(e));
     return OPUS_OK;
 }
 

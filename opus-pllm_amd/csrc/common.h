@@ -268,11 +268,16 @@ struct AttnPrefixParams {
     half_t *out;
     int nh, nkv, hd;
     float scale;
+    const int32_t *par = nullptr;   // launch_attn_tree only: parent row of every row of the pass (-1: a child of the root)
 };
 // workgroup table of launch_attn_prefix for the row lists off[0 .. P] (blocks = nullptr: count only); returns the block count
 int attn_prefix_blocks(const int32_t *off, int P, int G, int n, int32_t *blocks);
 int attn_prefix_max_blocks(int R, int P, int G, int n);   // an upper bound of that count for R rows over P prefix rows
 hipError_t launch_attn_prefix(const AttnPrefixParams &p, int nblocks, hipStream_t s);
+// attn_tree.hip: tree attention of opus_llama_score_tree.  The same parameters with n = 1 (one new position per row: a trie node)
+// and par set: row r attends to the cache slots of its prefix row, then to r, par[r], par[par[r]], ... (rows of this pass, the
+// chain ends at -1).  blocks: attn_prefix_blocks(off, P, G, 1).
+hipError_t launch_attn_tree(const AttnPrefixParams &p, int nblocks, hipStream_t s);
 
 // contact.hip: ESM-2 contact maps (opus_esm2_contacts_packed).  One layer's accumulation over token-packed proteins cu[B + 1]
 // (rows <cls> residues <eos>): Q / K rows of stride ld (head h at column h hd; q scaled and both rotated as the attention takes
@@ -343,6 +348,16 @@ hipError_t launch_gather_rows2(const float *x, int64_t n_x, const float *y, int6
 // target < 0: 0, target >= V: NaN; lse may be null)
 hipError_t launch_xent(const half_t *logits, int64_t ld, int R, int V, const int32_t *targets, float *logprob, float *lse,
                        hipStream_t s);
+// score.hip: trie scoring behind launch_xent's lse over the n logits rows of a chunk [n, V].  Edge e (row erow[e] - row0 of the
+// chunk, token etok[e]) writes node_lp[eslot[e]] = l[row][tok] - lse[row]; stop entry k (row srow[k] - row0, id set sset[k] =
+// ids[soff[set] .. soff[set + 1])) writes stop_lp[sslot[k]] = log sum_ids exp(l[row][id] - lse[row]), ids added in list order.
+hipError_t launch_tree_edges(const half_t *logits, int64_t ld, const float *lse, int row0, const int32_t *erow, const int32_t *etok,
+                             const int32_t *eslot, int n_edges, float *node_lp, const int32_t *srow, const int32_t *sset,
+                             const int32_t *sslot, int n_stops, const int32_t *ids, const int32_t *soff, float *stop_lp, hipStream_t s);
+// score.hip: member_lp[p, m] = sum of node_lp[p, v] over the path of member node mnode[trie[p], m] in root-to-leaf order (fp32;
+// -inf where mnode < 0).  par / depth [tries, ld_nodes] describe each distinct trie, node_lp [P, ld_nodes], mnode [tries, M].
+hipError_t launch_tree_path_sums(const float *node_lp, const int32_t *trie, const int32_t *par, const int32_t *depth,
+                                 const int32_t *mnode, int P, int M, int ld_nodes, float *member_lp, hipStream_t s);
 hipError_t launch_relu_h(half_t *x, int64_t n, hipStream_t s);
 hipError_t launch_fill_synth(void *dst, int dtype, int64_t rows, int64_t cols, uint64_t seed, float std,
                              float mean, int64_t rb, int64_t rs, int64_t ro, int tiled, uint64_t fold_seed,

@@ -3,6 +3,8 @@
 //   gather_rows : out[r] = x[rows[r]] for fp32 residual-stream rows (launch_take_last with an index list); gather_rows2 the
 //                 same over two sources (opus_llama_score_continuations: continuation rows and the prefix's last rows)
 //   xent        : per row of operand-dtype logits [R, V] and target y: lse = logsumexp(l), logprob = l[y] - lse (fp32)
+//   tree_edges  : trie scoring (opus_llama_score_tree): many (row, token) edges and stop-id sums read from one chunk of logits
+//   tree_path_sums : a member's log-prob = the sum of its path's node log-probs (opus_trie_path_sums)
 #include "common.h"
 
 namespace opus {
@@ -144,6 +146,74 @@ hipError_t launch_xent(const half_t *logits, int64_t ld, int R, int V, const int
     if (V < 1 || ld < V) return hipErrorInvalidValue;
     if (V >= 4096) hipLaunchKernelGGL(xent_kernel<4>, dim3(R), dim3(256), 0, s, logits, ld, R, V, targets, logprob, lse);
     else hipLaunchKernelGGL(xent_kernel<1>, dim3((R + 3) / 4), dim3(256), 0, s, logits, ld, R, V, targets, logprob, lse);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------ trie scoring
+// A thread per edge, then a thread per stop entry.  Every output slot is written by exactly one thread and every sum runs in list
+// order: no atomics, bitwise repeatable.
+__global__ __launch_bounds__(256) void tree_edges_kernel(const half_t *__restrict__ logits, int64_t ld, const float *__restrict__ lse,
+                                                         int row0, const int32_t *__restrict__ erow, const int32_t *__restrict__ etok,
+                                                         const int32_t *__restrict__ eslot, int n_edges, float *__restrict__ node_lp,
+                                                         const int32_t *__restrict__ srow, const int32_t *__restrict__ sset,
+                                                         const int32_t *__restrict__ sslot, int n_stops,
+                                                         const int32_t *__restrict__ ids, const int32_t *__restrict__ soff,
+                                                         float *__restrict__ stop_lp) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n_edges) {
+        const int r = erow[i] - row0;
+        node_lp[eslot[i]] = (float)logits[(int64_t)r * ld + etok[i]] - lse[r];
+    } else if (i < n_edges + n_stops) {
+        const int k = i - n_edges, r = srow[k] - row0, set = sset[k];
+        const half_t *p = logits + (int64_t)r * ld;
+        const float base = lse[r];
+        float sum = 0.f;
+        for (int j = soff[set]; j < soff[set + 1]; ++j) sum += __expf((float)p[ids[j]] - base);
+        stop_lp[sslot[k]] = __logf(sum);
+    }
+}
+hipError_t launch_tree_edges(const half_t *logits, int64_t ld, const float *lse, int row0, const int32_t *erow, const int32_t *etok,
+                             const int32_t *eslot, int n_edges, float *node_lp, const int32_t *srow, const int32_t *sset,
+                             const int32_t *sslot, int n_stops, const int32_t *ids, const int32_t *soff, float *stop_lp, hipStream_t s) {
+    const int n = n_edges + n_stops;
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(tree_edges_kernel, dim3((n + 255) / 256), dim3(256), 0, s, logits, ld, lse, row0, erow, etok, eslot, n_edges,
+                       node_lp, srow, sset, sslot, n_stops, ids, soff, stop_lp);
+    return hipGetLastError();
+}
+
+// A thread per (prefix row, member).  The path is added root to leaf: step k re-walks the parent chain from the member's node to
+// its ancestor at depth k + 1 (depth^2 / 2 table reads for a path of a few tokens; no per-thread array, so no scratch memory).
+__global__ __launch_bounds__(256) void tree_path_sums_kernel(const float *__restrict__ node_lp, const int32_t *__restrict__ trie,
+                                                             const int32_t *__restrict__ par, const int32_t *__restrict__ depth,
+                                                             const int32_t *__restrict__ mnode, int P, int M, int ld_nodes,
+                                                             float *__restrict__ member_lp) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)P * M) return;
+    const int p = (int)(i / M), m = (int)(i - (int64_t)p * M);
+    const int t = trie[p];
+    const int leaf = mnode[(int64_t)t * M + m];
+    if (leaf < 0) {
+        member_lp[i] = -INFINITY;
+        return;
+    }
+    const int32_t *pa = par + (int64_t)t * ld_nodes;
+    const float *lp = node_lp + (int64_t)p * ld_nodes;
+    const int d = depth[(int64_t)t * ld_nodes + leaf];
+    float sum = 0.f;
+    for (int k = 1; k <= d; ++k) {
+        int v = leaf;
+        for (int up = d - k; up > 0; --up) v = pa[v];
+        sum += lp[v];
+    }
+    member_lp[i] = sum;
+}
+hipError_t launch_tree_path_sums(const float *node_lp, const int32_t *trie, const int32_t *par, const int32_t *depth,
+                                 const int32_t *mnode, int P, int M, int ld_nodes, float *member_lp, hipStream_t s) {
+    if (P <= 0 || M <= 0) return hipSuccess;
+    const int64_t n = (int64_t)P * M;
+    hipLaunchKernelGGL(tree_path_sums_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, node_lp, trie, par, depth, mnode, P,
+                       M, ld_nodes, member_lp);
     return hipGetLastError();
 }
 

@@ -11,6 +11,11 @@ tokenizer_seq_token -> left-pad -> generate -> decode, cut at '###' -> gather in
 through the modality projectors ONCE at M = shard size (>= 512: MFMA-bound GEMMs), decode batches consume the protein tokens.
 Differences, all deliberate: the gather moves token ids
 (int tensor all-gather over RCCL) instead of pickled strings, task metrics (metrics_computing_opi.py) are not run.
+
+`--allowed_terms FILE --rank_terms K [--rank_with_stop]` (not in the reference): no generation.  Each batch's prompts are prefilled
+once (cache_prefix), the trie of the allowed terms is scored behind them in one tree pass (score_trie) and every saved item carries
+`"ranked_terms": [[term, logprob], ...]`, its K most probable terms (`generated` is the first of them): the per-term scores that
+function prediction is evaluated with.  --rank_with_stop adds the log-probability of ending the answer right behind the term.
 """
 from __future__ import annotations
 
@@ -119,6 +124,28 @@ def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperatu
     return torch.cat(outs) if outs else torch.empty((0, max_new), dtype=torch.long, device=dev)
 
 
+def rank_terms(model, tokenizer, items, input_path, batch_size, trie, k, with_stop=False, device=None):
+    """--rank_terms: per item the K best members of `trie` behind its prompt -> (log-probs fp32 [n, K] descending, member indices
+    [n, K]).  One cache_prefix + one score_trie per batch; nothing is generated."""
+    dev = device or model.device
+    k = min(int(k), len(trie.member_ids))
+    vals, idx = [], []
+    for i in range(0, len(items), batch_size):
+        batch = items[i:i + batch_size]
+        prompts = [build_prompt(q["instruction"], input_path) for q in batch]
+        ids = [opa.tokenizer_seq_token(p, tokenizer, opa.DEFAULT_SEQ_TOKEN_INDEX, return_tensors="pt").to(dev) for p in prompts]
+        ids = opa.left_pad_sequence(ids, padding_value=tokenizer.pad_token_id, batch_first=True)
+        mask = ids != tokenizer.pad_token_id
+        with torch.inference_mode():
+            prefix = model.cache_prefix(ids, seq=[q["input"] for q in batch], attention_mask=mask)
+            v, j = model.score_trie(prefix, trie, include_stop=with_stop).topk(k)
+        vals.append(v)
+        idx.append(j)
+    if not vals:
+        return torch.empty((0, k), dtype=torch.float32, device=dev), torch.empty((0, k), dtype=torch.long, device=dev)
+    return torch.cat(vals), torch.cat(idx)
+
+
 def prompt_capacity(tokenizer, items, input_path, n_prot_tokens) -> int:
     """Decoder positions the longest prompt of the shard needs after the splice (each <seq> becomes n_prot_tokens)."""
     need = 1
@@ -146,15 +173,27 @@ def eval_model(args):
     max_new = max_new_tokens_for(args.input_path) if args.max_new_tokens is None else args.max_new_tokens
     model_name = opa.get_model_name_from_path(args.model_base_path)
     cstp_path = return_cstp_path(args.opus_pllm_weights_path, "modality_encoder/modality_encoding_adapter.ckpt")
+    n_rank = int(getattr(args, "rank_terms", 0) or 0)
+    if n_rank and not getattr(args, "allowed_terms", None):
+        raise ValueError("--rank_terms needs --allowed_terms (the vocabulary to rank)")
+    held = {}
+
+    def capacity(tok, cfg):
+        need = prompt_capacity(tok, mine, args.input_path, cfg.n_prot_tokens)
+        if n_rank:                                    # the terms' positions sit behind the prompt: room for the longest of them
+            held["trie"] = token_constraint(args, tok)
+            need += held["trie"].max_depth
+        return dict(max_prompt=max(args.max_prompt or 0, need))
     # capacity of the context: the reference has no cap; here the KV cache is sized once, from what this run will really ask for
     tokenizer, model, _ = load_pretrained_model(args.model_base_path, args.opus_pllm_weights_path, model_name,
                                                 args.load_8bit, args.load_4bit, switch_projector_type=args.switch_projector_type,
                                                 cstp_path=cstp_path, device=f"cuda:{local}", max_batch=args.batch_size * max(1, args.num_beams),
                                                 max_enc_tokens=args.max_residues + 2, max_prompt=8, max_new_tokens=max_new,
-                                                capacity_from=lambda tok, cfg: dict(
-                                                    max_prompt=max(args.max_prompt or 0, prompt_capacity(tok, mine, args.input_path, cfg.n_prot_tokens))))
+                                                capacity_from=capacity)
     dev = torch.device("cuda", local)
     t0 = time.time()
+    if n_rank:
+        return _eval_ranked_terms(args, qs, mine, tokenizer, model, held["trie"], n_rank, dev, rank, world, t0)
     logits = [] if args.dump_logits else None
     proc_kw = logits_processor_kwargs(args)
     trie = token_constraint(args, tokenizer)          # --allowed_terms: built once, uploaded once per context
@@ -191,6 +230,25 @@ def eval_model(args):
         torch.distributed.destroy_process_group()
 
 
+def _eval_ranked_terms(args, qs, mine, tokenizer, model, trie, k, dev, rank, world, t0):
+    vals, idx = rank_terms(model, tokenizer, mine, args.input_path, args.batch_size, trie, k,
+                           bool(getattr(args, "rank_with_stop", False)), dev)
+    all_vals = odist.all_gather_logits(vals.contiguous()).cpu()
+    all_idx = odist.all_gather_ids(idx.contiguous(), 0).cpu()
+    if rank == 0:
+        dt = time.time() - t0
+        names = trie.member_strings
+        result = []
+        for q, v, j in zip(qs, all_vals.tolist(), all_idx.tolist()):
+            ranked = [[names[m], lp] for m, lp in zip(j, v)]
+            result.append({"ground_truth": q["output"], "generated": ranked[0][0], "ranked_terms": ranked})
+        print(f"entries/sec: {len(qs) / dt}, time elapsed: {dt}")
+        with open(args.save_path, "w") as f:
+            json.dump(result, f)
+    if world > 1:
+        torch.distributed.destroy_process_group()
+
+
 if __name__ == "__main__":
     p = argparse.ArgumentParser()
     p.add_argument("--model-base-path", type=str, default="synthetic:c1_tiny")
@@ -221,6 +279,11 @@ if __name__ == "__main__":
                         "(greedy or sampling; computed on the GPU in the decode loop)")
     p.add_argument("--dump_logits", type=str, default=None,
                    help="parity dump: save the fp32 last-step logits of every item ([n, V], input order) to this .pt file")
+    p.add_argument("--rank_terms", type=int, default=0, metavar="K",
+                   help="with --allowed_terms: no generation; score every allowed term behind each prompt in one tree pass and save "
+                        "the K most probable ones with their log-probabilities as `ranked_terms`")
+    p.add_argument("--rank_with_stop", action="store_true",
+                   help="with --rank_terms: add the log-probability of ending the answer right behind the term")
     add_logits_processor_args(p)
     add_constraint_args(p)
     eval_model(p.parse_args())

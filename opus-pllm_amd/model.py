@@ -956,6 +956,85 @@ class OpusLlamaForCausalLM:
         self._leave()
         return ContinuationScores(token_lp, logprob, lens.to(dev))
 
+    # ------------------------------------------------------------------ trie scoring
+    @torch.no_grad()
+    def score_trie(self, prefix: "OpusPrefix", trie, include_stop: bool = False) -> "TrieScores":
+        """Exact log-probabilities of EVERY member of a TokenTrie behind a cached prefix, in one tree pass: each trie node is one
+        new decoder position that attends to the cached prompt and to its own ancestors, and a member's log-prob is the sum of
+        the edge log-probs on its path - what score_continuations(prefix, [member_ids[m]], prefix_rows=[p]).logprob gives, without
+        re-computing the shared token prefixes once per member.  `trie`: a TokenTrie (every prefix row scores it) or
+        TokenTrie.per_row([...]) with one trie per prefix row.  include_stop adds log sum_{s in S} p(s | prompt + member), S = the
+        trie's end ids (+ the separator's first id): what the constraint allows in a completing state besides the children; it
+        costs one decoder row per leaf (without it only the nodes that have a child are evaluated).  Returns TrieScores.  Reads
+        the KV cache, writes neither it nor the decode state.  A stale handle or one of another context raises OpusError -6; a
+        member deeper than constraint.TRIE_MAX_DEPTH or a path beyond max_prompt + max_new_tokens positions raises -2."""
+        from .constraint import PerRowTokenTrie, TokenTrie, TRIE_MAX_DEPTH, plan_trie_score
+        cfg = self.cfg
+        if not isinstance(prefix, OpusPrefix):
+            raise TypeError("score_trie() needs the OpusPrefix that cache_prefix() returned")
+        if isinstance(trie, TokenTrie):
+            tries = [trie] * prefix.rows
+        elif isinstance(trie, PerRowTokenTrie):
+            if trie.n_rows() != prefix.rows:
+                raise ValueError(f"TokenTrie.per_row of {trie.n_rows()} tries for {prefix.rows} prefix rows")
+            tries = list(trie.tries)
+        else:
+            raise TypeError("score_trie() needs a TokenTrie or TokenTrie.per_row(...)")
+        deepest = max(t.max_depth for t in tries)
+        if deepest > TRIE_MAX_DEPTH:
+            raise _cabi.OpusError(-2, f"score_trie: a member of {deepest} ids, the depth limit is {TRIE_MAX_DEPTH}")
+        ctx_cap = cfg.max_prompt + cfg.max_new_tokens
+        for p, t in enumerate(tries):
+            if int(prefix.lengths[p]) + t.max_depth > ctx_cap:
+                raise _cabi.OpusError(-2, f"score_trie: prompt of {int(prefix.lengths[p])} tokens + a member of {t.max_depth} ids exceed "
+                                          f"the context's {ctx_cap} positions (max_prompt + max_new_tokens)")
+            if max(max(t.node_tok), max(t.stop_ids())) >= cfg.dec_vocab:
+                raise ValueError(f"trie ids must lie in [0, {cfg.dec_vocab})")
+        cc = _cabi.CConfig.from_config(cfg)
+        cap = int(self._lib.opus_llama_dec_rows_cap(C.byref(cc)))
+        if cap < 1:
+            raise _cabi.OpusError(-2, "score_trie: bad config")
+        key = (prefix.rows, bool(include_stop), cap)                     # (a trie does not change after construction)
+        if key not in trie._score_plans:
+            trie._score_plans[key] = plan_trie_score(tries, include_stop, cap)
+        plan = trie._score_plans[key]
+        P, N, M, dev = plan.P, plan.N, plan.M, self.device
+        ptr = lambda a: a.ctypes.data if a.size else None                # noqa: E731
+        s = self._enter()
+        with torch.cuda.stream(self._stream):
+            node_lp = torch.zeros((P, N + 1), dtype=torch.float32, device=dev)
+            stop_node = torch.full((P, N + 1), float("-inf"), dtype=torch.float32, device=dev) if include_stop else None
+            for ps in plan.passes:
+                n_sets = len(plan.tries) if ps.stop_row.size else 0
+                n_ids = int(plan.stop_ids.size) if ps.stop_row.size else 0
+                n_scratch = int(self._lib.opus_llama_score_tree_scratch_bytes(C.byref(cc), ps.rows, ps.score_src.size, ps.edge_row.size,
+                                                                              ps.stop_row.size, n_ids, n_sets))
+                if n_scratch < 0:
+                    raise _cabi.OpusError(-2, f"score_trie: a pass of {ps.rows} rows")
+                scratch = torch.empty((n_scratch,), dtype=torch.uint8, device=dev)
+                emb = None
+                if ps.rows:
+                    emb = self.model.embed_tokens(torch.from_numpy(ps.tok.astype(np.int64)).to(dev)).to(_cabi.operand_dtype()).contiguous()
+                _cabi.check(self._lib.opus_llama_score_tree(
+                    self._ctx, emb.data_ptr() if emb is not None else None, ps.rows, ptr(ps.prow), ptr(ps.parent), ptr(ps.depth),
+                    ps.score_src.size, ptr(ps.score_src), ps.edge_row.size, ptr(ps.edge_row), ptr(ps.edge_tok), ptr(ps.edge_slot),
+                    ps.stop_row.size, ptr(ps.stop_row), ptr(ps.stop_set), ptr(ps.stop_slot), n_ids, ptr(plan.stop_ids), n_sets,
+                    ptr(plan.stop_off), prefix._last_rows.data_ptr(), P, prefix._epoch, node_lp.data_ptr(),
+                    stop_node.data_ptr() if include_stop else None, P * (N + 1), scratch.data_ptr(), n_scratch, s))
+            d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)   # noqa: E731
+            trie_of_row, member_node = d(plan.trie_of_row), d(plan.member_node)
+            par, depth = d(plan.node_par), d(plan.node_depth)
+            member_lp = torch.empty((P, M), dtype=torch.float32, device=dev)
+            _cabi.check(self._lib.opus_trie_path_sums(self._ctx, node_lp.data_ptr(), trie_of_row.data_ptr(), par.data_ptr(),
+                                                      depth.data_ptr(), member_node.data_ptr(), P, M, N + 1, member_lp.data_ptr(), s))
+            stop_lp = None
+            if include_stop:
+                mn = member_node[trie_of_row.long()].long()                      # [P, M], -1 beyond a row's members
+                stop_lp = torch.gather(stop_node, 1, mn.clamp(min=0)).masked_fill(mn < 0, float("-inf"))
+            torch.cuda.current_stream().synchronize()
+        self._leave()
+        return TrieScores(member_lp, stop_lp, node_lp, torch.from_numpy(plan.n_members).to(dev), plan.rows_evaluated)
+
     # ------------------------------------------------------------------ parity taps (tests / bench)
     def prefill_logits(self, embeds: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
         B, T, _ = embeds.shape
@@ -1087,6 +1166,25 @@ class ContinuationScores:
 
     def __init__(self, token_logprobs: torch.Tensor, logprob: torch.Tensor, n_tokens: torch.Tensor):
         self.token_logprobs, self.logprob, self.n_tokens = token_logprobs, logprob, n_tokens
+
+
+class TrieScores:
+    """What score_trie() returns.  member_logprob fp32 [P, M] = log p(member's tokens | prompt p); stop_logprob [P, M] (None
+    without include_stop); logprob = their sum (member_logprob without a stop term); node_logprobs fp32 [P, N + 1] per trie node
+    (column 0, the root, is 0); n_members [P]; rows_evaluated: the decoder rows the call ran through the layers, all passes.
+    With per-row tries M and N are the maxima: -inf (node_logprobs: 0) beyond a row's own count."""
+
+    def __init__(self, member_logprob, stop_logprob, node_logprobs, n_members, rows_evaluated: int):
+        self.member_logprob, self.stop_logprob, self.node_logprobs = member_logprob, stop_logprob, node_logprobs
+        self.n_members, self.rows_evaluated = n_members, int(rows_evaluated)
+        self.logprob = member_logprob if stop_logprob is None else member_logprob + stop_logprob
+
+    def topk(self, k: int):
+        """(values, member indices), [P, k] each: descending, ties to the lower member index."""
+        if k < 1 or k > self.logprob.shape[1]:
+            raise ValueError(f"topk: k={k} for {self.logprob.shape[1]} members")
+        vals, idx = torch.sort(self.logprob, dim=1, descending=True, stable=True)
+        return vals[:, :k], idx[:, :k]
 
 
 # capacities of the processor kernel (include/opus_pllm.h, opus_set_logits_processors)
