@@ -399,6 +399,23 @@ int opus_debug_gemm_rowscale(opus_ctx *ctx, const void *d_A, const void *d_W1, f
  * the stored projection; *fused (HOST) = 1 when the rotation ran in the GEMM's epilogue (large M, head_dim 64). */
 int opus_debug_gemm_rope(opus_ctx *ctx, const void *d_A, const void *d_W, const float *d_bias, void *d_out, int32_t M,
                          int32_t D, int32_t K, int32_t T, int32_t heads, int32_t allow_fuse, int32_t *fused, void *stream);
+/* The LayerNorm / RMSNorm fused around the big tiled GEMM as opus_esm2_encode (pre-LN blocks, modeling_esm.py EsmLayer) and
+ * opus_llama_prefill (LlamaRMSNorm) issue it, three steps:
+ *   X <- X + A W1^T (+ b1)   fp32 [M,N1] in place; the GEMM also writes fp16(X) to d_xh [M,N1] and, per row and 64-column slab,
+ *                            (sum x, sum x^2) to d_part [M, N1/64, 2]
+ *   d_stat [M,2] = (mu, rstd) of every row from the partials (rms != 0: (0, rsqrt(mean x^2 + eps)))
+ *   C = epi(rstd (fp16(X) W2^T - mu s) + c2)   fp16 [M, N2 or N2/2]: W2 = W diag(gamma) [N2,N1], d_c2 = W beta + b (or NULL),
+ *                            d_colsum s[n] = sum_k W2[n][k] (LayerNorm; NULL with rms); epi 0 / 1 (GELU) / 2 (gate-up, rms only).
+ * rope_T > 0 (epi 0, N2 = 3 D, head_dim 64): the ESM rotary runs in the consumer's epilogue as in opus_debug_gemm_rope, row m at
+ * position m % rope_T or, with d_rope_pos int32 [M] (token-packed batches), d_rope_pos[m].  A fp16 [M,K1]; W1, W2 panel-tiled.
+ * d_part / d_xh / d_stat are the caller's.  *produced (HOST) = 1 when the first GEMM left the partials; 0: its shape is off the
+ * fused form, nothing further ran (no stand-alone fallback).  plan (HOST, int32[10]): what the big tiled GEMM launched for the
+ * first ([0..5)) and the second ([5..10)) GEMM - whole-K tiles, tail tiles cut into k-parts, parts per tail tile, combine
+ * (0 none, 1 pair inside the launch, 2 reduce kernel), rotary fused; -1 where that kernel did not run. */
+int opus_debug_gemm_ln(opus_ctx *ctx, const void *d_A, const void *d_W1, const float *d_b1, float *d_X, float *d_part, void *d_xh,
+                       float *d_stat, const void *d_W2, const float *d_c2, const float *d_colsum, void *d_C, int32_t M, int32_t N1,
+                       int32_t K1, int32_t N2, int32_t epi, int32_t rms, float eps, int32_t rope_T, const int32_t *d_rope_pos,
+                       int32_t *produced, int32_t *plan, void *stream);
 int opus_debug_attention(opus_ctx *ctx, const void *d_Q, const void *d_K, const void *d_V, void *d_O,
                          const int32_t *d_kstart, const int32_t *d_kend, int32_t B, int32_t T, int32_t heads,
                          int32_t group, int32_t head_dim, int32_t causal, float scale, void *stream);

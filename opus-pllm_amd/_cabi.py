@@ -137,6 +137,8 @@ SIGNATURES = {
     "opus_debug_token_constraint": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P]),
     "opus_debug_gemm_rowscale": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                            C.c_float, C.POINTER(C.c_int32), _P]),
+    "opus_debug_gemm_ln": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
 }
 
 _lib: Optional[C.CDLL] = None

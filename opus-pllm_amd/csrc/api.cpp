@@ -170,6 +170,7 @@ struct opus_ctx {
     half_t *rq_ln_xh = nullptr;
     int rq_ln_done = 0;
     const float *rq_ln_stat = nullptr, *rq_ln_colsum = nullptr;   // consumer
+    int *rq_pp_plan = nullptr;           // one-shot (HOST): the next GEMM's launch_pp reports its plan here (GemmParams::pp_plan)
     bool xln_tiled = false;              // d_xln currently holds fp16(x) in fragment order
     const float *xh_src = nullptr;       // fp32 buffer whose fp16 copy + sum-of-squares partials are valid
     bool use_row_scale = false;          // one-shot: the next gemm() multiplies its rows by the rstd from d_ssq
@@ -594,6 +595,8 @@ static int gemm_any(opus_ctx *c, hipStream_t s, const half_t *A, const float *Af
     if (c->rq_ln_part) { p.xh_out = c->rq_ln_xh; p.ssq_out = nullptr; p.ln_part = c->rq_ln_part; p.ln_done = &c->rq_ln_done; c->rq_ln_part = nullptr; }
     if (c->rq_ln_stat) { p.ln_stat = c->rq_ln_stat; p.ln_colsum = c->rq_ln_colsum; c->rq_ln_stat = c->rq_ln_colsum = nullptr; }
     p.combine_cnt = c->d_cnt;
+    p.pp_plan = c->rq_pp_plan;
+    c->rq_pp_plan = nullptr;
     p.a_tiled = c->rq_a_tiled; p.xh_tiled = c->rq_xh_tiled; p.c_tiled = c->rq_c_tiled;
     c->rq_a_tiled = c->rq_xh_tiled = c->rq_c_tiled = 0;
     const int nout = epi == EPI_SILU_GU16 ? N / 2 : N;
@@ -2492,6 +2495,52 @@ extern "C" int opus_debug_gemm_rowscale(opus_ctx *c, const void *A, const void *
     *fused = c->xh_src != nullptr && (N1 & 255) == 0 && gemm_goes_wide(M, N2) ? 1 : 0;
     const int nout = epi == EPI_SILU_GU16 ? N2 / 2 : N2;
     return gemm_norm(c, s, X, eps, c->d_xn, (const half_t *)W2, M, N2, N1, epi, Cp, nout, 0);
+}
+
+// The norm fused around gemm_pp_kernel exactly as encode() (LayerNorm) and prefill() (RMSNorm) issue it:
+//   X <- X + A W1^T (+ b1)       (fp32 in place; the epilogue / pair combine / tail reduce also writes fp16(X) and the partials)
+//   stat = ln_finalize(part)     ((mu, rstd) per row; rms: (0, rsqrt(mean x^2 + eps)))
+//   C  = epi(rstd (fp16(X) W2^T - mu s) + c2), optionally rotated (rope_T > 0: the ESM QKV form, N2 = 3 D)
+// part / xh / stat are the caller's; plan (HOST) receives launch_pp's report of both GEMMs.  *produced = 0: the producer GEMM did
+// not leave the partials (shape off gemm_pp_kernel's fused form) and nothing after it ran - no stand-alone fallback here.
+extern "C" int opus_debug_gemm_ln(opus_ctx *c, const void *A, const void *W1, const float *b1, float *X, float *part, void *xh,
+                                  float *stat, const void *W2, const float *c2, const float *colsum, void *Cp, int32_t M, int32_t N1,
+                                  int32_t K1, int32_t N2, int32_t epi, int32_t rms, float eps, int32_t rope_T,
+                                  const int32_t *rope_pos, int32_t *produced, int32_t *plan, void *stream) {
+    if (!c || !A || !W1 || !X || !part || !xh || !stat || !W2 || !Cp || !produced || !plan)
+        return fail(OPUS_EBADARG, "debug_gemm_ln: null pointer");
+    if (M < 1 || N1 < 64 || N1 % 64 || K1 < 64 || K1 % 64 || N2 < 32) return fail(OPUS_ESHAPE, "debug_gemm_ln: shape");
+    if (epi != EPI_NONE && epi != EPI_GELU && epi != EPI_SILU_GU16) return fail(OPUS_EBADARG, "debug_gemm_ln: epilogue 0, 1 or 2");
+    if (epi == EPI_SILU_GU16 && (!rms || c2 || colsum || N2 % 32))
+        return fail(OPUS_EBADARG, "debug_gemm_ln: the gate / up epilogue is the RMSNorm form (no bias, no column sums)");
+    if (rms ? colsum != nullptr : colsum == nullptr) return fail(OPUS_EBADARG, "debug_gemm_ln: column sums go with LayerNorm only");
+    if (rope_pos && rope_T < 1) return fail(OPUS_EBADARG, "debug_gemm_ln: rope_pos needs rope_T");
+    if (rope_T > 0 && (epi != EPI_NONE || N2 % 3 || (N2 / 3) % 64 || c->cfg.enc_dim / c->cfg.enc_heads != 64 ||
+                       rope_T > c->cfg.max_enc_tokens))
+        return fail(OPUS_ESHAPE, "debug_gemm_ln: rotary needs EPI_NONE, N2 = 3 D, head_dim 64 and rope_T within the context's table");
+    HIPC(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    c->phase = PH_OTHER;
+    for (int i = 0; i < 2 * PP_PLAN_WORDS; ++i) plan[i] = -1;
+    HIPC(hipMemsetAsync(c->d_cnt, 0, HANDOFF_ERR * sizeof(int32_t), s));       // hand-off words start from zero, as at the head of encode / prefill
+    if (gemm_goes_pp(M, N1)) { c->rq_ln_part = part; c->rq_ln_xh = (half_t *)xh; }   // (asked of the big tiled GEMM only, as the path does)
+    c->rq_pp_plan = plan;
+    OPC(gemm(c, s, (const half_t *)A, K1, (const half_t *)W1, M, N1, K1, b1, EPI_NONE, X, X, N1, 1));
+    *produced = c->rq_ln_done;
+    if (!c->rq_ln_done) return OPUS_OK;
+    KL(KC_NORM, 8.0 * M * (N1 / 64), launch_ln_finalize(part, M, N1 / 64, N1, eps, rms, stat, s));
+    c->rq_ln_stat = stat; c->rq_ln_colsum = colsum;
+    c->rq_pp_plan = plan + PP_PLAN_WORDS;
+    if (rope_T > 0) {
+        const int D = N2 / 3;
+        c->rq_rope_cs = c->cs_enc; c->rq_rope_T = rope_T; c->rq_rope_cols = 2 * D; c->rq_rope_qcols = D;
+        c->rq_rope_qscale = 0.125f;                                      // head_dim 64
+        c->rq_rope_pos = rope_pos;
+    }
+    const int nout = epi == EPI_SILU_GU16 ? N2 / 2 : N2;
+    OPC(gemm(c, s, (const half_t *)xh, N1, (const half_t *)W2, M, N2, N1, c2, epi, nullptr, Cp, nout, 0));
+    if (rope_T > 0 && !c->rq_rope_done) return fail(OPUS_ESTATE, "debug_gemm_ln: the consumer GEMM did not fuse the rotary");
+    return OPUS_OK;
 }
 
 // The QKV projection of the batched decode step exactly as decode_step() issues it (narrow output routed through the

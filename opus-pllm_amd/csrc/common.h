@@ -178,7 +178,14 @@ struct GemmParams {
     int stagger = 0;              // gemm_pp_kernel: late start of half of the first round, in units of ~4 us (see the kernel)
     int no_rot = 0;               // A/B aid (OPUS_NO_KROT): weight-streaming kernels walk k from chunk 0 in every workgroup
     long long *trace = nullptr;   // tuning aid (OPUS_PP_TRACE): gemm_pp_kernel writes 4 wall-clock stamps per workgroup
+    // launch_pp reports what it launched in pp_plan[0 .. PP_PLAN_WORDS) (HOST; nullptr: no report, nothing else changes):
+    // [0] tiles of whole K, [1] tail tiles cut into k-parts, [2] k-parts per tail tile (1: no tail split), [3] how the parts are
+    // combined (PP_TAIL_NONE / PP_TAIL_PAIR: inside the launch / PP_TAIL_REDUCE: pp_tail_reduce_kernel), [4] 1 = the rotary ran
+    // in the epilogue.  A GEMM that another kernel takes leaves the words as they were.
+    int *pp_plan = nullptr;
 };
+constexpr int PP_PLAN_WORDS = 5;
+enum PpTail { PP_TAIL_NONE = 0, PP_TAIL_PAIR = 1, PP_TAIL_REDUCE = 2 };
 
 // Flash-style attention over strided Q/K/V (fp16).  Q(b,h,t,:) = Q + b*q_sb + t*q_st + h*HD etc.;
 // kv head of q head h is h / group.  Key j of batch row b is visible to query i iff

@@ -1822,6 +1822,11 @@ static hipError_t launch_pp(const GemmParams &p_in, hipStream_t s) {
     const bool pair_mode = (!p.out_f32 && !p.residual) || (EPI == EPI_NONE && p.out_f32 && p.residual);
     const bool pair = split == 2 && p.combine_cnt && !g_knobs.misc[6] && pair_mode && (p.ldc & 7) == 0 && (p.ldr & 3) == 0 && (p.N & 255) == 0;
     if (!pair) p.combine_cnt = nullptr;
+    if (p.pp_plan) {
+        p.pp_plan[0] = full; p.pp_plan[1] = tail; p.pp_plan[2] = split;
+        p.pp_plan[3] = split == 1 ? PP_TAIL_NONE : pair ? PP_TAIL_PAIR : PP_TAIL_REDUCE;
+        p.pp_plan[4] = rope ? 1 : 0;
+    }
     OPUS_LAUNCH(KC_PP, kern, dim3(full + tail * split), dim3(512), 8 * 16384, s, p, bm, bn, full, split);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || split == 1 || pair) return e;

@@ -100,8 +100,11 @@ hipError_t launch_l2norm(const float *x, int64_t rows, int D, half_t *out, hipSt
 }
 
 // (mu, rstd) of every row from the per-64-column (sum x, sum x^2) partials of the LayerNorm-producing GEMM epilogue
-// (GemmParams::ln_part), summed in a fixed order.  var = E[x^2] - mu^2 in fp32 (clamped at 0): the residual streams this serves
-// have |mu| of the order of the standard deviation or below, where the cancellation costs a few ulps of the variance.
+// (GemmParams::ln_part), summed in a fixed order.  var = E[x^2] - mu^2 in fp32 (clamped at 0): the cancellation costs
+// (1 + mu^2 / var) ulps of the variance.  Measured on MI355X against fp64 (tests/test_gpu_ln_fusion.py, 1280 .. 5120 columns),
+// relative error of rstd: 1.4e-7 at |mu| / sigma = 0, 2.9e-7 at 1, 1.3e-5 at 8, 9.5e-4 at 64; a constant row (var = 0, eps = 1e-5
+// decides) 2.7e-6.  The consumer's fp16(x) hand-off loses more than this does: the fused form matches the
+// stand-alone kernels up to |mu| ~ sigma and is 5 x (40 x) less accurate at |mu| = 8 (64) sigma; OPUS_NO_LN_FUSION=1 there.
 __global__ __launch_bounds__(256) void ln_finalize_kernel(const float2 *__restrict__ part, int64_t rows, int nslab, float inv_d,
                                                           float eps, int rms, float2 *__restrict__ stat) {
     // 16 lanes per row: lane q takes slabs q, q + 16, ... (all requested at once), then a fixed-order 16-lane tree

@@ -232,4 +232,18 @@ for s in range(4):                                            # slots 349 .. 352
     for t in toks:
         model.decode_logits(t)
 out["long_decode_vs_prefill"] = worst
+del model
+
+# ---- G: the norms fused around the big tiled GEMM on this build (tests/test_gpu_ln_fusion.py holds the fp16 row): three cells of
+# the chain X <- X + A W1^T | (mu, rstd) | C = epi(rstd (bf16(X) W'^T - mu s) + c2) against fp64 - no tail split on either side,
+# a pair combine on both sides, pp_tail_reduce_kernel (8 parts) on both sides; every cell holds rows of mu / sigma 0, 1, 8 and 64
+from ln_fusion_checks import make_ctx, run_case, summarize
+cfg = opa.llama3_8b(max_batch=64, max_enc_tokens=1026, max_prompt=104, max_new_tokens=16)
+ctx = make_ctx(cfg, dev)
+out["ln_fusion"] = {}
+for tag, (M, N1, K1, N2, epi) in (("no_tail", (7670, 1280, 1280, 3840, 0)), ("pair", (8960, 2560, 2560, 10240, 1)),
+                                  ("reduce", (6650, 2560, 2560, 7680, 0))):
+    out["ln_fusion"][tag] = summarize(run_case(ctx, dev, M, N1, K1, N2, epi=epi, seed=7))
+_cabi.check(lib.opus_check_error(ctx, None))
+lib.opus_ctx_destroy(ctx)
 print("BF16_CHECK " + json.dumps(out), flush=True)

@@ -35,3 +35,15 @@ def test_bf16_build_runs_the_path():
     # decode steps at 349 .. 352 positions vs prefill of the longer prompt, rows left-padded by 0 .. 150 (bound as the 96-position form)
     assert o["long_attn_decode_abs"] <= 2.4e-2, o
     assert o["long_decode_vs_prefill"] < 1.5e-2, o
+    # the norms fused around the big tiled GEMM (tests/ln_fusion_checks.py; the fp16 row is tests/test_gpu_ln_fusion.py): each
+    # figure is error / bound.  X, the partials and (mu, rstd) are fp32 work: the fp16 row's bounds; bf16(X) == X rounded bit for
+    # bit; the consumer against its own algebra in fp64: 8 x the fp16 rule (1.6e-2 max |ref| + 1e-5); accuracy against the exact
+    # norm followed by the GEMM: the host model's fused-form error with bf16 rounding + that rule, per class of rows
+    want = dict(no_tail=([150, 0, 1, 0, 0], [450, 0, 1, 0, 0]), pair=([256, 94, 2, 1, 0], [1280, 120, 2, 1, 0]),
+                reduce=([256, 4, 8, 2, 0], [768, 12, 8, 2, 0]))
+    for tag, (pp, pc) in want.items():
+        c = o["ln_fusion"][tag]
+        assert c["produced"] == 1 and c["plan_producer"] == pp and c["plan_consumer"] == pc, (tag, c)
+        assert c["flags_ok"], (tag, c)
+        for k in ("x", "partials", "stat", "algebra", "accuracy"):
+            assert c[k] <= 1.0, (tag, k, c)
