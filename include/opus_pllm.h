@@ -420,6 +420,28 @@ int opus_debug_attention(opus_ctx *ctx, const void *d_Q, const void *d_K, const 
                          const int32_t *d_kstart, const int32_t *d_kend, int32_t B, int32_t T, int32_t heads,
                          int32_t group, int32_t head_dim, int32_t causal, float scale, void *stream);
 
+/* attn_prefill_kernel launched as opus_esm2_encode* / opus_llama_prefill launch it: one launch, the caller's pointers and strides
+ * as they stand, no buffer of the context involved.  Element (b, t, head h, d) of Q is d_Q[b * q_sb + t * q_st + h * head_dim + d]
+ * (K / V: kv head h / group; O likewise with o_sb / o_st), strides in 16-bit elements - so Q / K / V may be column ranges of one
+ * fused projection buffer ([rows, 3 D] of the encoder, [rows, (heads + 2 kv) head_dim] of the decoder).  Three forms:
+ *   padded        d_cu NULL: B rows of T tokens, key j of row b visible iff d_kstart[b] <= j < d_kend[b] (NULL = 0 / T) and
+ *                 (!causal || j <= i); a query without a visible key gives zeros;
+ *   token-packed  d_cu int32 [B + 1] (device): row b = tokens d_cu[b] .. d_cu[b + 1] - 1 of the buffers, all of them keys and
+ *                 queries; T = the longest row; batch strides, d_kstart and d_kend are ignored; causal must be 0
+ *                 (OPUS_EUNSUPPORTED otherwise: the path has no such form);
+ *   ... q_trim    token-packed with q_trim = 1 (T > 2): the first and the last token of every row are keys but not queries,
+ *                 their rows of O are left as they were.
+ * *qt_used (HOST) = the 16-query tiles per wave the launcher chose (1 or 2; knob "misc3" = 1 swaps the choice); 0 when nothing
+ * was launched.  Errors: OPUS_EBADARG for a null ctx / Q / K / V / O / qt_used, OPUS_ESHAPE for B, T, heads, group < 1, heads
+ * not a multiple of group, a stride < 1 or q_trim without d_cu or with T <= 2 - all before any device call; OPUS_EHIP, with no
+ * launch, where the launcher refuses: a q / k / v stride that is no multiple of 8 elements (o: 4), T * max(k_st, v_st) * 2 >= 2^31
+ * bytes (32-bit buffer offsets), head_dim other than 16 / 32 / 64 / 128. */
+int opus_debug_attn_prefill(opus_ctx *ctx, const void *d_Q, const void *d_K, const void *d_V, void *d_O, int64_t q_st, int64_t k_st,
+                            int64_t v_st, int64_t o_st, int64_t q_sb, int64_t k_sb, int64_t v_sb, int64_t o_sb,
+                            const int32_t *d_kstart, const int32_t *d_kend, const int32_t *d_cu, int32_t B, int32_t T,
+                            int32_t heads, int32_t group, int32_t head_dim, int32_t causal, int32_t q_trim, float scale,
+                            int32_t *qt_used, void *stream);
+
 /* attn_decode_kernel as opus_llama_decode_step launches it, alone, on layer 0 of this context's KV cache (kernel-level parity
  * of rows D3 / D4 at any cache length: transformers' eager attention over a cache, modeling_llama.py:191-213, reached from
  * language_model/opus_llama.py:127).  d_qkv fp16 [B, (heads + 2 kv) hd]: the new token's q | k | v projections, not yet rotated;

@@ -2682,6 +2682,36 @@ extern "C" int opus_debug_attention(opus_ctx *c, const void *Q, const void *K, c
     return OPUS_OK;
 }
 
+// attn_prefill_kernel launched as the product launches it: the caller's pointers and strides go into AttnParams as they stand
+// (the encoder's [rows, 3 D] buffer, the decoder's [rows, (nh + 2 nkv) hd] one), token-packed (d_cu) with or without q_trim, or
+// padded with d_kstart / d_kend.  No buffer of the context is touched.  *qt_used (HOST) = the query tiles per wave the launcher
+// took (0 when nothing was launched).
+extern "C" int opus_debug_attn_prefill(opus_ctx *c, const void *Q, const void *K, const void *V, void *O, int64_t q_st, int64_t k_st,
+                                       int64_t v_st, int64_t o_st, int64_t q_sb, int64_t k_sb, int64_t v_sb, int64_t o_sb,
+                                       const int32_t *kstart, const int32_t *kend, const int32_t *cu, int32_t B, int32_t T,
+                                       int32_t heads, int32_t group, int32_t hd, int32_t causal, int32_t q_trim, float scale,
+                                       int32_t *qt_used, void *stream) {
+    if (qt_used) *qt_used = 0;
+    if (!c || !Q || !K || !V || !O || !qt_used) return fail(OPUS_EBADARG, "debug_attn_prefill: null pointer");
+    if (B < 1 || T < 1 || heads < 1 || group < 1 || heads % group || hd < 1) return fail(OPUS_ESHAPE, "debug_attn_prefill: shape");
+    if (q_st < 1 || k_st < 1 || v_st < 1 || o_st < 1) return fail(OPUS_ESHAPE, "debug_attn_prefill: token strides must be positive");
+    if (causal && cu) return fail(OPUS_EUNSUPPORTED, "debug_attn_prefill: no causal token-packed form");
+    if (q_trim && (!cu || T <= 2)) return fail(OPUS_ESHAPE, "debug_attn_prefill: q_trim needs cu and T > 2");
+    HIPC(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    AttnParams a;
+    a.Q = (const half_t *)Q; a.K = (const half_t *)K; a.V = (const half_t *)V; a.O = (half_t *)O;
+    a.q_st = q_st; a.k_st = k_st; a.v_st = v_st; a.o_st = o_st;
+    a.q_sb = cu ? 0 : q_sb; a.k_sb = cu ? 0 : k_sb; a.v_sb = cu ? 0 : v_sb; a.o_sb = cu ? 0 : o_sb;
+    a.kstart = kstart; a.kend = kend; a.cu = cu; a.q_trim = q_trim ? 1 : 0;
+    a.B = B; a.T = T; a.heads = heads; a.group = group; a.head_dim = hd; a.causal = causal ? 1 : 0; a.scale = scale;
+    const int kvh = heads / group;
+    KLF(KC_ATTN_PREFILL, 2.0 * B * T * hd * (2.0 * heads + 2.0 * kvh), (causal ? 2.0 : 4.0) * B * (double)T * T * heads * hd,
+        launch_attn_prefill(a, s));
+    *qt_used = attn_prefill_query_tiles(a);
+    return OPUS_OK;
+}
+
 // attn_decode_kernel exactly as decode_step() launches it (finished fp16 projections in, no k-part slabs), on layer 0 of this
 // context's KV cache: the history d_k_hist / d_v_hist fp16 [B, kv heads, L, hd] (keys already rotated, as the cache holds them)
 // is copied into slots 0 .. L-1 (L = T0 + step), the step word, kstart[] and the rotary rows of the step are set as the

@@ -349,6 +349,14 @@ static hipError_t launch_qt(const AttnParams &p, hipStream_t s) {
     else OPUS_LAUNCH(KC_ATTN_PREFILL, (attn_prefill_kernel<HD, false, QT>), grid, dim3(256), 0, s, p);
     return hipGetLastError();
 }
+// The rule behind launch_hd's choice, stated once: two query tiles per wave up to head_dim 64 once the grid of 128-query
+// blocks is large (the measurements are in launch_hd); knob misc3 swaps the two forms (A/B aid).  opus_debug_attn_prefill
+// reports it, so that a kernel-level test knows which instance it ran.
+int attn_prefill_query_tiles(const AttnParams &p) {
+    bool one = !(p.head_dim <= 64 && (int64_t)p.B * p.heads * cdiv(p.T, 128) >= 512);
+    if (g_knobs.misc[3]) one = !one;                                 // A/B aid
+    return one ? 1 : 2;
+}
 template <int HD>
 static hipError_t launch_hd(const AttnParams &p, hipStream_t s) {
     // Measured (tools/bench_attn.py ab, one MI355X, both forms in one process, round 3 after the softmax clean-up: one copy of
@@ -364,9 +372,7 @@ static hipError_t launch_hd(const AttnParams &p, hipStream_t s) {
     //  behind it, so that T = 514 needs 4 blocks instead of 5.  320-thread workgroups at 157 VGPRs fit two to a CU (10 of 12
     //  wave slots) where 256-thread ones fit three, and the fifth waves that leave at once do not give the slots back in
     //  time: 64 x 514: 281 vs 167 us, 64 x 512: 158 vs 138 us, 32 x 1026 x 40: 685 vs 542 us.)
-    bool one = !(HD <= 64 && (int64_t)p.B * p.heads * cdiv(p.T, 128) >= 512);
-    if (g_knobs.misc[3]) one = !one;                                 // A/B aid
-    return one ? launch_qt<HD, 1>(p, s) : launch_qt<HD, 2>(p, s);
+    return attn_prefill_query_tiles(p) == 1 ? launch_qt<HD, 1>(p, s) : launch_qt<HD, 2>(p, s);
 }
 
 hipError_t launch_attn_prefill(const AttnParams &p, hipStream_t s) {

@@ -259,6 +259,7 @@ __device__ __forceinline__ void block_row_rstd(const float *__restrict__ ssq, in
 bool gemm_goes_wide(int M, int N);
 bool gemm_goes_pp(int M, int N);     // would launch_gemm route an fp16-A GEMM of this shape to gemm_pp_kernel (the big tiled kernel)?   // would launch_gemm route an fp16-A GEMM of this shape to gemm_wide_kernel?
 hipError_t launch_attn_prefill(const AttnParams &p, hipStream_t s);
+int attn_prefill_query_tiles(const AttnParams &p);   // 16-query tiles per wave (1 / 2) that launch_attn_prefill takes for p (HOST)
 // attn_prefix.hip: attention of continuation rows over a cached prefix + their own positions (opus_llama_score_continuations).
 // Continuation row r has n positions at rows r n .. r n + n - 1 of qkv ([rows][(nh + 2 nkv) hd], q and k rotated); the rows that
 // belong to prefix row p are list[off[p] .. off[p + 1]).  Keys: cache slots kstart[p] .. Tp - 1 of row p ([P][nkv][slot][hd] at
