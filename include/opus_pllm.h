@@ -208,7 +208,7 @@ int opus_debug_attn_prefix(opus_ctx *ctx, const void *d_qkv, const void *d_k_his
  * row), h_par (parent row in this pass, -1 for a child of the root; otherwise an EARLIER row of the same prefix row one level up)
  * and h_depth (1 .. opus_llama_tree_max_depth(), else OPUS_ESHAPE).  A row at depth d sits at position Tp - kstart + d - 1 of its
  * prefix row (at most max_prompt + max_new_tokens positions in all, else OPUS_ESHAPE) and attends to the prefix row's cache slots,
- * its ancestors and itself (attn_tree_kernel).  Scoring: h_score_src [n_score] lists the rows whose logits are needed - a row
+ * its ancestors and itself (attn_prefix_kernel, tree form).  Scoring: h_score_src [n_score] lists the rows whose logits are needed - a row
  * of the pass, or -(p) - 1 for the last position of prefix row p (d_last_rows fp32 [P, H] of opus_llama_prefix); the lm_head runs
  * once per entry.  Edge e (h_edge_row ascending indices into that list, h_edge_tok, h_edge_slot) writes
  * d_node_lp[slot] = log_softmax(logits(row))[tok]; stop entry k (h_stop_row ascending, h_stop_set, h_stop_slot) writes
@@ -237,7 +237,7 @@ int32_t opus_llama_tree_max_depth(void);
  * [P, ld_nodes], d_member_node int32 [tries, M], d_trie int32 [P], d_member_lp fp32 [P, M]; all device. */
 int opus_trie_path_sums(opus_ctx *ctx, const float *d_node_lp, const int32_t *d_trie, const int32_t *d_par, const int32_t *d_depth,
                         const int32_t *d_member_node, int32_t P, int32_t M, int32_t ld_nodes, float *d_member_lp, void *stream);
-/* attn_tree_kernel alone, on layer 0 of this context's KV cache: the arguments of opus_debug_attn_prefix with one position per row
+/* attn_prefix_kernel's tree form alone, on layer 0 of this context's KV cache: the arguments of opus_debug_attn_prefix with one position per row
  * (d_qkv [R, (heads + 2 kv) hd]) and the host tables h_par / h_depth [R] of opus_llama_score_tree.  Row r attends to slots
  * kstart[p] .. Tp - 1 of p = h_src[r], to its ancestors and to itself.  d_out [R, heads hd].  Leaves the context without a prefill. */
 int opus_debug_attn_tree(opus_ctx *ctx, const void *d_qkv, const void *d_k_hist, const void *d_v_hist, const int32_t *d_kstart,

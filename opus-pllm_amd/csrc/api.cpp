@@ -202,7 +202,7 @@ static void new_epoch(opus_ctx *c) { c->epoch = ++g_epoch; }
 // Continuation rows of opus_llama_score_continuations in the prefill's layer loop: B rows of T new positions behind a cached prefix.
 // No mask / kstart upload, no cache write, no decode state: rotary (learned positions for OPT) at Tp - kstart[p] + t through
 // nkst[b] = kstart[p] - Tp, and attn_prefix_kernel instead of the causal prefill attention.  opus_llama_score_tree runs trie nodes
-// the same way: T = 1, nkst[b] = kstart[p] - Tp - (depth - 1), and attn.par set selects attn_tree_kernel.
+// the same way: T = 1, nkst[b] = kstart[p] - Tp - (depth - 1), and attn.par set selects the kernel's tree form.
 struct ContRows {
     const int32_t *nkst;          // [B] device
     AttnPrefixParams attn;        // layer-independent fields (kc / vc are set per layer)
@@ -1119,7 +1119,7 @@ static int attn_prefix(opus_ctx *c, hipStream_t s, const ContRows &cr, int l, in
     const int QKV = (g.dec_heads + 2 * g.dec_kv_heads) * g.dec_head_dim, QD = g.dec_heads * g.dec_head_dim;
     // algorithmic bytes: the rows' projections + output, and every (prefix row, kv head)'s visible cache slots once
     KLF(KC_ATTN_PREFILL, 2.0 * M * (QKV + QD) + 4.0 * cr.nblocks * g.dec_kv_heads * g.dec_head_dim * a.Tp,
-        4.0 * M * (double)QD * (a.Tp + a.n), a.par ? launch_attn_tree(a, cr.nblocks, s) : launch_attn_prefix(a, cr.nblocks, s));
+        4.0 * M * (double)QD * (a.Tp + a.n), launch_attn_prefix(a, cr.nblocks, s));
     return OPUS_OK;
 }
 
@@ -1560,6 +1560,33 @@ static void build_prefix_tables(const opus_config &g, const std::vector<int32_t>
     attn_prefix_blocks(t.w.data() + t.off, P, G, n, t.w.data() + t.blocks);
     t.gidx = (int)t.w.size();
 }
+// the kernel's parameters for the tables t uploaded at d_tbl (par, for the tree form, is set by the caller that has it)
+static AttnPrefixParams prefix_params(const opus_ctx *c, const int32_t *d_tbl, const PrefixTables &t, int Tp, int n, const half_t *qkv,
+                                      const half_t *kc, const half_t *vc, half_t *out) {
+    const opus_config &g = c->cfg;
+    AttnPrefixParams a;
+    a.kc = kc; a.vc = vc; a.cache_sb = c->cache_sb; a.cache_sh = c->cache_sh; a.kstart = c->d_kstart; a.Tp = Tp;
+    a.qkv = qkv; a.n = n; a.list = d_tbl + t.list; a.off = d_tbl + t.off; a.blocks = d_tbl + t.blocks; a.out = out;
+    a.nh = g.dec_heads; a.nkv = g.dec_kv_heads; a.hd = g.dec_head_dim; a.scale = 1.0f / sqrtf((float)g.dec_head_dim);
+    return a;
+}
+// is the prefix handle (P, epoch) of opus_llama_prefix still what this context's cache holds?
+static int check_current_prefix(const opus_ctx *c, const char *who, int P, int64_t epoch) {
+    if (!c->prefilled || epoch != c->epoch || (int)c->h_kstart.size() != c->cur_B || P != c->cur_B)
+        return fail(OPUS_ESTATE, "%s: the prefix is not this context's current one (a later call prefilled or permuted the cache, or "
+                                 "the handle belongs to another context)", who);
+    return OPUS_OK;
+}
+// layer 0 of the KV cache <- a history d_k_hist / d_v_hist [rows, kv heads, L, hd] (slots 0 .. L - 1) and kstart <- d_kstart [rows]
+// (the kernel-level debug entries)
+static int seed_cache(opus_ctx *c, hipStream_t s, const void *d_k_hist, const void *d_v_hist, const int32_t *d_kstart, int rows, int L) {
+    const int nkv = c->cfg.dec_kv_heads;
+    const size_t pitch = (size_t)c->cache_sh * sizeof(half_t), roww = (size_t)L * c->cfg.dec_head_dim * sizeof(half_t);
+    HIPC(hipMemcpy2DAsync(c->kc, pitch, d_k_hist, roww, roww, (size_t)rows * nkv, hipMemcpyDeviceToDevice, s));
+    HIPC(hipMemcpy2DAsync(c->vc, pitch, d_v_hist, roww, roww, (size_t)rows * nkv, hipMemcpyDeviceToDevice, s));
+    HIPC(hipMemcpyAsync(c->d_kstart, d_kstart, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    return OPUS_OK;
+}
 
 extern "C" int opus_llama_prefix(opus_ctx *c, const void *d_embeds, const uint8_t *d_mask, int32_t B, int32_t T, float *d_last_logits,
                                  float *d_last_rows, int64_t *epoch, void *stream) {
@@ -1600,9 +1627,7 @@ extern "C" int opus_llama_score_continuations(opus_ctx *c, const void *d_embeds,
     const opus_config &g = c->cfg;
     if (R < 1 || n < 1 || n > g.max_prompt)
         return fail(OPUS_ESHAPE, "score_continuations: R=%d rows of n=%d positions (1 <= n <= max_prompt=%d)", R, n, g.max_prompt);
-    if (!c->prefilled || epoch != c->epoch || (int)c->h_kstart.size() != c->cur_B || P != c->cur_B)
-        return fail(OPUS_ESTATE, "score_continuations: the prefix is not this context's current one (a later call prefilled or "
-                                 "permuted the cache, or the handle belongs to another context)");
+    OPC(check_current_prefix(c, "score_continuations", P, epoch));
     const int Tp = c->cur_T, ctx_cap = g.max_prompt + g.max_new_tokens;
     int64_t N = 0;
     for (int r = 0; r < R; ++r) {
@@ -1644,10 +1669,7 @@ extern "C" int opus_llama_score_continuations(opus_ctx *c, const void *d_embeds,
         ContRows cr;
         cr.nkst = tbl + t.nkst;
         cr.nblocks = t.nblocks;
-        AttnPrefixParams &a = cr.attn;
-        a.kc = a.vc = nullptr; a.cache_sb = c->cache_sb; a.cache_sh = c->cache_sh; a.kstart = c->d_kstart; a.Tp = Tp;
-        a.qkv = c->d_qkv; a.n = n; a.list = tbl + t.list; a.off = tbl + t.off; a.blocks = tbl + t.blocks; a.out = c->d_ctx;
-        a.nh = g.dec_heads; a.nkv = g.dec_kv_heads; a.hd = g.dec_head_dim; a.scale = 1.0f / sqrtf((float)g.dec_head_dim);
+        cr.attn = prefix_params(c, tbl, t, Tp, n, c->d_qkv, nullptr, nullptr, c->d_ctx);
         const half_t *emb = reinterpret_cast<const half_t *>(d_embeds) + r0 * n * (int64_t)H;
         OPC(prefill(c, s, emb, nullptr, Rg, n, true, &cr));
         c->phase = PH_SCORE;
@@ -1663,6 +1685,44 @@ extern "C" int opus_llama_score_continuations(opus_ctx *c, const void *d_embeds,
     return OPUS_OK;
 }
 
+// The shared body of opus_debug_attn_prefix / opus_debug_attn_tree (h_par: the tree form, n = 1), after their argument checks:
+// seeds layer 0 of the cache, builds and uploads the tables, one timed launch.  Leaves the context without a prefill.
+static int debug_attn_prefix_run(opus_ctx *c, const char *who, const void *d_qkv, const void *d_k_hist, const void *d_v_hist,
+                                 const int32_t *d_kstart, int P, int Tp, int R, int n, const int32_t *h_src, const int32_t *h_par,
+                                 void *d_out, void *stream) {
+    const opus_config &g = c->cfg;
+    HIPC(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int nkv = g.dec_kv_heads, hd = g.dec_head_dim, G = g.dec_heads / nkv;
+    std::vector<int32_t> kst(P);
+    HIPC(hipMemcpyAsync(kst.data(), d_kstart, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    for (int p = 0; p < P; ++p)
+        if (kst[p] < 0 || kst[p] >= Tp) return fail(OPUS_EBADARG, "%s: kstart[%d]=%d outside [0, %d)", who, p, kst[p], Tp);
+    c->prefilled = false;                                     // (the cache no longer belongs to a prefill)
+    new_epoch(c);
+    OPC(seed_cache(c, s, d_k_hist, d_v_hist, d_kstart, P, Tp));
+    PrefixTables t;
+    build_prefix_tables(g, kst, Tp, h_src, R, n, t);
+    const int o_par = (int)t.w.size();
+    if (h_par) t.w.insert(t.w.end(), h_par, h_par + R);
+    int32_t *d_tbl = nullptr;
+    HIPC(hipMalloc((void **)&d_tbl, t.w.size() * sizeof(int32_t)));
+    hipError_t e = hipMemcpyAsync(d_tbl, t.w.data(), t.w.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
+    AttnPrefixParams a = prefix_params(c, d_tbl, t, Tp, n, (const half_t *)d_qkv, c->kc, c->vc, (half_t *)d_out);
+    if (h_par) a.par = d_tbl + o_par;
+    c->phase = PH_SCORE;
+    if (e == hipSuccess) {
+        Timed tm(c, s, KC_ATTN_PREFILL, 2.0 * R * n * (double)(G + 2) * nkv * hd * 2 + 4.0 * t.nblocks * nkv * hd * Tp,
+                 4.0 * R * n * (double)G * nkv * hd * (Tp + n));
+        e = launch_attn_prefix(a, t.nblocks, s);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(d_tbl);
+    if (e != hipSuccess) return fail(OPUS_EHIP, "%s failed: %s", who, hipGetErrorString(e));
+    return OPUS_OK;
+}
+
 // attn_prefix_kernel alone, as opus_llama_score_continuations launches it, on layer 0 of this context's KV cache: the prefix
 // d_k_hist / d_v_hist [P, kv heads, Tp, hd] (keys rotated, as the cache holds them) is copied into slots 0 .. Tp - 1 and d_kstart
 // [P] into the context's kstart; d_qkv [R n, (heads + 2 kv) hd]: the continuation rows' projections, q and k already rotated;
@@ -1675,44 +1735,12 @@ extern "C" int opus_debug_attn_prefix(opus_ctx *c, const void *d_qkv, const void
         return fail(OPUS_ESHAPE, "debug_attn_prefix: P=%d Tp=%d R=%d n=%d exceed the context (%d, %d)", P, Tp, R, n, g.max_batch, g.max_prompt);
     for (int r = 0; r < R; ++r)
         if (h_src[r] < 0 || h_src[r] >= P) return fail(OPUS_EBADARG, "debug_attn_prefix: prefix row %d of row %d outside [0, %d)", h_src[r], r, P);
-    HIPC(hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    const int nkv = g.dec_kv_heads, hd = g.dec_head_dim, G = g.dec_heads / nkv;
-    std::vector<int32_t> kst(P);
-    HIPC(hipMemcpyAsync(kst.data(), d_kstart, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIPC(hipStreamSynchronize(s));
-    for (int p = 0; p < P; ++p)
-        if (kst[p] < 0 || kst[p] >= Tp) return fail(OPUS_EBADARG, "debug_attn_prefix: kstart[%d]=%d outside [0, %d)", p, kst[p], Tp);
-    c->prefilled = false;                                     // (the cache no longer belongs to a prefill)
-    new_epoch(c);
-    const size_t pitch = (size_t)c->cache_sh * sizeof(half_t), roww = (size_t)Tp * hd * sizeof(half_t);
-    HIPC(hipMemcpy2DAsync(c->kc, pitch, d_k_hist, roww, roww, (size_t)P * nkv, hipMemcpyDeviceToDevice, s));
-    HIPC(hipMemcpy2DAsync(c->vc, pitch, d_v_hist, roww, roww, (size_t)P * nkv, hipMemcpyDeviceToDevice, s));
-    HIPC(hipMemcpyAsync(c->d_kstart, d_kstart, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    PrefixTables t;
-    build_prefix_tables(g, kst, Tp, h_src, R, n, t);
-    int32_t *d_tbl = nullptr;
-    HIPC(hipMalloc((void **)&d_tbl, t.w.size() * sizeof(int32_t)));
-    hipError_t e = hipMemcpyAsync(d_tbl, t.w.data(), t.w.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
-    AttnPrefixParams a;
-    a.kc = c->kc; a.vc = c->vc; a.cache_sb = c->cache_sb; a.cache_sh = c->cache_sh; a.kstart = c->d_kstart; a.Tp = Tp;
-    a.qkv = (const half_t *)d_qkv; a.n = n; a.list = d_tbl + t.list; a.off = d_tbl + t.off; a.blocks = d_tbl + t.blocks;
-    a.out = (half_t *)d_out; a.nh = g.dec_heads; a.nkv = nkv; a.hd = hd; a.scale = 1.0f / sqrtf((float)hd);
-    c->phase = PH_SCORE;
-    if (e == hipSuccess) {
-        Timed tm(c, s, KC_ATTN_PREFILL, 2.0 * R * n * (double)(G + 2) * nkv * hd * 2 + 4.0 * t.nblocks * nkv * hd * Tp,
-                 4.0 * R * n * (double)G * nkv * hd * (Tp + n));
-        e = launch_attn_prefix(a, t.nblocks, s);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(d_tbl);
-    if (e != hipSuccess) return fail(OPUS_EHIP, "debug_attn_prefix failed: %s", hipGetErrorString(e));
-    return OPUS_OK;
+    return debug_attn_prefix_run(c, "debug_attn_prefix", d_qkv, d_k_hist, d_v_hist, d_kstart, P, Tp, R, n, h_src, nullptr, d_out, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ trie scoring
 // opus_llama_score_tree = one pass of a token trie's nodes behind the cached prefix: every row is one new position (a node) that
-// attends to its prefix row's cache slots and to its own ancestors in the pass (attn_tree_kernel).  The planning (which nodes,
+// attends to its prefix row's cache slots and to its own ancestors in the pass (attn_prefix_kernel's tree form).  The planning (which nodes,
 // which order, which pass) is the caller's (opus-pllm_amd/constraint.py, plan_trie_score); this entry checks every table it is
 // given before anything reaches a kernel.
 enum { TREE_MAX_DEPTH = 64 };
@@ -1782,9 +1810,7 @@ extern "C" int opus_llama_score_tree(opus_ctx *c, const void *d_embeds, int32_t 
         (n_edges && (!h_edge_row || !h_edge_tok || !h_edge_slot)) ||
         (n_stops && (!h_stop_row || !h_stop_set || !h_stop_slot || !h_stop_ids || !h_stop_off || !d_stop_lp)))
         return fail(OPUS_EBADARG, "score_tree: null pointer");
-    if (!c->prefilled || epoch != c->epoch || (int)c->h_kstart.size() != c->cur_B || P != c->cur_B)
-        return fail(OPUS_ESTATE, "score_tree: the prefix is not this context's current one (a later call prefilled or permuted the "
-                                 "cache, or the handle belongs to another context)");
+    OPC(check_current_prefix(c, "score_tree", P, epoch));
     const int Tp = c->cur_T, ctx_cap = g.max_prompt + g.max_new_tokens, V = g.dec_vocab, H = g.dec_dim;
     OPC(check_tree_rows("score_tree", rows, P, h_src, h_par, h_depth));
     for (int r = 0; r < rows; ++r)
@@ -1846,11 +1872,8 @@ extern "C" int opus_llama_score_tree(opus_ctx *c, const void *d_embeds, int32_t 
         ContRows cr;
         cr.nkst = tbl + t.nkst;
         cr.nblocks = t.nblocks;
-        AttnPrefixParams &a = cr.attn;
-        a.kc = a.vc = nullptr; a.cache_sb = c->cache_sb; a.cache_sh = c->cache_sh; a.kstart = c->d_kstart; a.Tp = Tp;
-        a.qkv = c->d_qkv; a.n = 1; a.list = tbl + t.list; a.off = tbl + t.off; a.blocks = tbl + t.blocks; a.out = c->d_ctx;
-        a.nh = g.dec_heads; a.nkv = g.dec_kv_heads; a.hd = g.dec_head_dim; a.scale = 1.0f / sqrtf((float)g.dec_head_dim);
-        a.par = tbl + o_par;
+        cr.attn = prefix_params(c, tbl, t, Tp, 1, c->d_qkv, nullptr, nullptr, c->d_ctx);
+        cr.attn.par = tbl + o_par;
         OPC(prefill(c, s, reinterpret_cast<const half_t *>(d_embeds), nullptr, rows, 1, true, &cr));
     }
     c->phase = PH_SCORE;
@@ -1885,8 +1908,8 @@ extern "C" int opus_trie_path_sums(opus_ctx *c, const float *d_node_lp, const in
     return OPUS_OK;
 }
 
-// attn_tree_kernel alone, as opus_llama_score_tree launches it, on layer 0 of this context's KV cache: the arguments of
-// opus_debug_attn_prefix with one position per row (d_qkv [R, (heads + 2 kv) hd]) and h_par / h_depth [R] (host): the parent row
+// attn_prefix_kernel's tree form alone, as opus_llama_score_tree launches it, on layer 0 of this context's KV cache: the arguments
+// of opus_debug_attn_prefix with one position per row (d_qkv [R, (heads + 2 kv) hd]) and h_par / h_depth [R] (host): the parent row
 // of every row (-1 at depth 1; an earlier row of the same prefix row one level up).  d_out [R, heads hd].
 extern "C" int opus_debug_attn_tree(opus_ctx *c, const void *d_qkv, const void *d_k_hist, const void *d_v_hist, const int32_t *d_kstart,
                                     int32_t P, int32_t Tp, int32_t R, const int32_t *h_src, const int32_t *h_par, const int32_t *h_depth,
@@ -1897,42 +1920,7 @@ extern "C" int opus_debug_attn_tree(opus_ctx *c, const void *d_qkv, const void *
     if (P < 1 || P > g.max_batch || Tp < 1 || Tp > g.max_prompt || R < 1)
         return fail(OPUS_ESHAPE, "debug_attn_tree: P=%d Tp=%d R=%d exceed the context (%d, %d)", P, Tp, R, g.max_batch, g.max_prompt);
     OPC(check_tree_rows("debug_attn_tree", R, P, h_src, h_par, h_depth));
-    HIPC(hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    const int nkv = g.dec_kv_heads, hd = g.dec_head_dim, G = g.dec_heads / nkv;
-    std::vector<int32_t> kst(P);
-    HIPC(hipMemcpyAsync(kst.data(), d_kstart, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIPC(hipStreamSynchronize(s));
-    for (int p = 0; p < P; ++p)
-        if (kst[p] < 0 || kst[p] >= Tp) return fail(OPUS_EBADARG, "debug_attn_tree: kstart[%d]=%d outside [0, %d)", p, kst[p], Tp);
-    c->prefilled = false;                                     // (the cache no longer belongs to a prefill)
-    new_epoch(c);
-    const size_t pitch = (size_t)c->cache_sh * sizeof(half_t), roww = (size_t)Tp * hd * sizeof(half_t);
-    HIPC(hipMemcpy2DAsync(c->kc, pitch, d_k_hist, roww, roww, (size_t)P * nkv, hipMemcpyDeviceToDevice, s));
-    HIPC(hipMemcpy2DAsync(c->vc, pitch, d_v_hist, roww, roww, (size_t)P * nkv, hipMemcpyDeviceToDevice, s));
-    HIPC(hipMemcpyAsync(c->d_kstart, d_kstart, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    PrefixTables t;
-    build_prefix_tables(g, kst, Tp, h_src, R, 1, t);
-    const int o_par = (int)t.w.size();
-    t.w.insert(t.w.end(), h_par, h_par + R);
-    int32_t *d_tbl = nullptr;
-    HIPC(hipMalloc((void **)&d_tbl, t.w.size() * sizeof(int32_t)));
-    hipError_t e = hipMemcpyAsync(d_tbl, t.w.data(), t.w.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
-    AttnPrefixParams a;
-    a.kc = c->kc; a.vc = c->vc; a.cache_sb = c->cache_sb; a.cache_sh = c->cache_sh; a.kstart = c->d_kstart; a.Tp = Tp;
-    a.qkv = (const half_t *)d_qkv; a.n = 1; a.list = d_tbl + t.list; a.off = d_tbl + t.off; a.blocks = d_tbl + t.blocks;
-    a.out = (half_t *)d_out; a.nh = g.dec_heads; a.nkv = nkv; a.hd = hd; a.scale = 1.0f / sqrtf((float)hd);
-    a.par = d_tbl + o_par;
-    c->phase = PH_SCORE;
-    if (e == hipSuccess) {
-        Timed tm(c, s, KC_ATTN_PREFILL, 2.0 * R * (double)(G + 2) * nkv * hd * 2 + 4.0 * t.nblocks * nkv * hd * Tp,
-                 4.0 * R * (double)G * nkv * hd * (Tp + 1));
-        e = launch_attn_tree(a, t.nblocks, s);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(d_tbl);
-    if (e != hipSuccess) return fail(OPUS_EHIP, "debug_attn_tree failed: %s", hipGetErrorString(e));
-    return OPUS_OK;
+    return debug_attn_prefix_run(c, "debug_attn_tree", d_qkv, d_k_hist, d_v_hist, d_kstart, P, Tp, R, 1, h_src, h_par, d_out, stream);
 }
 
 // opus_generate_scored's outputs (opus_ctx::gen_outs)
@@ -2730,10 +2718,8 @@ extern "C" int opus_debug_attn_decode(opus_ctx *c, const void *d_qkv, const void
     if (L > 0 && (!d_k_hist || !d_v_hist)) return fail(OPUS_EBADARG, "debug_attn_decode: history is null");
     HIPC(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    const size_t pitch = (size_t)c->cache_sh * sizeof(half_t), roww = (size_t)L * hd * sizeof(half_t);
-    HIPC(hipMemcpy2DAsync(c->kc, pitch, d_k_hist, roww, roww, (size_t)B * nkv, hipMemcpyDeviceToDevice, s));
-    HIPC(hipMemcpy2DAsync(c->vc, pitch, d_v_hist, roww, roww, (size_t)B * nkv, hipMemcpyDeviceToDevice, s));
-    HIPC(hipMemcpyAsync(c->d_kstart, d_kstart, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    const size_t pitch = (size_t)c->cache_sh * sizeof(half_t);
+    OPC(seed_cache(c, s, d_k_hist, d_v_hist, d_kstart, B, L));
     OPC(reset_step(c, s, T0, step));
     // (the embedding kernel with a zero-width row: only its rotary-row part runs)
     HIPC(launch_embed_tokens(c->d_next, nullptr, B, 0, 1, c->d_xl, nullptr, nullptr, 0, c->cs_dec, c->d_kstart, c->d_step, -1, hd / 2,

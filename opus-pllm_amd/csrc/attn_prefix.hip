@@ -1,16 +1,30 @@
-// Prefix attention of opus_llama_score_continuations: the queries are NEW positions (continuation rows), the keys are a cached
-// prefix plus the continuation's own positions.
+// Attention of NEW rows over a cached prefix, in two forms of one kernel: attn_prefix_kernel<HD, TREE>.
 //
+// Flat form (TREE = false, opus_llama_score_continuations): the queries are continuation rows of n positions each.
 //   continuation row r (prefix row p = src[r], n positions, query t):
 //     keys = cache slots kstart[p] .. Tp - 1 of row p (K rotated when the prefix was prefilled)
 //          + the row's own positions 0 .. t (causal; projections rotated by the caller at positions Tp - kstart[p] + t)
 //
+// Tree form (TREE = true, opus_llama_score_tree; selected by AttnPrefixParams::par): every row is ONE new position (n = 1, fixed
+// at compile time), a node of a token trie behind the cached prompt.
+//   row r (prefix row p = src[r], parent row par[r] of the same pass or -1 for a child of the root):
+//     keys = cache slots kstart[p] .. Tp - 1 of row p
+//          + rows r, par[r], par[par[r]], ... of this pass's projections (rotated by the caller at Tp - kstart[p] + depth - 1)
+//
 // Work split.  One workgroup per (prefix row p, kv head hk, block of 128 stacked queries).  The queries of a prefix row are
-// STACKED: every continuation i of p (the rows src maps to p, in the order of the list), every head of the GQA group and every
+// STACKED: every row i of p (the rows src maps to p, in the order of the list), every head of the GQA group and every
 // position t form one index q = (i G + gh) n + t.  The prefix's K / V tiles are then read once per (p, hk) and query block and
 // shared by all K continuations and all G heads of the group (K options x 4 heads x 6 positions = 96 queries: one workgroup),
-// instead of once per continuation row and head.  The own-position keys of a block are the n positions of the continuations
-// the block's queries belong to (a block-diagonal causal mask over that short virtual key list).
+// instead of once per continuation row and head.  In the flat form the own-position keys of a block are the n positions of the
+// continuations the block's queries belong to (a block-diagonal causal mask over that short virtual key list), tiled like the
+// cache part.
+//
+// In the tree form the ancestor part is not tiled: a query has at most `depth` such keys and no two queries of a block need
+// share any, so a virtual key list of the block would cost every query the block's whole list.  Instead each query walks its
+// own parent chain after the cache part: the four lanes (li, g = 0 .. 3) that hold a query take 8 dims of each 32-dim step of
+// q . k (the MFMA B-fragment they already hold), two xor-shuffles complete the score, and every lane updates the 4 output dims
+// per 16-dim tile that it owns in the MFMA result layout.  The cost per query is its own depth, whatever else the pass holds.
+// The chain is walked from the node up to the root in a fixed order, so the same inputs give bitwise the same output.
 //
 // Per wave 32 queries (two 16-query tiles, QT = 2); 64-key tiles staged in LDS (K row-major, V transposed so that the P V
 // product reads V^T rows as 8-byte pieces).  The products are swapped, as in attn_prefill.hip, so that a query lives on a lane:
@@ -30,7 +44,7 @@ constexpr int PQT = 2;             // 16-query tiles per wave
 constexpr int PQB = 4 * 16 * PQT;  // queries per workgroup
 constexpr int VT_PAD = 8;          // halfs of padding behind each row of the transposed V image (row pitch 72: 144 B)
 
-template <int HD>
+template <int HD, bool TREE>
 __global__ __launch_bounds__(256) void attn_prefix_kernel(AttnPrefixParams p) {
     constexpr int KS = HD < 32 ? 1 : HD / 32;   // MFMA k-steps of QK^T (head_dim 16: one step, upper half zero)
     constexpr int NO = HD / 16;                 // output dim tiles
@@ -44,12 +58,12 @@ __global__ __launch_bounds__(256) void attn_prefix_kernel(AttnPrefixParams p) {
     const int g = lane >> 4, li = lane & 15;
     const int pr = p.blocks[2 * blockIdx.x], q0 = p.blocks[2 * blockIdx.x + 1];
     const int hk = blockIdx.y;
-    const int G = p.nh / p.nkv, n = p.n, Gn = G * n;
+    const int G = p.nh / p.nkv, n = TREE ? 1 : p.n, Gn = G * n;   // (TREE: the divisions by n fold)
     const int lo = p.off[pr], cnt = p.off[pr + 1] - lo;
     const int nq = cnt * Gn;                                    // stacked queries of this prefix row
     const int QKV = (p.nh + 2 * p.nkv) * HD, QD = p.nh * HD;
     const int kbeg = p.kstart[pr], Lp = p.Tp - kbeg;           // visible cache slots kbeg .. Tp - 1
-    // own-position keys of the block: the n positions of continuations i_lo .. i_hi
+    // own-position keys of the block (flat form): the n positions of continuations i_lo .. i_hi
     const int qlast = (q0 + PQB < nq ? q0 + PQB : nq) - 1;
     const int i_lo = q0 / Gn, i_hi = qlast / Gn;
     const int nself = (i_hi - i_lo + 1) * n;
@@ -57,9 +71,10 @@ __global__ __launch_bounds__(256) void attn_prefix_kernel(AttnPrefixParams p) {
     const half_t *kc = p.kc + (int64_t)pr * p.cache_sb + (int64_t)hk * p.cache_sh;
     const half_t *vc = p.vc + (int64_t)pr * p.cache_sb + (int64_t)hk * p.cache_sh;
 
-    // this lane's queries: (continuation i, head gh, position t) -> Q row and the own-key window [jlo, jhi] of the virtual list
+    // this lane's queries: (row i, head gh, position t) -> Q row; flat form: the own-key window [jlo, jhi] of the virtual list,
+    // tree form: the node's row of the pass
     h8 qf[PQT][KS];
-    int jlo[PQT], jhi[PQT];
+    int jlo[PQT], jhi[PQT], qrow[PQT];
     int64_t orow[PQT];
     bool qok[PQT];
 #pragma unroll
@@ -78,6 +93,7 @@ __global__ __launch_bounds__(256) void attn_prefix_kernel(AttnPrefixParams p) {
         }
         jlo[u] = (i - i_lo) * n;
         jhi[u] = jlo[u] + t;
+        qrow[u] = r;
         orow[u] = row * QD + (int64_t)(hk * G + gh) * HD;
     }
     const bool wave_live = q0 + wave * 16 * PQT < nq;          // (wave-uniform)
@@ -200,7 +216,7 @@ __global__ __launch_bounds__(256) void attn_prefix_kernel(AttnPrefixParams p) {
             }
     };
 
-    for (int self = 0; self < 2; ++self) {
+    for (int self = 0; self < (TREE ? 1 : 2); ++self) {            // (the tree form has no tiled own part)
         const int nk = self ? nself : Lp;
         for (int kt = 0; kt < nk; kt += PKB) {
             __syncthreads();                                        // (the previous tile's readers are done)
@@ -211,6 +227,50 @@ __global__ __launch_bounds__(256) void attn_prefix_kernel(AttnPrefixParams p) {
     }
 
     if (!wave_live) return;
+
+    if constexpr (TREE) {
+        // the node and its ancestors: one key per step and query, walked up the parent chain (lanes past the end repeat the
+        // block's last query, so every lane of the wave holds a valid chain; a finished chain idles at cur = -1)
+        int cur[PQT];
+#pragma unroll
+        for (int u = 0; u < PQT; ++u) cur[u] = qrow[u];
+        while (__any(cur[0] >= 0 || cur[1] >= 0)) {
+#pragma unroll
+            for (int u = 0; u < PQT; ++u) {
+                const bool act = cur[u] >= 0;
+                const int kr = act ? cur[u] : qrow[u];
+                const half_t *kp = p.qkv + (int64_t)kr * QKV + QD + (int64_t)hk * HD;
+                const half_t *vp = kp + (int64_t)p.nkv * HD;
+                float dot = 0.f;
+#pragma unroll
+                for (int s = 0; s < KS; ++s) {
+                    const int d = 32 * s + 8 * g;
+                    if (d < HD) {
+                        const h8 kf = *reinterpret_cast<const h8 *>(kp + d);
+#pragma unroll
+                        for (int x = 0; x < 8; ++x) dot = fmaf((float)qf[u][s][x], (float)kf[x], dot);
+                    }
+                }
+                dot += __shfl_xor(dot, 16, 64);
+                dot += __shfl_xor(dot, 32, 64);
+                const float sv = act ? dot : -INFINITY;
+                const float mnew = fmaxf(mrow[u], sv);
+                const float msafe = mnew == -INFINITY ? 0.f : mnew;
+                const float alpha = __builtin_amdgcn_exp2f((mrow[u] - msafe) * sc);       // 1 when the maximum stays, 0 from -inf
+                const float pe = act ? __builtin_amdgcn_exp2f((sv - msafe) * sc) : 0.f;
+                lrow[u] = lrow[u] * alpha + (g == 0 ? pe : 0.f);      // (lrow is a per-lane partial: the key counts once)
+                mrow[u] = mnew;
+#pragma unroll
+                for (int d = 0; d < NO; ++d) {
+                    const h4 vv = *reinterpret_cast<const h4 *>(vp + 16 * d + 4 * g);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) o[u][d][r] = fmaf(pe, (float)vv[r], o[u][d][r] * alpha);
+                }
+                cur[u] = act ? p.par[kr] : -1;
+            }
+        }
+    }
+
 #pragma unroll
     for (int u = 0; u < PQT; ++u) {
         float l = lrow[u];
@@ -245,18 +305,24 @@ int attn_prefix_blocks(const int32_t *off, int P, int G, int n, int32_t *blocks)
 
 int attn_prefix_max_blocks(int R, int P, int G, int n) { return (int)(((int64_t)R * G * n) / PQB) + P; }
 
-hipError_t launch_attn_prefix(const AttnPrefixParams &p, int nblocks, hipStream_t s) {
-    if (nblocks <= 0) return hipSuccess;
-    if (p.nkv < 1 || p.nh % p.nkv || p.n < 1 || p.Tp < 1) return hipErrorInvalidValue;
-    const dim3 grid(nblocks, p.nkv);
+template <bool TREE>
+static hipError_t launch_form(const AttnPrefixParams &p, dim3 grid, hipStream_t s) {
     switch (p.hd) {
-        case 16: OPUS_LAUNCH(KC_ATTN_PREFILL, attn_prefix_kernel<16>, grid, dim3(256), 0, s, p); break;
-        case 32: OPUS_LAUNCH(KC_ATTN_PREFILL, attn_prefix_kernel<32>, grid, dim3(256), 0, s, p); break;
-        case 64: OPUS_LAUNCH(KC_ATTN_PREFILL, attn_prefix_kernel<64>, grid, dim3(256), 0, s, p); break;
-        case 128: OPUS_LAUNCH(KC_ATTN_PREFILL, attn_prefix_kernel<128>, grid, dim3(256), 0, s, p); break;
+        case 16: OPUS_LAUNCH(KC_ATTN_PREFILL, (attn_prefix_kernel<16, TREE>), grid, dim3(256), 0, s, p); break;
+        case 32: OPUS_LAUNCH(KC_ATTN_PREFILL, (attn_prefix_kernel<32, TREE>), grid, dim3(256), 0, s, p); break;
+        case 64: OPUS_LAUNCH(KC_ATTN_PREFILL, (attn_prefix_kernel<64, TREE>), grid, dim3(256), 0, s, p); break;
+        case 128: OPUS_LAUNCH(KC_ATTN_PREFILL, (attn_prefix_kernel<128, TREE>), grid, dim3(256), 0, s, p); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+
+hipError_t launch_attn_prefix(const AttnPrefixParams &p, int nblocks, hipStream_t s) {
+    if (nblocks <= 0) return hipSuccess;
+    const bool tree = p.par != nullptr;                         // (the tree form: one position per row)
+    if (p.nkv < 1 || p.nh % p.nkv || p.n < 1 || p.Tp < 1 || (tree && p.n != 1)) return hipErrorInvalidValue;
+    const dim3 grid(nblocks, p.nkv);
+    return tree ? launch_form<true>(p, grid, s) : launch_form<false>(p, grid, s);
 }
 
 }  // namespace opus

@@ -276,16 +276,14 @@ struct AttnPrefixParams {
     half_t *out;
     int nh, nkv, hd;
     float scale;
-    const int32_t *par = nullptr;   // launch_attn_tree only: parent row of every row of the pass (-1: a child of the root)
+    const int32_t *par = nullptr;   // tree form only (selects it): parent row of every row of the pass (-1: a child of the root)
 };
 // workgroup table of launch_attn_prefix for the row lists off[0 .. P] (blocks = nullptr: count only); returns the block count
 int attn_prefix_blocks(const int32_t *off, int P, int G, int n, int32_t *blocks);
 int attn_prefix_max_blocks(int R, int P, int G, int n);   // an upper bound of that count for R rows over P prefix rows
+// par set selects the tree form (opus_llama_score_tree): n must be 1 (one new position per row: a trie node) and row r attends to
+// the cache slots of its prefix row, then to r, par[r], par[par[r]], ... (rows of this pass, the chain ends at -1).
 hipError_t launch_attn_prefix(const AttnPrefixParams &p, int nblocks, hipStream_t s);
-// attn_tree.hip: tree attention of opus_llama_score_tree.  The same parameters with n = 1 (one new position per row: a trie node)
-// and par set: row r attends to the cache slots of its prefix row, then to r, par[r], par[par[r]], ... (rows of this pass, the
-// chain ends at -1).  blocks: attn_prefix_blocks(off, P, G, 1).
-hipError_t launch_attn_tree(const AttnPrefixParams &p, int nblocks, hipStream_t s);
 
 // contact.hip: ESM-2 contact maps (opus_esm2_contacts_packed).  One layer's accumulation over token-packed proteins cu[B + 1]
 // (rows <cls> residues <eos>): Q / K rows of stride ld (head h at column h hd; q scaled and both rotated as the attention takes
