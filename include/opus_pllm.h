@@ -379,6 +379,14 @@ int opus_debug_gemm_norm(opus_ctx *ctx, const float *d_A, const void *d_W, void 
  * wrote a finished output instead and nothing is copied. */
 int opus_debug_gemm_slabs(opus_ctx *ctx, const void *d_A, const void *d_W, float *d_slabs, int32_t M, int32_t N, int32_t K,
                           int32_t *ks, void *stream);
+/* What the launchers launched for the last GEMM issued on this context (opus_debug_gemm, opus_debug_gemm_norm,
+ * opus_debug_gemm_slabs, or a path call): plan (HOST) receives 8 ints - [0] kernel class (index into the class list of
+ * opus_timing_names), [1] row-tile template argument (MT; TM of the ring kernel; 0: none), [2], [3] TN, NS of the ring kernel,
+ * [4] the skinny kernel's LDS-staged-activation flag, [5] panels per workgroup of gemm_stream_kernel, [6] k-parts over workgroups
+ * (big tiled GEMM: per tail tile), [7] how they become the output: 0 one k-part, 1 splitk_reduce_kernel, 2 splitk_reduce4_kernel,
+ * 3 inside the launch (gemm_stream_kernel), 4 the big tiled GEMM's pair hand-off, 5 pp_tail_reduce_kernel, 6 raw slabs left
+ * (opus_debug_gemm_slabs).  All -1: no GEMM yet, or the launcher refused the last one.  Added within ABI 10 (a new symbol only). */
+int opus_debug_gemm_plan(opus_ctx *ctx, int32_t *plan);
 /* Process-wide tuning knob of the benchmarks / parity tests (no reference counterpart): "no_stream" = 1 routes the narrow
  * GEMMs of the batched decode step through the round-2 split-K kernels instead of gemm_stream_kernel; "pp_gm" = tile rows
  * per rasterisation group of the big tiled GEMM; "debug_a_tiled" = 1: opus_debug_gemm takes A in fragment order; "no_ln_fusion" = 1: stand-alone normalisation kernels

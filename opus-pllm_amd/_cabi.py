@@ -105,6 +105,7 @@ SIGNATURES = {
     "opus_set_sampling_top_k": (C.c_int, [_P, C.c_int32]),
     "opus_set_stop_sequence": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int32]),
     "opus_debug_gemm_slabs": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _P]),
+    "opus_debug_gemm_plan": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "opus_debug_knob": (C.c_int, [_P, C.c_char_p, C.c_int32]),
     "opus_stat": (C.c_int64, [_P, C.c_char_p]),
     "opus_debug_attn_decode": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),

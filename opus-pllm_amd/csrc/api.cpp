@@ -171,6 +171,7 @@ struct opus_ctx {
     int rq_ln_done = 0;
     const float *rq_ln_stat = nullptr, *rq_ln_colsum = nullptr;   // consumer
     int *rq_pp_plan = nullptr;           // one-shot (HOST): the next GEMM's launch_pp reports its plan here (GemmParams::pp_plan)
+    int gemm_plan[GEMM_PLAN_WORDS] = {-1, -1, -1, -1, -1, -1, -1, -1};   // the launchers' report of this context's last GEMM (GemmParams::plan; opus_debug_gemm_plan)
     bool xln_tiled = false;              // d_xln currently holds fp16(x) in fragment order
     const float *xh_src = nullptr;       // fp32 buffer whose fp16 copy + sum-of-squares partials are valid
     bool use_row_scale = false;          // one-shot: the next gemm() multiplies its rows by the rstd from d_ssq
@@ -597,6 +598,8 @@ static int gemm_any(opus_ctx *c, hipStream_t s, const half_t *A, const float *Af
     p.combine_cnt = c->d_cnt;
     p.pp_plan = c->rq_pp_plan;
     c->rq_pp_plan = nullptr;
+    for (int i = 0; i < GEMM_PLAN_WORDS; ++i) c->gemm_plan[i] = -1;
+    p.plan = c->gemm_plan;
     p.a_tiled = c->rq_a_tiled; p.xh_tiled = c->rq_xh_tiled; p.c_tiled = c->rq_c_tiled;
     c->rq_a_tiled = c->rq_xh_tiled = c->rq_c_tiled = 0;
     const int nout = epi == EPI_SILU_GU16 ? N / 2 : N;
@@ -2550,6 +2553,15 @@ extern "C" int opus_debug_gemm_slabs(opus_ctx *c, const void *A, const void *W, 
     *ks = c->rq_ks;
     if (c->rq_ks > 1 && d_slabs)
         HIPC(hipMemcpyAsync(d_slabs, c->gemm_ws, (size_t)c->rq_ks * M * N * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return OPUS_OK;
+}
+
+// What the launchers launched for the last GEMM issued on this context (opus_debug_gemm, opus_debug_gemm_norm,
+// opus_debug_gemm_slabs or any path call): GemmParams::plan, GEMM_PLAN_WORDS ints to HOST memory; all -1: no GEMM yet, or the
+// launcher refused the last one before it chose a kernel.
+extern "C" int opus_debug_gemm_plan(opus_ctx *c, int32_t *plan) {
+    if (!c || !plan) return fail(OPUS_EBADARG, "debug_gemm_plan: null pointer");
+    for (int i = 0; i < GEMM_PLAN_WORDS; ++i) plan[i] = c->gemm_plan[i];
     return OPUS_OK;
 }
 

@@ -183,9 +183,24 @@ struct GemmParams {
     // combined (PP_TAIL_NONE / PP_TAIL_PAIR: inside the launch / PP_TAIL_REDUCE: pp_tail_reduce_kernel), [4] 1 = the rotary ran
     // in the epilogue.  A GEMM that another kernel takes leaves the words as they were.
     int *pp_plan = nullptr;
+    // every launcher reports what it launched in plan[0 .. GEMM_PLAN_WORDS) (HOST; nullptr: no report, nothing else changes):
+    // [0] kernel class (KC_*), [1] row-tile template argument (MT; TM of the ring kernel; 0: the kernel has none), [2] / [3] TN / NS
+    // of the ring kernel (else 0), [4] the skinny kernel's ALDS flag (else 0), [5] the stream kernel's P (else 0), [6] k-parts over
+    // workgroups (gemm_pp_kernel: per tail tile; 1: K is not cut), [7] how the k-parts become the output (GemmCombine)
+    int *plan = nullptr;
 };
 constexpr int PP_PLAN_WORDS = 5;
 enum PpTail { PP_TAIL_NONE = 0, PP_TAIL_PAIR = 1, PP_TAIL_REDUCE = 2 };
+constexpr int GEMM_PLAN_WORDS = 8;
+// GC_NONE: one k-part; GC_REDUCE / GC_REDUCE4: splitk_reduce_kernel / splitk_reduce4_kernel behind the launch; GC_IN_LAUNCH: the
+// workgroup of gemm_stream_kernel that arrives last; GC_PP_PAIR / GC_PP_REDUCE: gemm_pp_kernel's pair hand-off / pp_tail_reduce_kernel;
+// GC_SLABS: nobody here - the raw slabs are the result (GemmParams::slab_only)
+enum GemmCombine { GC_NONE = 0, GC_REDUCE = 1, GC_REDUCE4 = 2, GC_IN_LAUNCH = 3, GC_PP_PAIR = 4, GC_PP_REDUCE = 5, GC_SLABS = 6 };
+inline void gemm_plan_set(const GemmParams &p, int klass, int mt, int tn, int ns, int alds, int P, int ks, int combine) {
+    if (!p.plan) return;
+    const int v[GEMM_PLAN_WORDS] = {klass, mt, tn, ns, alds, P, ks, combine};
+    for (int i = 0; i < GEMM_PLAN_WORDS; ++i) p.plan[i] = v[i];
+}
 
 // Flash-style attention over strided Q/K/V (fp16).  Q(b,h,t,:) = Q + b*q_sb + t*q_st + h*HD etc.;
 // kv head of q head h is h / group.  Key j of batch row b is visible to query i iff

@@ -523,6 +523,7 @@ static hipError_t launch_skinny_t(const GemmParams &p, hipStream_t s) {
         hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_skinny_kernel<MT, EPI, NORM, ALDS>), lds);
         if (ea != hipSuccess) return ea;
     }
+    gemm_plan_set(p, KC_SKINNY, MT, 0, 0, ALDS ? 1 : 0, 0, 1, GC_NONE);
     OPUS_LAUNCH(KC_SKINNY, (gemm_skinny_kernel<MT, EPI, NORM, ALDS>), dim3(groups), dim3(64 * W), lds, s, p);
     return hipGetLastError();
 }
@@ -1827,6 +1828,7 @@ static hipError_t launch_pp(const GemmParams &p_in, hipStream_t s) {
         p.pp_plan[3] = split == 1 ? PP_TAIL_NONE : pair ? PP_TAIL_PAIR : PP_TAIL_REDUCE;
         p.pp_plan[4] = rope ? 1 : 0;
     }
+    gemm_plan_set(p, KC_PP, 0, 0, 0, 0, 0, split, split == 1 ? GC_NONE : pair ? GC_PP_PAIR : GC_PP_REDUCE);
     OPUS_LAUNCH(KC_PP, kern, dim3(full + tail * split), dim3(512), 8 * 16384, s, p, bm, bn, full, split);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || split == 1 || pair) return e;
@@ -1979,7 +1981,9 @@ static hipError_t launch_reduce(const GemmParams &p, int ks, hipStream_t s) {
         q.xh_out = nullptr;
     }
     if (tl_launch_ev) tl_launch_ev->aux_bytes = 4.0 * ks * p.M * p.N + (double)p.M * nout * ((p.out_f32 ? 4 : 2) + (p.residual ? 4 : 0));
-    if (EPI == EPI_NONE && (p.N & 255) == 0 && ((p.ldc | p.ldr) & 3) == 0)
+    const bool by4 = EPI == EPI_NONE && (p.N & 255) == 0 && ((p.ldc | p.ldr) & 3) == 0;
+    if (p.plan) p.plan[7] = by4 ? GC_REDUCE4 : GC_REDUCE;
+    if (by4)
         OPUS_LAUNCH(KC_REDUCE, splitk_reduce4_kernel, dim3(cdiv((int64_t)p.M * p.N, 1024)), dim3(256), 0, s, q, ks);
     else
         OPUS_LAUNCH(KC_REDUCE, (splitk_reduce_kernel<EPI>), dim3(cdiv((int64_t)p.M * nout, 256)), dim3(256), 0, s, q, ks);
@@ -2250,6 +2254,7 @@ static hipError_t launch_wide(const GemmParams &p, hipStream_t s) {
     const int lds = 2 * (MT <= 4 ? 8 : 4) * 16 * MT * 128 + 16 * MT * (int)sizeof(float);   // two stages + the rows' 1 / rms
     hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_wide_kernel<MT, EPI>), lds);
     if (ea != hipSuccess) return ea;
+    gemm_plan_set(p, KC_WIDE, MT, 0, 0, 0, 0, ks, ks == 1 ? GC_NONE : GC_SLABS);   // (launch_reduce names the reduce it takes)
     if (ks > 1 && p.row_ssq) {       // k-parts leave raw slabs: the row scale is applied by whoever combines them, not here
         GemmParams q = p;
         q.row_ssq = nullptr;
@@ -2282,6 +2287,7 @@ static hipError_t launch_mid_t(const GemmParams &p, hipStream_t s) {
         if (ea != hipSuccess) return ea;
     }
     if (p.row_ssq && ks == 1) return hipErrorInvalidValue;            // only the split-K reduce applies a row scale here
+    gemm_plan_set(p, KC_MID, MT, 0, 0, 0, 0, ks, GC_NONE);
     OPUS_LAUNCH(KC_MID, (gemm_mid_kernel<MT, EPI, NORM>), dim3(blocks, ks), dim3(256), lds, s, p, ks);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || ks == 1) return e;
@@ -2326,6 +2332,7 @@ static hipError_t launch_ring(const GemmParams &p, hipStream_t s, bool allow_spl
     hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_ring_kernel<TM, TN, NS, EPI>), LDS);
     if (ea != hipSuccess) return ea;
     if (p.row_ssq && ks == 1) return hipErrorInvalidValue;            // only the split-K reduce applies a row scale here
+    gemm_plan_set(p, KC_RING, TM, TN, NS, 0, 0, ks, GC_NONE);
     OPUS_LAUNCH(KC_RING, (gemm_ring_kernel<TM, TN, NS, EPI>), dim3(bm * bn, ks), dim3(512), LDS, s, p, bm, bn, ks);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || ks == 1) return e;
@@ -2365,6 +2372,7 @@ static hipError_t launch_tile_e(const GemmParams &p, hipStream_t s) {
         if (ks < 1) ks = 1;
     }
     if (p.row_ssq && ks == 1) return hipErrorInvalidValue;            // only the split-K reduce applies a row scale here
+    gemm_plan_set(p, KC_TILE, 0, 0, 0, 0, 0, ks, GC_NONE);
     OPUS_LAUNCH(KC_TILE, (gemm_tile_kernel<EPI>), dim3(ntile * ks), dim3(256), 65536, s, p, tm, tn, ks);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || ks == 1) return e;

@@ -403,6 +403,7 @@ static hipError_t launch_stream_t(const GemmParams &p_in, const StreamPlan &pl, 
         }
     }
     if (pl.ks & (pl.ks - 1)) return hipErrorInvalidValue;               // (the kernel cuts K with a shift)
+    gemm_plan_set(p_in, KC_STREAM, MT, 0, 0, 0, P, pl.ks, pl.ks == 1 ? GC_NONE : combine ? GC_IN_LAUNCH : GC_SLABS);   // (launch_splitk_reduce names its reduce)
     OPUS_LAUNCH(KC_STREAM, (gemm_stream_kernel<MT, P, NT, U, EPI>), dim3(npanels / P, pl.ks), dim3(NT), lds, s, p, pl.ks);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || pl.ks == 1 || p_in.slab_only || combine) return e;

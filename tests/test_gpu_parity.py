@@ -92,10 +92,15 @@ def test_synthetic_fill_matches_numpy_twin(dev):
     # >= 192 tiles of 256 x 256: the ping-pong 256 x 256 x 64 kernel (ragged M/N; 5, 1, 2, 10 K-tiles: prologue / tail paths)
     (4100, 3000, 320, 1, 0, False), (3000, 4100, 64, 0, 1, True), (2600, 5120, 128, 2, 0, False), (3900, 3328, 640, 0, 0, False),
     # more than 256 tiles with a last round at most half full: its tiles are cut into k-parts (tail split) and combined by
-    # pp_tail_reduce_kernel - every epilogue / output type, ragged M and N inside the tail tiles
+    # pp_tail_reduce_kernel where the saved part of a tile time exceeds the cost - the plain and the GELU tuple (5 parts each),
+    # ragged M and N inside the tail tiles.  The other two stay UNSPLIT: (1280, 13312, 1024) has 260 tiles, 4 parts would save
+    # 36 x 0.75 = 27 us against 30 us of slabs + reduce; (4608, 4608, 512) has 8 k-tiles, 2 parts would save 12 us against 22.
+    # (gate / up through pp_tail_reduce_kernel: tests/gemm_cells_ref.py, (3300, 5088, 1280))
     (1300, 11100, 1280, 0, 0, False), (1280, 13312, 1024, 2, 0, False), (2304, 7424, 1280, 1, 0, False), (4608, 4608, 512, 0, 1, True),
     # 384 tiles = 1.5 rounds with a long K: the 128 tail tiles are cut in TWO k-parts, combined inside the launch (the half that
-    # arrives second adds the first one's accumulators and runs the kernel's own epilogue): fp32 + residual, GELU fp16, gate/up
+    # arrives second adds the first one's accumulators and runs the kernel's own epilogue): fp32 + residual, GELU fp16.  The gate / up
+    # tuple has 12 x 64 = 768 tiles, three full rounds and NO tail (the gate / up pair hand-off: tests/gemm_cells_ref.py,
+    # (3072, 8192, 3072) and (3000, 8192, 1536))
     (6144, 4096, 4096, 0, 1, True), (3072, 8192, 3072, 1, 0, False), (3072, 16384, 3072, 2, 0, False),
     # 630 tiles, 118 tail tiles in two k-parts with GELU + fp32 output + residual: the epilogue mode WITHOUT an in-launch pair
     # combine - these tiles must go through pp_tail_reduce_kernel (round-4 advisor finding: the launcher sent them to the pair path
@@ -103,8 +108,12 @@ def test_synthetic_fill_matches_numpy_twin(dev):
     (16000, 2560, 2560, 1, 1, True),
 ])
 def test_gemm_kernels(micro, dev, M, N, K, epi, f32out, resid):
-    """Both GEMM kernels (skinny M<=64, tile M>64), every epilogue, ragged M/N, vs fp64 on fp16 operands."""
+    """The GEMM kernels, every epilogue, ragged M/N, vs fp64 on fp16 operands.  Which kernel, row tile, k-parts and combine step a
+    tuple reaches is asserted: the launchers' report must be what tests/gemm_cells_ref.py restates (every tuple is a case of its
+    table, filed under the cell it fills; tests/test_gpu_gemm_cells.py runs it again on exact inputs in a poisoned layout)."""
     from opus_pllm_amd import _cabi
+    import gemm_cells_checks as cells
+    import gemm_cells_ref as cells_ref
     cfg, model, _ = micro
     g = torch.Generator().manual_seed(M * 7 + N)
     A = (torch.randn(M, K, generator=g) * 0.5).half()
@@ -136,6 +145,8 @@ def test_gemm_kernels(micro, dev, M, N, K, epi, f32out, resid):
                                             None if dR is None else dR.data_ptr(), out.data_ptr(), M, N, K, epi,
                                             1 if f32out else 0, None))
     torch.cuda.synchronize()
+    want = cells_ref.route(M, N, K, epi, cells_ref.F32R if f32out else cells_ref.F16)
+    assert want is not None and cells.report(model._ctx) == want, (cells.report(model._ctx), want)
     err = (out.double().cpu() - acc).abs().max().item()
     assert err <= 2e-3 * acc.abs().max().item() + 1e-5, err
 
@@ -171,9 +182,11 @@ def test_gemm_operand_of_4_gib_takes_64_bit_addressing(micro, dev):
     (64, 28672, 4096, 2), (50, 208, 192, 0), (33, 2048, 512, 2), (60, 4096, 14336, 0),
 ])
 def test_gemm_fused_rmsnorm(micro, dev, M, N, K, epi):
-    """C = epi(rmsnorm(X) W'^T) with X the fp32 residual stream: skinny (M <= 16) and mid (M <= 128) kernels,
-    with and without k-parts."""
+    """C = epi(rmsnorm(X) W'^T) with X the fp32 residual stream: the skinny kernel (M <= 4: the first tuple) and
+    gemm_mid_kernel<2 / 4, ., NORM> (5 .. 64 rows), with and without k-parts; the route is asserted as in test_gemm_kernels."""
     from opus_pllm_amd import _cabi
+    import gemm_cells_checks as cells
+    import gemm_cells_ref as cells_ref
     from opus_pllm_amd.weights import tile_weight
     cfg, model, _ = micro
     g = torch.Generator().manual_seed(M * 13 + N)
@@ -190,6 +203,8 @@ def test_gemm_fused_rmsnorm(micro, dev, M, N, K, epi):
     out = torch.empty(M, nout, dtype=torch.float16, device=dev)
     _cabi.check(_cabi.lib().opus_debug_gemm_norm(model._ctx, dX.data_ptr(), dW.data_ptr(), out.data_ptr(), M, N, K, epi, 0, 1e-5, None))
     torch.cuda.synchronize()
+    want = cells_ref.route(M, N, K, epi, cells_ref.F16, norm=True)
+    assert want is not None and cells.report(model._ctx) == want, (cells.report(model._ctx), want)
     err = (out.double().cpu() - acc).abs().max().item()
     # the kernel rounds h (not h/rms) to fp16: same relative precision, tolerance scaled by the output range
     assert err <= 4e-3 * acc.abs().max().item() + 1e-5, err
@@ -246,8 +261,11 @@ def test_pingpong_gemm_repeats_bit_identically(micro, dev):
     from opus_pllm_amd import _cabi
     from opus_pllm_amd.weights import tile_weight
     cfg, model, _ = micro
-    # (the third shape has 128 tail tiles in two k-parts combined inside the launch: whichever half arrives first, a + b is the same)
-    for (M, N, K, epi) in [(4352, 4352, 1280, 0), (3000, 8192, 448, 2), (6144, 4096, 3072, 0)]:
+    # (the third and the fourth shape have 128 tail tiles in two k-parts combined inside the launch - plain and the gate / up pair
+    #  hand-off: whichever half arrives first, a + b is the same; the second one, with 7 k-tiles, is never split)
+    import gemm_cells_checks as cells
+    import gemm_cells_ref as cells_ref
+    for (M, N, K, epi) in [(4352, 4352, 1280, 0), (3000, 8192, 448, 2), (6144, 4096, 3072, 0), (3000, 8192, 1536, 2)]:
         g = torch.Generator().manual_seed(K)
         A = (torch.randn(M, K, generator=g) * 0.5).half().to(dev)
         W = (torch.randn(N, K, generator=g) / K ** 0.5).half().to(dev)
@@ -260,6 +278,8 @@ def test_pingpong_gemm_repeats_bit_identically(micro, dev):
                                                     epi, 0, None))
             outs.append(out)
         torch.cuda.synchronize()
+        want = cells_ref.route(M, N, K, epi, cells_ref.F16)
+        assert cells.report(model._ctx) == want and (want.combine == cells_ref.PP_PAIR) == (K >= 1536), (cells.report(model._ctx), want)
         assert all(torch.equal(outs[0], o) for o in outs[1:])
         ref = A.double() @ W.double().T
         if epi == 2:
