@@ -460,6 +460,23 @@ int opus_debug_attn_prefill(opus_ctx *ctx, const void *d_Q, const void *d_K, con
 int opus_debug_attn_decode(opus_ctx *ctx, const void *d_qkv, const void *d_k_hist, const void *d_v_hist, const int32_t *d_kstart,
                            int32_t B, int32_t T0, int32_t step, void *d_out, void *d_k_new, void *d_v_new, void *stream);
 
+/* The same single launch in every form opus_llama_decode_step gives attn_decode_kernel.  The input is EITHER d_qkv (as above) OR
+ * the fused form of 4 < B <= 64: d_slabs fp32 [ks, B, (heads + 2 kv) hd], the raw k-part slabs of the QKV GEMM (ks = 1 .. 8), with
+ * d_row_ssq fp32 [B, row_nblk] - the sums of squares of the GEMM's input rows in blocks, over K columns in all -, eps and an
+ * optional d_bias fp32 [(heads + 2 kv) hd]: the kernel itself forms (sum of slabs) * rsqrt(sum(row_ssq[b]) / K + eps) + bias and
+ * rounds it to the operand type before the rotary.  All of them the caller's pointers as they stand.  out_tiled = 1: d_out holds
+ * 16 ceil(B / 16) rows in the fragment order a tiled-A GEMM reads (csrc/common.h tiled_off); rows >= B are not written.
+ * d_k_cache / d_v_cache (optional) [B, kv, max_prompt + max_new_tokens, hd]: layer 0's whole cache after the launch.
+ * *gp_used (HOST) = the query heads per workgroup the launcher chose (1 = one workgroup per head, 2 / 4 / 8 = per kv group);
+ * 0 when nothing was launched.  Errors, all before any device call: OPUS_EBADARG for a null ctx / d_kstart / d_out / gp_used /
+ * history and for both or neither of d_qkv / d_slabs; OPUS_ESHAPE for B, T0, step outside the context, ks outside 1 .. 8,
+ * row_nblk < 1 or K < 1, slabs without d_row_ssq, out_tiled with heads * hd not a multiple of 64. */
+int opus_debug_attn_decode_form(opus_ctx *ctx, const void *d_qkv, const float *d_slabs, int32_t ks, const float *d_row_ssq,
+                                int32_t row_nblk, int32_t K, float eps, const float *d_bias, const void *d_k_hist,
+                                const void *d_v_hist, const int32_t *d_kstart, int32_t B, int32_t T0, int32_t step,
+                                int32_t out_tiled, void *d_out, void *d_k_new, void *d_v_new, void *d_k_cache, void *d_v_cache,
+                                int32_t *gp_used, void *stream);
+
 /* Synchronises `stream` and returns OPUS_EHIP if an in-launch split-K hand-off of this context gave up waiting since the last
  * check (see Conventions; the results of the calls in between are invalid), OPUS_OK otherwise.  opus_generate_* make the same
  * check before they return.  No reference counterpart (torch raises asynchronously on device-side faults). */

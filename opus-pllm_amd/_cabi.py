@@ -109,6 +109,8 @@ SIGNATURES = {
     "opus_debug_knob": (C.c_int, [_P, C.c_char_p, C.c_int32]),
     "opus_stat": (C.c_int64, [_P, C.c_char_p]),
     "opus_debug_attn_decode": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "opus_debug_attn_decode_form": (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_float, _P, _P, _P, _P, C.c_int32,
+                                              C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.POINTER(C.c_int32), _P]),
     "opus_llama_forward": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, C.c_int64, _P]),
     "opus_llama_forward_scratch_bytes": (C.c_int64, [C.POINTER(CConfig), C.c_int32, C.c_int32]),
     "opus_llama_prefix": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_int64), _P]),

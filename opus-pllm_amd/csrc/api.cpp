@@ -2712,6 +2712,63 @@ extern "C" int opus_debug_attn_prefill(opus_ctx *c, const void *Q, const void *K
     return OPUS_OK;
 }
 
+// The input of one debug launch of attn_decode_kernel: finished projections (qkv) or the fused form the decode step takes at
+// 4 < B <= 64 (raw k-part slabs + the sums of squares of the GEMM's input rows + an optional bias), the caller's pointers as they stand
+struct DecodeForm {
+    const void *qkv = nullptr;
+    const float *slabs = nullptr, *row_ssq = nullptr, *bias = nullptr;
+    int ks = 0, row_nblk = 0, K = 0, out_tiled = 0;
+    float eps = 0.f;
+    void *k_cache = nullptr, *v_cache = nullptr;      // (optional) layer 0's whole cache afterwards [B, kv, ctx_cap, hd]
+    int32_t *gp_used = nullptr;                       // (optional, host) query heads per workgroup of the launch
+};
+// the range checks both decode debug entries share (before any device call)
+static int debug_attn_decode_check(opus_ctx *c, const char *who, const void *d_k_hist, const void *d_v_hist, int B, int T0, int step) {
+    const opus_config &g = c->cfg;
+    if (B < 1 || B > g.max_batch || T0 < 1 || T0 > g.max_prompt || step < 0 || step >= g.max_new_tokens)
+        return fail(OPUS_ESHAPE, "%s: B=%d T0=%d step=%d exceed the context (%d, %d, %d)", who, B, T0, step, g.max_batch,
+                    g.max_prompt, g.max_new_tokens);
+    if (T0 + step > 0 && (!d_k_hist || !d_v_hist)) return fail(OPUS_EBADARG, "%s: history is null", who);
+    return OPUS_OK;
+}
+// layer 0 of the cache <- the history, the step word, kstart[] and the rotary rows of the step as the embedding kernel sets them,
+// then ONE launch of attn_decode_kernel with the parameters attn_decode() gives it for this input form
+static int debug_attn_decode_launch(opus_ctx *c, const DecodeForm &f, const void *d_k_hist, const void *d_v_hist, const int32_t *d_kstart,
+                                    int B, int T0, int step, void *d_out, void *d_k_new, void *d_v_new, void *stream) {
+    const opus_config &g = c->cfg;
+    const int L = T0 + step, nkv = g.dec_kv_heads, hd = g.dec_head_dim, ctx_cap = g.max_prompt + g.max_new_tokens;
+    HIPC(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t pitch = (size_t)c->cache_sh * sizeof(half_t);
+    OPC(seed_cache(c, s, d_k_hist, d_v_hist, d_kstart, B, L));
+    OPC(reset_step(c, s, T0, step));
+    // (the embedding kernel with a zero-width row: only its rotary-row part runs)
+    HIPC(launch_embed_tokens(c->d_next, nullptr, B, 0, 1, c->d_xl, nullptr, nullptr, 0, c->cs_dec, c->d_kstart, c->d_step, -1, hd / 2,
+                             c->cs_row, nullptr, 0, s));
+    AttnDecodeParams a;
+    a.qkv = (const half_t *)f.qkv; a.slabs = nullptr; a.ks = 0; a.slab_stride = 0; a.row_ssq = nullptr; a.row_nblk = 0; a.eps = 0.f; a.K = 0;
+    a.bias = nullptr;
+    if (f.slabs) {
+        a.qkv = nullptr; a.slabs = f.slabs; a.ks = f.ks; a.slab_stride = (int64_t)B * (g.dec_heads + 2 * nkv) * hd;
+        a.row_ssq = f.row_ssq; a.row_nblk = f.row_nblk; a.eps = f.eps; a.K = f.K; a.bias = f.bias;
+    }
+    a.cs_row = c->cs_row; a.kstart = c->d_kstart; a.step = c->d_step; a.T0 = -1; a.nh = g.dec_heads; a.nkv = nkv;
+    a.kc = c->kc; a.vc = c->vc; a.cache_sb = c->cache_sb; a.cache_sh = c->cache_sh;
+    a.ctx_cap = ctx_cap; a.scale = 1.0f / sqrtf((float)hd); a.out = (half_t *)d_out; a.out_tiled = f.out_tiled;
+    c->phase = PH_DECODE;
+    KL(KC_ATTN_DECODE, 4.0 * B * nkv * hd * (L + 1), launch_attn_decode(a, B, hd, s));
+    if (f.gp_used) *f.gp_used = attn_decode_group(B, g.dec_heads, nkv);
+    const size_t one = (size_t)hd * sizeof(half_t);
+    if (d_k_new) HIPC(hipMemcpy2DAsync(d_k_new, one, c->kc + (size_t)L * hd, pitch, one, (size_t)B * nkv, hipMemcpyDeviceToDevice, s));
+    if (d_v_new) HIPC(hipMemcpy2DAsync(d_v_new, one, c->vc + (size_t)L * hd, pitch, one, (size_t)B * nkv, hipMemcpyDeviceToDevice, s));
+    const size_t all = (size_t)ctx_cap * hd * sizeof(half_t);
+    if (f.k_cache) HIPC(hipMemcpy2DAsync(f.k_cache, all, c->kc, pitch, all, (size_t)B * nkv, hipMemcpyDeviceToDevice, s));
+    if (f.v_cache) HIPC(hipMemcpy2DAsync(f.v_cache, all, c->vc, pitch, all, (size_t)B * nkv, hipMemcpyDeviceToDevice, s));
+    c->prefilled = false;                                     // (the cache no longer belongs to a prefill)
+    new_epoch(c);
+    return OPUS_OK;
+}
+
 // attn_decode_kernel exactly as decode_step() launches it (finished fp16 projections in, no k-part slabs), on layer 0 of this
 // context's KV cache: the history d_k_hist / d_v_hist fp16 [B, kv heads, L, hd] (keys already rotated, as the cache holds them)
 // is copied into slots 0 .. L-1 (L = T0 + step), the step word, kstart[] and the rotary rows of the step are set as the
@@ -2722,34 +2779,42 @@ extern "C" int opus_debug_attn_decode(opus_ctx *c, const void *d_qkv, const void
                                       const int32_t *d_kstart, int32_t B, int32_t T0, int32_t step, void *d_out, void *d_k_new,
                                       void *d_v_new, void *stream) {
     if (!c || !d_qkv || !d_kstart || !d_out) return fail(OPUS_EBADARG, "debug_attn_decode: null pointer");
-    const opus_config &g = c->cfg;
-    const int L = T0 + step, nkv = g.dec_kv_heads, hd = g.dec_head_dim;
-    if (B < 1 || B > g.max_batch || T0 < 1 || T0 > g.max_prompt || step < 0 || step >= g.max_new_tokens)
-        return fail(OPUS_ESHAPE, "debug_attn_decode: B=%d T0=%d step=%d exceed the context (%d, %d, %d)", B, T0, step, g.max_batch,
-                    g.max_prompt, g.max_new_tokens);
-    if (L > 0 && (!d_k_hist || !d_v_hist)) return fail(OPUS_EBADARG, "debug_attn_decode: history is null");
-    HIPC(hipSetDevice(c->device));
-    hipStream_t s = (hipStream_t)stream;
-    const size_t pitch = (size_t)c->cache_sh * sizeof(half_t);
-    OPC(seed_cache(c, s, d_k_hist, d_v_hist, d_kstart, B, L));
-    OPC(reset_step(c, s, T0, step));
-    // (the embedding kernel with a zero-width row: only its rotary-row part runs)
-    HIPC(launch_embed_tokens(c->d_next, nullptr, B, 0, 1, c->d_xl, nullptr, nullptr, 0, c->cs_dec, c->d_kstart, c->d_step, -1, hd / 2,
-                             c->cs_row, nullptr, 0, s));
-    AttnDecodeParams a;
-    a.qkv = (const half_t *)d_qkv; a.slabs = nullptr; a.ks = 0; a.slab_stride = 0; a.row_ssq = nullptr; a.row_nblk = 0; a.eps = 0.f; a.K = 0;
-    a.bias = nullptr;
-    a.cs_row = c->cs_row; a.kstart = c->d_kstart; a.step = c->d_step; a.T0 = -1; a.nh = g.dec_heads; a.nkv = nkv;
-    a.kc = c->kc; a.vc = c->vc; a.cache_sb = c->cache_sb; a.cache_sh = c->cache_sh;
-    a.ctx_cap = g.max_prompt + g.max_new_tokens; a.scale = 1.0f / sqrtf((float)hd); a.out = (half_t *)d_out; a.out_tiled = 0;
-    c->phase = PH_DECODE;
-    KL(KC_ATTN_DECODE, 4.0 * B * nkv * hd * (L + 1), launch_attn_decode(a, B, hd, s));
-    const size_t one = (size_t)hd * sizeof(half_t);
-    if (d_k_new) HIPC(hipMemcpy2DAsync(d_k_new, one, c->kc + (size_t)L * hd, pitch, one, (size_t)B * nkv, hipMemcpyDeviceToDevice, s));
-    if (d_v_new) HIPC(hipMemcpy2DAsync(d_v_new, one, c->vc + (size_t)L * hd, pitch, one, (size_t)B * nkv, hipMemcpyDeviceToDevice, s));
-    c->prefilled = false;                                     // (the cache no longer belongs to a prefill)
-    new_epoch(c);
-    return OPUS_OK;
+    OPC(debug_attn_decode_check(c, "debug_attn_decode", d_k_hist, d_v_hist, B, T0, step));
+    DecodeForm f;
+    f.qkv = d_qkv;
+    return debug_attn_decode_launch(c, f, d_k_hist, d_v_hist, d_kstart, B, T0, step, d_out, d_k_new, d_v_new, stream);
+}
+
+// The same launch in every form the product takes (tests/test_gpu_attn_decode.py): the input either finished projections
+// (d_qkv) or, as decode_step() at 4 < B <= 64, d_slabs fp32 [ks, B, (heads + 2 kv) hd] raw k-part slabs with d_row_ssq fp32
+// [B, row_nblk] (the sums of squares of the GEMM's input rows over K columns), eps and an optional d_bias fp32 - summed, scaled
+// by rsqrt(sum / K + eps), biased and rounded by the attention kernel itself; the output row-major or fragment-ordered
+// (out_tiled: 16 ceil(B / 16) rows at tiled_off).  d_k_cache / d_v_cache (optional) [B, kv heads, max_prompt + max_new_tokens,
+// hd]: layer 0's cache after the launch.  *gp_used (HOST) = the query heads per workgroup the launcher took, 0 when nothing
+// was launched.  Every refusal comes before the first device call.
+extern "C" int opus_debug_attn_decode_form(opus_ctx *c, const void *d_qkv, const float *d_slabs, int32_t ks, const float *d_row_ssq,
+                                           int32_t row_nblk, int32_t K, float eps, const float *d_bias, const void *d_k_hist,
+                                           const void *d_v_hist, const int32_t *d_kstart, int32_t B, int32_t T0, int32_t step,
+                                           int32_t out_tiled, void *d_out, void *d_k_new, void *d_v_new, void *d_k_cache,
+                                           void *d_v_cache, int32_t *gp_used, void *stream) {
+    if (gp_used) *gp_used = 0;
+    if (!c || !d_kstart || !d_out || !gp_used) return fail(OPUS_EBADARG, "debug_attn_decode_form: null pointer");
+    if ((d_qkv != nullptr) == (d_slabs != nullptr))
+        return fail(OPUS_EBADARG, "debug_attn_decode_form: exactly one of d_qkv and d_slabs must be given");
+    OPC(debug_attn_decode_check(c, "debug_attn_decode_form", d_k_hist, d_v_hist, B, T0, step));
+    if (d_slabs) {
+        if (ks < 1 || ks > 8) return fail(OPUS_ESHAPE, "debug_attn_decode_form: ks=%d outside 1 .. 8", ks);
+        if (row_nblk < 1 || K < 1) return fail(OPUS_ESHAPE, "debug_attn_decode_form: row_nblk=%d K=%d must be positive", row_nblk, K);
+        if (!d_row_ssq) return fail(OPUS_ESHAPE, "debug_attn_decode_form: slabs come with the rows' sums of squares (d_row_ssq)");
+    }
+    if (out_tiled && (int64_t)c->cfg.dec_heads * c->cfg.dec_head_dim % 64)
+        return fail(OPUS_ESHAPE, "debug_attn_decode_form: out_tiled needs heads * head_dim = %d to be a multiple of 64",
+                    c->cfg.dec_heads * c->cfg.dec_head_dim);
+    DecodeForm f;
+    f.qkv = d_qkv; f.slabs = d_slabs; f.row_ssq = d_row_ssq; f.bias = d_slabs ? d_bias : nullptr;
+    f.ks = ks; f.row_nblk = row_nblk; f.K = K; f.eps = eps; f.out_tiled = out_tiled ? 1 : 0;
+    f.k_cache = d_k_cache; f.v_cache = d_v_cache; f.gp_used = gp_used;
+    return debug_attn_decode_launch(c, f, d_k_hist, d_v_hist, d_kstart, B, T0, step, d_out, d_k_new, d_v_new, stream);
 }
 
 // Run-time tuning knobs (A/B aids of the benchmarks and tests; process-wide): "no_stream", "pp_gm", "misc0" .. "misc7".

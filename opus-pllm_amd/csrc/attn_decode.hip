@@ -451,14 +451,18 @@ static hipError_t launch_t(const AttnDecodeParams &p, int B, hipStream_t s) {
     return hipGetLastError();
 }
 
+// query heads per workgroup for a launch of B rows (1, or the group size 2 / 4 / 8): the grouped form only when the per-head
+// form would already fill the chip several times over; a group size without a grouped instance stays per-head
+int attn_decode_group(int B, int nh, int nkv) {
+    const int G = nh / nkv;
+    static const int group_min = getenv("OPUS_ATTN_GROUP_MIN") ? atoi(getenv("OPUS_ATTN_GROUP_MIN")) : 256;   // tuning aid
+    const bool grouped = G > 1 && (int64_t)B * nkv >= group_min;
+    return grouped && (G == 2 || G == 4 || G == 8) ? G : 1;
+}
+
 template <int HD>
 static hipError_t launch_hd(const AttnDecodeParams &p, int B, hipStream_t s) {
-    const int G = p.nh / p.nkv;
-    // grouped form only when the per-head form would already fill the chip several times over
-    static const int group_min = getenv("OPUS_ATTN_GROUP_MIN") ? atoi(getenv("OPUS_ATTN_GROUP_MIN")) : 256;   // tuning aid
-    const bool grouped = G > 1 && (int64_t)B * p.nkv >= group_min;
-    if (!grouped) return launch_t<HD, 1>(p, B, s);
-    switch (G) {
+    switch (attn_decode_group(B, p.nh, p.nkv)) {
         case 2: return launch_t<HD, 2>(p, B, s);
         case 4: return launch_t<HD, 4>(p, B, s);
         case 8: return launch_t<HD, 8>(p, B, s);

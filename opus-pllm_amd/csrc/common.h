@@ -509,6 +509,7 @@ struct AttnDecodeParams {
     long long *trace = nullptr; // tuning aid (OPUS_ATTN_TRACE): 8 wall-clock stamps per workgroup
 };
 hipError_t launch_attn_decode(const AttnDecodeParams &p, int B, int hd, hipStream_t s);
+int attn_decode_group(int B, int nh, int nkv);   // the GP (query heads per workgroup) launch_attn_decode takes: 1, 2, 4 or 8
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
