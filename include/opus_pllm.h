@@ -157,6 +157,15 @@ int opus_splice_pad(opus_ctx *ctx, const int64_t *d_ids, const uint8_t *d_mask, 
  * fills the context's KV cache and resets its step counter. */
 int opus_llama_prefill(opus_ctx *ctx, const void *d_embeds, const uint8_t *d_mask, int32_t B, int32_t T,
                        float *d_last_logits, void *stream);
+/* opus_llama_prefill on B prompts that leaves B nret decoder rows (generate(num_return_sequences=nret): the prompt is prefilled
+ * once, on B rows; B nret <= max_batch, else OPUS_ESHAPE; nret < 1: OPUS_EBADARG).  Afterwards the context is as after a prefill
+ * of every prompt repeated nret times (transformers' _expand_inputs_for_generation, row b nret + j = prompt b): the KV cache rows
+ * b nret + j hold prompt b's keys and values in every layer (the cache append stores them nret times from registers), the
+ * first-slot table and the last-position logits are replicated, and opus_llama_decode_step, opus_last_logits and opus_kv_reorder
+ * work on B nret rows.  The prefill's arithmetic is that of the plain B-row call: the logits of rows b nret + j are bit-identical
+ * to its row b.  d_last_logits (optional) fp32 [B nret, V].  nret == 1: exactly opus_llama_prefill. */
+int opus_llama_prefill_fanout(opus_ctx *ctx, const void *d_embeds, const uint8_t *d_mask, int32_t B, int32_t T, int32_t nret,
+                              float *d_last_logits, void *stream);
 /* Row D3: one decode step for the B rows of the last prefill: tok int32 [B] -> logits fp32 [B,V]. */
 int opus_llama_decode_step(opus_ctx *ctx, const int32_t *d_tok, float *d_logits, void *stream);
 
@@ -308,6 +317,16 @@ int opus_generate_scored(opus_ctx *ctx, const void *d_embeds, const uint8_t *d_m
                          const int32_t *eos_ids, int32_t n_eos, int32_t pad_id, float temperature, float top_p, uint64_t seed,
                          int32_t *d_out_ids, int32_t *n_out, float *d_token_logprobs, float *d_scores, float *d_logits,
                          void *stream);
+/* opus_generate_scored with nret decoder rows per prompt: embeds / mask carry B prompts, prefilled once (opus_llama_prefill_fanout);
+ * the loop, d_out_ids [B nret, max_new] and the outputs ([B nret, max_new], [max_new, B nret, V]) are those of a B nret-row batch,
+ * decoder row r = b nret + j being the j-th sample of prompt b with its draws keyed by (seed, r, step).  EOS ids, the stop
+ * sequence, the logits processors and the token constraint act per decoder row; a constraint with B start states gives row r the
+ * start state r / nret.  The captured step is that of a B nret-row batch (no graph of its own).  nret == 1: exactly
+ * opus_generate_scored. */
+int opus_generate_scored_fanout(opus_ctx *ctx, const void *d_embeds, const uint8_t *d_mask, int32_t B, int32_t T, int32_t nret,
+                                int32_t max_new, const int32_t *eos_ids, int32_t n_eos, int32_t pad_id, float temperature,
+                                float top_p, uint64_t seed, int32_t *d_out_ids, int32_t *n_out, float *d_token_logprobs,
+                                float *d_scores, float *d_logits, void *stream);
 /* Diagnostic: opus_generate_scored's fused arg-max / log-sum-exp pass on fp32 logits [B, V] (B <= max_batch, any V >= 1; rows
  * need no alignment): d_idx [B] the arg-max (lowest index among ties, bitwise what the greedy step picks), d_lse [B]. */
 int opus_debug_argmax_lse(opus_ctx *ctx, const float *d_logits, int32_t B, int32_t V, int32_t *d_idx, float *d_lse, void *stream);
@@ -347,7 +366,8 @@ int opus_debug_logits_process(opus_ctx *ctx, float *d_logits, int32_t B, int32_t
  *   n_states + 1 offsets from 0 to n_edges) and moves to edge_next[e] on edge e; a state with completing[s] != 0 allows the
  *   n_end end ids (1 to 64) too.  State 0 is the end state (no edges, completing): a row goes there on an end id and on any id
  *   its state did not allow (a finished row's pads), and may then only emit end ids.  Every other state allows something.
- *   start: n_start = 1 (every row starts there) or one start state per row (n_start = the batch of the generate calls).
+ *   start: n_start = 1 (every row starts there) or one start state per row (n_start = the batch of the generate calls; with
+ *     opus_generate_scored_fanout: one per PROMPT, decoder row r starting at start[r / nret]).
  * Per step and row the kernel takes one transition on the id generated last (no walk over the history) and stores -inf to every
  * logit outside the allowed set; allowed logits are not touched.  d_scores of opus_generate_scored hold the masked scores,
  * d_logits and d_token_logprobs stay raw.  Only "on / off" is part of the captured step's identity: another table, other start

@@ -14,7 +14,7 @@ per batch row: the best M (opus_beam_topk; `do_sample=False`) or M drawn without
         tokens, src, done = state.step(scores, idx)
         if done: break
         <reorder the KV cache rows by src>; <decode `tokens`>
-    ids = state.result()
+    ids = state.result()                 # or result(N): the N best of every row, [B N, n]
 """
 from __future__ import annotations
 
@@ -94,11 +94,20 @@ class BeamState:
         done = not (bool(self.unsat.any()) and not bool(hits.all()))
         return next_tok, src, done
 
-    def result(self) -> np.ndarray:
-        """int64 [B, n]: the best finished sequence of every batch row, cropped to the longest of them (rows that finished earlier
-        keep the fill value behind their last token), as `_beam_search` returns `sequences`."""
-        n = int(self.seq_len[:, 0].max()) if self.B else 0
-        return self.seq[:, 0, :n].copy()
+    def result(self, num_return_sequences: int = 1) -> np.ndarray:
+        """int64 [B N, n]: the N = num_return_sequences best finished sequences of every batch row, best first (row b N + j: the
+        j-th of batch row b), cropped to the longest of them (rows that finished earlier keep the fill value behind their last
+        token), as `_beam_search` returns `sequences`."""
+        N = self._n_best(num_return_sequences)
+        n = int(self.seq_len[:, :N].max()) if self.B else 0
+        return self.seq[:, :N, :n].reshape(self.B * N, n).copy()
 
-    def result_scores(self) -> np.ndarray:
-        return self.beam_scores[:, 0].copy()
+    def result_scores(self, num_return_sequences: int = 1) -> np.ndarray:
+        """float32 [B N]: `sequences_scores` of result(num_return_sequences)."""
+        return self.beam_scores[:, :self._n_best(num_return_sequences)].reshape(-1).copy()
+
+    def _n_best(self, n: int) -> int:
+        n = int(n)
+        if n < 1 or n > self.K:
+            raise ValueError(f"`num_return_sequences` ({n}) has to lie in 1 .. `num_beams` ({self.K})")
+        return n

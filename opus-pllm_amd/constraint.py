@@ -311,6 +311,14 @@ class PerRowTokenTrie:
     def n_rows(self) -> Optional[int]:
         return len(self.tries)
 
+    def row_trie(self, row: int, num_return_sequences: int = 1) -> TokenTrie:
+        """The trie decoder row `row` follows.  generate(num_return_sequences=N) runs N rows per prompt, row b N + j being the
+        j-th sample of prompt b (transformers' `_expand_inputs_for_generation`): row r follows tries[r // N]."""
+        n = int(num_return_sequences)
+        if n < 1 or not 0 <= int(row) < len(self.tries) * n:
+            raise IndexError(f"row {row} outside the {len(self.tries)} x {n} decoder rows")
+        return self.tries[int(row) // n]
+
 
 def _compile(tries: Sequence[TokenTrie], which: Sequence[int]) -> CompiledConstraint:
     counts, toks, nxts, comp = [0], [], [], [1]           # state 0: the end state

@@ -152,6 +152,7 @@ struct opus_ctx {
     TokenConstraintDesc *d_cons = nullptr;
     int32_t *d_cstate = nullptr, *d_cstep = nullptr;
     int32_t cons_n_start = 0, cons_max_id = -1;
+    int32_t cons_start_div = 1;          // TokenConstraintDesc::start_div as the device descriptor holds it
     // row-scale fusion (GemmParams::xh_out / row_ssq): one-shot request for the next gemm() and its outcome
     half_t *rq_xh = nullptr;
     int rq_done = 0;
@@ -1071,10 +1072,19 @@ extern "C" int opus_splice_pad(opus_ctx *c, const int64_t *d_ids, const uint8_t 
 }
 
 // ------------------------------------------------------------------------------------------------ decoder
-static int lm_head(opus_ctx *c, hipStream_t s, int B) {
+static int lm_head(opus_ctx *c, hipStream_t s, int B, float *out = nullptr) {
     const opus_config &g = c->cfg;   // final RMSNorm (folded weight) fused into the lm_head GEMM
-    return gemm_norm(c, s, c->d_xl, g.dec_rms_eps, c->d_xln, c->lm_head, B, g.dec_vocab, g.dec_dim, EPI_NONE, c->d_logits,
+    return gemm_norm(c, s, c->d_xl, g.dec_rms_eps, c->d_xln, c->lm_head, B, g.dec_vocab, g.dec_dim, EPI_NONE, out ? out : c->d_logits,
                      g.dec_vocab, 1);
+}
+
+// End of a fanned-out prefill (nret > 1): the lm_head left the B prompts' last-position logits in d_probs (free until the sampling
+// head runs); one launch replicates them into d_logits rows b nret + j and kstart[b] into kstart[b nret + j].  The K / V cache rows
+// were replicated by the append itself (launch_dec_rope_cache's nret).
+static int fanout_rows(opus_ctx *c, hipStream_t s, int B, int nret) {
+    const opus_config &g = c->cfg;
+    KL(KC_OTHER, 4.0 * (B + B * nret) * g.dec_vocab, launch_row_fanout(c->d_probs, c->d_logits, g.dec_vocab, B, nret, c->d_kstart, s));
+    return OPUS_OK;
 }
 
 
@@ -1127,7 +1137,7 @@ static int attn_prefix(opus_ctx *c, hipStream_t s, const ContRows &cr, int l, in
 }
 
 static int opt_layer(opus_ctx *c, hipStream_t s, const DecLayer &L, int l, float *x, half_t *xn, int M, int B, int T, bool decode,
-                     const ContRows *cont = nullptr) {
+                     const ContRows *cont = nullptr, int nret = 1) {
     const opus_config &g = c->cfg;
     const int H = g.dec_dim, F = g.dec_ffn, nh = g.dec_heads, nkv = g.dec_kv_heads, hd = g.dec_head_dim;
     const int QKV = (nh + 2 * nkv) * hd, QD = nh * hd;
@@ -1141,7 +1151,7 @@ static int opt_layer(opus_ctx *c, hipStream_t s, const DecLayer &L, int l, float
     } else {
         KL(KC_OTHER, 4.0 * M * QKV,
            launch_dec_rope_cache(c->d_qkv, c->cs_dec, c->d_kstart, B, T, nh, nkv, hd, c->kc + l * c->cache_sl,
-                                 c->vc + l * c->cache_sl, c->cache_sb, c->cache_sh, s));
+                                 c->vc + l * c->cache_sl, c->cache_sb, c->cache_sh, s, nret));
         AttnParams a;
         a.Q = c->d_qkv; a.K = c->d_qkv + QD; a.V = c->d_qkv + QD + nkv * hd;
         a.q_sb = a.k_sb = a.v_sb = (int64_t)T * QKV;
@@ -1164,27 +1174,28 @@ static int opt_layer(opus_ctx *c, hipStream_t s, const DecLayer &L, int l, float
     return OPUS_OK;
 }
 
-static int lm_head_opt(opus_ctx *c, hipStream_t s, int B) {
+static int lm_head_opt(opus_ctx *c, hipStream_t s, int B, float *out = nullptr) {
     const opus_config &g = c->cfg;
     KL(KC_NORM, 6.0 * B * g.dec_dim, launch_layernorm(c->d_xl, c->dec_lnfw, c->dec_lnfb, g.dec_rms_eps, B, g.dec_dim, c->d_xln, nullptr, s));
-    return gemm(c, s, c->d_xln, g.dec_dim, c->lm_head, B, g.dec_vocab, g.dec_dim, nullptr, EPI_NONE, nullptr, c->d_logits,
+    return gemm(c, s, c->d_xln, g.dec_dim, c->lm_head, B, g.dec_vocab, g.dec_dim, nullptr, EPI_NONE, nullptr, out ? out : c->d_logits,
                 g.dec_vocab, 1);
 }
 
 static int prefill_opt(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8_t *mask, int B, int T, bool all_rows,
-                       const ContRows *cont) {
+                       const ContRows *cont, int nret) {
     const opus_config &g = c->cfg;
     const int H = g.dec_dim, M = B * T;
     HIPC(hipMemsetAsync(c->d_cnt, 0, HANDOFF_ERR * sizeof(int32_t), s));
     if (!cont) KL(KC_OTHER, 1.0 * M, launch_mask_to_kstart(mask, B, T, c->d_kstart, s));
     KL(KC_OTHER, 6.0 * M * H, launch_h2f(embeds, c->d_x, (int64_t)M * H, s));
     KL(KC_OTHER, 10.0 * M * H, launch_add_pos(c->d_x, c->dec_pos, cont ? cont->nkst : c->d_kstart, nullptr, 0, B, T, H, g.dec_max_pos + 1, s));
-    for (int l = 0; l < g.dec_layers; ++l) OPC(opt_layer(c, s, c->dec[l], l, c->d_x, c->d_xn, M, B, T, false, cont));
+    for (int l = 0; l < g.dec_layers; ++l) OPC(opt_layer(c, s, c->dec[l], l, c->d_x, c->d_xn, M, B, T, false, cont, nret));
     if (all_rows) return OPUS_OK;
     KL(KC_OTHER, 8.0 * B * H, launch_take_last(c->d_x, B, T, H, c->d_xl, s));
-    OPC(lm_head_opt(c, s, B));
+    OPC(lm_head_opt(c, s, B, nret > 1 ? c->d_probs : nullptr));
+    if (nret > 1) OPC(fanout_rows(c, s, B, nret));
     OPC(reset_step(c, s, T));
-    c->cur_B = B;
+    c->cur_B = B * nret;
     c->cur_T = T;
     c->prefilled = true;
     return OPUS_OK;
@@ -1205,8 +1216,10 @@ static int decode_step_opt(opus_ctx *c, hipStream_t s) {
 // d_x for opus_llama_forward; no lm_head, and the context is left without a prefill (decode_step fails until the next one).
 // cont: the B rows are continuations behind the cached prefix (ContRows; implies all_rows, mask unused): the KV cache, kstart,
 // the step word and the decode state are left as they are.
+// nret > 1 (never with all_rows or cont): the fanned-out prefill - the B prompts run once, and the context is left as after a prefill of
+// every prompt repeated nret times (cur_B = B nret; cache rows, kstart and the last logits of prompt b in rows b nret + j).
 static int prefill(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8_t *mask, int B, int T, bool all_rows = false,
-                   const ContRows *cont = nullptr) {
+                   const ContRows *cont = nullptr, int nret = 1) {
     c->phase = cont ? PH_SCORE : PH_PREFILL;
     if (cont) {
         all_rows = true;
@@ -1217,7 +1230,7 @@ static int prefill(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8
             c->cur_B = 0;
         }
     }
-    if (c->cfg.dec_arch == 1) return prefill_opt(c, s, embeds, mask, B, T, all_rows, cont);
+    if (c->cfg.dec_arch == 1) return prefill_opt(c, s, embeds, mask, B, T, all_rows, cont, nret);
     const opus_config &g = c->cfg;
     const int H = g.dec_dim, F = g.dec_ffn, nh = g.dec_heads, nkv = g.dec_kv_heads, hd = g.dec_head_dim;
     const int QKV = (nh + 2 * nkv) * hd, QD = nh * hd;
@@ -1250,7 +1263,7 @@ static int prefill(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8
         } else {
             KL(KC_OTHER, 4.0 * M * QKV,
                launch_dec_rope_cache(c->d_qkv, c->cs_dec, c->d_kstart, B, T, nh, nkv, hd, c->kc + l * c->cache_sl,
-                                     c->vc + l * c->cache_sl, c->cache_sb, c->cache_sh, s));
+                                     c->vc + l * c->cache_sl, c->cache_sb, c->cache_sh, s, nret));
             AttnParams a;
             a.Q = c->d_qkv; a.K = c->d_qkv + QD; a.V = c->d_qkv + QD + nkv * hd;
             a.q_sb = a.k_sb = a.v_sb = (int64_t)T * QKV;
@@ -1305,9 +1318,10 @@ static int prefill(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8
         KL(KC_OTHER, 8.0 * B * H, launch_take_last(c->d_x, B, T, H, c->d_xl, s));
         c->xh_src = nullptr;
     }
-    OPC(lm_head(c, s, B));
+    OPC(lm_head(c, s, B, nret > 1 ? c->d_probs : nullptr));
+    if (nret > 1) OPC(fanout_rows(c, s, B, nret));
     OPC(reset_step(c, s, T));
-    c->cur_B = B;
+    c->cur_B = B * nret;
     c->cur_T = T;
     c->prefilled = true;
     return OPUS_OK;
@@ -1410,6 +1424,25 @@ extern "C" int opus_llama_prefill(opus_ctx *c, const void *d_embeds, const uint8
     OPC(prefill(c, s, (const half_t *)d_embeds, d_mask, B, T));
     if (d_last_logits)
         HIPC(hipMemcpyAsync(d_last_logits, c->d_logits, (size_t)B * c->cfg.dec_vocab * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return OPUS_OK;
+}
+
+static int check_fanout(opus_ctx *c, int B, int nret, const char *who) {
+    if (nret < 1) return fail(OPUS_EBADARG, "%s: nret=%d (at least 1)", who, nret);
+    if ((int64_t)B * nret > c->cfg.max_batch)
+        return fail(OPUS_ESHAPE, "%s: B x nret = %d x %d decoder rows, the context holds max_batch=%d", who, B, nret, c->cfg.max_batch);
+    return OPUS_OK;
+}
+
+extern "C" int opus_llama_prefill_fanout(opus_ctx *c, const void *d_embeds, const uint8_t *d_mask, int32_t B, int32_t T, int32_t nret,
+                                         float *d_last_logits, void *stream) {
+    OPC(need_ready(c));
+    OPC(check_prefill_args(c, d_embeds, d_mask, B, T));
+    OPC(check_fanout(c, B, nret, "prefill_fanout"));
+    hipStream_t s = (hipStream_t)stream;
+    OPC(prefill(c, s, (const half_t *)d_embeds, d_mask, B, T, false, nullptr, nret));
+    if (d_last_logits)
+        HIPC(hipMemcpyAsync(d_last_logits, c->d_logits, (size_t)B * nret * c->cfg.dec_vocab * sizeof(float), hipMemcpyDeviceToDevice, s));
     return OPUS_OK;
 }
 
@@ -2047,14 +2080,25 @@ static int greedy_body(opus_ctx *c, hipStream_t s, int max_new, int n_eos, int p
     return decode_step(c, s, c->d_next);
 }
 
+// TokenConstraintDesc::start_div of the device descriptor (uploaded only when it changes: the plain call launches nothing here)
+static int set_cons_start_div(opus_ctx *c, int32_t div, hipStream_t s) {
+    if (div == c->cons_start_div) return OPUS_OK;
+    int32_t *w = reinterpret_cast<int32_t *>(c->d_cons) + offsetof(TokenConstraintDesc, start_div) / sizeof(int32_t);
+    HIPC(launch_upload_i32(&div, 1, w, s));
+    c->cons_start_div = div;
+    return OPUS_OK;
+}
+
 static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mask, int32_t B, int32_t T, int32_t max_new,
                          const int32_t *eos_ids, int32_t n_eos, int32_t pad_id, float temperature, float top_p, uint64_t seed,
-                         int32_t *d_out_ids, int32_t *n_out, void *stream, const GenOutDesc *outs = nullptr) {
+                         int32_t *d_out_ids, int32_t *n_out, void *stream, const GenOutDesc *outs = nullptr, int32_t nret = 1) {
     OPC(need_ready(c));
     if (temperature < 0.f || top_p <= 0.f || top_p > 1.f) return fail(OPUS_EBADARG, "generate: temperature >= 0 and 0 < top_p <= 1");
     c->samp_temp = temperature;
     c->samp_top_p = top_p;
     OPC(check_prefill_args(c, d_embeds, d_mask, B, T));
+    OPC(check_fanout(c, B, nret, "generate"));
+    const int32_t BN = B * nret;             // decoder rows: the loop, its buffers and the captured step are those of a BN-row batch
     if (!d_out_ids || !n_out) return fail(OPUS_EBADARG, "generate_greedy: null pointer");
     if (max_new < 1 || max_new > c->cfg.max_new_tokens)
         return fail(OPUS_ESHAPE, "generate_greedy: max_new=%d exceeds max_new_tokens=%d", max_new, c->cfg.max_new_tokens);
@@ -2074,6 +2118,7 @@ static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mas
     }
     if (c->cons_on && c->cons_n_start != 1 && c->cons_n_start != B)
         return fail(OPUS_ESHAPE, "generate: the token constraint has %d per-row start states, the batch %d rows", c->cons_n_start, B);
+    if (c->cons_on) OPC(set_cons_start_div(c, nret, s));    // one start state per prompt: decoder row r starts at start[r / nret]
     if (c->lproc_on || c->cons_on) {
         if (c->lproc_on && max_new > LP_MAX_HIST)
             return fail(OPUS_ESHAPE, "generate: logits processors keep a history of at most %d ids (max_new=%d)", LP_MAX_HIST, max_new);
@@ -2084,9 +2129,9 @@ static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mas
             OPC(upload_gen_desc(GenOutDesc{outs->token_lp, outs->scores, nullptr, nullptr}, c->d_gen_proc, s));
         }
     }
-    HIPC(hipMemsetAsync(c->d_fin, 0, B * sizeof(int32_t), s));
+    HIPC(hipMemsetAsync(c->d_fin, 0, BN * sizeof(int32_t), s));
     HIPC(hipMemsetAsync(c->d_nunf, 0, (size_t)max_new * sizeof(int32_t), s));
-    OPC(prefill(c, s, (const half_t *)d_embeds, d_mask, B, T));
+    OPC(prefill(c, s, (const half_t *)d_embeds, d_mask, B, T, false, nullptr, nret));
     c->gen_outs = gen_outs;              // (the prefill's own launches are the same either way)
     struct GenOutsReset { opus_ctx *c; ~GenOutsReset() { c->gen_outs = 0; } } gen_outs_reset{c};
 
@@ -2094,7 +2139,7 @@ static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mas
     const bool use_graph = s != nullptr && !c->timing && !getenv("OPUS_NO_GRAPH");
     auto find_graph = [&]() -> opus_ctx::GraphEntry * {
         for (auto &e : c->graphs)
-            if (e.exec && e.B == B && e.maxnew == max_new && e.pad == pad_id && e.neos == n_eos && e.out == d_out_ids &&
+            if (e.exec && e.B == BN && e.maxnew == max_new && e.pad == pad_id && e.neos == n_eos && e.out == d_out_ids &&
                 e.temp == temperature && e.top_p == top_p && e.outs == gen_outs && e.lproc == c->lproc_on && e.cons == c->cons_on) return &e;
         return nullptr;
     };
@@ -2124,7 +2169,7 @@ static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mas
                 (void)hipGraphDestroy(graph);
                 if (ee != hipSuccess) return fail(OPUS_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(ee));
                 ++c->graph_instantiations;
-                e.B = B; e.maxnew = max_new; e.pad = pad_id; e.neos = n_eos; e.temp = temperature; e.top_p = top_p; e.out = d_out_ids;
+                e.B = BN; e.maxnew = max_new; e.pad = pad_id; e.neos = n_eos; e.temp = temperature; e.top_p = top_p; e.out = d_out_ids;
                 e.outs = gen_outs;
                 e.lproc = c->lproc_on;
                 e.cons = c->cons_on;
@@ -2322,10 +2367,12 @@ extern "C" int opus_set_token_constraint(opus_ctx *c, int32_t n_states, const in
     h.start = reinterpret_cast<const int32_t *>(t + o_sta);
     h.state = c->d_cstate;
     h.n_states = n_states; h.n_end = n_end; h.n_start = n_start; h.state_stride = c->cfg.max_batch;
+    h.start_div = 1;
     HIPC(launch_upload_i32(reinterpret_cast<const int32_t *>(&h), (int)(sizeof(h) / sizeof(int32_t)),
                            reinterpret_cast<int32_t *>(c->d_cons), s));
     HIPC(hipStreamSynchronize(s));           // the host arrays are the caller's again
     c->cons_n_start = n_start;
+    c->cons_start_div = 1;
     c->cons_max_id = max_id;
     c->cons_on = true;
     return OPUS_OK;
@@ -2348,6 +2395,7 @@ extern "C" int opus_debug_token_constraint(opus_ctx *c, float *d_logits, int32_t
     HIPC(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     c->phase = PH_OTHER;
+    OPC(set_cons_start_div(c, 1, s));
     for (int32_t t = 0; t < hist_len; ++t) {
         HIPC(launch_upload_i32(&t, 1, c->d_cstep, s));
         HIPC(launch_token_constraint(nullptr, B, V, d_hist, hist_stride, c->d_cstep, hist_len, c->d_cons, s));
@@ -2387,6 +2435,20 @@ extern "C" int opus_generate_scored(opus_ctx *c, const void *d_embeds, const uin
     const GenOutDesc outs{d_token_logprobs, d_scores, d_logits, nullptr};
     return generate_impl(c, d_embeds, d_mask, B, T, max_new, eos_ids, n_eos, pad_id, temperature, temperature > 0.f ? top_p : 1.f,
                          temperature > 0.f ? seed : 0, d_out_ids, n_out, stream, &outs);
+}
+
+/* opus_generate_scored on B prompts with nret decoder rows each: one prefill of the B prompts (opus_llama_prefill_fanout), then the
+   loop of a B nret-row batch - decoder row r = b nret + j is the j-th sample of prompt b, its draws keyed by (seed, r, step).  The
+   ids and the outputs are sized by B nret rows.  nret == 1: exactly opus_generate_scored. */
+extern "C" int opus_generate_scored_fanout(opus_ctx *c, const void *d_embeds, const uint8_t *d_mask, int32_t B, int32_t T, int32_t nret,
+                                           int32_t max_new, const int32_t *eos_ids, int32_t n_eos, int32_t pad_id, float temperature,
+                                           float top_p, uint64_t seed, int32_t *d_out_ids, int32_t *n_out, float *d_token_logprobs,
+                                           float *d_scores, float *d_logits, void *stream) {
+    if (!c) return fail(OPUS_EBADARG, "ctx is null");
+    if (!(temperature >= 0.f)) return fail(OPUS_EBADARG, "generate_scored_fanout: temperature must be >= 0 (0 = greedy)");
+    const GenOutDesc outs{d_token_logprobs, d_scores, d_logits, nullptr};
+    return generate_impl(c, d_embeds, d_mask, B, T, max_new, eos_ids, n_eos, pad_id, temperature, temperature > 0.f ? top_p : 1.f,
+                         temperature > 0.f ? seed : 0, d_out_ids, n_out, stream, &outs, nret);
 }
 
 /* Diagnostic: the fused arg-max / log-sum-exp pass of opus_generate_scored on fp32 logits [B, V] (B <= max_batch, any V >= 1):

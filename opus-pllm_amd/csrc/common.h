@@ -349,7 +349,9 @@ hipError_t launch_esm_rope(half_t *qkv, const float *cs, int B, int T, int heads
                            hipStream_t s, const int32_t *pos = nullptr);   // pos: per-row positions (packed batches; B * T rows)
 hipError_t launch_dec_rope_cache(half_t *qkv, const float *cs, const int32_t *kstart, int B, int T, int nh,
                                  int nkv, int hd, half_t *kc, half_t *vc, int64_t cache_sb, int64_t cache_sh,
-                                 hipStream_t s);
+                                 hipStream_t s, int nret = 1);   // nret > 1: prompt b's K / V to the cache rows b nret + j, j < nret
+// dst[b nret + j] = src[b] (fp32 rows of width V, src != dst) and kstart[0 .. B) -> kstart[b nret + j] in place (staged in LDS)
+hipError_t launch_row_fanout(const float *src, float *dst, int V, int B, int nret, int32_t *kstart, hipStream_t s);
 hipError_t launch_h2f(const half_t *in, float *out, int64_t n, hipStream_t s);
 // x[b,:] = fp32(emb[tok[b]]); optionally also the fp16 copy xh and the per-256-column sums of squares ssq[b][H/256] (the
 // producer side of the row-scale RMSNorm fusion, GemmParams::row_ssq)
@@ -466,6 +468,7 @@ struct TokenConstraintDesc {
     const int32_t *start;              // [n_start] start state of every row (n_start == 1: shared)
     int32_t *state;                    // [2, state_stride] the rows' states, double-buffered by the parity of the step
     int32_t n_states, n_end, n_start, state_stride;
+    int32_t start_div, unused;         // row b starts at start[b / start_div] (the fanned-out generate: one start state per prompt)
 };
 // in place on logits [B, V] (row stride V): one transition per row on hist[b * ld + *step - 1] (the start state at *step == 0),
 // then -inf outside the state's allowed set.  logits == nullptr: the transition only.

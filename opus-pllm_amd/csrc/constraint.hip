@@ -41,7 +41,7 @@ __global__ __launch_bounds__(TC_THREADS) void token_constraint_kernel(float *__r
         t = t < 0 ? 0 : (t > max_hist ? max_hist : t);
         int s;
         if (t == 0) {
-            s = d.start[d.n_start > 1 ? b : 0];
+            s = d.start[d.n_start > 1 ? b / d.start_div : 0];
         } else {
             int cur = d.state[((t - 1) & 1) * d.state_stride + b];
             if ((unsigned)cur >= (unsigned)d.n_states) cur = 0;

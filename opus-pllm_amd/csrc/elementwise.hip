@@ -114,10 +114,13 @@ hipError_t launch_esm_rope(half_t *qkv, const float *cs, int B, int T, int heads
 // on the fused [B*T, (nh+2nkv)*hd] buffer, then K and V appended to the cache [b][kvh][slot t][hd].
 // kc == nullptr: rotary only, no cache write (continuation rows of opus_llama_score_continuations, whose kstart[b] is the prefix
 // row's first slot minus its length: positions Tp - kstart[p] + t).
-__global__ __launch_bounds__(256) void dec_rope_cache_kernel(half_t *__restrict__ qkv, const float *__restrict__ cs,
-                                                             const int32_t *__restrict__ kstart, int T, int nh, int nkv,
-                                                             int hd, half_t *__restrict__ kc, half_t *__restrict__ vc,
-                                                             int64_t cache_sb, int64_t cache_sh, int64_t total) {
+// FAN (the fanned-out prefill of opus_llama_prefill_fanout): prompt b's rotated K and its V, held in registers, go to the nret cache
+// rows b nret + j instead of row b - no second read, no temporary; without FAN the body is the plain append.
+template <bool FAN>
+__device__ __forceinline__ void dec_rope_cache_body(half_t *__restrict__ qkv, const float *__restrict__ cs,
+                                                    const int32_t *__restrict__ kstart, int T, int nh, int nkv, int hd,
+                                                    half_t *__restrict__ kc, half_t *__restrict__ vc, int64_t cache_sb,
+                                                    int64_t cache_sh, int64_t total, int nret) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const int half = hd >> 1, vph = half >> 3;
@@ -133,22 +136,54 @@ __global__ __launch_bounds__(256) void dec_rope_cache_kernel(half_t *__restrict_
     rope8(base, half, cs + ((int64_t)pos * half + v * 8) * 2, 1.0f);
     if (hh >= nh && kc) {
         const int kh = hh - nh;
-        half_t *kd = kc + b * cache_sb + kh * cache_sh + (int64_t)t * hd + v * 8;
-        half_t *vd = vc + b * cache_sb + kh * cache_sh + (int64_t)t * hd + v * 8;
         const half_t *vs = base + (int64_t)nkv * hd;
-        *reinterpret_cast<h8 *>(kd) = *reinterpret_cast<h8 *>(base);
-        *reinterpret_cast<h8 *>(kd + half) = *reinterpret_cast<h8 *>(base + half);
-        *reinterpret_cast<h8 *>(vd) = *reinterpret_cast<const h8 *>(vs);
-        *reinterpret_cast<h8 *>(vd + half) = *reinterpret_cast<const h8 *>(vs + half);
+        if constexpr (!FAN) {
+            half_t *kd = kc + b * cache_sb + kh * cache_sh + (int64_t)t * hd + v * 8;
+            half_t *vd = vc + b * cache_sb + kh * cache_sh + (int64_t)t * hd + v * 8;
+            *reinterpret_cast<h8 *>(kd) = *reinterpret_cast<h8 *>(base);
+            *reinterpret_cast<h8 *>(kd + half) = *reinterpret_cast<h8 *>(base + half);
+            *reinterpret_cast<h8 *>(vd) = *reinterpret_cast<const h8 *>(vs);
+            *reinterpret_cast<h8 *>(vd + half) = *reinterpret_cast<const h8 *>(vs + half);
+        } else {
+            const h8 k0 = *reinterpret_cast<h8 *>(base), k1 = *reinterpret_cast<h8 *>(base + half);
+            const h8 v0 = *reinterpret_cast<const h8 *>(vs), v1 = *reinterpret_cast<const h8 *>(vs + half);
+            const int64_t off = kh * cache_sh + (int64_t)t * hd + v * 8;
+            for (int j = 0; j < nret; ++j) {
+                const int64_t o = ((int64_t)b * nret + j) * cache_sb + off;
+                *reinterpret_cast<h8 *>(kc + o) = k0;
+                *reinterpret_cast<h8 *>(kc + o + half) = k1;
+                *reinterpret_cast<h8 *>(vc + o) = v0;
+                *reinterpret_cast<h8 *>(vc + o + half) = v1;
+            }
+        }
     }
 }
 
+__global__ __launch_bounds__(256) void dec_rope_cache_kernel(half_t *__restrict__ qkv, const float *__restrict__ cs,
+                                                             const int32_t *__restrict__ kstart, int T, int nh, int nkv,
+                                                             int hd, half_t *__restrict__ kc, half_t *__restrict__ vc,
+                                                             int64_t cache_sb, int64_t cache_sh, int64_t total) {
+    dec_rope_cache_body<false>(qkv, cs, kstart, T, nh, nkv, hd, kc, vc, cache_sb, cache_sh, total, 1);
+}
+
+__global__ __launch_bounds__(256) void dec_rope_cache_fan_kernel(half_t *__restrict__ qkv, const float *__restrict__ cs,
+                                                                 const int32_t *__restrict__ kstart, int T, int nh, int nkv,
+                                                                 int hd, half_t *__restrict__ kc, half_t *__restrict__ vc,
+                                                                 int64_t cache_sb, int64_t cache_sh, int64_t total, int nret) {
+    dec_rope_cache_body<true>(qkv, cs, kstart, T, nh, nkv, hd, kc, vc, cache_sb, cache_sh, total, nret);
+}
+
+// nret > 1: the B prompts' K / V land in the cache rows b nret .. b nret + nret - 1 (the caller checks B nret <= the cache's rows)
 hipError_t launch_dec_rope_cache(half_t *qkv, const float *cs, const int32_t *kstart, int B, int T, int nh, int nkv,
-                                 int hd, half_t *kc, half_t *vc, int64_t cache_sb, int64_t cache_sh, hipStream_t s) {
+                                 int hd, half_t *kc, half_t *vc, int64_t cache_sb, int64_t cache_sh, hipStream_t s, int nret) {
     if (hd & 15) return hipErrorInvalidValue;
     const int64_t total = (int64_t)B * T * (nh + nkv) * (hd >> 4);
-    hipLaunchKernelGGL(dec_rope_cache_kernel, dim3(cdiv(total, 256)), dim3(256), 0, s, qkv, cs, kstart, T, nh, nkv, hd,
-                       kc, vc, cache_sb, cache_sh, total);
+    if (nret > 1 && kc)
+        hipLaunchKernelGGL(dec_rope_cache_fan_kernel, dim3(cdiv(total, 256)), dim3(256), 0, s, qkv, cs, kstart, T, nh, nkv, hd,
+                           kc, vc, cache_sb, cache_sh, total, nret);
+    else
+        hipLaunchKernelGGL(dec_rope_cache_kernel, dim3(cdiv(total, 256)), dim3(256), 0, s, qkv, cs, kstart, T, nh, nkv, hd,
+                           kc, vc, cache_sb, cache_sh, total);
     return hipGetLastError();
 }
 
@@ -1163,6 +1198,37 @@ __global__ void mask_to_kstart_kernel(const uint8_t *__restrict__ mask, int B, i
 }
 hipError_t launch_mask_to_kstart(const uint8_t *mask, int B, int T, int32_t *kstart, hipStream_t s) {
     hipLaunchKernelGGL(mask_to_kstart_kernel, dim3(cdiv(B, 64)), dim3(64), 0, s, mask, B, T, kstart);
+    return hipGetLastError();
+}
+
+// Row fan-out behind the fanned-out prefill: dst[b nret + j] = src[b] for fp32 rows of width V (the last-position logits; src and
+// dst are different buffers, so no prompt's source row is overwritten by an earlier prompt's replicas), and kstart[0 .. B) ->
+// kstart[b nret + j] IN PLACE by the one extra workgroup, which stages the B values in LDS before it writes any.
+__global__ __launch_bounds__(256) void row_fanout_kernel(const float *__restrict__ src, float *__restrict__ dst, int V, int B,
+                                                         int nret, int32_t *kstart) {
+    extern __shared__ int32_t s_kst[];
+    const int r = blockIdx.y, tid = threadIdx.x;
+    if (r == B * nret) {
+        if (blockIdx.x != 0) return;
+        for (int b = tid; b < B; b += 256) s_kst[b] = kstart[b];
+        __syncthreads();
+        for (int q = tid; q < B * nret; q += 256) kstart[q] = s_kst[q / nret];
+        return;
+    }
+    const float *in = src + (int64_t)(r / nret) * V;
+    float *out = dst + (int64_t)r * V;
+    if ((V & 3) == 0) {                                  // (both buffers are 16-byte aligned: rows stay so when V % 4 == 0)
+        for (int i = blockIdx.x * 256 + tid; i < (V >> 2); i += gridDim.x * 256)
+            reinterpret_cast<float4 *>(out)[i] = reinterpret_cast<const float4 *>(in)[i];
+    } else {
+        for (int i = blockIdx.x * 256 + tid; i < V; i += gridDim.x * 256) out[i] = in[i];
+    }
+}
+hipError_t launch_row_fanout(const float *src, float *dst, int V, int B, int nret, int32_t *kstart, hipStream_t s) {
+    if (B < 1 || nret < 1 || V < 1 || src == dst) return hipErrorInvalidValue;
+    const int gx = (int)cdiv(cdiv(V, 4), 256);
+    hipLaunchKernelGGL(row_fanout_kernel, dim3(gx > 64 ? 64 : gx, B * nret + 1), dim3(256), (size_t)B * sizeof(int32_t), s, src, dst,
+                       V, B, nret, kstart);
     return hipGetLastError();
 }
 

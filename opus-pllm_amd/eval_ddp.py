@@ -16,6 +16,11 @@ Differences, all deliberate: the gather moves token ids
 once (cache_prefix), the trie of the allowed terms is scored behind them in one tree pass (score_trie) and every saved item carries
 `"ranked_terms": [[term, logprob], ...]`, its K most probable terms (`generated` is the first of them): the per-term scores that
 function prediction is evaluated with.  --rank_with_stop adds the log-probability of ending the answer right behind the term.
+
+`--num_return_sequences N` (the reference's eval/eval_total_ablation.sh samples every dataset five times, one whole run per repeat):
+N answers per item from ONE run - a call takes batch_size // N prompts, encodes and prefills them once and decodes batch_size rows
+(generate(num_return_sequences=N)); every saved item carries its N answers as `"generated_all"` beside `"generated"`, which keeps
+the first.  With N = 1 the output file is what it was.
 """
 from __future__ import annotations
 
@@ -37,7 +42,7 @@ from opus_pllm_amd.prompt import (add_constraint_args, add_logits_processor_args
 
 def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperature=0.0, top_p=0.7, num_beams=1,
              use_input_embed=False, device=None, logits_out=None, stop_sequence=None, inflight=1, logprobs_out=None,
-             processors=None):
+             processors=None, num_return_sequences=1):
     """The batch loop of run_opus_ddp.py:88-134 over this rank's items -> [n, max_new] new ids (rows padded with eos).
 
     use_input_embed (two-stage pipeline): the `input_embed` vectors of the WHOLE shard go through the modality
@@ -52,8 +57,16 @@ def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperatu
     the same, sampled ids because every batch's sampler seed is drawn HERE, in input order, from torch's global generator
     (torch.manual_seed reproduces a run whatever `inflight` is) and handed to generate(seed=...).
     processors (--repetition_penalty / --no_repeat_ngram_size / --min_new_tokens, --allowed_terms): generate() keywords of its
-    logits processors and of the token constraint (prefix_allowed_tokens_fn: one TokenTrie, built once, for every batch)."""
+    logits processors and of the token constraint (prefix_allowed_tokens_fn: one TokenTrie, built once, for every batch).
+    num_return_sequences = N > 1 (--num_return_sequences): a call takes batch_size // N prompts and returns N rows for each
+    (generate(num_return_sequences=N): one encode and one prefill per prompt); the result is [n N, max_new], item i's answers in
+    rows i N .. i N + N - 1, and the other outputs have n N rows too."""
     dev = device or model.device
+    nret = int(num_return_sequences)
+    if nret < 1:
+        raise ValueError(f"--num_return_sequences has to be at least 1 (got {nret})")
+    if nret > 1:
+        batch_size = prompts_per_call(batch_size, nret)
     prot_all = None
     if use_input_embed and items:
         prot_all = model.project_dataset(torch.tensor([q["input_embed"] for q in items], dtype=torch.float32, device=dev))
@@ -74,6 +87,8 @@ def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperatu
         mask = ids != tokenizer.pad_token_id
         extra = {} if prot_all is None else {"protein_tokens": prot_all[i:i + len(batch)]}
         extra.update(processors or {})
+        if nret > 1:
+            extra["num_return_sequences"] = nret
         if logprobs_out is not None:
             extra.update(return_dict_in_generate=True, output_token_logprobs=True)
         with torch.inference_mode():
@@ -87,7 +102,7 @@ def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperatu
             lps[j] = (lp, out.n_tokens)
             out = out.sequences
         if logits_out is not None:
-            last[j] = m.last_logits(len(batch))
+            last[j] = m.last_logits(len(batch) * nret)
         full = torch.full((out.shape[0], max_new), tokenizer.eos_token_id, dtype=torch.long, device=dev)
         full[:, : out.shape[1]] = out
         outs[j] = full
@@ -122,6 +137,28 @@ def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperatu
     if logprobs_out is not None:
         logprobs_out.extend(lps)
     return torch.cat(outs) if outs else torch.empty((0, max_new), dtype=torch.long, device=dev)
+
+
+def prompts_per_call(batch_size: int, num_return_sequences: int) -> int:
+    """--num_return_sequences N: prompts of one generate call, batch_size // N (its N answers each fill the batch_size rows)."""
+    if num_return_sequences > batch_size:
+        raise ValueError(f"--num_return_sequences {num_return_sequences} exceeds --batch_size {batch_size} (the decoder rows of a call)")
+    return batch_size // num_return_sequences
+
+
+def build_result(qs, texts, num_return_sequences: int = 1):
+    """The saved items: texts holds N = num_return_sequences answers per item, item i's in texts[i N : i N + N].  `generated` is
+    the first of them; with N > 1 `generated_all` lists all N (N = 1: the file of a run without the flag)."""
+    N = int(num_return_sequences)
+    if len(texts) != len(qs) * N:
+        raise ValueError(f"{len(texts)} answers for {len(qs)} items x {N}")
+    result = []
+    for k, q in enumerate(qs):
+        r = {"ground_truth": q["output"], "generated": texts[k * N]}
+        if N > 1:
+            r["generated_all"] = list(texts[k * N:(k + 1) * N])
+        result.append(r)
+    return result
 
 
 def rank_terms(model, tokenizer, items, input_path, batch_size, trie, k, with_stop=False, device=None):
@@ -200,10 +237,11 @@ def eval_model(args):
     if trie is not None:
         proc_kw["prefix_allowed_tokens_fn"] = trie
     lps = [] if args.save_logprobs else None
+    N = int(getattr(args, "num_return_sequences", 1) or 1)
     local_ids = annotate(model, tokenizer, mine, args.input_path, args.batch_size, max_new, args.temperature, args.top_p,
                          args.num_beams, args.use_input_embed, dev, logits,
                          tokenizer.encode("###", add_special_tokens=False) if args.stop_at_hashes else None, inflight=args.inflight,
-                         logprobs_out=lps, processors=proc_kw)
+                         logprobs_out=lps, processors=proc_kw, num_return_sequences=N)
     all_ids = odist.all_gather_ids(local_ids, tokenizer.eos_token_id)
     if lps is not None:         # [n, max_new] log-probabilities and [n] counted positions, in rank order
         loc_lp = torch.cat([x[0] for x in lps]) if lps else torch.empty((0, max_new), dtype=torch.float32, device=dev)
@@ -217,10 +255,10 @@ def eval_model(args):
     if rank == 0:
         dt = time.time() - t0
         texts = [after_process_output(t) for t in tokenizer.batch_decode(all_ids, skip_special_tokens=True)]
-        result = [{"ground_truth": q["output"], "generated": t} for q, t in zip(qs, texts)]
-        if lps is not None:     # over the row's counted tokens (its EOS / "###" included)
+        result = build_result(qs, texts, N)
+        if lps is not None:     # over the row's counted tokens (its EOS / "###" included); N > 1: of the item's first answer
             for k, r in enumerate(result):
-                row = all_lp[k, : int(all_n[k])]
+                row = all_lp[k * N, : int(all_n[k * N])]
                 r["logprob"] = float(row.double().sum())
                 r["token_logprobs"] = [float(v) for v in row]
         print(f"entries/sec: {n / dt}, time elapsed: {dt}")
@@ -249,7 +287,7 @@ def _eval_ranked_terms(args, qs, mine, tokenizer, model, trie, k, dev, rank, wor
         torch.distributed.destroy_process_group()
 
 
-if __name__ == "__main__":
+def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser()
     p.add_argument("--model-base-path", type=str, default="synthetic:c1_tiny")
     p.add_argument("--opus-pllm-weights-path", type=str, default="synthetic")
@@ -258,6 +296,9 @@ if __name__ == "__main__":
     p.add_argument("--temperature", type=float, default=0.1)        # reference default: sampling (run_opus_ddp.py:156)
     p.add_argument("--top_p", type=float, default=0.7)
     p.add_argument("--num_beams", type=int, default=1)
+    p.add_argument("--num_return_sequences", type=int, default=1, metavar="N",
+                   help="N answers per item from one run (sampling, or the N best of --num_beams): a call takes batch_size // N "
+                        "prompts, prefilled once; items are saved with `generated_all` (N answers) beside `generated` (the first)")
     p.add_argument("--max_new_tokens", type=int, default=None)
     p.add_argument("--switch_projector_type", type=str, default="mlp2x_gelu")
     p.add_argument("--load-4bit", action="store_true")
@@ -286,4 +327,8 @@ if __name__ == "__main__":
                    help="with --rank_terms: add the log-probability of ending the answer right behind the term")
     add_logits_processor_args(p)
     add_constraint_args(p)
-    eval_model(p.parse_args())
+    return p
+
+
+if __name__ == "__main__":
+    eval_model(build_parser().parse_args())

@@ -388,7 +388,16 @@ class OpusLlamaForCausalLM:
         Constrained decoding (greedy and sampling): prefix_allowed_tokens_fn=TokenTrie(...) / TokenTrie.per_row([...])
         (constraint.py) - transformers' PrefixConstrainedLogitsProcessor as a device automaton, behind min_new_tokens and in front
         of the warpers; `scores` are -inf outside the allowed set, `logits` and `token_logprobs` stay raw.  Any other callable
-        raises NotImplementedError (a Python callback cannot run inside the captured decode step), and so does num_beams > 1."""
+        raises NotImplementedError (a Python callback cannot run inside the captured decode step), and so does num_beams > 1.
+        num_return_sequences=N (transformers' semantics and row layout): with do_sample=True the result has B N rows, row b N + j
+        the j-th sample of prompt b (`_expand_inputs_for_generation`).  The proteins are encoded and projected and the prompts
+        prefilled ONCE, on B rows; the prefill leaves B N decoder rows (opus_llama_prefill_fanout) and the decode loop is that of
+        a B N-row batch, the draw of row r at step t keyed by (seed, r, t).  Every output is [B N, ...]; EOS ids, the stop
+        sequence, the processors and a TokenTrie act per decoder row, and TokenTrie.per_row of B tries gives row r trie r // N.
+        `seq`, `seq_embedding` and `protein_tokens` carry B entries.  With num_beams=K >= N the N best finished hypotheses of
+        every prompt come back best first ([B N, n], `sequences_scores` [B N]); the beams' prefill stays on B K rows.  Greedy
+        search with N > 1, N > num_beams and N < 1 raise ValueError as transformers does; B N > max_batch raises OpusError.
+        N = 1 (or absent) is the call without the argument."""
         return_dict = bool(kwargs.pop("return_dict_in_generate", False))
         want = {k: bool(kwargs.pop(k, False)) for k in ("output_scores", "output_logits", "output_token_logprobs",
                                                          "output_attentions", "output_hidden_states")}
@@ -411,6 +420,15 @@ class OpusLlamaForCausalLM:
         if return_dict and num_beams > 1 and (want["output_scores"] or want["output_logits"] or want["output_token_logprobs"]):
             raise NotImplementedError("with num_beams > 1, return_dict_in_generate returns `sequences` and `sequences_scores` only: "
                                       "output_scores / output_logits / output_token_logprobs are built for greedy and sampling")
+        nret = kwargs.pop("num_return_sequences", 1)
+        nret = 1 if nret is None else int(nret)
+        if nret < 1:
+            raise ValueError(f"`num_return_sequences` has to be an integer strictly greater than 0 (got {nret})")
+        if num_beams <= 1 and not do_sample and nret != 1:     # (GenerationConfig.validate's messages)
+            raise ValueError("Greedy methods without beam search do not support `num_return_sequences` different than 1 "
+                             f"(got {nret}).")
+        if num_beams > 1 and nret > num_beams:
+            raise ValueError(f"`num_return_sequences` ({nret}) has to be smaller or equal to `num_beams` ({num_beams}).")
         max_new = int(kwargs.pop("max_new_tokens", 32))
         kwargs.pop("use_cache", None)
         self.set_stop_sequence(kwargs.pop("stop_sequence", None))          # extension (opt-in "###" early stop), see below
@@ -455,6 +473,9 @@ class OpusLlamaForCausalLM:
             pad_id = eos[0] if eos else 0
         if inputs is None:
             raise ValueError("generate() needs input ids")
+        if num_beams <= 1 and nret > 1 and inputs.shape[0] * nret > self.cfg.max_batch:
+            raise _cabi.OpusError(-2, f"num_return_sequences runs batch x num_return_sequences = {inputs.shape[0]} x {nret} decoder "
+                                      f"rows: the context holds max_batch={self.cfg.max_batch}")
         if seq is not None:
             _, _, mask, _, embeds, _ = self.prepare_inputs_labels_for_multimodal(
                 inputs, None, attention_mask if attention_mask is not None else torch.ones_like(inputs, dtype=torch.bool),
@@ -471,14 +492,14 @@ class OpusLlamaForCausalLM:
         self._set_logits_processors(lproc)
         self._set_token_constraint(constraint)
         if num_beams > 1:
-            ids = self._beam_search(embeds, mask, max_new, eos, beam_pad, num_beams, sampler)
+            ids = self._beam_search(embeds, mask, max_new, eos, beam_pad, num_beams, sampler, nret)
             if not return_dict:
                 return ids
             return GenerateBeamDecoderOnlyOutput(sequences=ids, sequences_scores=self.last_beam_scores.to(self.device))
         if not return_dict:
-            return self._greedy(embeds, mask, max_new, eos, int(pad_id), sampler)
+            return self._greedy(embeds, mask, max_new, eos, int(pad_id), sampler, nret=nret)
         return self._greedy(embeds, mask, max_new, eos, int(pad_id), sampler,
-                            outputs=(want["output_token_logprobs"], want["output_scores"], want["output_logits"]))
+                            outputs=(want["output_token_logprobs"], want["output_scores"], want["output_logits"]), nret=nret)
 
     def compute_transition_scores(self, sequences: torch.Tensor, scores, beam_indices: Optional[torch.Tensor] = None,
                                   normalize_logits: bool = False) -> torch.Tensor:
@@ -518,13 +539,13 @@ class OpusLlamaForCausalLM:
             _cabi.check(self._lib.opus_set_sampling_top_k(self._ctx, int(k)))
             self._top_k = int(k)
 
-    def _beam_search(self, embeds, mask, max_new, eos, pad_id, K, sampler=None) -> torch.Tensor:
+    def _beam_search(self, embeds, mask, max_new, eos, pad_id, K, sampler=None, nret: int = 1) -> torch.Tensor:
         """transformers GenerationMixin._beam_search (what run_opus_ddp.py:129,158 reaches with --num_beams K): B x K decoder rows,
         per step the device picks the M continuations of every batch row out of the K V - the best M by accumulated log-probability
         (opus_beam_topk; temperature 0) or, with `sampler` (temperature > 0: beam-sample), M drawn without replacement after the
         warpers (opus_beam_sample_topk) - and permutes the KV cache rows of the surviving beams (opus_kv_reorder); the host keeps
-        the O(K) bookkeeping (beam.BeamState).  Returns the best finished sequence of every row [B, n] (rows that stopped
-        earlier are filled as HF fills them)."""
+        the O(K) bookkeeping (beam.BeamState).  Returns the nret best finished sequences of every row [B nret, n], best first (rows
+        that stopped earlier are filled as HF fills them); last_beam_scores [B nret]."""
         from .beam import BeamState
         B, T, _ = embeds.shape
         cfg = self.cfg
@@ -575,8 +596,8 @@ class OpusLlamaForCausalLM:
                 d_tok = torch.from_numpy(tok.reshape(-1).astype(np.int32)).to(self.device)
                 _cabi.check(self._lib.opus_llama_decode_step(self._ctx, d_tok.data_ptr(), None, s))
         self._leave()
-        self.last_beam_scores = torch.from_numpy(state.result_scores())
-        return torch.from_numpy(state.result()).to(self.device)
+        self.last_beam_scores = torch.from_numpy(state.result_scores(nret))
+        return torch.from_numpy(state.result(nret)).to(self.device)
 
     def set_stop_sequence(self, ids: Optional[Sequence[int]]) -> None:
         """Opt-in early stop: a row is finished once its new ids end with `ids` (at most 8) - e.g.
@@ -627,9 +648,12 @@ class OpusLlamaForCausalLM:
             self._leave()
         self._constraint = constraint
 
-    def _greedy(self, embeds, mask, max_new, eos, pad_id, sampler=None, outputs=None):
-        """outputs = (token_logprobs, scores, logits) flags: a GenerateDecoderOnlyOutput instead of the ids."""
-        B, T, _ = embeds.shape
+    def _greedy(self, embeds, mask, max_new, eos, pad_id, sampler=None, outputs=None, nret: int = 1):
+        """outputs = (token_logprobs, scores, logits) flags: a GenerateDecoderOnlyOutput instead of the ids.
+        nret > 1: the B prompts are prefilled once and decoded as B nret rows (opus_generate_scored_fanout); every result has
+        B nret rows.  nret == 1 takes the entries it always took."""
+        P, T, _ = embeds.shape                           # P prompts, B decoder rows
+        B = P * nret
         V = self.cfg.dec_vocab
         embeds = embeds.contiguous()
         mask = mask.to(torch.uint8).contiguous()
@@ -656,9 +680,18 @@ class OpusLlamaForCausalLM:
                     lg = None                                   # greedy: the processed scores are the logits - one tensor
                 t, p, sd = (sampler[0], sampler[1], sampler[2]) if sampler is not None else (0.0, 1.0, 0)
                 ptr = lambda x: None if x is None else x.data_ptr()                          # noqa: E731
-                _cabi.check(self._lib.opus_generate_scored(self._ctx, embeds.data_ptr(), mask.data_ptr(), B, T, max_new,
-                                                           eos_arr, len(eos), pad_id, t, p, sd, out.data_ptr(), C.byref(n_out),
-                                                           ptr(lp), ptr(sc), ptr(lg), s))
+                if nret > 1:
+                    _cabi.check(self._lib.opus_generate_scored_fanout(self._ctx, embeds.data_ptr(), mask.data_ptr(), P, T, nret, max_new,
+                                                                      eos_arr, len(eos), pad_id, t, p, sd, out.data_ptr(),
+                                                                      C.byref(n_out), ptr(lp), ptr(sc), ptr(lg), s))
+                else:
+                    _cabi.check(self._lib.opus_generate_scored(self._ctx, embeds.data_ptr(), mask.data_ptr(), B, T, max_new,
+                                                               eos_arr, len(eos), pad_id, t, p, sd, out.data_ptr(), C.byref(n_out),
+                                                               ptr(lp), ptr(sc), ptr(lg), s))
+            elif nret > 1:                               # (sampling: greedy search takes no num_return_sequences)
+                _cabi.check(self._lib.opus_generate_scored_fanout(self._ctx, embeds.data_ptr(), mask.data_ptr(), P, T, nret, max_new,
+                                                                  eos_arr, len(eos), pad_id, sampler[0], sampler[1], sampler[2],
+                                                                  out.data_ptr(), C.byref(n_out), None, None, None, s))
             elif sampler is None:
                 _cabi.check(self._lib.opus_generate_greedy(self._ctx, embeds.data_ptr(), mask.data_ptr(), B, T, max_new,
                                                            eos_arr, len(eos), pad_id, out.data_ptr(), C.byref(n_out), s))
@@ -1036,15 +1069,22 @@ class OpusLlamaForCausalLM:
         return TrieScores(member_lp, stop_lp, node_lp, torch.from_numpy(plan.n_members).to(dev), plan.rows_evaluated)
 
     # ------------------------------------------------------------------ parity taps (tests / bench)
-    def prefill_logits(self, embeds: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    def prefill_logits(self, embeds: torch.Tensor, mask: torch.Tensor, num_return_sequences: int = 1) -> torch.Tensor:
+        """Last-position logits fp32 [B, V].  num_return_sequences = N > 1: the fanned-out prefill (opus_llama_prefill_fanout) -
+        [B N, V], row b N + j = prompt b, and decode_logits() then takes B N tokens."""
         B, T, _ = embeds.shape
+        N = int(num_return_sequences)
         embeds = embeds.to(self.device, _cabi.operand_dtype()).contiguous()
         mask = mask.to(self.device).to(torch.uint8).contiguous()
         s = self._enter()
         with torch.cuda.stream(self._stream):
-            logits = torch.empty((B, self.cfg.dec_vocab), dtype=torch.float32, device=self.device)
-            _cabi.check(self._lib.opus_llama_prefill(self._ctx, embeds.data_ptr(), mask.data_ptr(), B, T,
-                                                     logits.data_ptr(), s))
+            logits = torch.empty((B * max(N, 1), self.cfg.dec_vocab), dtype=torch.float32, device=self.device)
+            if N != 1:
+                _cabi.check(self._lib.opus_llama_prefill_fanout(self._ctx, embeds.data_ptr(), mask.data_ptr(), B, T, N,
+                                                                logits.data_ptr(), s))
+            else:
+                _cabi.check(self._lib.opus_llama_prefill(self._ctx, embeds.data_ptr(), mask.data_ptr(), B, T,
+                                                         logits.data_ptr(), s))
         self._leave()
         return logits
 
