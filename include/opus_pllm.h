@@ -262,6 +262,22 @@ int opus_esm2_contacts_packed(opus_ctx *ctx, const int32_t *d_tokens, const int3
                               void *d_scratch, int64_t scratch_bytes, void *stream);
 /* Scratch bytes of opus_esm2_contacts_packed for these proteins (about 4 sum n^2 + 4 sum n * layers * heads); -1 on bad arguments. */
 int64_t opus_esm2_contacts_scratch_bytes(const opus_config *cfg, const int32_t *h_cu, int32_t B);
+/* ESM-2 masked-LM head (fair-esm RobertaLMHead / transformers EsmLMHead) on the final states the last opus_esm2_encode* /
+ * opus_esm2_contacts_packed call left in the context: d_out fp32 [R, enc_vocab] = LN(gelu(h Wd^T + bd)) We^T + b for the R rows
+ * d_rows (device int32) names on that call's token axis (packed: 0 .. cu[B] - 1; padded: b T + t); the list may be unsorted and
+ * may repeat, an index outside the axis gives a NaN row; NULL means rows 0 .. R - 1.  log_softmax != 0: the log-softmax over the
+ * enc_vocab columns instead of the logits.  After a packed call the <cls> / <eos> rows hold no state (see opus_esm2_encode_packed).
+ * Needs the optional weights "enc.lm.dense.weight" (operand type, panel-tiled [enc_dim, enc_dim]), "enc.lm.dense.bias",
+ * "enc.lm.ln.weight", "enc.lm.ln.bias" fp32 [enc_dim], "enc.lm.bias" fp32 [enc_vocab] and, when the output projection is not tied
+ * to the token embedding, "enc.lm.weight" (operand type, row-major [enc_vocab, enc_dim]).  Errors: OPUS_ESTATE when the context
+ * holds no complete encoder result (none yet, one that failed, or opus_debug_esm2_lm_head since); OPUS_EBADARG when the head is
+ * not bound (the message names the tensors); OPUS_ESHAPE for R outside 1 .. max_batch * max_enc_tokens (without a list: the
+ * call's rows).  Up to 128 rows the dense step has one launch shape: a row's result does not depend on the other rows of the
+ * call.  Touches neither the KV cache nor the decode state.  Phase "encode", kernel class "mlm" (+ the dense step's GEMM class). */
+int opus_esm2_lm_head(opus_ctx *ctx, const int32_t *d_rows, int32_t R, int32_t log_softmax, float *d_out, void *stream);
+/* The same two steps on caller-supplied fp32 states d_hidden [R, enc_dim] (kernel tests).  The states are staged where the
+ * encoder leaves its own, so the context holds no encoder result afterwards. */
+int opus_debug_esm2_lm_head(opus_ctx *ctx, const float *d_hidden, int32_t R, int32_t log_softmax, float *d_out, void *stream);
 /* Diagnostic: one layer's contact accumulation alone.  d_q / d_k: operand-dtype rows of stride ld elements, head h at column
  * h * head_dim (q already scaled, both rotated), token-packed proteins h_cu[B + 1] (host, at least 2 tokens each).  Over the
  * interior positions (tokens 1 .. n_b) of P_h = softmax over all of the protein's keys of q k^T: d_A [sum n_b^2] =
@@ -548,7 +564,7 @@ int64_t opus_stat(opus_ctx *ctx, const char *name);
  * belongs to, and its ALGORITHMIC bytes and FLOPs.  opus_timing_get sums the records since the last reset that match
  * kernel_class and phase ("*" = any); opus_timing_names returns "class,class,...;phase,phase,..." .  Classes and phases are
  * addressed by name, never by position.  Order of the lists: phases are append-only ("score" last); among the classes "xent"
- * stays the last entry, as published since opus_llama_forward, and a class added later ("contact", "constraint", "logitproc") is
+ * stays the last entry, as published since opus_llama_forward, and a class added later ("contact", "constraint", "mlm", "logitproc") is
  * listed in front of it ("logitproc" keeps its place next to "xent"). */
 int opus_timing_enable(opus_ctx *ctx, int32_t on);
 int opus_timing_reset(opus_ctx *ctx);

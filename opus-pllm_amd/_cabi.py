@@ -131,6 +131,8 @@ SIGNATURES = {
     "opus_esm2_contacts_scratch_bytes": (C.c_int64, [C.POINTER(CConfig), C.POINTER(C.c_int32), C.c_int32]),
     "opus_debug_contacts": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P,
                                       _P, C.c_int64, _P]),
+    "opus_esm2_lm_head": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
+    "opus_debug_esm2_lm_head": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
     "opus_generate_scored": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32,
                                        C.c_float, C.c_float, C.c_uint64, _P, C.POINTER(C.c_int32), _P, _P, _P, _P]),
     "opus_llama_prefill_fanout": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),

@@ -20,6 +20,9 @@ ALL_TOKS: List[str] = ["<cls>", "<pad>", "<eos>", "<unk>"] + list(_STANDARD) + [
 TOK_TO_IDX = {t: i for i, t in enumerate(ALL_TOKS)}
 CLS_IDX, PAD_IDX, EOS_IDX, UNK_IDX, MASK_IDX = 0, 1, 2, 3, 32
 _SPECIALS = [t for t in ALL_TOKS if len(t) > 1]
+# the 20 standard residues in alphabetical order and their column ids in the 33-column logits of the masked-LM head
+STANDARD_RESIDUES = "ACDEFGHIKLMNPQRSTVWY"
+STANDARD_RESIDUE_IDS: List[int] = [TOK_TO_IDX[c] for c in STANDARD_RESIDUES]
 
 
 # Byte table of the fast path: every single-character symbol -> its id, ASCII whitespace -> -1 (dropped), anything else -> -2
@@ -85,7 +88,11 @@ def batch_convert(seqs: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
 def batch_convert_packed(seqs: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
     """Token-packed form of `batch_convert` -> (tokens int32 [sum(len_b)], cu int32 [B + 1]): the rows <cls> residues <eos> back
     to back WITHOUT padding and their offsets (cu[0] = 0); what opus_esm2_encode_packed consumes."""
-    enc = [encode_array(s) for s in seqs]
+    return pack_token_arrays([encode_array(s) for s in seqs])
+
+
+def pack_token_arrays(enc: Sequence[np.ndarray]) -> Tuple[np.ndarray, np.ndarray]:
+    """`batch_convert_packed` for residue ids that are already encoded (the masked copies of a mutation scan)."""
     cu = np.zeros((len(enc) + 1,), dtype=np.int32)
     for b, e in enumerate(enc):
         cu[b + 1] = cu[b] + len(e) + 2

@@ -212,6 +212,28 @@ def contact_head_from_esm2(sd: Dict[str, torch.Tensor]) -> Optional[Dict[str, to
     return {"enc.contact.weight": w.float().reshape(-1), "enc.contact.bias": b.float().reshape(1)}
 
 
+def mlm_head_from_esm2(sd: Dict[str, torch.Tensor]) -> Optional[Dict[str, torch.Tensor]]:
+    """fair_esm ESM2 state dict -> the masked-LM head (RobertaLMHead: lm_head.dense, lm_head.layer_norm, lm_head.weight,
+    lm_head.bias) under the canonical names enc.lm.dense.{weight,bias}, enc.lm.ln.{weight,bias}, enc.lm.bias, or None when the
+    checkpoint has no head.  lm_head.weight is the token embedding in every published ESM-2 checkpoint (the model ties them):
+    enc.lm.weight is returned only when the checkpoint holds a table that differs from embed_tokens.weight."""
+    def strip(k):
+        for p in ("encoder.sentence_encoder.", "encoder.", "sentence_encoder."):
+            if k.startswith(p):
+                return k[len(p):]
+        return k
+    sd = {strip(k): v for k, v in sd.items()}
+    names = {"enc.lm.dense.weight": "lm_head.dense.weight", "enc.lm.dense.bias": "lm_head.dense.bias",
+             "enc.lm.ln.weight": "lm_head.layer_norm.weight", "enc.lm.ln.bias": "lm_head.layer_norm.bias", "enc.lm.bias": "lm_head.bias"}
+    if any(v not in sd for v in names.values()):
+        return None
+    out = {k: sd[v].float() for k, v in names.items()}
+    w, emb = sd.get("lm_head.weight"), sd.get("embed_tokens.weight")
+    if w is not None and (emb is None or w.shape != emb.shape or not torch.equal(w.float(), emb.float())):
+        out["enc.lm.weight"] = w.float()
+    return out
+
+
 def canonical_from_cstp(ckpt: dict) -> Dict[str, torch.Tensor]:
     sd = ckpt.get("state_dict", ckpt)
     return {"proj.weight": sd["protein_projection.linear.weight"], "proj.bias": sd["protein_projection.linear.bias"]}
@@ -318,7 +340,7 @@ def load_pretrained_model(model_base_path, adapter_path, model_name, load_8bit=F
     """-> (tokenizer, model, context_len), as model/builder.py:29-131.
 
     Extra keyword arguments (all optional): device, max_batch, max_enc_tokens, max_prompt, max_new_tokens (context
-    capacity), seed (synthetic presets).  load_4bit / load_8bit select bitsandbytes quantisation in the reference (a
+    capacity), seed and mlm_head (synthetic presets: the seed, and whether the synthetic masked-LM head is bound).  load_4bit / load_8bit select bitsandbytes quantisation in the reference (a
     CUDA-only library, out of scope): the weights are loaded unquantised in fp16 and a warning says so.
     """
     if load_8bit or load_4bit:
@@ -341,7 +363,7 @@ def load_pretrained_model(model_base_path, adapter_path, model_name, load_8bit=F
         tokenizer = SyntheticTokenizer(cfg.dec_vocab)
         if capacity_from is not None:
             cfg = cfg.with_capacity(**capacity_from(tokenizer, cfg)).validate()
-        weights = DeviceWeights.synthetic(cfg, int(kwargs.pop("seed", 0)), device)
+        weights = DeviceWeights.synthetic(cfg, int(kwargs.pop("seed", 0)), device, mlm_head=bool(kwargs.pop("mlm_head", False)))
         model = OpusLlamaForCausalLM(cfg, weights, device, eos_token_id=tokenizer.eos_token_id,
                                      pad_token_id=tokenizer.pad_token_id)
         return tokenizer, model, 512
@@ -394,6 +416,9 @@ def load_pretrained_model(model_base_path, adapter_path, model_name, load_8bit=F
     head = load_esm2_contact_head(esm_path, esm.get("model", esm))
     if head is not None:
         canon.update(head)          # (bound beside the fused tensors: get_amino_acid_embeddings(return_contacts=True))
+    lm = mlm_head_from_esm2(esm.get("model", esm))
+    if lm is not None:
+        canon.update(lm)            # (likewise: get_residue_logits / score_mutations)
     weights = DeviceWeights.from_canonical(cfg, canon, device, lora=lora)
     eos = resolve_eos_token_id(hf_cfg, tokenizer.eos_token_id, model_base_path)
     model = OpusLlamaForCausalLM(cfg, weights, device, eos_token_id=eos, pad_token_id=tokenizer.pad_token_id)

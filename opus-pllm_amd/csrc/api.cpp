@@ -80,6 +80,7 @@ struct opus_ctx {
     float *e_x, *e_hid, *p_pool_dummy, *e_part, *e_stat;
     int32_t *e_cu, *e_pos;
     std::vector<int32_t> h_cu;           // host copy of the packed encoder's row offsets (source of the async upload)
+    int64_t enc_rows = 0;                // token rows of e_hid the last encoder call left complete (0: none - opus_esm2_lm_head refuses)
     half_t *e_xn, *e_qkv, *e_ctx, *e_h1;
     half_t *p_xn, *p_y, *p_z[2];
     float *d_x, *d_xl, *d_logits, *d_pval, *gemm_ws, *d_probs, *d_zpart, *d_spart, *d_part, *d_stat;
@@ -728,6 +729,7 @@ static int esm2_encode_rows(opus_ctx *c, hipStream_t s, const int32_t *d_tokens,
                             int M, float *d_pooled, const ContactRun *ct = nullptr) {
     const opus_config &g = c->cfg;
     c->phase = PH_ENCODE;
+    c->enc_rows = 0;                               // (e_hid is being rewritten: valid again when every launch below was enqueued)
     const int D = g.enc_dim, F = g.enc_ffn, nh = g.enc_heads, hd = D / nh;
     const bool packed = d_cu != nullptr;
     HIPC(hipMemsetAsync(c->d_cnt, 0, HANDOFF_ERR * sizeof(int32_t), s));       // hand-off words start from zero on every call
@@ -802,6 +804,7 @@ static int esm2_encode_rows(opus_ctx *c, hipStream_t s, const int32_t *d_tokens,
         KLF(KC_CONTACT, 12.0 * n2 + 8.0 * ni * C * cdiv((int64_t)ct->n_max, 64), 2.0 * n2 * C,
             launch_esm_contact_finish(ct->A, ct->vec, ct->sw, d_cu, B, C, ct->n_max, ct->bias, ct->out, s));
     }
+    c->enc_rows = M;
     return OPUS_OK;
 }
 
@@ -942,6 +945,69 @@ extern "C" int opus_esm2_last_hidden(opus_ctx *c, float *d_out, int32_t B, int32
     HIPC(hipMemcpyAsync(d_out, c->e_hid, (size_t)B * T * c->cfg.enc_dim * sizeof(float), hipMemcpyDeviceToDevice,
                         (hipStream_t)stream));
     return OPUS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ masked-LM head
+// logits = LN(gelu_erf(h Wd^T + bd)) We^T + b on R rows of `src` (the context's e_hid, or opus_debug_esm2_lm_head's copy in it):
+// gather-and-cast into e_xn, the dense step through the GEMM router into e_h1 (erf-GELU epilogue, as fc1), mlm_head_kernel.
+// Up to MLM_FIXED_ROWS rows the dense step is ONE launch shape (the operand padded with zero rows to that many): a row's logits
+// then do not depend on how many other rows, or which, share the call - the masked scan's copies give the same bits however
+// they are grouped - and the skinny / mid routes, whose summation orders differ, are not involved.  More rows: the router's
+// choice for M = R.
+constexpr int MLM_FIXED_ROWS = 128;
+static const char *MLM_TENSORS = "enc.lm.dense.{weight,bias}, enc.lm.ln.{weight,bias}, enc.lm.bias (enc.lm.weight when untied)";
+
+static int mlm_head_rows(opus_ctx *c, hipStream_t s, const float *src, int64_t src_rows, const int32_t *d_rows, int R,
+                         int log_softmax, float *d_out) {
+    const opus_config &g = c->cfg;
+    const int64_t De = g.enc_dim, V = g.enc_vocab, Me = (int64_t)g.max_batch * g.max_enc_tokens;
+    if (V > 64) return fail(OPUS_EUNSUPPORTED, "esm2_lm_head: enc_vocab=%d, at most 64 columns are built", g.enc_vocab);
+    if (g.enc_ffn < g.enc_dim) return fail(OPUS_EUNSUPPORTED, "esm2_lm_head: enc_ffn < enc_dim (the dense step's output uses the fc1 buffer)");
+    for (const char *n : {"enc.lm.dense.weight", "enc.lm.dense.bias", "enc.lm.ln.weight", "enc.lm.ln.bias", "enc.lm.bias"})
+        if (!c->w.count(n)) return fail(OPUS_EBADARG, "esm2_lm_head: the masked-LM head is not bound ('%s' missing; it needs %s)", n, MLM_TENSORS);
+    const half_t *wd, *we;
+    const float *bd, *lw, *lb, *bv;
+    GW("enc.lm.dense.weight", OPUS_F16, (std::vector<int64_t>{De, De}), wd);
+    GW("enc.lm.dense.bias", OPUS_F32, (std::vector<int64_t>{De}), bd);
+    GW("enc.lm.ln.weight", OPUS_F32, (std::vector<int64_t>{De}), lw);
+    GW("enc.lm.ln.bias", OPUS_F32, (std::vector<int64_t>{De}), lb);
+    GW("enc.lm.bias", OPUS_F32, (std::vector<int64_t>{V}), bv);
+    if (c->w.count("enc.lm.weight")) GW("enc.lm.weight", OPUS_F16, (std::vector<int64_t>{V, De}), we);
+    else we = c->enc_emb;                                            // tied to the token embedding, as fair-esm and transformers tie it
+    const int fixed = (int)std::min<int64_t>(MLM_FIXED_ROWS, Me);
+    const int Mg = R <= fixed ? fixed : R;
+    const int saved_phase = c->phase;
+    c->phase = PH_ENCODE;
+    KL(KC_MLM, 6.0 * R * De, launch_mlm_gather(src, src_rows, d_rows, R, Mg, (int)De, c->e_xn, s));
+    OPC(gemm(c, s, c->e_xn, De, wd, Mg, (int)De, (int)De, bd, EPI_GELU, nullptr, c->e_h1, De, 0));
+    KLF(KC_MLM, 2.0 * R * De + 2.0 * V * De + 4.0 * R * V, 2.0 * R * V * De,
+        launch_mlm_head(c->e_h1, lw, lb, g.enc_ln_eps, we, bv, R, (int)De, (int)V, log_softmax ? 1 : 0, d_out, s));
+    c->phase = saved_phase;
+    return OPUS_OK;
+}
+
+extern "C" int opus_esm2_lm_head(opus_ctx *c, const int32_t *d_rows, int32_t R, int32_t log_softmax, float *d_out, void *stream) {
+    OPC(need_ready(c));
+    if (!d_out) return fail(OPUS_EBADARG, "esm2_lm_head: null pointer");
+    if (c->enc_rows < 1)
+        return fail(OPUS_ESTATE, "esm2_lm_head: the context holds no encoder result (call opus_esm2_encode* / opus_esm2_contacts_packed first; "
+                                 "opus_debug_esm2_lm_head overwrites it)");
+    const int64_t Me = (int64_t)c->cfg.max_batch * c->cfg.max_enc_tokens;
+    if (R < 1 || R > Me || (!d_rows && R > c->enc_rows))
+        return fail(OPUS_ESHAPE, "esm2_lm_head: R=%d out of range (1 .. %lld; without a row list at most the %lld rows of the last encoder call)",
+                    R, (long long)Me, (long long)c->enc_rows);
+    return mlm_head_rows(c, (hipStream_t)stream, c->e_hid, c->enc_rows, d_rows, R, log_softmax, d_out);
+}
+
+extern "C" int opus_debug_esm2_lm_head(opus_ctx *c, const float *d_hidden, int32_t R, int32_t log_softmax, float *d_out, void *stream) {
+    OPC(need_ready(c));
+    if (!d_hidden || !d_out) return fail(OPUS_EBADARG, "debug_esm2_lm_head: null pointer");
+    const int64_t Me = (int64_t)c->cfg.max_batch * c->cfg.max_enc_tokens;
+    if (R < 1 || R > Me) return fail(OPUS_ESHAPE, "debug_esm2_lm_head: R=%d out of range (1 .. %lld)", R, (long long)Me);
+    hipStream_t s = (hipStream_t)stream;
+    c->enc_rows = 0;                                                 // the states go where the encoder leaves its own
+    HIPC(hipMemcpyAsync(c->e_hid, d_hidden, (size_t)R * c->cfg.enc_dim * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return mlm_head_rows(c, s, c->e_hid, R, nullptr, R, log_softmax, d_out);
 }
 
 // ------------------------------------------------------------------------------------------------ projectors
@@ -2929,7 +2995,7 @@ extern "C" int opus_timing_reset(opus_ctx *c) {
     return OPUS_OK;
 }
 static const char *kclass_names[KC_COUNT] = {"gemm_skinny", "gemm_mid", "gemm_wide", "gemm_ring", "gemm_pp", "gemm_tile", "splitk_reduce",
-                                            "attn_prefill", "attn_decode", "norm", "other", "gemm_stream", "contact", "constraint", "logitproc",
+                                            "attn_prefill", "attn_decode", "norm", "other", "gemm_stream", "contact", "constraint", "mlm", "logitproc",
                                             "xent"};
 static const char *phase_names[PH_COUNT] = {"encode", "project", "splice", "prefill", "decode", "other", "score"};
 

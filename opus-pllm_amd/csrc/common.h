@@ -52,7 +52,7 @@ int skinny_max_m();   // rows up to which the skinny kernel is used (default 4, 
 constexpr int MID_MAX_M = 64;   // (65..128 rows measured faster on the split-K tile kernel)
 // kernel classes of the per-launch timing (opus_timing_get): one per kernel family
 enum KClass { KC_SKINNY = 0, KC_MID, KC_WIDE, KC_RING, KC_PP, KC_TILE, KC_REDUCE, KC_ATTN_PREFILL, KC_ATTN_DECODE, KC_NORM,
-              KC_OTHER, KC_STREAM, KC_CONTACT, KC_CONSTRAINT, KC_LOGITPROC, KC_XENT, KC_COUNT };
+              KC_OTHER, KC_STREAM, KC_CONTACT, KC_CONSTRAINT, KC_MLM, KC_LOGITPROC, KC_XENT, KC_COUNT };
 // Ordering rule of the published class list (opus_timing_names, include/opus_pllm.h): "xent" stays its last entry, as published
 // since opus_llama_forward, and a class added later goes in front of it.  Classes are looked up by name, never by index.
 // phases of the path a launch belongs to (set by the entry points of api.cpp)
@@ -327,6 +327,12 @@ hipError_t launch_esm_contact_finish(const float *A, const float *vec, const flo
                                      const float *bias, float *out, hipStream_t s);
 
 // norm.hip
+// mlm.hip: ESM-2 masked-LM head (opus_esm2_lm_head).  launch_mlm_gather: rows idx[0 .. R) (null: 0 .. R - 1) of the fp32 states
+// src [src_rows, D] -> operand rows dst [Mg, D], rows R .. Mg - 1 zero, an index out of range a NaN row.  launch_mlm_head:
+// out[R, V] = LN(y) We^T + bias (We row-major [V, D], V <= 64), log-softmax over the V columns on request.
+hipError_t launch_mlm_gather(const float *src, int64_t src_rows, const int32_t *idx, int R, int Mg, int D, half_t *dst, hipStream_t s);
+hipError_t launch_mlm_head(const half_t *y, const float *lnw, const float *lnb, float eps, const half_t *We, const float *bias,
+                           int64_t R, int D, int V, int log_softmax, float *out, hipStream_t s);
 hipError_t launch_layernorm(const float *x, const float *w, const float *b, float eps, int64_t rows, int D,
                             half_t *out_h, float *out_f, hipStream_t s);   // (w == b == nullptr: (x - mu) rstd, no affine part)
 // (mu, rstd) per row from the per-slab (sum x, sum x^2) partials the LayerNorm-producing GEMM epilogue left (GemmParams::ln_part)

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _cabi
-from .alphabet import batch_convert, batch_convert_packed
+from .alphabet import batch_convert, batch_convert_packed, encode_array, pack_token_arrays
 from .config import OpusConfig
 from .constants import DEFAULT_SEQ_TOKEN_INDEX, IGNORE_INDEX
 from .weights import DeviceWeights
@@ -42,6 +42,24 @@ class _ProteinEncoderHandle:
         mismatch; this is the intended behaviour."""
         seqs = [d[1] if isinstance(d, (tuple, list)) else d for d in data]
         return self._owner._amino_acid_embeddings(seqs, return_contacts)
+
+    def get_residue_logits(self, data, log_softmax: bool = False):
+        """The masked-LM head's logits per residue: data = [(label, sequence)] (or plain sequences, which may contain <mask>) ->
+        list of fp32 [n_i, 33] on the model's device, row j = residue j of protein i (the <cls> / <eos> rows are dropped), equal to
+        fair-esm's model(tokens)["logits"][i, 1 : n_i + 1] and transformers' EsmForMaskedLM; log_softmax=True: their log-softmax
+        over the 33 columns.  One packed encoder call per max_batch proteins, the head on the residue rows only."""
+        seqs = [d[1] if isinstance(d, (tuple, list)) else d for d in data]
+        return self._owner._residue_logits(seqs, log_softmax)
+
+    def score_mutations(self, data, mutations=None, mode: str = "masked-marginals", positions=None, offset_idx: int = 1):
+        """Variant-effect scores as fair-esm's examples/variant-prediction/predict.py computes them -> mlm.MutationScores.
+        mode "wt-marginals": one pass over the unmasked sequences; "masked-marginals": row j from the copy whose residue j is
+        <mask> (the host builds the copies, max_batch per encoder call, copies of different proteins share a call, the head runs
+        on one gathered row per copy).  positions: per protein the 0-based residues to scan (default: all, or with mutations
+        the ones they mention).  mutations: per protein a list of strings such as "A23G" or "A23G:L40P" (positions count from
+        offset_idx; a multiple mutation is the sum of its parts); a string that does not fit its protein raises ValueError."""
+        seqs = [d[1] if isinstance(d, (tuple, list)) else d for d in data]
+        return self._owner._score_mutations(seqs, mutations, mode, positions, offset_idx)
 
 
 class _InnerModel:
@@ -208,6 +226,120 @@ class OpusLlamaForCausalLM:
         finally:
             self._leave()
         return (embs, maps) if return_contacts else embs
+
+    # ------------------------------------------------------------------ masked-LM head
+    def _need_mlm_head(self) -> None:
+        w = self.weights
+        if not w.has_mlm_head():
+            raise ValueError("no masked-LM head is bound: it is read from the ESM-2 checkpoint's lm_head.{dense,layer_norm}.{weight,bias}, "
+                             "lm_head.weight and lm_head.bias (builder.mlm_head_from_esm2, the checkpoint OPUS_ESM2_CKPT names), or "
+                             "made by DeviceWeights.synthetic(..., mlm_head=True) / DeviceWeights.set_mlm_head")
+        key = tuple(w.extra[k].data_ptr() for k in w.MLM_NAMES) + (w.extra["enc.lm.weight"].data_ptr() if "enc.lm.weight" in w.extra else 0,)
+        if getattr(self, "_mlm_bound", None) != key:      # (a head set after this context was made: bind it now)
+            w.bind(self._ctx)
+            self._mlm_bound = key
+
+    def _mlm_rows(self, encs: List[np.ndarray], rows: List[Sequence[int]], log_softmax: bool):
+        """Token arrays (residue ids, no <cls> / <eos>) through the packed encoder, max_batch per call, and the head on residue
+        rows `rows[i]` (0-based) of each -> (list of fp32 [len(rows[i]), enc_vocab], encoder calls, rows evaluated)."""
+        cfg = self.cfg
+        V = cfg.enc_vocab
+        outs: List[torch.Tensor] = []
+        calls = nrows = 0
+        s = self._enter()
+        try:
+            for i0 in range(0, len(encs), cfg.max_batch):
+                group = encs[i0:i0 + cfg.max_batch]
+                toks, cu = pack_token_arrays(group)
+                B = len(cu) - 1
+                longest = int((cu[1:] - cu[:-1]).max())
+                if longest > cfg.max_enc_tokens:
+                    raise _cabi.OpusError(-2, f"protein of {longest - 2} residues exceeds max_enc_tokens={cfg.max_enc_tokens}")
+                idx = np.concatenate([np.asarray(rows[i0 + b], dtype=np.int32).reshape(-1) + np.int32(int(cu[b]) + 1) for b in range(B)])
+                R = int(idx.size)
+                out = torch.empty((R, V), dtype=torch.float32, device=self.device)
+                if R:
+                    cu_arr = (C.c_int32 * (B + 1))(*[int(v) for v in cu])
+                    pooled = torch.empty((B, cfg.enc_dim), dtype=torch.float32, device=self.device)
+                    with torch.cuda.stream(self._stream):
+                        d_tok = torch.from_numpy(toks).to(self.device, non_blocking=True)
+                        d_idx = torch.from_numpy(idx).to(self.device, non_blocking=True)
+                        _cabi.check(self._lib.opus_esm2_encode_packed(self._ctx, d_tok.data_ptr(), cu_arr, B, pooled.data_ptr(), s))
+                        _cabi.check(self._lib.opus_esm2_lm_head(self._ctx, d_idx.data_ptr(), R, 1 if log_softmax else 0, out.data_ptr(), s))
+                        for t in (d_tok, d_idx, pooled, out):
+                            t.record_stream(self._stream)
+                    self._last_enc_shape = (1, int(cu[-1]))
+                    calls += 1
+                    nrows += R
+                off = 0
+                for b in range(B):
+                    k = len(rows[i0 + b])
+                    outs.append(out[off:off + k])
+                    off += k
+        finally:
+            self._leave()
+        return outs, calls, nrows
+
+    def _residue_logits(self, seqs: List[str], log_softmax: bool = False):
+        self._need_mlm_head()
+        encs = [encode_array(q) for q in seqs]
+        return self._mlm_rows(encs, [np.arange(len(e), dtype=np.int32) for e in encs], log_softmax)[0]
+
+    def _score_mutations(self, seqs: List[str], mutations=None, mode: str = "masked-marginals", positions=None, offset_idx: int = 1):
+        from . import mlm
+        if mode not in mlm.MODES:
+            raise ValueError(f"mode must be one of {mlm.MODES}, got {mode!r}")
+        self._need_mlm_head()
+        cfg = self.cfg
+        encs = [encode_array(q) for q in seqs]
+        P = len(encs)
+        for name, v in (("mutations", mutations), ("positions", positions)):
+            if v is not None and len(v) != P:
+                raise ValueError(f"{name} holds {len(v)} lists for {P} proteins")
+        parsed = None if mutations is None else [[mlm.parse_mutation(m, encs[i], offset_idx) for m in mutations[i]] for i in range(P)]
+        lens = [len(e) for e in encs]
+        scan = mlm.scan_positions(lens, positions, parsed)
+        if mode == "wt-marginals":
+            got, calls, nrows = self._mlm_rows(encs, scan, True)
+        else:
+            plan = mlm.plan_masked_copies(scan, lens, cfg.max_batch, cfg.max_enc_tokens)
+            copies = [c for call in plan for c in call]
+            got, calls, nrows = self._mlm_rows([mlm.masked_copy(encs[i], j) for i, j in copies], [[j] for _, j in copies], True)
+        # one table over all proteins' residues (NaN where not scanned), its wild-type column and the sums in a handful of
+        # launches; the per-protein results are views of it
+        V = cfg.enc_vocab
+        offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        N = int(offs[-1])
+        rows = np.concatenate([np.asarray(scan[i], dtype=np.int64).reshape(-1) + offs[i] for i in range(P)]) if P else np.zeros(0, np.int64)
+        flat = torch.cat(got, 0) if got else torch.empty((0, V), dtype=torch.float32, device=self.device)
+        if rows.size == N:                    # every row scanned (ascending, no repeats): the table as it stands
+            LP = flat
+        else:
+            LP = torch.full((N, V), float("nan"), dtype=torch.float32, device=self.device)
+            if rows.size:
+                LP[torch.from_numpy(rows).to(self.device)] = flat
+        tok = torch.from_numpy(np.concatenate(encs).astype(np.int64) if N else np.zeros(0, np.int64)).to(self.device)
+        WT = LP.gather(1, tok[:, None])[:, 0]
+        SC = LP - WT[:, None]
+        # per-protein sums through a padded [P, longest] matrix: a fixed summation order (no atomics), one launch
+        seg = torch.from_numpy(np.repeat(np.arange(P, dtype=np.int64), lens)).to(self.device)
+        pos = torch.from_numpy((np.arange(N, dtype=np.int64) - np.repeat(offs[:-1], lens))).to(self.device)
+        pad = torch.zeros((P, max(lens, default=0) or 1), dtype=torch.float32, device=self.device)
+        pad[seg, pos] = torch.nan_to_num(WT, nan=0.0)
+        pll = pad.sum(1)
+        cnt = torch.tensor([float(len(ps)) for ps in scan], dtype=torch.float32, device=self.device)
+        res = mlm.MutationScores(mode, [], [], [], None, None, None if parsed is None else [], nrows, calls, scan)
+        for i in range(P):
+            a, b = int(offs[i]), int(offs[i + 1])
+            res.log_probs.append(LP[a:b])
+            res.wt_log_prob.append(WT[a:b])
+            res.scores.append(SC[a:b])
+            if parsed is not None:
+                res.mutation_scores.append(torch.stack([sum(res.scores[i][idx, mt] for idx, _, mt in mut) for mut in parsed[i]])
+                                           if parsed[i] else LP.new_empty((0,)))
+        res.pseudo_log_likelihood = pll
+        res.pseudo_perplexity = torch.exp(-pll / cnt)
+        return res
 
     def _encode_padded(self, seqs: List[str], bucket: int = 256) -> torch.Tensor:
         """list[str] -> pooled fp32 [B, enc_dim].  Mixed lengths are processed in length buckets

@@ -179,6 +179,31 @@ def contact_head(cfg: OpusConfig, seed: int = 0) -> Dict[str, np.ndarray]:
             "enc.contact.bias": hash_normal(tensor_seed("enc.contact.bias", seed), 0, 1, 0.5)}
 
 
+MLM_HEAD_NAMES = ("enc.lm.dense.weight", "enc.lm.dense.bias", "enc.lm.ln.weight", "enc.lm.ln.bias", "enc.lm.bias")
+
+
+def mlm_head_spec(cfg: OpusConfig, tied: bool = True) -> List[Tuple[str, Tuple[int, ...], float, float]]:
+    """[(name, shape, std, mean)] of the synthetic masked-LM head.  The dense layer is an ordinary Linear of the synthetic
+    model (1 / sqrt(De)).  The output projection is the token embedding (std 1, tied as fair-esm and transformers tie it), so a
+    LayerNorm gain of 1 would give logits of std sqrt(De) - 8 at the micro width, 36 at ESM-2 650M, a one-hot softmax; the gain
+    2 / sqrt(De) keeps them at a standard deviation of about 2 at every width, far from both one-hot and constant.  The
+    output bias (std 0.5) moves every column separately.  tied=False adds enc.lm.weight, a table of its own."""
+    De, V = cfg.enc_dim, cfg.enc_vocab
+    g = 2.0 / math.sqrt(De)
+    out = [("enc.lm.dense.weight", (De, De), 1.0 / math.sqrt(De), 0.0), ("enc.lm.dense.bias", (De,), 0.02, 0.0),
+           ("enc.lm.ln.weight", (De,), 0.05 * g, g), ("enc.lm.ln.bias", (De,), 0.02, 0.0), ("enc.lm.bias", (V,), 0.5, 0.0)]
+    if not tied:
+        out.append(("enc.lm.weight", (V, De), 1.0, 0.0))
+    return out
+
+
+def mlm_head(cfg: OpusConfig, seed: int = 0, tied: bool = True) -> Dict[str, np.ndarray]:
+    """The synthetic masked-LM head (canonical names enc.lm.*), each tensor from its own stream (tensor_seed of its name).  Kept
+    out of canonical_spec like the contact head: optional, and param_count / the loaders enumerate that list."""
+    return {name: hash_normal(tensor_seed(name, seed), 0, int(np.prod(shape)), std, mean).reshape(shape)
+            for name, shape, std, mean in mlm_head_spec(cfg, tied)}
+
+
 # ---------------------------------------------------------------------------------------------
 # synthetic inputs (SURVEY 8d "Synthetic inputs")
 RESIDUES = "ACDEFGHIKLMNPQRSTVWY"

@@ -161,7 +161,7 @@ class DeviceWeights:
         self.device = device
         self.tensors: Dict[str, torch.Tensor] = {}
         # optional tensors bound beside the fused ones (the ESM-2 contact head: enc.contact.weight fp32 [enc_layers * enc_heads],
-        # enc.contact.bias fp32 [1]); opus_weights_ready does not need them
+        # enc.contact.bias fp32 [1]; the ESM-2 masked-LM head: enc.lm.*); opus_weights_ready does not need them
         self.extra: Dict[str, torch.Tensor] = {}
 
     CONTACT_NAMES = ("enc.contact.weight", "enc.contact.bias")
@@ -175,6 +175,36 @@ class DeviceWeights:
             raise ValueError(f"contact head: weight [{C}] and bias [1] expected, got {tuple(w.shape)} and {tuple(b.shape)}")
         self.extra["enc.contact.weight"] = w.to(self.device).contiguous()
         self.extra["enc.contact.bias"] = b.to(self.device).contiguous()
+
+    MLM_NAMES = synth.MLM_HEAD_NAMES          # (+ the optional enc.lm.weight of an untied output projection)
+
+    def set_mlm_head(self, head: Dict[str, "np.ndarray | torch.Tensor"]) -> None:
+        """Bind the masked-LM head (canonical names enc.lm.dense.{weight,bias}, enc.lm.ln.{weight,bias}, enc.lm.bias and,
+        when the output projection is not tied to enc.embed_tokens, enc.lm.weight) at the next bind(): the two matrices in the
+        build's operand type (the dense one panel-tiled for the GEMM kernels, the output table row-major), the vectors in fp32."""
+        De, V = self.cfg.enc_dim, self.cfg.enc_vocab
+        missing = [k for k in self.MLM_NAMES if k not in head]
+        if missing:
+            raise ValueError(f"masked-LM head: {missing} missing")
+        shapes = {"enc.lm.dense.weight": (De, De), "enc.lm.dense.bias": (De,), "enc.lm.ln.weight": (De,), "enc.lm.ln.bias": (De,),
+                  "enc.lm.bias": (V,), "enc.lm.weight": (V, De)}
+        new = {}
+        with torch.cuda.device(self.device):
+            for k, sh in shapes.items():
+                if k not in head:
+                    continue
+                t = head[k]
+                t = torch.as_tensor(np.asarray(t)) if not torch.is_tensor(t) else t
+                if tuple(t.shape) != sh:
+                    raise ValueError(f"masked-LM head: {k} has shape {tuple(t.shape)}, expected {sh}")
+                mat = len(sh) == 2
+                t = t.to(self.device).to(_cabi.operand_dtype() if mat else torch.float32).contiguous()
+                new[k] = tile_weight(t) if k == "enc.lm.dense.weight" else t
+        self.extra.pop("enc.lm.weight", None)
+        self.extra.update(new)
+
+    def has_mlm_head(self) -> bool:
+        return all(k in self.extra for k in self.MLM_NAMES)
 
     # -- construction -------------------------------------------------------------------------
     def _alloc(self, f: Fused) -> torch.Tensor:
@@ -225,6 +255,8 @@ class DeviceWeights:
             self._derive(spec, None, None, folded_vec)
             if all(k in canon for k in self.CONTACT_NAMES):
                 self.set_contact_head(canon["enc.contact.weight"], canon["enc.contact.bias"])
+            if all(k in canon for k in self.MLM_NAMES):
+                self.set_mlm_head({k: v for k, v in canon.items() if k.startswith("enc.lm.")})
             torch.cuda.synchronize(self.device)
         return self
 
@@ -243,9 +275,10 @@ class DeviceWeights:
                 raise ValueError(f.derive)
 
     @classmethod
-    def synthetic(cls, cfg: OpusConfig, seed: int, device, stream: int = 0, contact_head: bool = False) -> "DeviceWeights":
+    def synthetic(cls, cfg: OpusConfig, seed: int, device, stream: int = 0, contact_head: bool = False,
+                  mlm_head: bool = False) -> "DeviceWeights":
         """Fill the fused tensors on the GPU with the deterministic synthetic model (synth.py twin); contact_head: also the
-        synthetic contact regression (synth.contact_head)."""
+        synthetic contact regression (synth.contact_head); mlm_head: also the synthetic masked-LM head (synth.mlm_head)."""
         self = cls(cfg, torch.device(device))
         lib = _cabi.lib()
         if not stream:      # the fills and _derive's torch ops on ONE stream: torch's current one (not the null stream beside it)
@@ -289,6 +322,8 @@ class DeviceWeights:
             if contact_head:
                 head = synth.contact_head(cfg, seed)
                 self.set_contact_head(head["enc.contact.weight"], head["enc.contact.bias"])
+            if mlm_head:
+                self.set_mlm_head(synth.mlm_head(cfg, seed))
         return self
 
     # -- binding ---------------------------------------------------------------------------------
