@@ -154,33 +154,11 @@ struct opus_ctx {
     int32_t *d_cstate = nullptr, *d_cstep = nullptr;
     int32_t cons_n_start = 0, cons_max_id = -1;
     int32_t cons_start_div = 1;          // TokenConstraintDesc::start_div as the device descriptor holds it
-    // row-scale fusion (GemmParams::xh_out / row_ssq): one-shot request for the next gemm() and its outcome
-    half_t *rq_xh = nullptr;
-    int rq_done = 0;
-    // one-shot request: fuse the ESM rotary into the next GEMM's epilogue (GemmParams::rope_*); rq_rope_done reports back
-    const float *rq_rope_cs = nullptr;
-    const int32_t *rq_rope_pos = nullptr;
-    int rq_rope_T = 0, rq_rope_cols = 0, rq_rope_qcols = 0, rq_rope_done = 0;
-    float rq_rope_qscale = 1.0f;
-    // one-shot requests for the next gemm(): route a narrow output through the wide kernel / leave raw k-part slabs
-    int rq_force_wide = 0, rq_slab_only = 0, rq_ks = 1;
-    // one-shot: the next gemm() reads A / writes the fp16 copy of its output in fragment order (GemmParams::a_tiled / xh_tiled)
-    int rq_a_tiled = 0, rq_xh_tiled = 0, rq_c_tiled = 0;
-    // one-shot requests, fused LayerNorm around gemm_pp_kernel (GemmParams::ln_*): producer (fp16(x) into e_xn + partials into
-    // e_part; rq_ln_done reports back) and consumer (rows scaled / shifted with e_stat and this column-sum vector)
-    float *rq_ln_part = nullptr;         // producer: partials here, fp16(x) into rq_ln_xh
-    half_t *rq_ln_xh = nullptr;
-    int rq_ln_done = 0;
-    const float *rq_ln_stat = nullptr, *rq_ln_colsum = nullptr;   // consumer
-    int *rq_pp_plan = nullptr;           // one-shot (HOST): the next GEMM's launch_pp reports its plan here (GemmParams::pp_plan)
     int gemm_plan[GEMM_PLAN_WORDS] = {-1, -1, -1, -1, -1, -1, -1, -1};   // the launchers' report of this context's last GEMM (GemmParams::plan; opus_debug_gemm_plan)
-    bool xln_tiled = false;              // d_xln currently holds fp16(x) in fragment order
-    const float *xh_src = nullptr;       // fp32 buffer whose fp16 copy + sum-of-squares partials are valid
-    bool use_row_scale = false;          // one-shot: the next gemm() multiplies its rows by the rstd from d_ssq
+    // row-scale fusion (GemmParams::ssq_out / row_ssq): the rows' sums of squares, written by the GEMM that is asked for the fp16
+    // copy of its output (GemmAsk::xh) and read by the one that scales its rows (GemmAsk::rs_on)
     float *d_ssq = nullptr;
     int64_t ssq_cap = 0;                 // floats in d_ssq
-    int ssq_nblk = 0;                    // blocks per row the last producer wrote (N / 256: split-K reduce, embedding; N / 16: gemm_stream)
-    float row_eps = 0.f;
     // timing
     bool timing = false;
     int phase = PH_OTHER;
@@ -574,36 +552,67 @@ struct Timed {
     }
 };
 
+// What one GEMM call asks for beyond shape, operands and epilogue (the fusion fields of GemmParams), built in the statement of the
+// call: GemmAsk().copy16(c->d_xln).tiled_a(wo_tiled).  The defaults ask for nothing.
+struct GemmAsk {
+    half_t *xh = nullptr;                // row-scale producer: fp16 copy of the output here, sums of squares of its rows into d_ssq
+    int xh_tiled = 0;                    //   ... the copy in fragment order
+    bool rs_on = false;                  // row-scale consumer: rows times the rstd from d_ssq (rs_nblk blocks per row, as the
+    float rs_eps = 0.f;                  //   producer reported them)
+    int rs_nblk = 0;
+    const float *rope_cs = nullptr;      // ESM rotary in the epilogue (GemmParams::rope_*)
+    const int32_t *rope_pos = nullptr;
+    int rope_T = 0, rope_cols = 0, rope_qcols = 0;
+    float rope_qscale = 1.0f;
+    float *ln_part = nullptr;            // fused-norm producer (GemmParams::ln_*): partials here, fp16(x) into ln_xh; takes
+    half_t *ln_xh = nullptr;             //   precedence over the row-scale producer
+    const float *ln_stat = nullptr, *ln_colsum = nullptr;   // fused-norm consumer
+    int force_wide = 0, slab_only = 0;   // route a narrow output through the wide kernel / leave raw k-part slabs
+    int a_tiled = 0, c_tiled = 0;        // A is read / the fp16 output is written in fragment order
+    int *pp_plan = nullptr;              // (HOST) launch_pp reports its plan here
+    // setters; a null first pointer leaves that request unasked
+    GemmAsk &copy16(half_t *dst, bool tiled = false) { xh = dst; xh_tiled = dst && tiled; return *this; }
+    GemmAsk &scale_rows(float eps, int nblk) { rs_on = true; rs_eps = eps; rs_nblk = nblk; return *this; }
+    GemmAsk &rope(const float *cs, const int32_t *pos, int T, int D, float qscale) {   // the q and k thirds of [q k v] x D, q scaled
+        if (cs) { rope_cs = cs; rope_pos = pos; rope_T = T; rope_cols = 2 * D; rope_qcols = D; rope_qscale = qscale; }
+        return *this;
+    }
+    GemmAsk &ln_produce(float *part, half_t *x16) { if (part) { ln_part = part; ln_xh = x16; } return *this; }
+    GemmAsk &ln_consume(const float *stat, const float *colsum) { if (stat) { ln_stat = stat; ln_colsum = colsum; } return *this; }
+    GemmAsk &slabs() { force_wide = slab_only = 1; return *this; }
+    GemmAsk &tiled_a(int on) { a_tiled = on; return *this; }
+    GemmAsk &tiled_c(int on) { c_tiled = on; return *this; }
+    GemmAsk &report_pp(int *plan) { pp_plan = plan; return *this; }
+};
+// What the launch reports back: the row-scale producer's copy was written (ssq_nblk blocks of sums of squares per row), the rotary
+// ran in the epilogue, the norm partials were written; ks > 1: that many raw k-part slabs were left (slab_only).
+struct GemmGot {
+    int xh_done = 0, rope_done = 0, ln_done = 0, ks = 1, ssq_nblk = 0;
+};
+
 static int gemm_any(opus_ctx *c, hipStream_t s, const half_t *A, const float *Af, float eps, int64_t lda, const half_t *W,
                     int M, int N, int K, const float *bias, int epi, const float *residual, void *C, int64_t ldc,
-                    int out_f32) {
+                    int out_f32, const GemmAsk &ask = GemmAsk(), GemmGot *got = nullptr) {
+    GemmGot mine;
+    if (!got) got = &mine;
+    *got = GemmGot();
     GemmParams p;
     p.A = A; p.Af = Af; p.norm_eps = eps; p.lda = lda; p.W = W; p.M = M; p.N = N; p.K = K; p.bias = bias;
     p.residual = residual; p.ldr = ldc; p.C = C; p.ldc = ldc; p.out_f32 = out_f32; p.epi = epi;
     p.ws = c->gemm_ws; p.ws_bytes = c->gemm_ws_bytes;
-    p.xh_out = c->rq_xh; p.ssq_out = c->d_ssq; p.fused_done = &c->rq_done; p.ssq_cap = c->ssq_cap; p.nblk_out = &c->ssq_nblk;
-    c->rq_done = 0;
-    c->rq_xh = nullptr;                  // one-shot
-    p.rope_cs = c->rq_rope_cs; p.rope_T = c->rq_rope_T; p.rope_cols = c->rq_rope_cols; p.rope_qcols = c->rq_rope_qcols;
-    p.rope_qscale = c->rq_rope_qscale; p.rope_done = &c->rq_rope_done; p.rope_pos = c->rq_rope_pos;
-    c->rq_rope_done = 0;
-    c->rq_rope_cs = nullptr;             // one-shot
-    c->rq_rope_pos = nullptr;
+    p.xh_out = ask.xh; p.ssq_out = c->d_ssq; p.fused_done = &got->xh_done; p.ssq_cap = c->ssq_cap; p.nblk_out = &got->ssq_nblk;
+    p.rope_cs = ask.rope_cs; p.rope_T = ask.rope_T; p.rope_cols = ask.rope_cols; p.rope_qcols = ask.rope_qcols;
+    p.rope_qscale = ask.rope_qscale; p.rope_done = &got->rope_done; p.rope_pos = ask.rope_pos;
     p.row_ssq = nullptr; p.row_nblk = 0;
-    if (c->use_row_scale) { p.row_ssq = c->d_ssq; p.row_nblk = c->ssq_nblk; p.norm_eps = c->row_eps; c->use_row_scale = false; }
-    c->rq_ks = 1;
-    p.force_wide = c->rq_force_wide; p.slab_only = c->rq_slab_only; p.ks_out = &c->rq_ks;
-    c->rq_force_wide = c->rq_slab_only = 0;
-    c->rq_ln_done = 0;
-    if (c->rq_ln_part) { p.xh_out = c->rq_ln_xh; p.ssq_out = nullptr; p.ln_part = c->rq_ln_part; p.ln_done = &c->rq_ln_done; c->rq_ln_part = nullptr; }
-    if (c->rq_ln_stat) { p.ln_stat = c->rq_ln_stat; p.ln_colsum = c->rq_ln_colsum; c->rq_ln_stat = c->rq_ln_colsum = nullptr; }
+    if (ask.rs_on) { p.row_ssq = c->d_ssq; p.row_nblk = ask.rs_nblk; p.norm_eps = ask.rs_eps; }
+    p.force_wide = ask.force_wide; p.slab_only = ask.slab_only; p.ks_out = &got->ks;
+    if (ask.ln_part) { p.xh_out = ask.ln_xh; p.ssq_out = nullptr; p.ln_part = ask.ln_part; p.ln_done = &got->ln_done; }
+    if (ask.ln_stat) { p.ln_stat = ask.ln_stat; p.ln_colsum = ask.ln_colsum; }
     p.combine_cnt = c->d_cnt;
-    p.pp_plan = c->rq_pp_plan;
-    c->rq_pp_plan = nullptr;
+    p.pp_plan = ask.pp_plan;
     for (int i = 0; i < GEMM_PLAN_WORDS; ++i) c->gemm_plan[i] = -1;
     p.plan = c->gemm_plan;
-    p.a_tiled = c->rq_a_tiled; p.xh_tiled = c->rq_xh_tiled; p.c_tiled = c->rq_c_tiled;
-    c->rq_a_tiled = c->rq_xh_tiled = c->rq_c_tiled = 0;
+    p.a_tiled = ask.a_tiled; p.xh_tiled = ask.xh_tiled; p.c_tiled = ask.c_tiled;
     const int nout = epi == EPI_SILU_GU16 ? N / 2 : N;
     // algorithmic bytes: the weights once + activations in + result out (+ the residual read)
     const double bytes = 2.0 * N * K + (Af ? 4.0 : 2.0) * M * K + (double)M * nout * (out_f32 ? 4 : 2) +
@@ -618,9 +627,22 @@ static int gemm_any(opus_ctx *c, hipStream_t s, const half_t *A, const float *Af
     return OPUS_OK;
 }
 static int gemm(opus_ctx *c, hipStream_t s, const half_t *A, int64_t lda, const half_t *W, int M, int N, int K,
-                const float *bias, int epi, const float *residual, void *C, int64_t ldc, int out_f32) {
-    return gemm_any(c, s, A, nullptr, 0.f, lda, W, M, N, K, bias, epi, residual, C, ldc, out_f32);
+                const float *bias, int epi, const float *residual, void *C, int64_t ldc, int out_f32,
+                const GemmAsk &ask = GemmAsk(), GemmGot *got = nullptr) {
+    return gemm_any(c, s, A, nullptr, 0.f, lda, W, M, N, K, bias, epi, residual, C, ldc, out_f32, ask, got);
 }
+// The shadow of the residual stream inside one prefill / decode step: which fp32 buffer currently has a valid fp16 copy (d_xn /
+// d_xln) with the sums of squares of its rows in d_ssq.  A producer GEMM sets it from its outcome, every gemm_norm() consumes it.
+struct ResidShadow {
+    const float *xh_src = nullptr;       // fp32 buffer whose fp16 copy + sum-of-squares partials are valid
+    int ssq_nblk = 0;                    // blocks per row the producer wrote (N / 256: split-K reduce, embedding; N / 16: gemm_stream)
+    bool xln_tiled = false;              // d_xln holds that copy in fragment order
+    void produced(const float *x, const GemmGot &got, bool tiled = false) {
+        xh_src = got.xh_done ? x : nullptr;
+        if (got.xh_done) ssq_nblk = got.ssq_nblk;
+        xln_tiled = got.xh_done && tiled;
+    }
+};
 static bool fuse_rows() {
     static const bool off = getenv("OPUS_NO_ROW_FUSION") != nullptr;   // A/B aid
     return !off;
@@ -637,26 +659,25 @@ static bool fuse_rows() {
 #define KL(klass, bytes, call) KLF(klass, bytes, 0.0, call)
 
 // C = epi(rmsnorm(X) W'^T) with the norm weight pre-folded into W': fused in the skinny kernel (M <= 64),
-// otherwise a weight-less rmsnorm kernel into `scratch` followed by the tile kernel.
-static int gemm_norm(opus_ctx *c, hipStream_t s, const float *X, float eps, half_t *scratch, const half_t *W, int M, int N,
-                     int K, int epi, void *C, int64_t ldc, int out_f32, const float *bias = nullptr) {
+// otherwise a weight-less rmsnorm kernel into `scratch` followed by the tile kernel.  Consumes the shadow; `ask` goes to the
+// one GEMM that runs.
+static int gemm_norm(opus_ctx *c, hipStream_t s, ResidShadow &sh, const float *X, float eps, half_t *scratch, const half_t *W, int M,
+                     int N, int K, int epi, void *C, int64_t ldc, int out_f32, const float *bias = nullptr,
+                     const GemmAsk &ask = GemmAsk(), GemmGot *got = nullptr) {
     static const bool no_mid = getenv("OPUS_NO_MID_GEMM") != nullptr;
     static const bool mid_v1 = getenv("OPUS_MID_V1") != nullptr;
-    if (c->xh_src == X && bias == nullptr && (K & 255) == 0 && gemm_goes_wide(M, N)) {
+    const bool shadowed = sh.xh_src == X;
+    sh.xh_src = nullptr;
+    if (shadowed && bias == nullptr && (K & 255) == 0 && gemm_goes_wide(M, N))
         // the producer's split-K reduce left fp16(X) in `scratch` and per-block sums of squares: no norm launch, the
         // wide kernel scales its rows instead
-        c->xh_src = nullptr;
-        c->use_row_scale = true;
-        c->row_eps = eps;
-        return gemm(c, s, scratch, K, W, M, N, K, nullptr, epi, nullptr, C, ldc, out_f32);
-    }
-    c->xh_src = nullptr;
+        return gemm(c, s, scratch, K, W, M, N, K, nullptr, epi, nullptr, C, ldc, out_f32, GemmAsk(ask).scale_rows(eps, sh.ssq_nblk), got);
     // 17..64 rows with a wide output (wgu, lm_head): the wide kernel wants fp16 activations, so norm separately
     const bool wide = M > SKINNY_MAX_M && N >= 16384 && !mid_v1;
     if (M <= SKINNY_MAX_M || (M <= MID_MAX_M && !no_mid && !wide))
-        return gemm_any(c, s, nullptr, X, eps, K, W, M, N, K, bias, epi, nullptr, C, ldc, out_f32);
+        return gemm_any(c, s, nullptr, X, eps, K, W, M, N, K, bias, epi, nullptr, C, ldc, out_f32, ask, got);
     KL(KC_NORM, 6.0 * M * K, launch_rmsnorm(X, nullptr, eps, M, K, scratch, s));
-    return gemm(c, s, scratch, K, W, M, N, K, bias, epi, nullptr, C, ldc, out_f32);
+    return gemm(c, s, scratch, K, W, M, N, K, bias, epi, nullptr, C, ldc, out_f32, ask, got);
 }
 
 static int need_ready(opus_ctx *c) {
@@ -755,17 +776,15 @@ static int esm2_encode_rows(opus_ctx *c, hipStream_t s, const int32_t *d_tokens,
     else attn_flops = 4.0 * B * (double)T * T * D;
     for (int l = 0; l < g.enc_layers; ++l) {
         const EncLayer &L = c->enc[l];
-        if (have_stat && qkv_pp) { c->rq_ln_stat = c->e_stat; c->rq_ln_colsum = L.sqkv; }
+        GemmAsk qkv;
+        GemmGot got;
+        if (have_stat && qkv_pp) qkv.ln_consume(c->e_stat, L.sqkv);
         else KL(KC_NORM, 6.0 * M * D, launch_layernorm(c->e_x, nullptr, nullptr, g.enc_ln_eps, M, D, c->e_xn, nullptr, s));
         // q <- rotary(q * hd^-0.5), k <- rotary(k): in the projection's epilogue when the big tiled kernel takes it (head_dim 64),
         // else by the stand-alone kernel on the stored projection (same arithmetic)
-        if (hd == 64) {
-            c->rq_rope_cs = c->cs_enc; c->rq_rope_T = packed ? g.max_enc_tokens : T; c->rq_rope_cols = 2 * D; c->rq_rope_qcols = D;
-            c->rq_rope_qscale = 1.0f / sqrtf((float)hd);
-            c->rq_rope_pos = packed ? c->e_pos : nullptr;
-        }
-        OPC(gemm(c, s, c->e_xn, D, L.wqkv, M, 3 * D, D, L.bqkv, EPI_NONE, nullptr, c->e_qkv, 3 * D, 0));
-        if (!c->rq_rope_done) {
+        if (hd == 64) qkv.rope(c->cs_enc, packed ? c->e_pos : nullptr, packed ? g.max_enc_tokens : T, D, 1.0f / sqrtf((float)hd));
+        OPC(gemm(c, s, c->e_xn, D, L.wqkv, M, 3 * D, D, L.bqkv, EPI_NONE, nullptr, c->e_qkv, 3 * D, 0, qkv, &got));
+        if (!got.rope_done) {
             if (packed) KL(KC_OTHER, 8.0 * M * D, launch_esm_rope(c->e_qkv, c->cs_enc, 1, M, nh, hd, 1.0f / sqrtf((float)hd), s, c->e_pos));
             else KL(KC_OTHER, 8.0 * M * D, launch_esm_rope(c->e_qkv, c->cs_enc, B, T, nh, hd, 1.0f / sqrtf((float)hd), s));
         }
@@ -782,15 +801,14 @@ static int esm2_encode_rows(opus_ctx *c, hipStream_t s, const int32_t *d_tokens,
         // holds no representation in those rows; knob "enc_full_last_layer" = 1 computes them (parity tests of every token's state).
         a.q_trim = packed && l + 1 == g.enc_layers && T > 2 && !g_knobs.enc_full_last_layer ? 1 : 0;
         KLF(KC_ATTN_PREFILL, 8.0 * M * D, attn_flops, launch_attn_prefill(a, s));
-        if (fc1_pp) { c->rq_ln_part = c->e_part; c->rq_ln_xh = c->e_xn; }
-        OPC(gemm(c, s, c->e_ctx, D, L.wo, M, D, D, L.bo, EPI_NONE, c->e_x, c->e_x, D, 1));
-        have_stat = c->rq_ln_done != 0;
-        if (have_stat) { OPC(finalize()); c->rq_ln_stat = c->e_stat; c->rq_ln_colsum = L.s1; }
+        OPC(gemm(c, s, c->e_ctx, D, L.wo, M, D, D, L.bo, EPI_NONE, c->e_x, c->e_x, D, 1, GemmAsk().ln_produce(fc1_pp ? c->e_part : nullptr, c->e_xn), &got));
+        have_stat = got.ln_done != 0;
+        if (have_stat) OPC(finalize());
         else KL(KC_NORM, 6.0 * M * D, launch_layernorm(c->e_x, nullptr, nullptr, g.enc_ln_eps, M, D, c->e_xn, nullptr, s));
-        OPC(gemm(c, s, c->e_xn, D, L.w1, M, F, D, L.b1, EPI_GELU, nullptr, c->e_h1, F, 0));
-        if (qkv_pp && l + 1 < g.enc_layers) { c->rq_ln_part = c->e_part; c->rq_ln_xh = c->e_xn; }
-        OPC(gemm(c, s, c->e_h1, F, L.w2, M, D, F, L.b2, EPI_NONE, c->e_x, c->e_x, D, 1));
-        have_stat = c->rq_ln_done != 0;
+        OPC(gemm(c, s, c->e_xn, D, L.w1, M, F, D, L.b1, EPI_GELU, nullptr, c->e_h1, F, 0, GemmAsk().ln_consume(have_stat ? c->e_stat : nullptr, L.s1)));
+        const bool next_pp = qkv_pp && l + 1 < g.enc_layers;
+        OPC(gemm(c, s, c->e_h1, F, L.w2, M, D, F, L.b2, EPI_NONE, c->e_x, c->e_x, D, 1, GemmAsk().ln_produce(next_pp ? c->e_part : nullptr, c->e_xn), &got));
+        have_stat = got.ln_done != 0;
         if (have_stat) OPC(finalize());
     }
     KL(KC_NORM, 8.0 * M * D, launch_layernorm(c->e_x, c->enc_lnfw, c->enc_lnfb, g.enc_ln_eps, M, D, nullptr, c->e_hid, s));
@@ -1138,9 +1156,9 @@ extern "C" int opus_splice_pad(opus_ctx *c, const int64_t *d_ids, const uint8_t 
 }
 
 // ------------------------------------------------------------------------------------------------ decoder
-static int lm_head(opus_ctx *c, hipStream_t s, int B, float *out = nullptr) {
+static int lm_head(opus_ctx *c, hipStream_t s, ResidShadow &sh, int B, float *out = nullptr) {
     const opus_config &g = c->cfg;   // final RMSNorm (folded weight) fused into the lm_head GEMM
-    return gemm_norm(c, s, c->d_xl, g.dec_rms_eps, c->d_xln, c->lm_head, B, g.dec_vocab, g.dec_dim, EPI_NONE, out ? out : c->d_logits,
+    return gemm_norm(c, s, sh, c->d_xl, g.dec_rms_eps, c->d_xln, c->lm_head, B, g.dec_vocab, g.dec_dim, EPI_NONE, out ? out : c->d_logits,
                      g.dec_vocab, 1);
 }
 
@@ -1162,10 +1180,26 @@ static int reset_step(opus_ctx *c, hipStream_t s, int T0, int step = 0) {
     return OPUS_OK;
 }
 
+// End of a prefill that keeps the last position only: the rows' last residual into d_xl (unless the last-layer tail left it there),
+// the family's lm_head (`head(out)`; nret > 1: into d_probs, fanned out from there), the step words and the decode state.
+template <class Head>
+static int finish_prefill(opus_ctx *c, hipStream_t s, int B, int T, int nret, bool have_last, Head head) {
+    const int H = c->cfg.dec_dim;
+    if (!have_last) KL(KC_OTHER, 8.0 * B * H, launch_take_last(c->d_x, B, T, H, c->d_xl, s));
+    OPC(head(nret > 1 ? c->d_probs : nullptr));
+    if (nret > 1) OPC(fanout_rows(c, s, B, nret));
+    OPC(reset_step(c, s, T));
+    c->cur_B = B * nret;
+    c->cur_T = T;
+    c->prefilled = true;
+    return OPUS_OK;
+}
+
 // decode-step attention of layer l over the projection output in d_qkv (rows of the last prefill, T prompt positions)
 // (slab_ks > 0: the QKV GEMM left slab_ks raw k-part slabs in the GEMM workspace and the sums of squares of its input rows in
-// d_ssq: summed, scaled and biased by the attention kernel itself)
-static int attn_decode(opus_ctx *c, hipStream_t s, int l, int B, int T, int slab_ks = 0, const float *bias = nullptr, int out_tiled = 0) {
+// d_ssq, sh.ssq_nblk blocks per row: summed, scaled and biased by the attention kernel itself)
+static int attn_decode(opus_ctx *c, hipStream_t s, const ResidShadow &sh, int l, int B, int T, int slab_ks = 0, const float *bias = nullptr,
+                       int out_tiled = 0) {
     const opus_config &g = c->cfg;
     AttnDecodeParams a;
     a.qkv = c->d_qkv; a.slabs = nullptr; a.ks = 0; a.slab_stride = 0; a.row_ssq = nullptr; a.row_nblk = 0; a.eps = 0.f; a.K = 0;
@@ -1173,7 +1207,7 @@ static int attn_decode(opus_ctx *c, hipStream_t s, int l, int B, int T, int slab
     if (slab_ks > 0) {
         const int64_t QKVd = (int64_t)(g.dec_heads + 2 * g.dec_kv_heads) * g.dec_head_dim;
         a.qkv = nullptr; a.slabs = c->gemm_ws; a.ks = slab_ks; a.slab_stride = (int64_t)B * QKVd;
-        a.row_ssq = c->d_ssq; a.row_nblk = c->ssq_nblk; a.eps = g.dec_rms_eps; a.K = g.dec_dim; a.bias = bias;
+        a.row_ssq = c->d_ssq; a.row_nblk = sh.ssq_nblk; a.eps = g.dec_rms_eps; a.K = g.dec_dim; a.bias = bias;
     }
     a.cs_row = c->cs_row; a.kstart = c->d_kstart; a.step = c->d_step; a.T0 = -1; a.nh = g.dec_heads; a.nkv = g.dec_kv_heads;   // (T0 < 0: d_step[1])
     a.kc = c->kc + l * c->cache_sl; a.vc = c->vc + l * c->cache_sl; a.cache_sb = c->cache_sb; a.cache_sh = c->cache_sh;
@@ -1202,32 +1236,39 @@ static int attn_prefix(opus_ctx *c, hipStream_t s, const ContRows &cr, int l, in
     return OPUS_OK;
 }
 
+// prefill attention of layer l over the B T projection rows in d_qkv: rotary + append to the KV cache (nret copies of every row) +
+// causal attention; continuation rows (cont): rotary at their own positions, no cache write, attention behind the cached prefix
+static int attn_prefill(opus_ctx *c, hipStream_t s, int l, int B, int T, const ContRows *cont, int nret) {
+    const opus_config &g = c->cfg;
+    const int nh = g.dec_heads, nkv = g.dec_kv_heads, hd = g.dec_head_dim, QKV = (nh + 2 * nkv) * hd, QD = nh * hd, M = B * T;
+    if (cont) {
+        KL(KC_OTHER, 4.0 * M * QKV, launch_dec_rope_cache(c->d_qkv, c->cs_dec, cont->nkst, B, T, nh, nkv, hd, nullptr, nullptr, 0, 0, s));
+        return attn_prefix(c, s, *cont, l, M);
+    }
+    KL(KC_OTHER, 4.0 * M * QKV,
+       launch_dec_rope_cache(c->d_qkv, c->cs_dec, c->d_kstart, B, T, nh, nkv, hd, c->kc + l * c->cache_sl,
+                             c->vc + l * c->cache_sl, c->cache_sb, c->cache_sh, s, nret));
+    AttnParams a;
+    a.Q = c->d_qkv; a.K = c->d_qkv + QD; a.V = c->d_qkv + QD + nkv * hd;
+    a.q_sb = a.k_sb = a.v_sb = (int64_t)T * QKV;
+    a.q_st = a.k_st = a.v_st = QKV;
+    a.O = c->d_ctx; a.o_sb = (int64_t)T * QD; a.o_st = QD;
+    a.kstart = c->d_kstart; a.kend = nullptr;
+    a.B = B; a.T = T; a.heads = nh; a.group = nh / nkv; a.head_dim = hd; a.causal = 1;
+    a.scale = 1.0f / sqrtf((float)hd);
+    KLF(KC_ATTN_PREFILL, 2.0 * M * (QKV + QD), 2.0 * B * (double)T * T * QD, launch_attn_prefill(a, s));
+    return OPUS_OK;
+}
+
 static int opt_layer(opus_ctx *c, hipStream_t s, const DecLayer &L, int l, float *x, half_t *xn, int M, int B, int T, bool decode,
                      const ContRows *cont = nullptr, int nret = 1) {
     const opus_config &g = c->cfg;
-    const int H = g.dec_dim, F = g.dec_ffn, nh = g.dec_heads, nkv = g.dec_kv_heads, hd = g.dec_head_dim;
-    const int QKV = (nh + 2 * nkv) * hd, QD = nh * hd;
+    const int H = g.dec_dim, F = g.dec_ffn;
+    const int QKV = (g.dec_heads + 2 * g.dec_kv_heads) * g.dec_head_dim, QD = g.dec_heads * g.dec_head_dim;
     KL(KC_NORM, 6.0 * M * H, launch_layernorm(x, L.ln1w, L.ln1b, g.dec_rms_eps, M, H, xn, nullptr, s));
     OPC(gemm(c, s, xn, H, L.wqkv, M, QKV, H, L.bqkv, EPI_NONE, nullptr, c->d_qkv, QKV, 0));
-    if (decode) {
-        OPC(attn_decode(c, s, l, B, T));
-    } else if (cont) {
-        KL(KC_OTHER, 4.0 * M * QKV, launch_dec_rope_cache(c->d_qkv, c->cs_dec, cont->nkst, B, T, nh, nkv, hd, nullptr, nullptr, 0, 0, s));
-        OPC(attn_prefix(c, s, *cont, l, M));
-    } else {
-        KL(KC_OTHER, 4.0 * M * QKV,
-           launch_dec_rope_cache(c->d_qkv, c->cs_dec, c->d_kstart, B, T, nh, nkv, hd, c->kc + l * c->cache_sl,
-                                 c->vc + l * c->cache_sl, c->cache_sb, c->cache_sh, s, nret));
-        AttnParams a;
-        a.Q = c->d_qkv; a.K = c->d_qkv + QD; a.V = c->d_qkv + QD + nkv * hd;
-        a.q_sb = a.k_sb = a.v_sb = (int64_t)T * QKV;
-        a.q_st = a.k_st = a.v_st = QKV;
-        a.O = c->d_ctx; a.o_sb = (int64_t)T * QD; a.o_st = QD;
-        a.kstart = c->d_kstart; a.kend = nullptr;
-        a.B = B; a.T = T; a.heads = nh; a.group = nh / nkv; a.head_dim = hd; a.causal = 1;
-        a.scale = 1.0f / sqrtf((float)hd);
-        KLF(KC_ATTN_PREFILL, 2.0 * M * (QKV + QD), 2.0 * B * (double)T * T * QD, launch_attn_prefill(a, s));
-    }
+    if (decode) OPC(attn_decode(c, s, ResidShadow(), l, B, T));
+    else OPC(attn_prefill(c, s, l, B, T, cont, nret));
     OPC(gemm(c, s, c->d_ctx, QD, L.wo, M, H, QD, L.bo, EPI_NONE, x, x, H, 1));
     KL(KC_NORM, 6.0 * M * H, launch_layernorm(x, L.ln2w, L.ln2b, g.dec_rms_eps, M, H, xn, nullptr, s));
     if (g.dec_act == 0) {
@@ -1257,14 +1298,7 @@ static int prefill_opt(opus_ctx *c, hipStream_t s, const half_t *embeds, const u
     KL(KC_OTHER, 10.0 * M * H, launch_add_pos(c->d_x, c->dec_pos, cont ? cont->nkst : c->d_kstart, nullptr, 0, B, T, H, g.dec_max_pos + 1, s));
     for (int l = 0; l < g.dec_layers; ++l) OPC(opt_layer(c, s, c->dec[l], l, c->d_x, c->d_xn, M, B, T, false, cont, nret));
     if (all_rows) return OPUS_OK;
-    KL(KC_OTHER, 8.0 * B * H, launch_take_last(c->d_x, B, T, H, c->d_xl, s));
-    OPC(lm_head_opt(c, s, B, nret > 1 ? c->d_probs : nullptr));
-    if (nret > 1) OPC(fanout_rows(c, s, B, nret));
-    OPC(reset_step(c, s, T));
-    c->cur_B = B * nret;
-    c->cur_T = T;
-    c->prefilled = true;
-    return OPUS_OK;
+    return finish_prefill(c, s, B, T, nret, false, [&](float *out) { return lm_head_opt(c, s, B, out); });
 }
 
 // the embedded new tokens are already in d_xl (decode_step)
@@ -1315,31 +1349,16 @@ static int prefill(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8
         KL(KC_NORM, 8.0 * M * (H / 64) + 8.0 * M, launch_ln_finalize(c->d_part, M, H / 64, H, g.dec_rms_eps, 1, c->d_stat, s));
         return OPUS_OK;
     };
+    ResidShadow sh;
+    GemmGot got;
     for (int l = 0; l < g.dec_layers; ++l) {
         const DecLayer &L = c->dec[l];
         if (have_stat && qkv_pp) {
-            c->rq_ln_stat = c->d_stat;
-            OPC(gemm(c, s, c->d_xn, H, L.wqkv, M, QKV, H, L.bqkv, EPI_NONE, nullptr, c->d_qkv, QKV, 0));
+            OPC(gemm(c, s, c->d_xn, H, L.wqkv, M, QKV, H, L.bqkv, EPI_NONE, nullptr, c->d_qkv, QKV, 0, GemmAsk().ln_consume(c->d_stat, nullptr)));
         } else {
-            OPC(gemm_norm(c, s, c->d_x, g.dec_rms_eps, c->d_xn, L.wqkv, M, QKV, H, EPI_NONE, c->d_qkv, QKV, 0, L.bqkv));
+            OPC(gemm_norm(c, s, sh, c->d_x, g.dec_rms_eps, c->d_xn, L.wqkv, M, QKV, H, EPI_NONE, c->d_qkv, QKV, 0, L.bqkv));
         }
-        if (cont) {
-            KL(KC_OTHER, 4.0 * M * QKV, launch_dec_rope_cache(c->d_qkv, c->cs_dec, cont->nkst, B, T, nh, nkv, hd, nullptr, nullptr, 0, 0, s));
-            OPC(attn_prefix(c, s, *cont, l, M));
-        } else {
-            KL(KC_OTHER, 4.0 * M * QKV,
-               launch_dec_rope_cache(c->d_qkv, c->cs_dec, c->d_kstart, B, T, nh, nkv, hd, c->kc + l * c->cache_sl,
-                                     c->vc + l * c->cache_sl, c->cache_sb, c->cache_sh, s, nret));
-            AttnParams a;
-            a.Q = c->d_qkv; a.K = c->d_qkv + QD; a.V = c->d_qkv + QD + nkv * hd;
-            a.q_sb = a.k_sb = a.v_sb = (int64_t)T * QKV;
-            a.q_st = a.k_st = a.v_st = QKV;
-            a.O = c->d_ctx; a.o_sb = (int64_t)T * QD; a.o_st = QD;
-            a.kstart = c->d_kstart; a.kend = nullptr;
-            a.B = B; a.T = T; a.heads = nh; a.group = nh / nkv; a.head_dim = hd; a.causal = 1;
-            a.scale = 1.0f / sqrtf((float)hd);
-            KLF(KC_ATTN_PREFILL, 2.0 * M * (QKV + QD), 2.0 * B * (double)T * T * QD, launch_attn_prefill(a, s));
-        }
+        OPC(attn_prefill(c, s, l, B, T, cont, nret));
         if (l + 1 == g.dec_layers && T > 1 && !all_rows && !g_knobs.misc[7]) {
             // Last layer: its K / V are in the cache for every position, but behind the attention only the LAST position of a row
             // is ever used (lm_head reads that row alone, opus_arch.py -> HF generate keeps the last logits): wo, gate/up and
@@ -1348,49 +1367,34 @@ static int prefill(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8
             half_t *ctx_last = c->d_qkv;                              // (the projections are consumed: the buffer is free)
             KL(KC_OTHER, 4.0 * B * QD, launch_take_last(reinterpret_cast<const float *>(c->d_ctx), B, T, QD / 2, reinterpret_cast<float *>(ctx_last), s));
             KL(KC_OTHER, 8.0 * B * H, launch_take_last(c->d_x, B, T, H, c->d_xl, s));
-            if (fuse_rows() && B <= 96) c->rq_xh = c->d_xln;
-            OPC(gemm(c, s, ctx_last, QD, L.wo, B, H, QD, nullptr, EPI_NONE, c->d_xl, c->d_xl, H, 1));
-            c->xh_src = c->rq_done ? c->d_xl : nullptr;
-            OPC(gemm_norm(c, s, c->d_xl, g.dec_rms_eps, c->d_xln, L.wgu, B, 2 * F, H, EPI_SILU_GU16, c->d_act, F, 0));
-            if (fuse_rows() && B <= 96) c->rq_xh = c->d_xln;
-            OPC(gemm(c, s, c->d_act, F, L.wd, B, H, F, nullptr, EPI_NONE, c->d_xl, c->d_xl, H, 1));
-            c->xh_src = c->rq_done ? c->d_xl : nullptr;
-            c->xln_tiled = false;
+            const GemmAsk copy_xl = GemmAsk().copy16(fuse_rows() && B <= 96 ? c->d_xln : nullptr);
+            OPC(gemm(c, s, ctx_last, QD, L.wo, B, H, QD, nullptr, EPI_NONE, c->d_xl, c->d_xl, H, 1, copy_xl, &got));
+            sh.produced(c->d_xl, got);
+            OPC(gemm_norm(c, s, sh, c->d_xl, g.dec_rms_eps, c->d_xln, L.wgu, B, 2 * F, H, EPI_SILU_GU16, c->d_act, F, 0));
+            OPC(gemm(c, s, c->d_act, F, L.wd, B, H, F, nullptr, EPI_NONE, c->d_xl, c->d_xl, H, 1, copy_xl, &got));
+            sh.produced(c->d_xl, got);
             last_rows_done = true;
             break;
         }
-        if (gu_pp) { c->rq_ln_part = c->d_part; c->rq_ln_xh = c->d_xn; }
-        else if (fuse_rows() && M <= 96) c->rq_xh = c->d_xn;      // (d_ssq holds 128 rows)
-        OPC(gemm(c, s, c->d_ctx, QD, L.wo, M, H, QD, nullptr, EPI_NONE, c->d_x, c->d_x, H, 1));
-        c->xh_src = c->rq_done ? c->d_x : nullptr;
-        have_stat = c->rq_ln_done != 0;
+        GemmAsk wo;
+        if (gu_pp) wo.ln_produce(c->d_part, c->d_xn);
+        else if (fuse_rows() && M <= 96) wo.copy16(c->d_xn);      // (d_ssq holds 128 rows)
+        OPC(gemm(c, s, c->d_ctx, QD, L.wo, M, H, QD, nullptr, EPI_NONE, c->d_x, c->d_x, H, 1, wo, &got));
+        sh.produced(c->d_x, got);
+        have_stat = got.ln_done != 0;
         if (have_stat) {
             OPC(finalize());
-            c->rq_ln_stat = c->d_stat;
-            OPC(gemm(c, s, c->d_xn, H, L.wgu, M, 2 * F, H, nullptr, EPI_SILU_GU16, nullptr, c->d_act, F, 0));
+            OPC(gemm(c, s, c->d_xn, H, L.wgu, M, 2 * F, H, nullptr, EPI_SILU_GU16, nullptr, c->d_act, F, 0, GemmAsk().ln_consume(c->d_stat, nullptr)));
         } else {
-            OPC(gemm_norm(c, s, c->d_x, g.dec_rms_eps, c->d_xn, L.wgu, M, 2 * F, H, EPI_SILU_GU16, c->d_act, F, 0));
+            OPC(gemm_norm(c, s, sh, c->d_x, g.dec_rms_eps, c->d_xn, L.wgu, M, 2 * F, H, EPI_SILU_GU16, c->d_act, F, 0));
         }
-        if (qkv_pp && l + 1 < g.dec_layers) { c->rq_ln_part = c->d_part; c->rq_ln_xh = c->d_xn; }
-        OPC(gemm(c, s, c->d_act, F, L.wd, M, H, F, nullptr, EPI_NONE, c->d_x, c->d_x, H, 1));
-        have_stat = c->rq_ln_done != 0;
+        const bool next_pp = qkv_pp && l + 1 < g.dec_layers;
+        OPC(gemm(c, s, c->d_act, F, L.wd, M, H, F, nullptr, EPI_NONE, c->d_x, c->d_x, H, 1, GemmAsk().ln_produce(next_pp ? c->d_part : nullptr, c->d_xn), &got));
+        have_stat = got.ln_done != 0;
         if (have_stat) OPC(finalize());
     }
-    if (all_rows) {
-        c->xh_src = nullptr;
-        return OPUS_OK;
-    }
-    if (!last_rows_done) {
-        KL(KC_OTHER, 8.0 * B * H, launch_take_last(c->d_x, B, T, H, c->d_xl, s));
-        c->xh_src = nullptr;
-    }
-    OPC(lm_head(c, s, B, nret > 1 ? c->d_probs : nullptr));
-    if (nret > 1) OPC(fanout_rows(c, s, B, nret));
-    OPC(reset_step(c, s, T));
-    c->cur_B = B * nret;
-    c->cur_T = T;
-    c->prefilled = true;
-    return OPUS_OK;
+    if (all_rows) return OPUS_OK;
+    return finish_prefill(c, s, B, T, nret, last_rows_done, [&](float *out) { return lm_head(c, s, sh, B, out); });
 }
 
 // One decode step for the token ids in d_tok (device): embeds them, runs the stack at slot T + *step,
@@ -1414,46 +1418,37 @@ static int decode_step(opus_ctx *c, hipStream_t s, const int32_t *d_tok) {
     KL(KC_OTHER, 6.0 * B * H, launch_embed_tokens(d_tok, c->dec_emb, B, H, g.dec_vocab, c->d_xl, rowscale ? c->d_xln : nullptr,
                                                   rowscale ? c->d_ssq : nullptr, qkv_tiled ? 1 : 0, c->cs_dec, c->d_kstart, c->d_step, -1,
                                                   hd / 2, c->cs_row, c->d_cnt, HANDOFF_ERR, s));     // (+ zeroes the hand-off words; T0 < 0: d_step[1])
-    c->xln_tiled = qkv_tiled;
-    c->xh_src = rowscale ? c->d_xl : nullptr;
-    if (rowscale) c->ssq_nblk = H >> 8;
     if (g.dec_arch == 1) return decode_step_opt(c, s);
+    ResidShadow sh;                      // (the embedding kernel is the first producer)
+    if (rowscale) { sh.xh_src = c->d_xl; sh.ssq_nblk = H >> 8; sh.xln_tiled = qkv_tiled; }
+    GemmGot got;
+    half_t *const copy_xl = fuse_rows() && B <= 96 ? c->d_xln : nullptr;   // fp16(x) + sums of squares, asked of wo and down
     for (int l = 0; l < g.dec_layers; ++l) {
         const DecLayer &L = c->dec[l];
-        if (rowscale && c->xh_src == c->d_xl) {
+        if (rowscale && sh.xh_src == c->d_xl) {
             // x is available as fp16 + sums of squares (from the embedding or the previous layer's down GEMM): the QKV
             // projection streams its weights through the wide kernel with k-parts and leaves the raw slabs; the attention
             // kernel sums them, applies the RMSNorm row scale and the bias on the fly - no norm launch, no reduce launch
-            c->xh_src = nullptr;
-            c->rq_force_wide = 1;
-            c->rq_slab_only = 1;
-            c->use_row_scale = true;
-            c->row_eps = g.dec_rms_eps;
-            c->rq_a_tiled = c->xln_tiled ? 1 : 0;
-            OPC(gemm(c, s, c->d_xln, H, L.wqkv, B, QKV, H, L.bqkv, EPI_NONE, nullptr, c->d_qkv, QKV, 0));
-            OPC(attn_decode(c, s, l, B, T, c->rq_ks > 1 ? c->rq_ks : 0, L.bqkv, wo_tiled ? 1 : 0));
+            sh.xh_src = nullptr;
+            OPC(gemm(c, s, c->d_xln, H, L.wqkv, B, QKV, H, L.bqkv, EPI_NONE, nullptr, c->d_qkv, QKV, 0,
+                     GemmAsk().slabs().scale_rows(g.dec_rms_eps, sh.ssq_nblk).tiled_a(sh.xln_tiled), &got));
+            OPC(attn_decode(c, s, sh, l, B, T, got.ks > 1 ? got.ks : 0, L.bqkv, wo_tiled ? 1 : 0));
         } else {
-            OPC(gemm_norm(c, s, c->d_xl, g.dec_rms_eps, c->d_xln, L.wqkv, B, QKV, H, EPI_NONE, c->d_qkv, QKV, 0, L.bqkv));
-            OPC(attn_decode(c, s, l, B, T, 0, nullptr, wo_tiled ? 1 : 0));
+            OPC(gemm_norm(c, s, sh, c->d_xl, g.dec_rms_eps, c->d_xln, L.wqkv, B, QKV, H, EPI_NONE, c->d_qkv, QKV, 0, L.bqkv));
+            OPC(attn_decode(c, s, sh, l, B, T, 0, nullptr, wo_tiled ? 1 : 0));
         }
-        c->xln_tiled = false;
-        if (fuse_rows() && B <= 96) c->rq_xh = c->d_xln;                 // (row-major: the gate/up kernel stages it by LDS-DMA)
-        c->rq_a_tiled = wo_tiled ? 1 : 0;
-        OPC(gemm(c, s, c->d_ctx, QD, L.wo, B, H, QD, nullptr, EPI_NONE, c->d_xl, c->d_xl, H, 1));
-        c->xh_src = c->rq_done ? c->d_xl : nullptr;
+        // (the copy row-major: the gate/up kernel stages it by LDS-DMA)
+        OPC(gemm(c, s, c->d_ctx, QD, L.wo, B, H, QD, nullptr, EPI_NONE, c->d_xl, c->d_xl, H, 1, GemmAsk().copy16(copy_xl).tiled_a(wo_tiled), &got));
+        sh.produced(c->d_xl, got);
         // the gate / up kernel writes silu(g) u in fragment order when the down projection will read it that way (only the wide
         // kernel - the row-scale form of gemm_norm - writes that layout)
-        const bool act_tiled = down_tiled && c->xh_src == c->d_xl && gemm_goes_wide(B, 2 * F);
-        c->rq_c_tiled = act_tiled ? 1 : 0;
-        OPC(gemm_norm(c, s, c->d_xl, g.dec_rms_eps, c->d_xln, L.wgu, B, 2 * F, H, EPI_SILU_GU16, c->d_act, F, 0));
+        const bool act_tiled = down_tiled && sh.xh_src == c->d_xl && gemm_goes_wide(B, 2 * F);
+        OPC(gemm_norm(c, s, sh, c->d_xl, g.dec_rms_eps, c->d_xln, L.wgu, B, 2 * F, H, EPI_SILU_GU16, c->d_act, F, 0, nullptr, GemmAsk().tiled_c(act_tiled)));
         const bool next_tiled = qkv_tiled && l + 1 < g.dec_layers;      // (the last layer's fp16(x) feeds lm_head: row-major)
-        if (fuse_rows() && B <= 96) { c->rq_xh = c->d_xln; c->rq_xh_tiled = next_tiled ? 1 : 0; }
-        c->rq_a_tiled = act_tiled ? 1 : 0;
-        OPC(gemm(c, s, c->d_act, F, L.wd, B, H, F, nullptr, EPI_NONE, c->d_xl, c->d_xl, H, 1));
-        c->xh_src = c->rq_done ? c->d_xl : nullptr;
-        c->xln_tiled = c->rq_done && next_tiled;
+        OPC(gemm(c, s, c->d_act, F, L.wd, B, H, F, nullptr, EPI_NONE, c->d_xl, c->d_xl, H, 1, GemmAsk().copy16(copy_xl, next_tiled).tiled_a(act_tiled), &got));
+        sh.produced(c->d_xl, got, next_tiled);
     }
-    OPC(lm_head(c, s, B));
+    OPC(lm_head(c, s, sh, B));
     KL(KC_OTHER, 8.0, launch_step_advance(c->d_step, s));
     return OPUS_OK;
 }
@@ -1555,12 +1550,12 @@ static int score_rows(opus_ctx *c, hipStream_t s, const float *X, int n, half_t 
                       float *lse) {
     const opus_config &g = c->cfg;
     const int H = g.dec_dim, V = g.dec_vocab;
-    c->xh_src = nullptr;
     if (g.dec_arch == 1) {
         KL(KC_NORM, 6.0 * n * H, launch_layernorm(X, c->dec_lnfw, c->dec_lnfb, g.dec_rms_eps, n, H, c->d_xn, nullptr, s));
         OPC(gemm(c, s, c->d_xn, H, c->lm_head, n, V, H, nullptr, EPI_NONE, nullptr, logits, V, 0));
     } else {   // RMSNorm folded into lm_head: fused into the skinny / mid kernels, a weight-less norm into d_xn otherwise
-        OPC(gemm_norm(c, s, X, g.dec_rms_eps, c->d_xn, c->lm_head, n, V, H, EPI_NONE, logits, V, 0));
+        ResidShadow none;                // (gathered rows: no producer left a copy of them)
+        OPC(gemm_norm(c, s, none, X, g.dec_rms_eps, c->d_xn, c->lm_head, n, V, H, EPI_NONE, logits, V, 0));
     }
     KL(KC_XENT, 2.0 * n * V + 12.0 * n, launch_xent(logits, V, n, V, targets, logprob, lse, s));
     return OPUS_OK;
@@ -2555,9 +2550,9 @@ extern "C" int opus_debug_gemm(opus_ctx *c, const void *A, const void *W, const 
     if (epi < 0 || epi > 2 || (epi == 2 && N % 32)) return fail(OPUS_EBADARG, "debug_gemm: epilogue");
     HIPC(hipSetDevice(c->device));
     const int nout = epi == EPI_SILU_GU16 ? N / 2 : N;
-    c->rq_a_tiled = g_knobs.debug_a_tiled;     // (tests: A handed over in fragment order, ceil(M / 16) * 16 rows)
+    // (tests: A handed over in fragment order, ceil(M / 16) * 16 rows)
     return gemm(c, (hipStream_t)stream, (const half_t *)A, K, (const half_t *)W, M, N, K, bias, epi, residual, Cp, nout,
-                out_f32);
+                out_f32, GemmAsk().tiled_a(g_knobs.debug_a_tiled));
 }
 
 extern "C" int opus_debug_gemm_norm(opus_ctx *c, const float *A, const void *W, void *Cp, int32_t M, int32_t N, int32_t K,
@@ -2586,12 +2581,11 @@ extern "C" int opus_debug_gemm_rope(opus_ctx *c, const void *A, const void *W, c
     HIPC(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const float qs = 1.0f / sqrtf((float)hd);
-    if (allow_fuse && hd == 64) {
-        c->rq_rope_cs = c->cs_enc; c->rq_rope_T = T; c->rq_rope_cols = 2 * D; c->rq_rope_qcols = D; c->rq_rope_qscale = qs;
-    }
-    OPC(gemm(c, s, (const half_t *)A, K, (const half_t *)W, M, 3 * D, K, bias, EPI_NONE, nullptr, out, 3 * D, 0));
-    *fused = c->rq_rope_done;
-    if (!c->rq_rope_done) HIPC(launch_esm_rope((half_t *)out, c->cs_enc, M / T, T, heads, hd, qs, s));
+    GemmGot got;
+    OPC(gemm(c, s, (const half_t *)A, K, (const half_t *)W, M, 3 * D, K, bias, EPI_NONE, nullptr, out, 3 * D, 0,
+             GemmAsk().rope(allow_fuse && hd == 64 ? c->cs_enc : nullptr, nullptr, T, D, qs), &got));
+    *fused = got.rope_done;
+    if (!got.rope_done) HIPC(launch_esm_rope((half_t *)out, c->cs_enc, M / T, T, heads, hd, qs, s));
     return OPUS_OK;
 }
 
@@ -2608,12 +2602,14 @@ extern "C" int opus_debug_gemm_rowscale(opus_ctx *c, const void *A, const void *
     if ((int64_t)M * N1 > (int64_t)g.max_batch * g.max_prompt * g.dec_dim) return fail(OPUS_ESHAPE, "debug_gemm_rowscale: M * N1 exceeds the scratch");
     HIPC(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    if (fuse_rows() && M <= 96) c->rq_xh = c->d_xn;
-    OPC(gemm(c, s, (const half_t *)A, K1, (const half_t *)W1, M, N1, K1, nullptr, EPI_NONE, X, X, N1, 1));
-    c->xh_src = c->rq_done ? X : nullptr;
-    *fused = c->xh_src != nullptr && (N1 & 255) == 0 && gemm_goes_wide(M, N2) ? 1 : 0;
+    ResidShadow sh;
+    GemmGot got;
+    OPC(gemm(c, s, (const half_t *)A, K1, (const half_t *)W1, M, N1, K1, nullptr, EPI_NONE, X, X, N1, 1,
+             GemmAsk().copy16(fuse_rows() && M <= 96 ? c->d_xn : nullptr), &got));
+    sh.produced(X, got);
+    *fused = sh.xh_src != nullptr && (N1 & 255) == 0 && gemm_goes_wide(M, N2) ? 1 : 0;
     const int nout = epi == EPI_SILU_GU16 ? N2 / 2 : N2;
-    return gemm_norm(c, s, X, eps, c->d_xn, (const half_t *)W2, M, N2, N1, epi, Cp, nout, 0);
+    return gemm_norm(c, s, sh, X, eps, c->d_xn, (const half_t *)W2, M, N2, N1, epi, Cp, nout, 0);
 }
 
 // The norm fused around gemm_pp_kernel exactly as encode() (LayerNorm) and prefill() (RMSNorm) issue it:
@@ -2642,23 +2638,18 @@ extern "C" int opus_debug_gemm_ln(opus_ctx *c, const void *A, const void *W1, co
     c->phase = PH_OTHER;
     for (int i = 0; i < 2 * PP_PLAN_WORDS; ++i) plan[i] = -1;
     HIPC(hipMemsetAsync(c->d_cnt, 0, HANDOFF_ERR * sizeof(int32_t), s));       // hand-off words start from zero, as at the head of encode / prefill
-    if (gemm_goes_pp(M, N1)) { c->rq_ln_part = part; c->rq_ln_xh = (half_t *)xh; }   // (asked of the big tiled GEMM only, as the path does)
-    c->rq_pp_plan = plan;
-    OPC(gemm(c, s, (const half_t *)A, K1, (const half_t *)W1, M, N1, K1, b1, EPI_NONE, X, X, N1, 1));
-    *produced = c->rq_ln_done;
-    if (!c->rq_ln_done) return OPUS_OK;
+    GemmGot got;
+    // (the partials are asked of the big tiled GEMM only, as the path does)
+    OPC(gemm(c, s, (const half_t *)A, K1, (const half_t *)W1, M, N1, K1, b1, EPI_NONE, X, X, N1, 1,
+             GemmAsk().ln_produce(gemm_goes_pp(M, N1) ? part : nullptr, (half_t *)xh).report_pp(plan), &got));
+    *produced = got.ln_done;
+    if (!got.ln_done) return OPUS_OK;
     KL(KC_NORM, 8.0 * M * (N1 / 64), launch_ln_finalize(part, M, N1 / 64, N1, eps, rms, stat, s));
-    c->rq_ln_stat = stat; c->rq_ln_colsum = colsum;
-    c->rq_pp_plan = plan + PP_PLAN_WORDS;
-    if (rope_T > 0) {
-        const int D = N2 / 3;
-        c->rq_rope_cs = c->cs_enc; c->rq_rope_T = rope_T; c->rq_rope_cols = 2 * D; c->rq_rope_qcols = D;
-        c->rq_rope_qscale = 0.125f;                                      // head_dim 64
-        c->rq_rope_pos = rope_pos;
-    }
     const int nout = epi == EPI_SILU_GU16 ? N2 / 2 : N2;
-    OPC(gemm(c, s, (const half_t *)xh, N1, (const half_t *)W2, M, N2, N1, c2, epi, nullptr, Cp, nout, 0));
-    if (rope_T > 0 && !c->rq_rope_done) return fail(OPUS_ESTATE, "debug_gemm_ln: the consumer GEMM did not fuse the rotary");
+    OPC(gemm(c, s, (const half_t *)xh, N1, (const half_t *)W2, M, N2, N1, c2, epi, nullptr, Cp, nout, 0,
+             GemmAsk().ln_consume(stat, colsum).report_pp(plan + PP_PLAN_WORDS)
+                 .rope(rope_T > 0 ? c->cs_enc : nullptr, rope_pos, rope_T, N2 / 3, 0.125f), &got));   // (head_dim 64)
+    if (rope_T > 0 && !got.rope_done) return fail(OPUS_ESTATE, "debug_gemm_ln: the consumer GEMM did not fuse the rotary");
     return OPUS_OK;
 }
 
@@ -2674,13 +2665,12 @@ extern "C" int opus_debug_gemm_slabs(opus_ctx *c, const void *A, const void *W, 
     if ((int64_t)M * N > (int64_t)g.max_batch * g.max_prompt * QKVd) return fail(OPUS_ESHAPE, "debug_gemm_slabs: M * N exceeds the scratch");
     HIPC(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    c->rq_force_wide = 1;
-    c->rq_slab_only = 1;
-    c->rq_a_tiled = g_knobs.debug_a_tiled;
-    OPC(gemm(c, s, (const half_t *)A, K, (const half_t *)W, M, N, K, nullptr, EPI_NONE, nullptr, c->d_qkv, N, 0));
-    *ks = c->rq_ks;
-    if (c->rq_ks > 1 && d_slabs)
-        HIPC(hipMemcpyAsync(d_slabs, c->gemm_ws, (size_t)c->rq_ks * M * N * sizeof(float), hipMemcpyDeviceToDevice, s));
+    GemmGot got;
+    OPC(gemm(c, s, (const half_t *)A, K, (const half_t *)W, M, N, K, nullptr, EPI_NONE, nullptr, c->d_qkv, N, 0,
+             GemmAsk().slabs().tiled_a(g_knobs.debug_a_tiled), &got));
+    *ks = got.ks;
+    if (got.ks > 1 && d_slabs)
+        HIPC(hipMemcpyAsync(d_slabs, c->gemm_ws, (size_t)got.ks * M * N * sizeof(float), hipMemcpyDeviceToDevice, s));
     return OPUS_OK;
 }
 
