@@ -46,7 +46,9 @@ enum opus_status {
     OPUS_ESTATE = -6        /* missing weights / call out of order */
 };
 
-enum opus_dtype { OPUS_F16 = 0, OPUS_F32 = 1, OPUS_I32 = 2, OPUS_I64 = 3, OPUS_U8 = 4 };
+/* OPUS_F8E4M3 (OCP e4m3fn codes) and OPUS_I8: the FP8 form of the decoder-layer weights only (opus_quantize_fp8); added within
+ * ABI 10 (new values only). */
+enum opus_dtype { OPUS_F16 = 0, OPUS_F32 = 1, OPUS_I32 = 2, OPUS_I64 = 3, OPUS_U8 = 4, OPUS_F8E4M3 = 5, OPUS_I8 = 6 };
 
 /* Shapes of the path.  The reference hard-codes or threads these through a global class
  * (model/builder.py:24-28, protein_projector/builder.py:7-13, protein_mlp/builder.py:11-15,
@@ -110,6 +112,21 @@ int opus_fill_synth(void *d_dst, int dtype, int64_t rows, int64_t cols, uint64_t
 /* Load-time re-layout of one GEMM weight: row-major fp16 W[N,K] (nn.Linear layout) -> the panel-tiled
  * layout the kernels stream (16-row x 64-k blocks in MFMA B-fragment order).  N % 16 == 0, K % 64 == 0. */
 int opus_tile_weight(const void *d_src, void *d_dst, int64_t N, int64_t K, void *stream);
+
+/* FP8 decoder weights (a decode-throughput option, not a capacity one: the fp16 tensors stay bound).  Quantises one decoder-layer
+ * weight after all load-time fusion and before tiling: row-major W[N,K] in the operand type (N % 16 == 0, K % 64 == 0) ->
+ *   d_e8  int8 [N]     e_n = the smallest integer with absmax_n 2^-e_n <= 448 (0 for an all-zero row; never below -120)
+ *   d_q8  N K bytes    OCP e4m3fn codes q = RNE(W 2^-e_n) in FP8 panels: block (p = n / 16, c = k / 64) is the 1 KB at
+ *                      ((p K / 64) + c) 1024; lane g 16 + li (n = 16 p + li) owns 16 bytes, bytes 0..7 = k 64 c + 8 g + j,
+ *                      bytes 8..15 = k 64 c + 32 + 8 g + j.  No code is NaN; a code whose value q 2^e_n would be subnormal in the
+ *                      operand type is +0; a code that rounding carried past the operand type's largest finite value is the next
+ *                      code towards zero
+ *   d_dq  (optional)   q 2^e_n in the operand type, row-major [N,K], exact; may be d_src (in place)
+ * Bind q8 / e8 as "dec.{l}.{wqkv,wo,wgu,wd}.q8" (OPUS_F8E4M3 [N,K]) / ".e8" (OPUS_I8 [N]) beside the panel-tiled dq bound under the
+ * usual name (Llama / Qwen2 layers; both tensors of a projection or neither): the decode step's GEMMs that have an FP8 form (the
+ * weight-streaming kernels: skinny at 1 .. 4 rows; stream, wide and mid at 5 .. 64 rows) then stream half the bytes of the same numbers; every other launch reads the fp16 tensor.
+ * Synchronises `stream`.  OPUS_EBADARG when a weight is not finite (the outputs are then not to be used).  Added within ABI 10. */
+int opus_quantize_fp8(const void *d_src, int64_t N, int64_t K, void *d_q8, void *d_e8, void *d_dq, void *stream);
 
 /* Rows E1-E4: ProteinSeqEmbeddingExtractor.get_protein_seq_embeddings (cstp_v3/modelling.py:37-57):
  * tokens int32 [B,T] (<cls> seq <eos>, pad = 1), lens int32 [B] (incl. <cls>,<eos>) ->
@@ -423,6 +440,13 @@ int opus_debug_gemm_slabs(opus_ctx *ctx, const void *d_A, const void *d_W, float
  * 3 inside the launch (gemm_stream_kernel), 4 the big tiled GEMM's pair hand-off, 5 pp_tail_reduce_kernel, 6 raw slabs left
  * (opus_debug_gemm_slabs).  All -1: no GEMM yet, or the launcher refused the last one.  Added within ABI 10 (a new symbol only). */
 int opus_debug_gemm_plan(opus_ctx *ctx, int32_t *plan);
+/* opus_debug_gemm (form 0), opus_debug_gemm_norm (form 1: d_A fp32, eps; no bias / residual) or opus_debug_gemm_slabs (form 2: d_C
+ * the slab buffer or NULL, *ks) with the FP8 form of W (opus_quantize_fp8: d_q8, d_e8) offered beside the panel-tiled d_W that holds
+ * the same values, as the decode step offers it.  Routing is that of the plain entries; *ran_w8 (HOST) = 1 when the routed kernel
+ * streamed the FP8 panels, 0 when it has no FP8 form and read d_W.  Added within ABI 10 (a new symbol only). */
+int opus_debug_gemm_w8(opus_ctx *ctx, int32_t form, const void *d_A, const void *d_W, const void *d_q8, const void *d_e8,
+                       const float *d_bias, const float *d_residual, void *d_C, int32_t M, int32_t N, int32_t K, int32_t epi,
+                       int32_t out_f32, float eps, int32_t *ks, int32_t *ran_w8, void *stream);
 /* Process-wide tuning knob of the benchmarks / parity tests (no reference counterpart): "no_stream" = 1 routes the narrow
  * GEMMs of the batched decode step through the round-2 split-K kernels instead of gemm_stream_kernel; "pp_gm" = tile rows
  * per rasterisation group of the big tiled GEMM; "debug_a_tiled" = 1: opus_debug_gemm takes A in fragment order; "no_ln_fusion" = 1: stand-alone normalisation kernels
@@ -555,7 +579,8 @@ int opus_last_logits(opus_ctx *ctx, float *d_out, int32_t B, void *stream);
  * a different number of rows / token budget / sampling setting is another graph (a few are kept).  "graph_replays": decode steps
  * launched from a graph.  "graphs_cached".  "decode_steps": decode steps the generate loops enqueued - with an EOS id or a stop
  * sequence the loop polls the rows' state with a bounded run-ahead and stops at most 2 steps after the last row finished (HF stops
- * at once; the extra steps emit pad ids only, the returned ids and n_out are exact). */
+ * at once; the extra steps emit pad ids only, the returned ids and n_out are exact).  "w8_gemms": GEMMs issued on this context
+ * (eagerly or while a graph was captured; replays are not counted) whose kernel streamed the FP8 panels. */
 int64_t opus_stat(opus_ctx *ctx, const char *name);
 
 /* Measurement support (bench.py).  With timing enabled (off by default; decode runs eagerly instead of from the

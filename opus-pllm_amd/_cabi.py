@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("OPUS_LIB_PATH") or os.path.join(_HERE, "lib", "libopu
 ABI_VERSION = 10
 
 OPUS_F16, OPUS_F32, OPUS_I32, OPUS_I64, OPUS_U8 = 0, 1, 2, 3, 4      # (OPUS_F16 = the build's 16-bit operand type)
+OPUS_F8E4M3, OPUS_I8 = 5, 6                                          # FP8 decoder weights: the panels' codes, the row exponents
 
 
 def operand_dtype():
@@ -68,6 +69,9 @@ SIGNATURES = {
     "opus_fill_synth": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.c_uint64, C.c_float, C.c_float,
                                   C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_uint64, C.c_float, C.c_float, _P]),
     "opus_tile_weight": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P]),
+    "opus_quantize_fp8": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P]),
+    "opus_debug_gemm_w8": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
     "opus_esm2_encode": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
     "opus_esm2_encode_packed": (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.c_int32, _P, _P]),
     "opus_esm2_last_hidden": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),

@@ -342,9 +342,15 @@ def load_pretrained_model(model_base_path, adapter_path, model_name, load_8bit=F
     Extra keyword arguments (all optional): device, max_batch, max_enc_tokens, max_prompt, max_new_tokens (context
     capacity), seed and mlm_head (synthetic presets: the seed, and whether the synthetic masked-LM head is bound).  load_4bit / load_8bit select bitsandbytes quantisation in the reference (a
     CUDA-only library, out of scope): the weights are loaded unquantised in fp16 and a warning says so.
+    decoder_weights=None | "fp8" | "fp8_dequantized": "fp8" quantises the decoder layers' projections to e4m3 with a power-of-two
+    scale per output row; the decode step's weight-streaming kernels read the FP8 panels, everything else computes with the dequantised
+    fp16 tensors (the same numbers); model.decoder_weight_format reports it.
     """
     if load_8bit or load_4bit:
         warnings.warn("NF4 / int8 loading is not built for MI355X (bitsandbytes is CUDA-only): loading unquantised fp16")
+    # decoder_weights="fp8": the decoder layers' projections also as FP8 panels for the decode step (weights.DeviceWeights._fp8) -
+    # a decode-throughput option that costs memory (the operand-type tensors stay); None: unquantised
+    decoder_weights = kwargs.pop("decoder_weights", None)
     rank = accelerator.process_index if accelerator is not None else int(os.environ.get("LOCAL_RANK", "0"))
     device = torch.device(kwargs.pop("device", f"cuda:{rank}"))
     cap = {k: kwargs.pop(k) for k in ("max_batch", "max_enc_tokens", "max_prompt", "max_new_tokens") if k in kwargs}
@@ -363,7 +369,8 @@ def load_pretrained_model(model_base_path, adapter_path, model_name, load_8bit=F
         tokenizer = SyntheticTokenizer(cfg.dec_vocab)
         if capacity_from is not None:
             cfg = cfg.with_capacity(**capacity_from(tokenizer, cfg)).validate()
-        weights = DeviceWeights.synthetic(cfg, int(kwargs.pop("seed", 0)), device, mlm_head=bool(kwargs.pop("mlm_head", False)))
+        weights = DeviceWeights.synthetic(cfg, int(kwargs.pop("seed", 0)), device, mlm_head=bool(kwargs.pop("mlm_head", False)),
+                                          decoder_weights=decoder_weights)
         model = OpusLlamaForCausalLM(cfg, weights, device, eos_token_id=tokenizer.eos_token_id,
                                      pad_token_id=tokenizer.pad_token_id)
         return tokenizer, model, 512
@@ -419,7 +426,7 @@ def load_pretrained_model(model_base_path, adapter_path, model_name, load_8bit=F
     lm = mlm_head_from_esm2(esm.get("model", esm))
     if lm is not None:
         canon.update(lm)            # (likewise: get_residue_logits / score_mutations)
-    weights = DeviceWeights.from_canonical(cfg, canon, device, lora=lora)
+    weights = DeviceWeights.from_canonical(cfg, canon, device, lora=lora, decoder_weights=decoder_weights)
     eos = resolve_eos_token_id(hf_cfg, tokenizer.eos_token_id, model_base_path)
     model = OpusLlamaForCausalLM(cfg, weights, device, eos_token_id=eos, pad_token_id=tokenizer.pad_token_id)
     context_len = hf_cfg.get("max_sequence_length", 512)     # builder.py:126-129

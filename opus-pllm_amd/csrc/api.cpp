@@ -51,6 +51,10 @@ struct EncLayer {   // the LayerNorm weights are folded into wqkv / w1 and the b
 struct DecLayer {   // arch 0: RMSNorm weights are folded into wqkv / wgu (and dec.lnf into lm_head) at load time
     const half_t *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wd = nullptr;
     const float *bqkv = nullptr;                      // Qwen2 q/k/v bias, OPT bias
+    // optional FP8 form of the four projections (dec.{l}.{wqkv,wo,wgu,wd}.q8 / .e8: the same values as the fp16 tensors, which
+    // then hold the dequantised weights); null: not bound.  Read by the decode step's GEMMs only (GemmAsk::w8).
+    const uint8_t *q8_qkv = nullptr, *q8_o = nullptr, *q8_gu = nullptr, *q8_d = nullptr;
+    const int8_t *e8_qkv = nullptr, *e8_o = nullptr, *e8_gu = nullptr, *e8_d = nullptr;
     // arch 1 (OPT / Galactica): LayerNorm affine parameters, fc1 / fc2 and the remaining biases
     const half_t *w1 = nullptr, *w2 = nullptr;
     const float *bo = nullptr, *b1 = nullptr, *b2 = nullptr, *ln1w = nullptr, *ln1b = nullptr, *ln2w = nullptr, *ln2b = nullptr;
@@ -154,6 +158,8 @@ struct opus_ctx {
     int32_t *d_cstate = nullptr, *d_cstep = nullptr;
     int32_t cons_n_start = 0, cons_max_id = -1;
     int32_t cons_start_div = 1;          // TokenConstraintDesc::start_div as the device descriptor holds it
+    int gemm_w8 = 0;                     // 1: this context's last GEMM streamed the FP8 panels (GemmParams::ran_w8)
+    int64_t w8_gemms = 0;                // GEMMs issued on this context that did (opus_stat("w8_gemms"))
     int gemm_plan[GEMM_PLAN_WORDS] = {-1, -1, -1, -1, -1, -1, -1, -1};   // the launchers' report of this context's last GEMM (GemmParams::plan; opus_debug_gemm_plan)
     // row-scale fusion (GemmParams::ssq_out / row_ssq): the rows' sums of squares, written by the GEMM that is asked for the fp16
     // copy of its output (GemmAsk::xh) and read by the one that scales its rows (GemmAsk::rs_on)
@@ -414,7 +420,10 @@ extern "C" int opus_bind_weight(opus_ctx *c, const char *name, const void *d_ptr
                                 const int64_t *shape) {
     if (!c || !name || !d_ptr || !shape) return fail(OPUS_EBADARG, "null argument");
     if (ndim < 1 || ndim > 4) return fail(OPUS_EBADARG, "ndim %d", ndim);
-    if (dtype != OPUS_F16 && dtype != OPUS_F32) return fail(OPUS_EBADARG, "weights are fp16 or fp32");
+    const size_t nlen = strlen(name);
+    const bool is_q8 = nlen > 3 && !strcmp(name + nlen - 3, ".q8"), is_e8 = nlen > 3 && !strcmp(name + nlen - 3, ".e8");
+    if (is_q8 ? dtype != OPUS_F8E4M3 : is_e8 ? dtype != OPUS_I8 : (dtype != OPUS_F16 && dtype != OPUS_F32))
+        return fail(OPUS_EBADARG, "weights are fp16 or fp32 (FP8 panels '*.q8': e4m3, their row exponents '*.e8': int8)");
     if (((uintptr_t)d_ptr) & 15) return fail(OPUS_EBADARG, "%s: pointer must be 16-byte aligned", name);
     Tensor t;
     t.p = d_ptr;
@@ -505,6 +514,18 @@ extern "C" int opus_weights_ready(opus_ctx *c) {
         if (g.dec_qkv_bias) GW(p + "bqkv", OPUS_F32, (std::vector<int64_t>{QKV}), L.bqkv);
         GW(p + "wgu", OPUS_F16, (std::vector<int64_t>{2 * F, H}), L.wgu);
         GW(p + "wd", OPUS_F16, (std::vector<int64_t>{H, F}), L.wd);
+        // the optional FP8 form, per projection: both tensors or neither
+        const struct { const char *n; int64_t N, K; const uint8_t **q; const int8_t **e; } w8[4] = {
+            {"wqkv", QKV, H, &L.q8_qkv, &L.e8_qkv}, {"wo", H, QD, &L.q8_o, &L.e8_o},
+            {"wgu", 2 * F, H, &L.q8_gu, &L.e8_gu}, {"wd", H, F, &L.q8_d, &L.e8_d}};
+        for (const auto &t : w8) {
+            *t.q = nullptr; *t.e = nullptr;
+            const bool hq = c->w.count(p + t.n + ".q8") != 0, he = c->w.count(p + t.n + ".e8") != 0;
+            if (!hq && !he) continue;
+            if (t.N % 16 || t.K % 64) return fail(OPUS_ESHAPE, "weight '%s%s.q8': FP8 panels need N %% 16 == 0 and K %% 64 == 0", p.c_str(), t.n);
+            GW(p + t.n + ".q8", OPUS_F8E4M3, (std::vector<int64_t>{t.N, t.K}), *t.q);
+            GW(p + t.n + ".e8", OPUS_I8, (std::vector<int64_t>{t.N}), *t.e);
+        }
     }
     if (g.dec_arch == 1) {
         GW("dec.pos", OPUS_F16, (std::vector<int64_t>{g.dec_max_pos + 2, H}), c->dec_pos);
@@ -570,6 +591,8 @@ struct GemmAsk {
     int force_wide = 0, slab_only = 0;   // route a narrow output through the wide kernel / leave raw k-part slabs
     int a_tiled = 0, c_tiled = 0;        // A is read / the fp16 output is written in fragment order
     int *pp_plan = nullptr;              // (HOST) launch_pp reports its plan here
+    const uint8_t *q8 = nullptr;         // FP8 form of W (GemmParams::q8 / e8): streamed by a kernel that has a W8 instantiation,
+    const int8_t *e8 = nullptr;          //   ignored by every other one (W holds the same values)
     // setters; a null first pointer leaves that request unasked
     GemmAsk &copy16(half_t *dst, bool tiled = false) { xh = dst; xh_tiled = dst && tiled; return *this; }
     GemmAsk &scale_rows(float eps, int nblk) { rs_on = true; rs_eps = eps; rs_nblk = nblk; return *this; }
@@ -583,6 +606,7 @@ struct GemmAsk {
     GemmAsk &tiled_a(int on) { a_tiled = on; return *this; }
     GemmAsk &tiled_c(int on) { c_tiled = on; return *this; }
     GemmAsk &report_pp(int *plan) { pp_plan = plan; return *this; }
+    GemmAsk &w8(const uint8_t *q, const int8_t *e) { if (q && e) { q8 = q; e8 = e; } return *this; }
 };
 // What the launch reports back: the row-scale producer's copy was written (ssq_nblk blocks of sums of squares per row), the rotary
 // ran in the epilogue, the norm partials were written; ks > 1: that many raw k-part slabs were left (slab_only).
@@ -612,6 +636,8 @@ static int gemm_any(opus_ctx *c, hipStream_t s, const half_t *A, const float *Af
     p.pp_plan = ask.pp_plan;
     for (int i = 0; i < GEMM_PLAN_WORDS; ++i) c->gemm_plan[i] = -1;
     p.plan = c->gemm_plan;
+    c->gemm_w8 = 0;
+    p.q8 = ask.q8; p.e8 = ask.e8; p.ran_w8 = &c->gemm_w8;
     p.a_tiled = ask.a_tiled; p.xh_tiled = ask.xh_tiled; p.c_tiled = ask.c_tiled;
     const int nout = epi == EPI_SILU_GU16 ? N / 2 : N;
     // algorithmic bytes: the weights once + activations in + result out (+ the residual read)
@@ -624,6 +650,7 @@ static int gemm_any(opus_ctx *c, hipStream_t s, const half_t *A, const float *Af
         e = launch_gemm(p, s, &klass);
     }
     if (e != hipSuccess) return fail(OPUS_EHIP, "gemm M=%d N=%d K=%d failed: %s", M, N, K, hipGetErrorString(e));
+    c->w8_gemms += c->gemm_w8;
     return OPUS_OK;
 }
 static int gemm(opus_ctx *c, hipStream_t s, const half_t *A, int64_t lda, const half_t *W, int M, int N, int K,
@@ -712,6 +739,27 @@ extern "C" int opus_tile_weight(const void *d_src, void *d_dst, int64_t N, int64
     if (!d_src || !d_dst || d_src == d_dst) return fail(OPUS_EBADARG, "tile_weight: null or aliased pointers");
     if (N < 16 || K < 64 || N % 16 || K % 64) return fail(OPUS_ESHAPE, "tile_weight: N %% 16 == 0 and K %% 64 == 0 required");
     HIPC(launch_tile_weight((const half_t *)d_src, (half_t *)d_dst, N, K, (hipStream_t)stream));
+    return OPUS_OK;
+}
+
+// FP8 form of one decoder-layer weight (csrc/quant.hip): row-major W[N, K] in the operand type -> q8 (FP8 panels, N K bytes),
+// e8 (int8 [N]) and, when d_dq is not null, the dequantised weights (operand type, row-major [N, K]; may be d_src itself).
+// Synchronises the stream: a weight that is not finite is reported (OPUS_EBADARG) and the outputs are not to be used.
+extern "C" int opus_quantize_fp8(const void *d_src, int64_t N, int64_t K, void *d_q8, void *d_e8, void *d_dq, void *stream) {
+    if (!d_src || !d_q8 || !d_e8) return fail(OPUS_EBADARG, "quantize_fp8: null pointer");
+    if (N < 16 || K < 64 || N % 16 || K % 64) return fail(OPUS_ESHAPE, "quantize_fp8: N %% 16 == 0 and K %% 64 == 0 required");
+    if ((((uintptr_t)d_src) | ((uintptr_t)d_q8) | ((uintptr_t)d_dq)) & 15) return fail(OPUS_EBADARG, "quantize_fp8: pointers must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    int *d_bad = nullptr;
+    HIPC(hipMalloc(&d_bad, sizeof(int)));
+    int bad = 0;
+    hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(int), s);
+    if (e == hipSuccess) e = launch_quantize_fp8((const half_t *)d_src, N, K, (uint8_t *)d_q8, (int8_t *)d_e8, (half_t *)d_dq, d_bad, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(d_bad);
+    if (e != hipSuccess) return fail(OPUS_EHIP, "quantize_fp8 failed: %s", hipGetErrorString(e));
+    if (bad) return fail(OPUS_EBADARG, "quantize_fp8: the weight holds a value that is not finite");
     return OPUS_OK;
 }
 
@@ -1431,21 +1479,22 @@ static int decode_step(opus_ctx *c, hipStream_t s, const int32_t *d_tok) {
             // kernel sums them, applies the RMSNorm row scale and the bias on the fly - no norm launch, no reduce launch
             sh.xh_src = nullptr;
             OPC(gemm(c, s, c->d_xln, H, L.wqkv, B, QKV, H, L.bqkv, EPI_NONE, nullptr, c->d_qkv, QKV, 0,
-                     GemmAsk().slabs().scale_rows(g.dec_rms_eps, sh.ssq_nblk).tiled_a(sh.xln_tiled), &got));
+                     GemmAsk().slabs().scale_rows(g.dec_rms_eps, sh.ssq_nblk).tiled_a(sh.xln_tiled).w8(L.q8_qkv, L.e8_qkv), &got));
             OPC(attn_decode(c, s, sh, l, B, T, got.ks > 1 ? got.ks : 0, L.bqkv, wo_tiled ? 1 : 0));
         } else {
-            OPC(gemm_norm(c, s, sh, c->d_xl, g.dec_rms_eps, c->d_xln, L.wqkv, B, QKV, H, EPI_NONE, c->d_qkv, QKV, 0, L.bqkv));
+            OPC(gemm_norm(c, s, sh, c->d_xl, g.dec_rms_eps, c->d_xln, L.wqkv, B, QKV, H, EPI_NONE, c->d_qkv, QKV, 0, L.bqkv,
+                          GemmAsk().w8(L.q8_qkv, L.e8_qkv)));
             OPC(attn_decode(c, s, sh, l, B, T, 0, nullptr, wo_tiled ? 1 : 0));
         }
         // (the copy row-major: the gate/up kernel stages it by LDS-DMA)
-        OPC(gemm(c, s, c->d_ctx, QD, L.wo, B, H, QD, nullptr, EPI_NONE, c->d_xl, c->d_xl, H, 1, GemmAsk().copy16(copy_xl).tiled_a(wo_tiled), &got));
+        OPC(gemm(c, s, c->d_ctx, QD, L.wo, B, H, QD, nullptr, EPI_NONE, c->d_xl, c->d_xl, H, 1, GemmAsk().copy16(copy_xl).tiled_a(wo_tiled).w8(L.q8_o, L.e8_o), &got));
         sh.produced(c->d_xl, got);
         // the gate / up kernel writes silu(g) u in fragment order when the down projection will read it that way (only the wide
         // kernel - the row-scale form of gemm_norm - writes that layout)
         const bool act_tiled = down_tiled && sh.xh_src == c->d_xl && gemm_goes_wide(B, 2 * F);
-        OPC(gemm_norm(c, s, sh, c->d_xl, g.dec_rms_eps, c->d_xln, L.wgu, B, 2 * F, H, EPI_SILU_GU16, c->d_act, F, 0, nullptr, GemmAsk().tiled_c(act_tiled)));
+        OPC(gemm_norm(c, s, sh, c->d_xl, g.dec_rms_eps, c->d_xln, L.wgu, B, 2 * F, H, EPI_SILU_GU16, c->d_act, F, 0, nullptr, GemmAsk().tiled_c(act_tiled).w8(L.q8_gu, L.e8_gu)));
         const bool next_tiled = qkv_tiled && l + 1 < g.dec_layers;      // (the last layer's fp16(x) feeds lm_head: row-major)
-        OPC(gemm(c, s, c->d_act, F, L.wd, B, H, F, nullptr, EPI_NONE, c->d_xl, c->d_xl, H, 1, GemmAsk().copy16(copy_xl, next_tiled).tiled_a(act_tiled), &got));
+        OPC(gemm(c, s, c->d_act, F, L.wd, B, H, F, nullptr, EPI_NONE, c->d_xl, c->d_xl, H, 1, GemmAsk().copy16(copy_xl, next_tiled).tiled_a(act_tiled).w8(L.q8_d, L.e8_d), &got));
         sh.produced(c->d_xl, got, next_tiled);
     }
     OPC(lm_head(c, s, sh, B));
@@ -2674,6 +2723,46 @@ extern "C" int opus_debug_gemm_slabs(opus_ctx *c, const void *A, const void *W, 
     return OPUS_OK;
 }
 
+// opus_debug_gemm (form 0: A in the operand type), opus_debug_gemm_norm (form 1: A fp32, eps) or opus_debug_gemm_slabs (form 2:
+// d_C = the slab buffer, *ks) with the FP8 form of W offered beside it, as decode_step() offers it: *ran_w8 (HOST) = 1 when the
+// routed kernel streamed the FP8 panels, 0 when it has no such form and read W.
+extern "C" int opus_debug_gemm_w8(opus_ctx *c, int32_t form, const void *A, const void *W, const void *q8, const void *e8,
+                                  const float *bias, const float *residual, void *Cp, int32_t M, int32_t N, int32_t K, int32_t epi,
+                                  int32_t out_f32, float eps, int32_t *ks, int32_t *ran_w8, void *stream) {
+    if (!c || !A || !W || !q8 || !e8 || !ran_w8) return fail(OPUS_EBADARG, "debug_gemm_w8: null pointer");
+    if (form < 0 || form > 2) return fail(OPUS_EBADARG, "debug_gemm_w8: form 0, 1 or 2");
+    if ((((uintptr_t)q8) & 15) || (((uintptr_t)e8) & 3)) return fail(OPUS_EBADARG, "debug_gemm_w8: d_q8 must be 16-byte, d_e8 4-byte aligned");
+    if (form != 2 && !Cp) return fail(OPUS_EBADARG, "debug_gemm_w8: null pointer");
+    if (M < 1 || N < 1 || K < 64 || K % 64) return fail(OPUS_ESHAPE, "debug_gemm_w8: K must be a positive multiple of 64");
+    if (epi < 0 || epi > 2 || (epi == 2 && N % 32)) return fail(OPUS_EBADARG, "debug_gemm_w8: epilogue");
+    HIPC(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int nout = epi == EPI_SILU_GU16 ? N / 2 : N;
+    const GemmAsk w8 = GemmAsk().w8((const uint8_t *)q8, (const int8_t *)e8);
+    *ran_w8 = 0;
+    if (form == 0) {
+        OPC(gemm(c, s, (const half_t *)A, K, (const half_t *)W, M, N, K, bias, epi, residual, Cp, nout, out_f32,
+                 GemmAsk(w8).tiled_a(g_knobs.debug_a_tiled)));
+    } else if (form == 1) {
+        if (M > MID_MAX_M) return fail(OPUS_ESHAPE, "debug_gemm_w8: the fused norm takes M <= 64");
+        if (epi == 1 || bias || residual) return fail(OPUS_EBADARG, "debug_gemm_w8: the fused norm takes epilogue 0 or 2, no bias, no residual");
+        OPC(gemm_any(c, s, nullptr, (const float *)A, eps, K, (const half_t *)W, M, N, K, nullptr, epi, nullptr, Cp, nout, out_f32, w8));
+    } else {
+        if (!ks || epi != 0 || N < 16) return fail(OPUS_EBADARG, "debug_gemm_w8: the slab form takes ks, the plain epilogue and N >= 16");
+        const opus_config &g = c->cfg;
+        const int64_t QKVd = (int64_t)(g.dec_heads + 2 * g.dec_kv_heads) * g.dec_head_dim;
+        if ((int64_t)M * N > (int64_t)g.max_batch * g.max_prompt * QKVd) return fail(OPUS_ESHAPE, "debug_gemm_w8: M * N exceeds the scratch");
+        GemmGot got;
+        OPC(gemm(c, s, (const half_t *)A, K, (const half_t *)W, M, N, K, nullptr, EPI_NONE, nullptr, c->d_qkv, N, 0,
+                 GemmAsk(w8).slabs().tiled_a(g_knobs.debug_a_tiled), &got));
+        *ks = got.ks;
+        if (got.ks > 1 && Cp)
+            HIPC(hipMemcpyAsync(Cp, c->gemm_ws, (size_t)got.ks * M * N * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    *ran_w8 = c->gemm_w8;
+    return OPUS_OK;
+}
+
 // What the launchers launched for the last GEMM issued on this context (opus_debug_gemm, opus_debug_gemm_norm,
 // opus_debug_gemm_slabs or any path call): GemmParams::plan, GEMM_PLAN_WORDS ints to HOST memory; all -1: no GEMM yet, or the
 // launcher refused the last one before it chose a kernel.
@@ -2969,6 +3058,7 @@ extern "C" int64_t opus_stat(opus_ctx *c, const char *name) {
     if (!strcmp(name, "graph_replays")) return c->graph_replays;
     if (!strcmp(name, "graphs_cached")) return (int64_t)c->graphs.size();
     if (!strcmp(name, "decode_steps")) return c->decode_steps;
+    if (!strcmp(name, "w8_gemms")) return c->w8_gemms;
     return -1;
 }
 

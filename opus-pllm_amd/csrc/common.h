@@ -104,6 +104,40 @@ __host__ __device__ __forceinline__ int64_t tiled_off(int row, int k, int K) {
     return ((int64_t)(row >> 4) * (K >> 6) + (k >> 6)) * 1024 + ((k & 63) >> 5) * 512 + ((((k & 31) >> 3) << 4) + (row & 15)) * 8 + (k & 7);
 }
 
+// FP8 decoder weights (quant.hip, DESIGN section 4 "FP8 panels").  W[N][K] as OCP e4m3fn codes with one power-of-two exponent per
+// row: block (p = n / 16, c = k / 64) is the 1 KB at ((p K / 64) + c) 1024 bytes; lane g 16 + li (n = 16 p + li) owns 16 bytes,
+// bytes 0 .. 7 = k 64 c + 8 g + e (the first k-step of the chunk), bytes 8 .. 15 = k 64 c + 32 + 8 g + e (the second): one wave-wide
+// 16-B load is 1 KB of contiguous HBM and, converted, both B operands of the chunk.
+__host__ __device__ __forceinline__ int64_t fp8_tiled_off(int64_t n, int64_t k, int64_t K) {
+    return ((n >> 4) * (K >> 6) + (k >> 6)) * 1024 + ((((k & 31) >> 3) << 4) + (n & 15)) * 16 + ((k & 63) >> 5) * 8 + (k & 7);
+}
+constexpr int W8_EXP_MIN = -120;            // floor of the row exponents (int8, and 2^e stays a normal fp32)
+#ifdef OPUS_BF16
+constexpr int OPERAND_MIN_EXP = -126, OPERAND_MAX_EXP = 127;     // binary exponents of the smallest normal / largest finite operand
+#else
+constexpr int OPERAND_MIN_EXP = -14, OPERAND_MAX_EXP = 15;
+#endif
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+// 16 e4m3fn codes (one lane's 16 bytes of an FP8 panel block) -> the two B operands of the chunk, exactly: every code is a
+// normal number (or zero) of either operand type (v_cvt_scalef32_pk_{f16,bf16}_fp8 with scale 1)
+__device__ __forceinline__ void fp8x16_to_h8(u32x4 q, h8 &lo, h8 &hi) {
+#ifdef OPUS_BF16
+#define OPUS_CVT_FP8(w, sel) __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)(w), 1.0f, sel)
+#else
+#define OPUS_CVT_FP8(w, sel) __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)(w), 1.0f, sel)
+#endif
+    const h2 a0 = OPUS_CVT_FP8(q[0], false), a1 = OPUS_CVT_FP8(q[0], true), a2 = OPUS_CVT_FP8(q[1], false), a3 = OPUS_CVT_FP8(q[1], true);
+    const h2 b0 = OPUS_CVT_FP8(q[2], false), b1 = OPUS_CVT_FP8(q[2], true), b2 = OPUS_CVT_FP8(q[3], false), b3 = OPUS_CVT_FP8(q[3], true);
+#undef OPUS_CVT_FP8
+    lo = h8{a0[0], a0[1], a1[0], a1[1], a2[0], a2[1], a3[0], a3[1]};
+    hi = h8{b0[0], b0[1], b1[0], b1[1], b2[0], b2[1], b3[0], b3[1]};
+}
+// 2^e of a row exponent (W8_EXP_MIN <= e <= 120)
+__device__ __forceinline__ float exp2_i8(int e) { return __builtin_bit_cast(float, (uint32_t)(e + 127) << 23); }
+// quant.hip: q8 (FP8 panels), e8 [N], dq (operand type, row-major [N, K]; may be null) from row-major src [N, K]; *bad (device,
+// zeroed by the caller) is set when a weight is not finite
+hipError_t launch_quantize_fp8(const half_t *src, int64_t N, int64_t K, uint8_t *q8, int8_t *e8, half_t *dq, int *bad, hipStream_t s);
+
 constexpr int HANDOFF_WORDS = 1024, HANDOFF_ERR = 1023;
 constexpr int HANDOFF_SPIN_LIMIT = 1 << 19;   // polls (s_sleep(4) + one L2 round trip each: >= 0.3 s) before a waiter gives up
 
@@ -188,6 +222,11 @@ struct GemmParams {
     // of the ring kernel (else 0), [4] the skinny kernel's ALDS flag (else 0), [5] the stream kernel's P (else 0), [6] k-parts over
     // workgroups (gemm_pp_kernel: per tail tile; 1: K is not cut), [7] how the k-parts become the output (GemmCombine)
     int *plan = nullptr;
+    // FP8 form of W (fp8_tiled_off panels + one exponent per row, the same values as W): a kernel that has a W8 instantiation
+    // streams these instead of W and sets *ran_w8 (HOST) = 1; every other kernel reads W as ever and leaves *ran_w8 alone
+    const uint8_t *q8 = nullptr;
+    const int8_t *e8 = nullptr;
+    int *ran_w8 = nullptr;
 };
 constexpr int PP_PLAN_WORDS = 5;
 enum PpTail { PP_TAIL_NONE = 0, PP_TAIL_PAIR = 1, PP_TAIL_REDUCE = 2 };

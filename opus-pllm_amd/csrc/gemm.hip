@@ -76,7 +76,11 @@ __device__ __forceinline__ float silu(float x) { return x * __builtin_amdgcn_rcp
 // double-buffered U chunks deep (2 * U KB in flight per wave).
 // !ALDS (16 < M <= 64 or huge K): A fragments come through a buffer descriptor (rows >= M read as
 // zeros without a branch), NORM accumulates sum(h^2) from those same loads.
-template <int MT, int EPI, bool NORM, bool ALDS>
+//
+// W8 (MT = 1): the weights come from the FP8 panels p.q8 - one 16-B load per lane and chunk instead of two, converted exactly to
+// the operand type in front of the MFMA (fp8x16_to_h8) - and the fp32 sums of column n are multiplied by 2^e8[n] in the epilogue,
+// ahead of the norm scale, bias, activation and residual.  Everything else - k-parts, rotation, staging, reduction - is the same.
+template <int MT, int EPI, bool NORM, bool ALDS, bool W8 = false>
 __global__ __launch_bounds__(1024) void gemm_skinny_kernel(GemmParams p) {
     extern __shared__ __attribute__((aligned(16))) float red[];
     OPUS_ARGS_ONE_BATCH(p);
@@ -105,7 +109,127 @@ __global__ __launch_bounds__(1024) void gemm_skinny_kernel(GemmParams p) {
 #pragma unroll
     for (int i = 0; i < MT; ++i) { acc[i] = f4{0.f, 0.f, 0.f, 0.f}; ssq[i] = 0.f; }
 
-    if constexpr (ALDS) {
+    if constexpr (W8) {
+        static_assert(!W8 || MT == 1, "the FP8 form is built for M <= 16");
+        constexpr int U = (NORM && !ALDS) ? 2 : 4;           // (four chunks of fp32 activations + the conversions: past 128 VGPRs)
+        const uint8_t *qp = p.q8 + ((int64_t)panel * chunks) * 1024 + lane * 16;
+        // (the rotated k-range of the LDS-staged form, as below)
+        const int nck = c1 - c0;
+        const int rot = (ALDS && !p.no_rot && nck >= 2) ? (int)((wave * 3u) % (unsigned)nck) : 0;
+        auto phys = [&](int c) { const int q = c + rot; return q < c1 ? q : q - nck; };
+        auto qload = [&](u32x4 (&q)[U], int c) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (c + u < c1) q[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(qp + (int64_t)phys(c + u) * 1024));
+                else q[u] = u32x4{0, 0, 0, 0};
+            }
+        };
+        if constexpr (ALDS) {
+            u32x4 qA[U], qB[U];
+            qload(qA, c0);                                  // weights first: HBM latency covers the staging
+            const int nthr = blockDim.x;
+            for (int m = 0; m < p.M; ++m) {
+                if (NORM) {
+                    const float4 *src = reinterpret_cast<const float4 *>(p.Af + (int64_t)m * p.lda);
+                    float s = 0.f;
+                    for (int i = tid; i < (p.K >> 2); i += nthr) {
+                        const float4 v = src[i];
+                        s += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+                        *reinterpret_cast<h4 *>(xs + (int64_t)m * p.K + 4 * i) = h4{(half_t)v.x, (half_t)v.y, (half_t)v.z, (half_t)v.w};
+                    }
+#pragma unroll
+                    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+                    if (lane == 0) wss[m * 16 + wave] = s;
+                } else {
+                    const h8 *src = reinterpret_cast<const h8 *>(p.A + (int64_t)m * p.lda);
+                    for (int i = tid; i < (p.K >> 3); i += nthr)
+                        *reinterpret_cast<h8 *>(xs + (int64_t)m * p.K + 8 * i) = src[i];
+                }
+            }
+            __syncthreads();
+            const int mr = li < p.M ? li : p.M - 1;          // rows >= M duplicate the last row: never stored
+            const h8 *xr = reinterpret_cast<const h8 *>(xs + (int64_t)mr * p.K + g * 8);
+            auto compute = [&](const u32x4 (&q)[U], int c) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int cc = phys(c + u < c1 ? c + u : c1 - 1);
+                    const h8 al = xr[cc * 8], ah = xr[cc * 8 + 4];
+                    h8 wl, wh;
+                    fp8x16_to_h8(q[u], wl, wh);
+                    acc[0] = mfma16(al, wl, acc[0]);
+                    acc[0] = mfma16(ah, wh, acc[0]);
+                }
+            };
+            for (int c = c0; c < c1; c += 2 * U) {
+                if (c + U < c1) qload(qB, c + U);
+                compute(qA, c);
+                if (c + U < c1) {
+                    if (c + 2 * U < c1) qload(qA, c + 2 * U);
+                    compute(qB, c + U);
+                }
+            }
+        } else {
+            // A rows through a buffer descriptor (rows >= M read as zeros), as the fp16 form below
+            constexpr int ESZ = NORM ? 4 : 2;
+            const __amdgpu_buffer_rsrc_t arsrc = __builtin_amdgcn_make_buffer_rsrc(
+                NORM ? (void *)p.Af : (void *)p.A, 0, (int)((int64_t)((p.M - 1) * p.lda + p.K) * ESZ), 0x00020000);
+            const int aoff = li < p.M ? (int)((li * p.lda + g * 8) * ESZ) : 0x40000000;
+            struct ARaw { u32x4 v[NORM ? 4 : 2]; };
+            auto load_a = [&](int c, ARaw &r) {
+                const int o = aoff + c * 64 * ESZ;
+                if (NORM) {
+                    r.v[0] = __builtin_amdgcn_raw_buffer_load_b128(arsrc, o, 0, 0);
+                    r.v[1] = __builtin_amdgcn_raw_buffer_load_b128(arsrc, o + 16, 0, 0);
+                    r.v[2] = __builtin_amdgcn_raw_buffer_load_b128(arsrc, o + 128, 0, 0);
+                    r.v[3] = __builtin_amdgcn_raw_buffer_load_b128(arsrc, o + 144, 0, 0);
+                } else {
+                    r.v[0] = __builtin_amdgcn_raw_buffer_load_b128(arsrc, o, 0, 0);
+                    r.v[1] = __builtin_amdgcn_raw_buffer_load_b128(arsrc, o + 64, 0, 0);
+                }
+            };
+            auto conv_a = [&](const ARaw &r, h8 &lo, h8 &hi) {
+                if (NORM) {
+                    const float4 a0 = __builtin_bit_cast(float4, r.v[0]), a1 = __builtin_bit_cast(float4, r.v[1]);
+                    const float4 b0 = __builtin_bit_cast(float4, r.v[2]), b1 = __builtin_bit_cast(float4, r.v[3]);
+                    ssq[0] += (a0.x * a0.x + a0.y * a0.y) + (a0.z * a0.z + a0.w * a0.w) + (a1.x * a1.x + a1.y * a1.y) +
+                              (a1.z * a1.z + a1.w * a1.w) + (b0.x * b0.x + b0.y * b0.y) + (b0.z * b0.z + b0.w * b0.w) +
+                              (b1.x * b1.x + b1.y * b1.y) + (b1.z * b1.z + b1.w * b1.w);
+                    lo = h8{(half_t)a0.x, (half_t)a0.y, (half_t)a0.z, (half_t)a0.w, (half_t)a1.x, (half_t)a1.y, (half_t)a1.z, (half_t)a1.w};
+                    hi = h8{(half_t)b0.x, (half_t)b0.y, (half_t)b0.z, (half_t)b0.w, (half_t)b1.x, (half_t)b1.y, (half_t)b1.z, (half_t)b1.w};
+                } else {
+                    lo = __builtin_bit_cast(h8, r.v[0]);
+                    hi = __builtin_bit_cast(h8, r.v[1]);
+                }
+            };
+            auto step = [&](u32x4 q, const ARaw &r) {
+                h8 al, ah, wl, wh;
+                conv_a(r, al, ah);
+                fp8x16_to_h8(q, wl, wh);
+                acc[0] = mfma16(al, wl, acc[0]);
+                acc[0] = mfma16(ah, wh, acc[0]);
+            };
+            int c = c0;
+            for (; c + U <= c1; c += U) {
+                u32x4 q[U];
+                ARaw ar[U];
+                qload(q, c);
+#pragma unroll
+                for (int u = 0; u < U; ++u) load_a(c + u, ar[u]);
+#pragma unroll
+                for (int u = 0; u < U; ++u) step(q[u], ar[u]);
+            }
+            for (; c < c1; ++c) {
+                const u32x4 q = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(qp + (int64_t)c * 1024));
+                ARaw ar;
+                load_a(c, ar);
+                step(q, ar);
+            }
+            if (NORM) {   // row m's squares sit in the 4 lanes (li = m, g = 0..3)
+                ssq[0] += __shfl_xor(ssq[0], 16, 64);
+                ssq[0] += __shfl_xor(ssq[0], 32, 64);
+            }
+        }
+    } else if constexpr (ALDS) {
         static_assert(!ALDS || MT == 1, "LDS-staged activations are for M <= 16");
         constexpr int U = 4;
         // two NAMED register sets (a runtime-indexed [2][U] array would be placed in scratch)
@@ -306,6 +430,10 @@ __global__ __launch_bounds__(1024) void gemm_skinny_kernel(GemmParams p) {
             }
             const int n = n0 + li;
             if (n >= p.N) continue;
+            if constexpr (W8) {                               // the row exponents (exact: a power of two on an fp32 sum)
+                acc[i][r] *= exp2_i8(p.e8[n]);
+                if (EPI == EPI_SILU_GU16) up[i][r] *= exp2_i8(p.e8[n + 16]);
+            }
             float v;
             int no;
             if (EPI == EPI_SILU_GU16) {
@@ -519,6 +647,18 @@ static hipError_t launch_skinny_t(const GemmParams &p, hipStream_t s) {
     W = wpp * PB;
     const size_t lds = (size_t)W * MT * (256 + 16) * sizeof(float) + 256 * sizeof(float) +
                        (ALDS ? (size_t)p.M * p.K * sizeof(half_t) : 0);
+    if constexpr (MT == 1) {
+        if (p.q8 && p.e8) {     // the FP8 form of the same launch: same grid, same workgroup, same LDS
+            if (lds > 48 * 1024) {
+                hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_skinny_kernel<1, EPI, NORM, ALDS, true>), lds);
+                if (ea != hipSuccess) return ea;
+            }
+            gemm_plan_set(p, KC_SKINNY, MT, 0, 0, ALDS ? 1 : 0, 0, 1, GC_NONE);
+            if (p.ran_w8) *p.ran_w8 = 1;
+            OPUS_LAUNCH(KC_SKINNY, (gemm_skinny_kernel<1, EPI, NORM, ALDS, true>), dim3(groups), dim3(64 * W), lds, s, p);
+            return hipGetLastError();
+        }
+    }
     if (lds > 48 * 1024) {
         hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_skinny_kernel<MT, EPI, NORM, ALDS>), lds);
         if (ea != hipSuccess) return ea;
@@ -550,7 +690,9 @@ static hipError_t launch_skinny_e(const GemmParams &p, hipStream_t s) {
 // (non-temporal, 8 KB in flight per wave).  Accumulators are C^T tiles (16-B epilogue accesses).
 // k-parts (gridDim.y > 1, chosen when N is too small to fill the chip) write fp32 slabs + partial
 // sum(h^2); splitk_reduce_kernel combines them in a fixed order.
-template <int MT, int EPI, bool NORM>
+// W8: the register sets hold one 16-B load per chunk from the FP8 panels p.q8, converted exactly in front of the MFMAs; the wave's
+// tile is multiplied by its columns' 2^e8 behind the main loop (ahead of the slabs, the norm scale and the gate / up exchange).
+template <int MT, int EPI, bool NORM, bool W8 = false>
 __global__ __launch_bounds__(256) void gemm_mid_kernel(GemmParams p, int ksplit) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int MP = 16 * MT;
@@ -625,11 +767,16 @@ __global__ __launch_bounds__(256) void gemm_mid_kernel(GemmParams p, int ksplit)
 #pragma unroll
     for (int i = 0; i < MT; ++i) acc[i] = f4{0.f, 0.f, 0.f, 0.f};
     // weights: two NAMED register sets of one stage each (runtime-indexed arrays would go to scratch)
-    h8 wlA[CH], whA[CH], wlB[CH], whB[CH];
-    auto w_load = [&](h8 (&wl)[CH], h8 (&wh)[CH], int c) {
+    typedef std::conditional_t<W8, u32x4, h8> wreg_t;               // (W8: the lane's 16 code bytes in wl, wh unused)
+    wreg_t wlA[CH], whA[CH], wlB[CH], whB[CH];
+    const uint8_t *qp = W8 ? p.q8 + ((int64_t)panel * chunks) * 1024 + lane * 16 : nullptr;
+    auto w_load = [&](wreg_t (&wl)[CH], wreg_t (&wh)[CH], int c) {
 #pragma unroll
         for (int u = 0; u < CH; ++u) {
-            if (c + u < c1) {
+            if constexpr (W8) {
+                if (c + u < c1) wl[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(qp + (int64_t)(c + u) * 1024));
+                else wl[u] = u32x4{0, 0, 0, 0};
+            } else if (c + u < c1) {
                 const h8 *ptr = reinterpret_cast<const h8 *>(wp + (int64_t)(c + u) * 1024);
                 wl[u] = __builtin_nontemporal_load(ptr);
                 wh[u] = __builtin_nontemporal_load(ptr + 64);
@@ -639,18 +786,26 @@ __global__ __launch_bounds__(256) void gemm_mid_kernel(GemmParams p, int ksplit)
             }
         }
     };
-    auto compute = [&](const h8 (&wl)[CH], const h8 (&wh)[CH], int buf) {
+    auto compute = [&](const wreg_t (&wl)[CH], const wreg_t (&wh)[CH], int buf) {
         const char *base = smem + buf * STAGE;
 #pragma unroll
-        for (int u = 0; u < CH; ++u)
+        for (int u = 0; u < CH; ++u) {
+            h8 w0, w1;
+            if constexpr (W8) {
+                fp8x16_to_h8(wl[u], w0, w1);
+            } else {
+                w0 = wl[u];
+                w1 = wh[u];
+            }
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
                 const int r = 16 * i + li;
                 const h8 a0 = *reinterpret_cast<const h8 *>(base + u * MP * 128 + r * 128 + ((g ^ ((r >> 1) & 7)) << 4));
                 const h8 a1 = *reinterpret_cast<const h8 *>(base + u * MP * 128 + r * 128 + (((4 + g) ^ ((r >> 1) & 7)) << 4));
-                acc[i] = mfma16(wl[u], a0, acc[i]);   // C^T tile
-                acc[i] = mfma16(wh[u], a1, acc[i]);
+                acc[i] = mfma16(w0, a0, acc[i]);   // C^T tile
+                acc[i] = mfma16(w1, a1, acc[i]);
             }
+        }
     };
     w_load(wlA, whA, c0);
     a_load(c0);
@@ -670,6 +825,15 @@ __global__ __launch_bounds__(256) void gemm_mid_kernel(GemmParams p, int ksplit)
         }
     }
 
+    if constexpr (W8) {   // this lane's four columns n = 16 panel + 4 g + r: the row exponents (exact: powers of two on fp32 sums)
+        const uint32_t e4 = *reinterpret_cast<const uint32_t *>(p.e8 + panel * 16 + 4 * g);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float sc = exp2_i8((int)(int8_t)(e4 >> (8 * r)));
+#pragma unroll
+            for (int i = 0; i < MT; ++i) acc[i][r] *= sc;
+        }
+    }
     // ---- row statistics ----
     if (NORM) {
         __syncthreads();
@@ -2008,7 +2172,10 @@ hipError_t launch_splitk_reduce(const GemmParams &p, int ks, hipStream_t s) {
 // weights and nothing waits on a barrier for 64 MFMAs at a time.  vmcnt counts LDS-DMA and register loads
 // together in issue order: the stage's DMA is issued before the 16 weight loads of the stage, of which at
 // most 8 are still in flight at the end, so `s_waitcnt vmcnt(8)` retires the DMA without draining the ring.
-template <int MT, int EPI>
+// W8: the ring holds one 16-B register per chunk from the FP8 panels p.q8 instead of two (LPC loads per chunk in the vmcnt
+// arithmetic below), converted exactly in front of the MFMAs; the wave's tile is multiplied by its columns' 2^e8 behind the main loop,
+// ahead of the slabs / the row scale / the gate-up exchange.
+template <int MT, int EPI, bool W8 = false>
 __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p, int ksplit) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     OPUS_ARGS_ONE_BATCH(p);
@@ -2018,6 +2185,7 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p, int ksplit
     constexpr int STAGE = SC * CIMG;
     constexpr int NPIECE = SC * MP / 8;                              // 1-KB DMA pieces per stage (8 rows x 128 B)
     constexpr int PW = NPIECE / 8;                                   // per wave (MT = 2: 4, MT = 4: 8)
+    constexpr int LPC = W8 ? 1 : 2;                                  // weight loads per chunk and lane
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, li = lane & 15;
@@ -2029,6 +2197,7 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p, int ksplit
     const int ky = blockIdx.y;
     const int c0 = kpart_begin(chunks, ky, ksplit), c1 = kpart_begin(chunks, ky + 1, ksplit);
     const half_t *wp = p.W + ((int64_t)panel * chunks) * 1024 + lane * 8;
+    const uint8_t *qp = W8 ? p.q8 + ((int64_t)panel * chunks) * 1024 + lane * 16 : nullptr;
 
     typedef const __attribute__((address_space(1))) void *gptr_t;
     typedef __attribute__((address_space(3))) void *lptr_t;
@@ -2067,11 +2236,16 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p, int ksplit
     for (int i = 0; i < MT; ++i) acc[i] = f4{0.f, 0.f, 0.f, 0.f};
     constexpr int U = 4;                                            // weight ring: 4 chunks = 8 KB per wave (8 measured slower)
     h8 wl[U], wh[U];
+    u32x4 wq[U];                                                    // (W8: the ring; wl / wh are then unused)
     auto w_load = [&](int u, int c) {
         if (c < c1) {
-            const h8 *ptr = reinterpret_cast<const h8 *>(wp + (int64_t)phys(c) * 1024);
-            wl[u] = __builtin_nontemporal_load(ptr);
-            wh[u] = __builtin_nontemporal_load(ptr + 64);
+            if constexpr (W8) {
+                wq[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(qp + (int64_t)phys(c) * 1024));
+            } else {
+                const h8 *ptr = reinterpret_cast<const h8 *>(wp + (int64_t)phys(c) * 1024);
+                wl[u] = __builtin_nontemporal_load(ptr);
+                wh[u] = __builtin_nontemporal_load(ptr + 64);
+            }
         }
     };
     int aoff[MT];
@@ -2089,10 +2263,31 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p, int ksplit
         asm volatile("global_load_dwordx4 %0, %2, off nt\n\tglobal_load_dwordx4 %1, %2, off offset:1024 nt"
                      : "=&v"(lo), "=&v"(hi) : "v"(ptr));            // (read-only weights: no memory clobber, so the
     };                                                                  //  LDS fragment reads can be scheduled around it)
+    auto ld_q = [&](u32x4 &q, const uint8_t *ptr) { asm volatile("global_load_dwordx4 %0, %1, off nt" : "=&v"(q) : "v"(ptr)); };
+    // chunk cn into ring slot u / the compiler fence on slot u / the counted wait on slot u / the chunk's MFMAs
+    auto ring_load = [&](int u, int cn) {
+        if constexpr (W8) ld_q(wq[u], qp + (int64_t)cn * 1024);
+        else ld_nt(wl[u], wh[u], wp + (int64_t)cn * 1024);
+    };
+    auto ring_pin = [&](int u) {
+        if constexpr (W8) asm volatile("" : "+v"(wq[u]));
+        else asm volatile("" : "+v"(wl[u]), "+v"(wh[u]));
+    };
+    auto ring_mul = [&](int u, int i, h8 a0, h8 a1) {
+        if constexpr (W8) {
+            h8 w0, w1;
+            fp8x16_to_h8(wq[u], w0, w1);
+            acc[i] = mfma16(w0, a0, acc[i]);   // C^T tile
+            acc[i] = mfma16(w1, a1, acc[i]);
+        } else {
+            acc[i] = mfma16(wl[u], a0, acc[i]);   // C^T tile
+            acc[i] = mfma16(wh[u], a1, acc[i]);
+        }
+    };
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const int cn = phys(c0 + u < c1 ? c0 + u : c1 - 1);
-        ld_nt(wl[u], wh[u], wp + (int64_t)cn * 1024);
+        ring_load(u, cn);
     }
     // 1 / rms of the activation rows for the fused RMSNorm (GemmParams::row_ssq), used in the epilogue: the workgroup sums the
     // producer's per-block sums of squares once, into LDS.  Requested BEHIND the first stage's DMA and weight loads (loads
@@ -2109,7 +2304,7 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p, int ksplit
         constexpr bool HAS_NEXT = decltype(has_next_tag)::value;
         constexpr int PWN = HAS_NEXT ? PW : 0;
         // the DMA of this stage was issued before the (at most) 2 U weight loads still in flight
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * U) : "memory");
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPC * U) : "memory");
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // this wave's fragment reads of the other buffer
         __builtin_amdgcn_s_barrier();
         if (HAS_NEXT) dma_stage(buf ^ 1, cs + SC);
@@ -2131,17 +2326,19 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p, int ksplit
             if (u8 + 1 < SC) read_chunk(u8 + 1, fa[(u8 + 1) & 1]);
             // younger than this chunk's pair (requested U chunks ago): the U-1 later refills, plus this stage's PW DMA
             // requests when the pair was requested before them (first U chunks of the stage)
-            if (u8 < U) asm volatile("s_waitcnt vmcnt(%2)" : "+v"(wl[u]), "+v"(wh[u]) : "n"(2 * (U - 1) + PWN));
-            else asm volatile("s_waitcnt vmcnt(%2)" : "+v"(wl[u]), "+v"(wh[u]) : "n"(2 * (U - 1)));
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                acc[i] = mfma16(wl[u], fa[u8 & 1][i][0], acc[i]);   // C^T tile
-                acc[i] = mfma16(wh[u], fa[u8 & 1][i][1], acc[i]);
+            if constexpr (W8) {
+                if (u8 < U) asm volatile("s_waitcnt vmcnt(%1)" : "+v"(wq[u]) : "n"(LPC * (U - 1) + PWN));
+                else asm volatile("s_waitcnt vmcnt(%1)" : "+v"(wq[u]) : "n"(LPC * (U - 1)));
+            } else {
+                if (u8 < U) asm volatile("s_waitcnt vmcnt(%2)" : "+v"(wl[u]), "+v"(wh[u]) : "n"(2 * (U - 1) + PWN));
+                else asm volatile("s_waitcnt vmcnt(%2)" : "+v"(wl[u]), "+v"(wh[u]) : "n"(2 * (U - 1)));
             }
+#pragma unroll
+            for (int i = 0; i < MT; ++i) ring_mul(u, i, fa[u8 & 1][i][0], fa[u8 & 1][i][1]);
             const int cn = phys(c + U < c1 ? c + U : c1 - 1);        // (clamped: a few redundant loads at the very end)
             // the refill overwrites registers the MFMAs above read: in/out operands order it behind them
-            asm volatile("" : "+v"(wl[u]), "+v"(wh[u]));
-            ld_nt(wl[u], wh[u], wp + (int64_t)cn * 1024);
+            ring_pin(u);
+            ring_load(u, cn);
         }
     };
     for (; cs + SC < c1; cs += SC, buf ^= 1) full_stage(std::true_type{});
@@ -2153,7 +2350,7 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p, int ksplit
     // everything the inline-asm loads have in flight is retired before the registers are handed back to the compiler
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
-    for (int u = 0; u < U; ++u) asm volatile("" : "+v"(wl[u]), "+v"(wh[u]));
+    for (int u = 0; u < U; ++u) ring_pin(u);
     if (cs < c1) {   // partial last stage: guarded loads (its DMA, issued a stage ago, has landed: vmcnt(0) above)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -2167,14 +2364,22 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p, int ksplit
                 for (int i = 0; i < MT; ++i) {
                     const h8 a0 = *reinterpret_cast<const h8 *>(base + u8 * CIMG + aoff[i]);
                     const h8 a1 = *reinterpret_cast<const h8 *>(base + u8 * CIMG + (aoff[i] ^ 64));
-                    acc[i] = mfma16(wl[u], a0, acc[i]);   // C^T tile
-                    acc[i] = mfma16(wh[u], a1, acc[i]);
+                    ring_mul(u, i, a0, a1);
                 }
                 w_load(u, c + U);
             }
         }
     }
 
+    if constexpr (W8) {   // this lane's four columns n = 16 panel + 4 g + r: the row exponents (exact: powers of two on fp32 sums)
+        const uint32_t e4 = *reinterpret_cast<const uint32_t *>(p.e8 + panel * 16 + 4 * g);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float sc = exp2_i8((int)(int8_t)(e4 >> (8 * r)));
+#pragma unroll
+            for (int i = 0; i < MT; ++i) acc[i][r] *= sc;
+        }
+    }
     if (ksplit > 1) {
         float *slab = p.ws + (int64_t)ky * p.M * p.N;
         if (panel_ok) {
@@ -2238,8 +2443,11 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p, int ksplit
 //  panels make 256 workgroups instead of 224 (what an [8 gate | 8 up] panel layout would allow with the pair product done across
 //  lanes): 41.8 vs 42.4 us on the 28672-column shape (-1.4 %; lm_head 207 vs 197 us), timing only.  0.6 us per layer is not
 //  worth a second copy of every gate / up weight: the 224-workgroup grid costs less than the sweep's 256-vs-224 pure-stream gap.)
-template <int MT, int EPI>
+template <int MT, int EPI, bool W8 = false>
 static hipError_t launch_wide(const GemmParams &p, hipStream_t s) {
+    if constexpr (!W8) {              // the FP8 form of the same launch: same grid, LDS, k-parts
+        if (p.q8 && p.e8) return launch_wide<MT, EPI, true>(p, s);
+    }
     const int blocks = cdiv((p.N + 15) >> 4, 8), chunks = p.K / 64;
     int ks = 1;
     if (p.ws && blocks < 200) {                                      // few column groups: split K over workgroups
@@ -2252,15 +2460,16 @@ static hipError_t launch_wide(const GemmParams &p, hipStream_t s) {
     }
     if (p.ks_out) *p.ks_out = ks;
     const int lds = 2 * (MT <= 4 ? 8 : 4) * 16 * MT * 128 + 16 * MT * (int)sizeof(float);   // two stages + the rows' 1 / rms
-    hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_wide_kernel<MT, EPI>), lds);
+    hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_wide_kernel<MT, EPI, W8>), lds);
     if (ea != hipSuccess) return ea;
     gemm_plan_set(p, KC_WIDE, MT, 0, 0, 0, 0, ks, ks == 1 ? GC_NONE : GC_SLABS);   // (launch_reduce names the reduce it takes)
+    if (W8 && p.ran_w8) *p.ran_w8 = 1;
     if (ks > 1 && p.row_ssq) {       // k-parts leave raw slabs: the row scale is applied by whoever combines them, not here
         GemmParams q = p;
         q.row_ssq = nullptr;
-        OPUS_LAUNCH(KC_WIDE, (gemm_wide_kernel<MT, EPI>), dim3(blocks, ks), dim3(512), lds, s, q, ks);
+        OPUS_LAUNCH(KC_WIDE, (gemm_wide_kernel<MT, EPI, W8>), dim3(blocks, ks), dim3(512), lds, s, q, ks);
     } else {
-        OPUS_LAUNCH(KC_WIDE, (gemm_wide_kernel<MT, EPI>), dim3(blocks, ks), dim3(512), lds, s, p, ks);
+        OPUS_LAUNCH(KC_WIDE, (gemm_wide_kernel<MT, EPI, W8>), dim3(blocks, ks), dim3(512), lds, s, p, ks);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || ks == 1 || p.slab_only) return e;
@@ -2268,8 +2477,11 @@ static hipError_t launch_wide(const GemmParams &p, hipStream_t s) {
 }
 
 
-template <int MT, int EPI, bool NORM>
+template <int MT, int EPI, bool NORM, bool W8 = false>
 static hipError_t launch_mid_t(const GemmParams &p, hipStream_t s) {
+    if constexpr (!W8 && MT <= 4) {   // the FP8 form of the same launch (MT = 6 / 8: beyond MID_MAX_M, never launched)
+        if (p.q8 && p.e8) return launch_mid_t<MT, EPI, NORM, true>(p, s);
+    }
     const int blocks = cdiv((p.N + 15) >> 4, 4), chunks = p.K / 64;
     // k-parts: enough workgroups for ~8 waves per CU, at least 4 chunks each, slabs within the workspace
     int ks = 1;
@@ -2283,12 +2495,13 @@ static hipError_t launch_mid_t(const GemmParams &p, hipStream_t s) {
     constexpr int CH = MT <= 2 ? 4 : 1;
     const size_t lds = 2 * CH * 16 * MT * 128 + 16 * MT * sizeof(float) + 2 * MT * 4 * 64 * sizeof(float);
     if (lds > 48 * 1024) {
-        hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_mid_kernel<MT, EPI, NORM>), lds);
+        hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_mid_kernel<MT, EPI, NORM, W8>), lds);
         if (ea != hipSuccess) return ea;
     }
     if (p.row_ssq && ks == 1) return hipErrorInvalidValue;            // only the split-K reduce applies a row scale here
     gemm_plan_set(p, KC_MID, MT, 0, 0, 0, 0, ks, GC_NONE);
-    OPUS_LAUNCH(KC_MID, (gemm_mid_kernel<MT, EPI, NORM>), dim3(blocks, ks), dim3(256), lds, s, p, ks);
+    if (W8 && p.ran_w8) *p.ran_w8 = 1;
+    OPUS_LAUNCH(KC_MID, (gemm_mid_kernel<MT, EPI, NORM, W8>), dim3(blocks, ks), dim3(256), lds, s, p, ks);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || ks == 1) return e;
     return launch_reduce<EPI>(p, ks, s);

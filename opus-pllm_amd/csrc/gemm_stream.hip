@@ -45,7 +45,10 @@ __device__ __forceinline__ float gelu_erf_s(float x) {   // same arithmetic as g
 }
 
 // MT row tiles of 16, P panels per workgroup, NT threads, U chunk sets in flight per wave
-template <int MT, int P, int NT, int U, int EPI>
+// W8: the weight blocks come from the FP8 panels p.q8 (1 KB per block: one 16-B load per lane, converted exactly to the operand
+// type in front of the MFMA) and every wave multiplies its partial tiles by the columns' 2^e8 before the combine, so the slabs,
+// the in-launch combine, the split-K reduce and the attention kernel that sums raw slabs all see the sums they see today.
+template <int MT, int P, int NT, int U, int EPI, bool W8 = false>
 __global__ __launch_bounds__(NT) void gemm_stream_kernel(GemmParams p, int ksplit) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // Every kernel argument the main path reads, fetched in ONE scalar batch: left to itself the compiler loads the 330-byte
@@ -92,7 +95,13 @@ __global__ __launch_bounds__(NT) void gemm_stream_kernel(GemmParams p, int kspli
     const int rot = (p.no_rot || nsteps < 2) ? 0 : (int)((blockIdx.x * 3u + (unsigned)ky) % (unsigned)nsteps);
 
     typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-    h8 wr[U][P][2];
+    std::conditional_t<W8, u32x4, h8> wr[U][P][W8 ? 1 : 2];
+    const uint8_t *qp[P];
+    if constexpr (W8) {
+        asm volatile("" ::"s"(p.q8), "s"(p.e8));
+#pragma unroll
+        for (int j = 0; j < P; ++j) qp[j] = p.q8 + ((int64_t)(panel0 + j) * chunks) * 1024 + lane * 16;
+    }
     u4 ar[U][MT][2];
     f4 acc[P][MT];
 #pragma unroll
@@ -111,9 +120,13 @@ __global__ __launch_bounds__(NT) void gemm_stream_kernel(GemmParams p, int kspli
         c = c < c1 ? c : c1 - 1;             // ragged last step: a harmless re-read, skipped by compute()
 #pragma unroll
         for (int j = 0; j < P; ++j) {
-            const h8 *ptr = reinterpret_cast<const h8 *>(wp[j] + (int64_t)c * 1024);
-            wr[u][j][0] = __builtin_nontemporal_load(ptr);
-            wr[u][j][1] = __builtin_nontemporal_load(ptr + 64);
+            if constexpr (W8) {
+                wr[u][j][0] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(qp[j] + (int64_t)c * 1024));
+            } else {
+                const h8 *ptr = reinterpret_cast<const h8 *>(wp[j] + (int64_t)c * 1024);
+                wr[u][j][0] = __builtin_nontemporal_load(ptr);
+                wr[u][j][1] = __builtin_nontemporal_load(ptr + 64);
+            }
         }
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
@@ -125,12 +138,20 @@ __global__ __launch_bounds__(NT) void gemm_stream_kernel(GemmParams p, int kspli
         constexpr int u = decltype(u_tag)::value;
         if (chunk_of(step) >= c1) return;    // wave-uniform
 #pragma unroll
-        for (int j = 0; j < P; ++j)
+        for (int j = 0; j < P; ++j) {
+            h8 w0, w1;
+            if constexpr (W8) {
+                fp8x16_to_h8(wr[u][j][0], w0, w1);
+            } else {
+                w0 = wr[u][j][0];
+                w1 = wr[u][j][1];
+            }
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
-                acc[j][i] = mfma16(wr[u][j][0], __builtin_bit_cast(h8, ar[u][i][0]), acc[j][i]);   // C^T tile
-                acc[j][i] = mfma16(wr[u][j][1], __builtin_bit_cast(h8, ar[u][i][1]), acc[j][i]);
+                acc[j][i] = mfma16(w0, __builtin_bit_cast(h8, ar[u][i][0]), acc[j][i]);   // C^T tile
+                acc[j][i] = mfma16(w1, __builtin_bit_cast(h8, ar[u][i][1]), acc[j][i]);
             }
+        }
     };
     // U named sets: set u holds step s with s % U == u (static register indices)
     auto for_sets = [&](auto &&f) {
@@ -156,6 +177,18 @@ __global__ __launch_bounds__(NT) void gemm_stream_kernel(GemmParams p, int kspli
     }
     if (p.trace && tid == 0) p.trace[wg * 8 + 2] = wall_clock64();
 
+    if constexpr (W8) {   // this lane's four columns n = 16 (panel0 + j) + 4 g + r: the row exponents (exact: powers of two on fp32 sums)
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+            const uint32_t e4 = *reinterpret_cast<const uint32_t *>(p.e8 + (panel0 + j) * 16 + 4 * g);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float sc = exp2_i8((int)(int8_t)(e4 >> (8 * r)));
+#pragma unroll
+                for (int i = 0; i < MT; ++i) acc[j][i][r] *= sc;
+            }
+        }
+    }
     // ---- combine the NW partial tiles through LDS, in wave order ----
     f4 *red = reinterpret_cast<f4 *>(smem);          // [NW][TILES][64] f4
 #pragma unroll
@@ -344,12 +377,15 @@ bool gemm_stream_ok(const GemmParams &p) {
     return gemm_stream_would(p.M, p.N, p.K, p.slab_only, p.a_tiled, p.row_ssq != nullptr, p.ws_bytes);
 }
 
-template <int MT, int P, int NT, int U, int EPI>
+template <int MT, int P, int NT, int U, int EPI, bool W8 = false>
 static hipError_t launch_stream_t(const GemmParams &p_in, const StreamPlan &pl, hipStream_t s) {
+    if constexpr (!W8) {      // the FP8 form of the same launch: same plan, grid, LDS and combine
+        if (p_in.q8 && p_in.e8) return launch_stream_t<MT, P, NT, U, EPI, true>(p_in, pl, s);
+    }
     GemmParams p = p_in;
     constexpr int NW = NT / 64;
     const size_t lds = (size_t)NW * P * MT * 1024 + 16;      // partial tiles + the "last arriver" word of the in-launch combine
-    hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_stream_kernel<MT, P, NT, U, EPI>), lds);
+    hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_stream_kernel<MT, P, NT, U, EPI, W8>), lds);
     if (ea != hipSuccess) return ea;
     const int npanels = p.N >> 4;
     // k-parts with a finished output: combined inside the launch by the workgroup that arrives last (no reduce launch)
@@ -374,7 +410,7 @@ static hipError_t launch_stream_t(const GemmParams &p_in, const StreamPlan &pl, 
             GemmParams q = p;
             q.trace = tb;
             for (int rep = 0; rep < 3; ++rep)      // (the third launch is reported: code and activations warm, weights from HBM if > caches)
-                hipLaunchKernelGGL((gemm_stream_kernel<MT, P, NT, U, EPI>), dim3(npanels / P, pl.ks), dim3(NT), lds, s, q, pl.ks);
+                hipLaunchKernelGGL((gemm_stream_kernel<MT, P, NT, U, EPI, W8>), dim3(npanels / P, pl.ks), dim3(NT), lds, s, q, pl.ks);
             (void)hipStreamSynchronize(s);
             std::vector<long long> h((size_t)nwg * 8);
             (void)hipMemcpy(h.data(), tb, h.size() * sizeof(long long), hipMemcpyDeviceToHost);
@@ -404,7 +440,8 @@ static hipError_t launch_stream_t(const GemmParams &p_in, const StreamPlan &pl, 
     }
     if (pl.ks & (pl.ks - 1)) return hipErrorInvalidValue;               // (the kernel cuts K with a shift)
     gemm_plan_set(p_in, KC_STREAM, MT, 0, 0, 0, P, pl.ks, pl.ks == 1 ? GC_NONE : combine ? GC_IN_LAUNCH : GC_SLABS);   // (launch_splitk_reduce names its reduce)
-    OPUS_LAUNCH(KC_STREAM, (gemm_stream_kernel<MT, P, NT, U, EPI>), dim3(npanels / P, pl.ks), dim3(NT), lds, s, p, pl.ks);
+    if (W8 && p.ran_w8) *p.ran_w8 = 1;
+    OPUS_LAUNCH(KC_STREAM, (gemm_stream_kernel<MT, P, NT, U, EPI, W8>), dim3(npanels / P, pl.ks), dim3(NT), lds, s, p, pl.ks);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || pl.ks == 1 || p_in.slab_only || combine) return e;
     return launch_splitk_reduce(p_in, pl.ks, s);                      // (applies bias / residual / row scale, writes xh_out + sums of squares)

@@ -224,6 +224,7 @@ def eval_model(args):
     # capacity of the context: the reference has no cap; here the KV cache is sized once, from what this run will really ask for
     tokenizer, model, _ = load_pretrained_model(args.model_base_path, args.opus_pllm_weights_path, model_name,
                                                 args.load_8bit, args.load_4bit, switch_projector_type=args.switch_projector_type,
+                                                decoder_weights=getattr(args, "decoder_weights", None),
                                                 cstp_path=cstp_path, device=f"cuda:{local}", max_batch=args.batch_size * max(1, args.num_beams),
                                                 max_enc_tokens=args.max_residues + 2, max_prompt=8, max_new_tokens=max_new,
                                                 capacity_from=capacity)
@@ -302,6 +303,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--max_new_tokens", type=int, default=None)
     p.add_argument("--switch_projector_type", type=str, default="mlp2x_gelu")
     p.add_argument("--load-4bit", action="store_true")
+    p.add_argument("--decoder_weights", choices=("fp8",), default=None,
+                   help="fp8: decoder-layer weights also as e4m3 panels for the decode step (faster decode, 1.5x the memory of those weights)")
     p.add_argument("--load-8bit", action="store_true")
     p.add_argument("--batch_size", type=int, default=8)          # hard-coded 8 in the reference (:75)
     p.add_argument("--max_residues", type=int, default=1024)

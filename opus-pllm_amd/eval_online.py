@@ -47,6 +47,7 @@ def eval_model(args):
     cstp_path = return_cstp_path(args.opus_pllm_weights_path, "modality_encoder/modality_encoding_adapter.ckpt")
     tokenizer, model, _ = load_pretrained_model(args.model_base_path, args.opus_pllm_weights_path, model_name,
                                                 args.load_8bit, args.load_4bit, switch_projector_type=args.switch_projector_type,
+                                                decoder_weights=getattr(args, "decoder_weights", None),
                                                 cstp_path=cstp_path, device="cuda:0", max_batch=max(1, args.num_beams),
                                                 max_enc_tokens=args.max_residues + 2, max_prompt=args.max_prompt,
                                                 max_new_tokens=max(args.max_new_tokens, 1))
@@ -80,6 +81,8 @@ if __name__ == "__main__":
     p.add_argument("--max_new_tokens", type=int, default=32)         # run_opus_online.py:101
     p.add_argument("--switch_projector_type", type=str, default="mlp2x_gelu")
     p.add_argument("--load-4bit", action="store_true")
+    p.add_argument("--decoder_weights", choices=("fp8",), default=None,
+                   help="fp8: decoder-layer weights also as e4m3 panels for the decode step (faster decode, 1.5x the memory of those weights)")
     p.add_argument("--load-8bit", action="store_true")
     p.add_argument("--max_residues", type=int, default=1024)
     p.add_argument("--max_prompt", type=int, default=256)

@@ -110,6 +110,12 @@ class OpusLlamaForCausalLM:
         g = self.generation_config
         return OpusLlamaForCausalLM(self.cfg, self.weights, self.device, eos_token_id=list(g.eos_token_id), pad_token_id=g.pad_token_id)
 
+    @property
+    def decoder_weight_format(self) -> str:
+        """What the decoder layers' projections are bound as: "fp16" / "bf16" (the build's operand type, unquantised), "fp8" (FP8
+        panels for the decode step beside the dequantised operand-type tensors) or "fp8_dequantized" (those tensors alone)."""
+        return self.weights.decoder_weight_format
+
     def __del__(self):
         try:
             if getattr(self, "_ctx", None) and self._ctx.value:

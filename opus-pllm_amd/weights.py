@@ -153,12 +153,43 @@ def untile_weight(t: torch.Tensor) -> torch.Tensor:
     return t.reshape(N // 16, K // 64, 2, 4, 16, 8).permute(0, 4, 1, 2, 3, 5).reshape(N, K).contiguous()
 
 
+def quantize_fp8(t: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Row-major operand-type [N,K] on the GPU -> (q8 uint8 [N,K]: e4m3fn codes in the FP8 panel layout, e8 int8 [N]: the row
+    exponents, dq: q 2^e in the operand type, row-major) via opus_quantize_fp8.  Raises OpusError when a weight is not finite."""
+    assert t.is_cuda and t.dtype == _cabi.operand_dtype() and t.dim() == 2 and t.is_contiguous()
+    N, K = t.shape
+    q8 = torch.empty((N, K), dtype=torch.uint8, device=t.device)
+    e8 = torch.empty((N,), dtype=torch.int8, device=t.device)
+    dq = torch.empty_like(t)
+    with torch.cuda.device(t.device):
+        _cabi.check(_cabi.lib().opus_quantize_fp8(t.data_ptr(), N, K, q8.data_ptr(), e8.data_ptr(), dq.data_ptr(),
+                                                  torch.cuda.current_stream(t.device).cuda_stream))
+    return q8, e8, dq
+
+
+def untile_fp8(q8: torch.Tensor) -> torch.Tensor:
+    """FP8 panels [N,K] -> the codes row-major (host-side index arithmetic; tests and debugging only)."""
+    N, K = q8.shape
+    return q8.reshape(N // 16, K // 64, 4, 16, 2, 8).permute(0, 3, 1, 4, 2, 5).reshape(N, K).contiguous()
+
+
+DECODER_WEIGHT_FORMATS = (None, "fp8", "fp8_dequantized")
+
+
+def fp8_names(cfg: OpusConfig) -> List[str]:
+    """The fused tensors decoder_weights="fp8" quantises: the four projections of every decoder layer (lm_head, the embeddings,
+    the encoder and the projectors stay as they are)."""
+    mats = ("wqkv", "wo", "w1", "w2") if cfg.dec_arch == 1 else ("wqkv", "wo", "wgu", "wd")
+    return [f"dec.{l}.{m}" for l in range(cfg.dec_layers) for m in mats]
+
+
 class DeviceWeights:
     """Fused weight tensors on one GPU + their binding to a library context."""
 
     def __init__(self, cfg: OpusConfig, device: torch.device):
         self.cfg = cfg
         self.device = device
+        self.decoder_weights: Optional[str] = None       # None | "fp8" | "fp8_dequantized" (from_canonical / synthetic)
         self.tensors: Dict[str, torch.Tensor] = {}
         # optional tensors bound beside the fused ones (the ESM-2 contact head: enc.contact.weight fp32 [enc_layers * enc_heads],
         # enc.contact.bias fp32 [1]; the ESM-2 masked-LM head: enc.lm.*); opus_weights_ready does not need them
@@ -214,13 +245,16 @@ class DeviceWeights:
 
     @classmethod
     def from_canonical(cls, cfg: OpusConfig, canon: Dict[str, "np.ndarray | torch.Tensor"], device,
-                       lora: Optional[Dict[str, Tuple[torch.Tensor, torch.Tensor, float, int]]] = None) -> "DeviceWeights":
+                       lora: Optional[Dict[str, Tuple[torch.Tensor, torch.Tensor, float, int]]] = None,
+                       decoder_weights: Optional[str] = None) -> "DeviceWeights":
         """Canonical tensors (reference parameter names, see synth.py) -> fused device tensors.
 
         `lora` maps a canonical weight name to (A [r,in], B [out,r], alpha, r): merged into that weight
         first, W += (alpha / r) B A, as peft merge_and_unload does at model/builder.py:107-109 (row L1).
+        `decoder_weights`: None, "fp8" or "fp8_dequantized" (_fp8 below).
         """
         self = cls(cfg, torch.device(device))
+        self._set_decoder_weights(decoder_weights)
         lib = _cabi.lib()
 
         def get(name, dtype):
@@ -250,6 +284,8 @@ class DeviceWeights:
                     folded_vec[f.name] = t.float() @ get(wanted[f.name], torch.float32)
                 if f.fold is not None:
                     t.copy_((t.float() * get(f.fold, torch.float32)[None, :]).to(_cabi.operand_dtype()))
+                if f.name in self._fp8_names:
+                    t = self._fp8(f.name, t)
                 if f.tiled:
                     self.tensors[f.name] = tile_weight(t)
             self._derive(spec, None, None, folded_vec)
@@ -259,6 +295,28 @@ class DeviceWeights:
                 self.set_mlm_head({k: v for k, v in canon.items() if k.startswith("enc.lm.")})
             torch.cuda.synchronize(self.device)
         return self
+
+    def _set_decoder_weights(self, decoder_weights: Optional[str]) -> None:
+        if decoder_weights not in DECODER_WEIGHT_FORMATS:
+            raise ValueError(f"decoder_weights={decoder_weights!r}: one of {DECODER_WEIGHT_FORMATS}")
+        self.decoder_weights = decoder_weights
+        self._fp8_names = set(fp8_names(self.cfg)) if decoder_weights else set()
+
+    def _fp8(self, name: str, t: torch.Tensor) -> torch.Tensor:
+        """The FP8 form of the fused decoder-layer weight `name` (row-major, after LoRA merge, concatenation / interleave and norm
+        fold, before tiling): per-row power-of-two exponent + e4m3fn codes (csrc/quant.hip).  Returns the dequantised weights
+        (exactly representable in the operand type), which take the weight's place, so prefill, forward, scoring and every decode
+        launch without an FP8 kernel compute with the same numbers.  "fp8" also keeps the codes and exponents, bound as
+        `name`.q8 / .e8 for the decode step (Llama / Qwen2; OPT / Galactica run on the dequantised tensors); "fp8_dequantized"
+        keeps the dequantised tensors alone (the comparison model)."""
+        q8, e8, dq = quantize_fp8(t.contiguous())
+        if self.decoder_weights == "fp8" and self.cfg.dec_arch == 0:
+            self.tensors[name + ".q8"], self.tensors[name + ".e8"] = q8, e8
+        return dq
+
+    @property
+    def decoder_weight_format(self) -> str:
+        return self.decoder_weights or ("bf16" if _cabi.BF16 else "fp16")
 
     def _derive(self, spec, unfolded, vector, folded_vec=None) -> None:
         """The derived vectors of the folded LayerNorms (Fused.derive): unfolded(name) -> fp32 [N, K] row-major weight before
@@ -276,10 +334,12 @@ class DeviceWeights:
 
     @classmethod
     def synthetic(cls, cfg: OpusConfig, seed: int, device, stream: int = 0, contact_head: bool = False,
-                  mlm_head: bool = False) -> "DeviceWeights":
+                  mlm_head: bool = False, decoder_weights: Optional[str] = None) -> "DeviceWeights":
         """Fill the fused tensors on the GPU with the deterministic synthetic model (synth.py twin); contact_head: also the
-        synthetic contact regression (synth.contact_head); mlm_head: also the synthetic masked-LM head (synth.mlm_head)."""
+        synthetic contact regression (synth.contact_head); mlm_head: also the synthetic masked-LM head (synth.mlm_head);
+        decoder_weights: None, "fp8" or "fp8_dequantized" (_fp8)."""
         self = cls(cfg, torch.device(device))
+        self._set_decoder_weights(decoder_weights)
         lib = _cabi.lib()
         if not stream:      # the fills and _derive's torch ops on ONE stream: torch's current one (not the null stream beside it)
             stream = torch.cuda.current_stream(self.device).cuda_stream
@@ -318,6 +378,8 @@ class DeviceWeights:
                     _cabi.check(lib.opus_fill_synth(t.data_ptr(), _cabi.OPUS_F16 if f.f16 else _cabi.OPUS_F32,
                                                     p.rows, p.cols, synth.tensor_seed(p.canon, seed), std, mean,
                                                     p.rb, p.rs, p.ro, 1 if f.tiled else 0, fseed, fstd, fmean, stream))
+                if f.name in self._fp8_names:            # (filled panel-tiled: back to rows, quantise, tile the dequantised weights)
+                    self.tensors[f.name] = tile_weight(self._fp8(f.name, untile_weight(t)))
             self._derive(fspec, unfolded, vector)
             if contact_head:
                 head = synth.contact_head(cfg, seed)
@@ -329,10 +391,11 @@ class DeviceWeights:
     # -- binding ---------------------------------------------------------------------------------
     def bind(self, ctx) -> None:
         lib = _cabi.lib()
+        codes = {torch.uint8: _cabi.OPUS_F8E4M3, torch.int8: _cabi.OPUS_I8}            # (the FP8 panels and their row exponents)
         for name, t in list(self.tensors.items()) + list(self.extra.items()):
             shape = (C.c_int64 * t.dim())(*t.shape)
             _cabi.check(lib.opus_bind_weight(ctx, name.encode(), t.data_ptr(),
-                                             _cabi.OPUS_F16 if t.dtype == _cabi.operand_dtype() else _cabi.OPUS_F32,
+                                             _cabi.OPUS_F16 if t.dtype == _cabi.operand_dtype() else codes.get(t.dtype, _cabi.OPUS_F32),
                                              t.dim(), shape))
         _cabi.check(lib.opus_weights_ready(ctx))
 
