@@ -360,6 +360,59 @@ int opus_generate_scored_fanout(opus_ctx *ctx, const void *d_embeds, const uint8
                                 int32_t max_new, const int32_t *eos_ids, int32_t n_eos, int32_t pad_id, float temperature,
                                 float top_p, uint64_t seed, int32_t *d_out_ids, int32_t *n_out, float *d_token_logprobs,
                                 float *d_scores, float *d_logits, void *stream);
+
+/* Detached prefixes (added within ABI 10).  A snapshot is the K and V of a prefill's rows copied out of the context's cache into
+ * memory the caller owns: d_k / d_v operand dtype [dec_layers][P][dec_kv_heads][Tp][dec_head_dim] (slot 0 first), d_kstart int32 [P]
+ * (device) the first real slot of every row, h_kstart the same on the host.  It never goes stale, can be used any number of times
+ * and from every context of the same configuration and weights.  K is stored rotated by slot - kstart, so a row's slots can be
+ * placed at other slots unchanged as long as kstart moves with them. */
+typedef struct opus_prefix_snap {
+    const void *d_k, *d_v;
+    const int32_t *d_kstart, *h_kstart;
+    int32_t P, Tp;
+} opus_prefix_snap;
+/* Bytes of d_k plus d_v (each half of it) of a snapshot of P rows x Tp slots: 2 * dec_layers * P * dec_kv_heads * Tp * dec_head_dim
+ * * 2; -1 on a bad config or P outside 1 .. max_batch, Tp outside 1 .. max_prompt + max_new_tokens. */
+int64_t opus_llama_prefix_bytes(const opus_config *cfg, int32_t P, int32_t Tp);
+/* Strided copy-out of the live cache: rows 0 .. R - 1, slots 0 .. T - 1 of every layer -> d_k / d_v [dec_layers][R][dec_kv_heads][T]
+ * [dec_head_dim], and (d_kstart not NULL) the rows' kstart -> d_kstart [R].  `epoch`: what opus_llama_prefix /
+ * opus_llama_prefill_behind returned; OPUS_ESTATE when the cache has been prefilled or permuted since.  Decode steps keep the epoch:
+ * T may reach past the prompt to read the slots they appended.  Changes nothing in the context. */
+int opus_llama_prefix_export(opus_ctx *ctx, int64_t epoch, int32_t R, int32_t T, void *d_k, void *d_v, int32_t *d_kstart, void *stream);
+/* Prefill behind a prefix: the snapshot + R suffix rows -> the context state of opus_llama_prefill on the concatenated prompts,
+ * without running the prefix again.  d_embeds operand dtype [R, n, H]: the suffix embeddings, RIGHT-padded to n positions; h_lens
+ * [R] (host) 1 <= n_r <= n; h_src [R] (host) the snapshot row of every decode row (any order, repeats, rows may go unused).
+ * Afterwards (T' = Tp + n, p = h_src[r], d_r = n - n_r): kstart'[r] = kstart[p] + d_r, the prefix of row r sits at slots
+ * kstart'[r] .. kstart'[r] + Tp - kstart[p] - 1 (kv_place_kernel: one launch, all layers, bits unchanged), suffix position t at slot
+ * Tp + d_r + t, every row ends at T' - 1, the last-position logits fp32 [R, V] are left for the decode loop (and copied to
+ * d_last_logits when not NULL), the step counter is 0, *epoch (when not NULL) the new cache epoch.  Slots below kstart'[r] and rows
+ * >= R are not written.  The suffix pass is the prefill's layer loop on R n rows with attn_prefix_kernel reading the snapshot; every
+ * position runs through the last layer (no last-layer shortcut).  OPUS_ESHAPE unless R <= max_batch, Tp + n <= max_prompt,
+ * R n <= max_batch max_prompt and 1 <= n_r <= n; OPUS_EBADARG for a row of h_src outside the snapshot. */
+int opus_llama_prefill_behind(opus_ctx *ctx, const opus_prefix_snap *snap, const void *d_embeds, int32_t R, int32_t n,
+                              const int32_t *h_lens, const int32_t *h_src, float *d_last_logits, int64_t *epoch, void *stream);
+/* opus_generate_scored with its prefill replaced by opus_llama_prefill_behind (greedy: temperature == 0; outputs optional, all NULL:
+ * the plain loop).  Everything behind the prefill is that of an R-row batch: the captured step and its cache key, EOS ids, stop
+ * sequence, logits processors, token constraint, the draws keyed by (seed, row, step). */
+int opus_generate_scored_behind(opus_ctx *ctx, const opus_prefix_snap *snap, const void *d_embeds, int32_t R, int32_t n,
+                                const int32_t *h_lens, const int32_t *h_src, int32_t max_new, const int32_t *eos_ids, int32_t n_eos,
+                                int32_t pad_id, float temperature, float top_p, uint64_t seed, int32_t *d_out_ids, int32_t *n_out,
+                                float *d_token_logprobs, float *d_scores, float *d_logits, void *stream);
+/* opus_llama_score_continuations / opus_llama_score_tree behind a snapshot instead of the context's current prefill: the same pass
+ * with the attention reading d_k / d_v (no epoch, P = snap->P; d_last_rows fp32 [P, H] as opus_llama_prefix returned them).  Write
+ * nothing but their outputs. */
+int opus_llama_score_continuations_detached(opus_ctx *ctx, const opus_prefix_snap *snap, const void *d_embeds, int32_t R, int32_t n,
+                                            const int32_t *h_lens, const int32_t *h_src, const float *d_last_rows,
+                                            const int32_t *d_targets, float *d_logprob, void *d_scratch, int64_t scratch_bytes,
+                                            void *stream);
+int opus_llama_score_tree_detached(opus_ctx *ctx, const opus_prefix_snap *snap, const void *d_embeds, int32_t rows,
+                                   const int32_t *h_src, const int32_t *h_par, const int32_t *h_depth, int32_t n_score,
+                                   const int32_t *h_score_src, int32_t n_edges, const int32_t *h_edge_row, const int32_t *h_edge_tok,
+                                   const int32_t *h_edge_slot, int32_t n_stops, const int32_t *h_stop_row, const int32_t *h_stop_set,
+                                   const int32_t *h_stop_slot, int32_t n_stop_ids, const int32_t *h_stop_ids, int32_t n_stop_sets,
+                                   const int32_t *h_stop_off, const float *d_last_rows, float *d_node_lp, float *d_stop_lp,
+                                   int64_t n_slots, void *d_scratch, int64_t scratch_bytes, void *stream);
+
 /* Diagnostic: opus_generate_scored's fused arg-max / log-sum-exp pass on fp32 logits [B, V] (B <= max_batch, any V >= 1; rows
  * need no alignment): d_idx [B] the arg-max (lowest index among ties, bitwise what the greedy step picks), d_lse [B]. */
 int opus_debug_argmax_lse(opus_ctx *ctx, const float *d_logits, int32_t B, int32_t V, int32_t *d_idx, float *d_lse, void *stream);

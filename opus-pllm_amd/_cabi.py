@@ -55,8 +55,25 @@ class CConfig(C.Structure):
 
 
 _P = C.c_void_p
+
+
+class CPrefixSnap(C.Structure):
+    """struct opus_prefix_snap (include/opus_pllm.h): a detached prefix's K / V, its kstart on the device and on the host."""
+    _fields_ = [("d_k", _P), ("d_v", _P), ("d_kstart", _P), ("h_kstart", C.POINTER(C.c_int32)), ("P", C.c_int32), ("Tp", C.c_int32)]
+
+
+_SNAP = C.POINTER(CPrefixSnap)
+_I32P = C.POINTER(C.c_int32)
 # name -> (restype, argtypes): every symbol include/opus_pllm.h declares
 SIGNATURES = {
+    "opus_llama_prefix_bytes": (C.c_int64, [C.POINTER(CConfig), C.c_int32, C.c_int32]),
+    "opus_llama_prefix_export": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "opus_llama_prefill_behind": (C.c_int, [_P, _SNAP, _P, C.c_int32, C.c_int32, _I32P, _I32P, _P, C.POINTER(C.c_int64), _P]),
+    "opus_generate_scored_behind": (C.c_int, [_P, _SNAP, _P, C.c_int32, C.c_int32, _I32P, _I32P, C.c_int32, _I32P, C.c_int32, C.c_int32,
+                                              C.c_float, C.c_float, C.c_uint64, _P, _I32P, _P, _P, _P, _P]),
+    "opus_llama_score_continuations_detached": (C.c_int, [_P, _SNAP, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    "opus_llama_score_tree_detached": (C.c_int, [_P, _SNAP, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, C.c_int32, _P,
+                                                 _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, _P]),
     "opus_abi_version": (C.c_int, []),
     "opus_operand_dtype": (C.c_int, []),
     "opus_last_error": (C.c_char_p, []),

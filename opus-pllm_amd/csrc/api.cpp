@@ -181,6 +181,10 @@ struct opus_ctx {
     // slot of every row of the last opus_llama_prefix (host copy for the continuation rows' positions).
     int64_t epoch = 0;
     std::vector<int32_t> h_kstart;
+    // opus_llama_prefill_behind's int32 tables (row lists, positions, lengths, workgroup table, gather index): an allocation of
+    // its own, made on first use for the largest pass the context can run
+    int32_t *behind_tbl = nullptr;
+    int64_t prefills_behind = 0;         // opus_stat("prefills_behind")
 };
 
 static std::atomic<int64_t> g_epoch{0};
@@ -194,6 +198,13 @@ struct ContRows {
     const int32_t *nkst;          // [B] device
     AttnPrefixParams attn;        // layer-independent fields (kc / vc are set per layer)
     int nblocks;
+    // a detached prefix (opus_prefix_snap): the layers' K / V come from the snapshot (layer stride snap_sl halfs; attn.cache_sb /
+    // cache_sh / kstart are the snapshot's) instead of the context's cache
+    const half_t *snap_k = nullptr, *snap_v = nullptr;
+    int64_t snap_sl = 0;
+    // opus_llama_prefill_behind: the rows' rotated K and V of positions t < app_lens[b] (device, [B]) are also appended to cache
+    // row b at slot attn.Tp + (T - app_lens[b]) + t
+    const int32_t *app_lens = nullptr;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -409,6 +420,7 @@ extern "C" int opus_ctx_destroy(opus_ctx *c) {
     if (c->lproc_mem) (void)hipFree(c->lproc_mem);
     if (c->cons_tab) (void)hipFree(c->cons_tab);
     if (c->cons_mem) (void)hipFree(c->cons_mem);
+    if (c->behind_tbl) (void)hipFree(c->behind_tbl);
     if (c->h_nunf) (void)hipHostFree(c->h_nunf);
     for (auto &e : c->poll_ev) if (e) (void)hipEventDestroy(e);
     delete c;
@@ -1275,8 +1287,8 @@ static int attn_decode(opus_ctx *c, hipStream_t s, const ResidShadow &sh, int l,
 static int attn_prefix(opus_ctx *c, hipStream_t s, const ContRows &cr, int l, int M) {
     const opus_config &g = c->cfg;
     AttnPrefixParams a = cr.attn;
-    a.kc = c->kc + l * c->cache_sl;
-    a.vc = c->vc + l * c->cache_sl;
+    a.kc = cr.snap_k ? cr.snap_k + l * cr.snap_sl : c->kc + l * c->cache_sl;
+    a.vc = cr.snap_v ? cr.snap_v + l * cr.snap_sl : c->vc + l * c->cache_sl;
     const int QKV = (g.dec_heads + 2 * g.dec_kv_heads) * g.dec_head_dim, QD = g.dec_heads * g.dec_head_dim;
     // algorithmic bytes: the rows' projections + output, and every (prefix row, kv head)'s visible cache slots once
     KLF(KC_ATTN_PREFILL, 2.0 * M * (QKV + QD) + 4.0 * cr.nblocks * g.dec_kv_heads * g.dec_head_dim * a.Tp,
@@ -1291,6 +1303,9 @@ static int attn_prefill(opus_ctx *c, hipStream_t s, int l, int B, int T, const C
     const int nh = g.dec_heads, nkv = g.dec_kv_heads, hd = g.dec_head_dim, QKV = (nh + 2 * nkv) * hd, QD = nh * hd, M = B * T;
     if (cont) {
         KL(KC_OTHER, 4.0 * M * QKV, launch_dec_rope_cache(c->d_qkv, c->cs_dec, cont->nkst, B, T, nh, nkv, hd, nullptr, nullptr, 0, 0, s));
+        if (cont->app_lens)
+            KL(KC_OTHER, 8.0 * M * nkv * hd, launch_kv_append(c->d_qkv, cont->app_lens, B, T, nh, nkv, hd, cont->attn.Tp, c->kc + l * c->cache_sl,
+                                                              c->vc + l * c->cache_sl, c->cache_sb, c->cache_sh, s));
         return attn_prefix(c, s, *cont, l, M);
     }
     KL(KC_OTHER, 4.0 * M * QKV,
@@ -1362,13 +1377,14 @@ static int decode_step_opt(opus_ctx *c, hipStream_t s) {
 
 // all_rows: every position of every row runs through the last layer too, and the final residual stream of all B T rows is left in
 // d_x for opus_llama_forward; no lm_head, and the context is left without a prefill (decode_step fails until the next one).
-// cont: the B rows are continuations behind the cached prefix (ContRows; implies all_rows, mask unused): the KV cache, kstart,
-// the step word and the decode state are left as they are.
+// cont: the B rows are continuations behind the cached prefix (ContRows; implies all_rows, mask unused): kstart, the step word
+// and the decode state are left as they are, and so is the KV cache unless ContRows::app_lens is set (opus_llama_prefill_behind:
+// the rows' K / V are appended behind their prefix; the caller then sets kstart, the step word and the decode state itself).
 // nret > 1 (never with all_rows or cont): the fanned-out prefill - the B prompts run once, and the context is left as after a prefill of
 // every prompt repeated nret times (cur_B = B nret; cache rows, kstart and the last logits of prompt b in rows b nret + j).
 static int prefill(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8_t *mask, int B, int T, bool all_rows = false,
                    const ContRows *cont = nullptr, int nret = 1) {
-    c->phase = cont ? PH_SCORE : PH_PREFILL;
+    c->phase = cont && !cont->app_lens ? PH_SCORE : PH_PREFILL;      // (rows that append to the cache: opus_llama_prefill_behind)
     if (cont) {
         all_rows = true;
     } else {
@@ -1723,6 +1739,44 @@ static int check_current_prefix(const opus_ctx *c, const char *who, int P, int64
                                  "the handle belongs to another context)", who);
     return OPUS_OK;
 }
+// Where a pass behind a prefix finds it: the context's current prefill (snap == nullptr: the handle's P and epoch are checked) or
+// a detached snapshot (opus_prefix_snap: no epoch - it never goes stale - and any context of the same configuration)
+struct PrefixSrc {
+    int P = 0, Tp = 0;
+    std::vector<int32_t> kst;            // first visible slot of every prefix row (host)
+    const opus_prefix_snap *snap = nullptr;
+    // the pass reads the snapshot instead of the context's cache: same kernel, other base pointers and strides
+    void apply(const opus_config &g, ContRows &cr) const {
+        if (!snap) return;
+        cr.snap_k = reinterpret_cast<const half_t *>(snap->d_k);
+        cr.snap_v = reinterpret_cast<const half_t *>(snap->d_v);
+        cr.attn.cache_sh = (int64_t)Tp * g.dec_head_dim;
+        cr.attn.cache_sb = cr.attn.cache_sh * g.dec_kv_heads;
+        cr.snap_sl = cr.attn.cache_sb * P;
+        cr.attn.kstart = snap->d_kstart;
+    }
+};
+static int resolve_prefix(const opus_ctx *c, const char *who, const opus_prefix_snap *snap, int P, int64_t epoch, PrefixSrc &ps) {
+    ps.snap = snap;
+    if (!snap) {
+        OPC(check_current_prefix(c, who, P, epoch));
+        ps.P = P;
+        ps.Tp = c->cur_T;
+        ps.kst = c->h_kstart;
+        return OPUS_OK;
+    }
+    if (!snap->d_k || !snap->d_v || !snap->d_kstart || !snap->h_kstart) return fail(OPUS_EBADARG, "%s: null pointer in the prefix snapshot", who);
+    if (snap->P < 1 || snap->P > c->cfg.max_batch || snap->Tp < 1 || snap->Tp > c->cfg.max_prompt)
+        return fail(OPUS_ESHAPE, "%s: a snapshot of %d rows x %d slots, the context holds max_batch=%d rows and max_prompt=%d slots", who,
+                    snap->P, snap->Tp, c->cfg.max_batch, c->cfg.max_prompt);
+    for (int p = 0; p < snap->P; ++p)
+        if (snap->h_kstart[p] < 0 || snap->h_kstart[p] >= snap->Tp)
+            return fail(OPUS_EBADARG, "%s: kstart[%d]=%d of the snapshot outside [0, %d)", who, p, snap->h_kstart[p], snap->Tp);
+    ps.P = snap->P;
+    ps.Tp = snap->Tp;
+    ps.kst.assign(snap->h_kstart, snap->h_kstart + snap->P);
+    return OPUS_OK;
+}
 // layer 0 of the KV cache <- a history d_k_hist / d_v_hist [rows, kv heads, L, hd] (slots 0 .. L - 1) and kstart <- d_kstart [rows]
 // (the kernel-level debug entries)
 static int seed_cache(opus_ctx *c, hipStream_t s, const void *d_k_hist, const void *d_v_hist, const int32_t *d_kstart, int rows, int L) {
@@ -1763,25 +1817,26 @@ extern "C" int64_t opus_llama_score_scratch_bytes(const opus_config *cfg, int32_
     return prefix_scratch_bytes(*cfg, R, n);
 }
 
-extern "C" int opus_llama_score_continuations(opus_ctx *c, const void *d_embeds, int32_t R, int32_t n, const int32_t *h_lens,
-                                              const int32_t *h_src, const float *d_last_rows, int32_t P, int64_t epoch,
-                                              const int32_t *d_targets, float *d_logprob, void *d_scratch, int64_t scratch_bytes,
-                                              void *stream) {
+static int score_continuations_impl(opus_ctx *c, const opus_prefix_snap *snap, const void *d_embeds, int32_t R, int32_t n,
+                                    const int32_t *h_lens, const int32_t *h_src, const float *d_last_rows, int32_t P, int64_t epoch,
+                                    const int32_t *d_targets, float *d_logprob, void *d_scratch, int64_t scratch_bytes, void *stream) {
     OPC(need_ready(c));
     if (!d_embeds || !h_lens || !h_src || !d_last_rows || !d_targets || !d_logprob || !d_scratch)
         return fail(OPUS_EBADARG, "score_continuations: null pointer");
     const opus_config &g = c->cfg;
     if (R < 1 || n < 1 || n > g.max_prompt)
         return fail(OPUS_ESHAPE, "score_continuations: R=%d rows of n=%d positions (1 <= n <= max_prompt=%d)", R, n, g.max_prompt);
-    OPC(check_current_prefix(c, "score_continuations", P, epoch));
-    const int Tp = c->cur_T, ctx_cap = g.max_prompt + g.max_new_tokens;
+    PrefixSrc ps;
+    OPC(resolve_prefix(c, "score_continuations", snap, P, epoch, ps));
+    P = ps.P;
+    const int Tp = ps.Tp, ctx_cap = g.max_prompt + g.max_new_tokens;
     int64_t N = 0;
     for (int r = 0; r < R; ++r) {
         if (h_src[r] < 0 || h_src[r] >= P) return fail(OPUS_EBADARG, "score_continuations: prefix row %d of row %d outside [0, %d)", h_src[r], r, P);
         if (h_lens[r] < 0 || h_lens[r] > n) return fail(OPUS_ESHAPE, "score_continuations: length %d of row %d outside [0, %d]", h_lens[r], r, n);
-        if (Tp - c->h_kstart[h_src[r]] + n > ctx_cap)
+        if (Tp - ps.kst[h_src[r]] + n > ctx_cap)
             return fail(OPUS_ESHAPE, "score_continuations: prefix of %d tokens + %d positions exceed the context's %d positions "
-                                     "(max_prompt + max_new_tokens)", Tp - c->h_kstart[h_src[r]], n, ctx_cap);
+                                     "(max_prompt + max_new_tokens)", Tp - ps.kst[h_src[r]], n, ctx_cap);
         N += h_lens[r];
     }
     if (N >= (1ll << 31)) return fail(OPUS_ESHAPE, "score_continuations: %lld scored tokens", (long long)N);
@@ -1800,7 +1855,7 @@ extern "C" int opus_llama_score_continuations(opus_ctx *c, const void *d_embeds,
     for (int64_t r0 = 0; r0 < R; r0 += Rg_max) {
         const int Rg = (int)std::min<int64_t>(Rg_max, R - r0);
         PrefixTables t;
-        build_prefix_tables(g, c->h_kstart, Tp, h_src + r0, Rg, n, t);
+        build_prefix_tables(g, ps.kst, Tp, h_src + r0, Rg, n, t);
         if (t.nblocks > attn_prefix_max_blocks(Rg, g.max_batch, G, n)) return fail(OPUS_EHIP, "score_continuations: block table overflow");
         // scored rows: token 0 of row r from the prefix's last row (gather index -(p) - 1), token j from position j - 1 of the pass
         int64_t Ng = 0;
@@ -1816,6 +1871,7 @@ extern "C" int opus_llama_score_continuations(opus_ctx *c, const void *d_embeds,
         cr.nkst = tbl + t.nkst;
         cr.nblocks = t.nblocks;
         cr.attn = prefix_params(c, tbl, t, Tp, n, c->d_qkv, nullptr, nullptr, c->d_ctx);
+        ps.apply(g, cr);
         const half_t *emb = reinterpret_cast<const half_t *>(d_embeds) + r0 * n * (int64_t)H;
         OPC(prefill(c, s, emb, nullptr, Rg, n, true, &cr));
         c->phase = PH_SCORE;
@@ -1829,6 +1885,23 @@ extern "C" int opus_llama_score_continuations(opus_ctx *c, const void *d_embeds,
         HIPC(hipStreamSynchronize(s));                              // (the table upload's host buffer is reused by the next pass)
     }
     return OPUS_OK;
+}
+
+extern "C" int opus_llama_score_continuations(opus_ctx *c, const void *d_embeds, int32_t R, int32_t n, const int32_t *h_lens,
+                                              const int32_t *h_src, const float *d_last_rows, int32_t P, int64_t epoch,
+                                              const int32_t *d_targets, float *d_logprob, void *d_scratch, int64_t scratch_bytes,
+                                              void *stream) {
+    return score_continuations_impl(c, nullptr, d_embeds, R, n, h_lens, h_src, d_last_rows, P, epoch, d_targets, d_logprob, d_scratch,
+                                    scratch_bytes, stream);
+}
+
+extern "C" int opus_llama_score_continuations_detached(opus_ctx *c, const opus_prefix_snap *snap, const void *d_embeds, int32_t R,
+                                                       int32_t n, const int32_t *h_lens, const int32_t *h_src, const float *d_last_rows,
+                                                       const int32_t *d_targets, float *d_logprob, void *d_scratch,
+                                                       int64_t scratch_bytes, void *stream) {
+    if (!snap) return fail(OPUS_EBADARG, "score_continuations_detached: null snapshot");
+    return score_continuations_impl(c, snap, d_embeds, R, n, h_lens, h_src, d_last_rows, 0, 0, d_targets, d_logprob, d_scratch,
+                                    scratch_bytes, stream);
 }
 
 // The shared body of opus_debug_attn_prefix / opus_debug_attn_tree (h_par: the tree form, n = 1), after their argument checks:
@@ -1940,13 +2013,13 @@ static int check_tree_rows(const char *who, int rows, int P, const int32_t *h_sr
     return OPUS_OK;
 }
 
-extern "C" int opus_llama_score_tree(opus_ctx *c, const void *d_embeds, int32_t rows, const int32_t *h_src, const int32_t *h_par,
-                                     const int32_t *h_depth, int32_t n_score, const int32_t *h_score_src, int32_t n_edges,
-                                     const int32_t *h_edge_row, const int32_t *h_edge_tok, const int32_t *h_edge_slot, int32_t n_stops,
-                                     const int32_t *h_stop_row, const int32_t *h_stop_set, const int32_t *h_stop_slot,
-                                     int32_t n_stop_ids, const int32_t *h_stop_ids, int32_t n_stop_sets, const int32_t *h_stop_off,
-                                     const float *d_last_rows, int32_t P, int64_t epoch, float *d_node_lp, float *d_stop_lp,
-                                     int64_t n_slots, void *d_scratch, int64_t scratch_bytes, void *stream) {
+static int score_tree_impl(opus_ctx *c, const opus_prefix_snap *snap, const void *d_embeds, int32_t rows, const int32_t *h_src,
+                           const int32_t *h_par, const int32_t *h_depth, int32_t n_score, const int32_t *h_score_src, int32_t n_edges,
+                           const int32_t *h_edge_row, const int32_t *h_edge_tok, const int32_t *h_edge_slot, int32_t n_stops,
+                           const int32_t *h_stop_row, const int32_t *h_stop_set, const int32_t *h_stop_slot, int32_t n_stop_ids,
+                           const int32_t *h_stop_ids, int32_t n_stop_sets, const int32_t *h_stop_off, const float *d_last_rows,
+                           int32_t P, int64_t epoch, float *d_node_lp, float *d_stop_lp, int64_t n_slots, void *d_scratch,
+                           int64_t scratch_bytes, void *stream) {
     OPC(need_ready(c));
     const opus_config &g = c->cfg;
     if (rows < 0 || rows > dec_rows_cap(g) || n_score < 0 || n_edges < 0 || n_stops < 0 || n_stop_ids < 0 || n_stop_sets < 0 || n_slots < 1)
@@ -1956,13 +2029,15 @@ extern "C" int opus_llama_score_tree(opus_ctx *c, const void *d_embeds, int32_t 
         (n_edges && (!h_edge_row || !h_edge_tok || !h_edge_slot)) ||
         (n_stops && (!h_stop_row || !h_stop_set || !h_stop_slot || !h_stop_ids || !h_stop_off || !d_stop_lp)))
         return fail(OPUS_EBADARG, "score_tree: null pointer");
-    OPC(check_current_prefix(c, "score_tree", P, epoch));
-    const int Tp = c->cur_T, ctx_cap = g.max_prompt + g.max_new_tokens, V = g.dec_vocab, H = g.dec_dim;
+    PrefixSrc ps;
+    OPC(resolve_prefix(c, "score_tree", snap, P, epoch, ps));
+    P = ps.P;
+    const int Tp = ps.Tp, ctx_cap = g.max_prompt + g.max_new_tokens, V = g.dec_vocab, H = g.dec_dim;
     OPC(check_tree_rows("score_tree", rows, P, h_src, h_par, h_depth));
     for (int r = 0; r < rows; ++r)
-        if (Tp - c->h_kstart[h_src[r]] + h_depth[r] > ctx_cap)
+        if (Tp - ps.kst[h_src[r]] + h_depth[r] > ctx_cap)
             return fail(OPUS_ESHAPE, "score_tree: prefix of %d tokens + depth %d exceed the context's %d positions (max_prompt + "
-                                     "max_new_tokens)", Tp - c->h_kstart[h_src[r]], h_depth[r], ctx_cap);
+                                     "max_new_tokens)", Tp - ps.kst[h_src[r]], h_depth[r], ctx_cap);
     for (int k = 0; k < n_score; ++k)
         if (h_score_src[k] >= rows || h_score_src[k] < -P)
             return fail(OPUS_EBADARG, "score_tree: scored source %d of entry %d outside [-%d, %d)", h_score_src[k], k, P, rows);
@@ -1992,7 +2067,7 @@ extern "C" int opus_llama_score_tree(opus_ctx *c, const void *d_embeds, int32_t 
     const int G = g.dec_heads / g.dec_kv_heads;
     const int64_t chunk = tree_chunk(g, n_score);
     PrefixTables t;
-    build_prefix_tables(g, c->h_kstart, Tp, h_src, rows, 1, t);
+    build_prefix_tables(g, ps.kst, Tp, h_src, rows, 1, t);
     if (t.nblocks > attn_prefix_max_blocks(rows, g.max_batch, G, 1)) return fail(OPUS_EHIP, "score_tree: block table overflow");
     for (int r = 0; r < rows; ++r) t.w[t.nkst + r] -= h_depth[r] - 1;      // position of a node at depth d: Tp - kstart[p] + d - 1
     auto put = [&](const int32_t *src, int64_t n) {
@@ -2020,6 +2095,7 @@ extern "C" int opus_llama_score_tree(opus_ctx *c, const void *d_embeds, int32_t 
         cr.nblocks = t.nblocks;
         cr.attn = prefix_params(c, tbl, t, Tp, 1, c->d_qkv, nullptr, nullptr, c->d_ctx);
         cr.attn.par = tbl + o_par;
+        ps.apply(g, cr);
         OPC(prefill(c, s, reinterpret_cast<const half_t *>(d_embeds), nullptr, rows, 1, true, &cr));
     }
     c->phase = PH_SCORE;
@@ -2038,6 +2114,172 @@ extern "C" int opus_llama_score_tree(opus_ctx *c, const void *d_embeds, int32_t 
         k0s = k1s;
     }
     HIPC(hipStreamSynchronize(s));                                          // (the host tables are the caller's: they may go away)
+    return OPUS_OK;
+}
+
+extern "C" int opus_llama_score_tree(opus_ctx *c, const void *d_embeds, int32_t rows, const int32_t *h_src, const int32_t *h_par,
+                                     const int32_t *h_depth, int32_t n_score, const int32_t *h_score_src, int32_t n_edges,
+                                     const int32_t *h_edge_row, const int32_t *h_edge_tok, const int32_t *h_edge_slot, int32_t n_stops,
+                                     const int32_t *h_stop_row, const int32_t *h_stop_set, const int32_t *h_stop_slot,
+                                     int32_t n_stop_ids, const int32_t *h_stop_ids, int32_t n_stop_sets, const int32_t *h_stop_off,
+                                     const float *d_last_rows, int32_t P, int64_t epoch, float *d_node_lp, float *d_stop_lp,
+                                     int64_t n_slots, void *d_scratch, int64_t scratch_bytes, void *stream) {
+    return score_tree_impl(c, nullptr, d_embeds, rows, h_src, h_par, h_depth, n_score, h_score_src, n_edges, h_edge_row, h_edge_tok,
+                           h_edge_slot, n_stops, h_stop_row, h_stop_set, h_stop_slot, n_stop_ids, h_stop_ids, n_stop_sets, h_stop_off,
+                           d_last_rows, P, epoch, d_node_lp, d_stop_lp, n_slots, d_scratch, scratch_bytes, stream);
+}
+
+extern "C" int opus_llama_score_tree_detached(opus_ctx *c, const opus_prefix_snap *snap, const void *d_embeds, int32_t rows,
+                                              const int32_t *h_src, const int32_t *h_par, const int32_t *h_depth, int32_t n_score,
+                                              const int32_t *h_score_src, int32_t n_edges, const int32_t *h_edge_row,
+                                              const int32_t *h_edge_tok, const int32_t *h_edge_slot, int32_t n_stops,
+                                              const int32_t *h_stop_row, const int32_t *h_stop_set, const int32_t *h_stop_slot,
+                                              int32_t n_stop_ids, const int32_t *h_stop_ids, int32_t n_stop_sets,
+                                              const int32_t *h_stop_off, const float *d_last_rows, float *d_node_lp, float *d_stop_lp,
+                                              int64_t n_slots, void *d_scratch, int64_t scratch_bytes, void *stream) {
+    if (!snap) return fail(OPUS_EBADARG, "score_tree_detached: null snapshot");
+    return score_tree_impl(c, snap, d_embeds, rows, h_src, h_par, h_depth, n_score, h_score_src, n_edges, h_edge_row, h_edge_tok,
+                           h_edge_slot, n_stops, h_stop_row, h_stop_set, h_stop_slot, n_stop_ids, h_stop_ids, n_stop_sets, h_stop_off,
+                           d_last_rows, 0, 0, d_node_lp, d_stop_lp, n_slots, d_scratch, scratch_bytes, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ detached prefixes
+// opus_llama_prefix_export copies a prefill's K / V out of the cache (a snapshot the caller owns); opus_llama_prefill_behind puts
+// snapshot rows back under R suffix rows and leaves the context as after a prefill of the concatenated prompts.
+
+static int64_t prefix_snap_halfs(const opus_config &g, int64_t rows, int64_t T) {
+    return (int64_t)g.dec_layers * rows * g.dec_kv_heads * T * g.dec_head_dim;
+}
+
+extern "C" int64_t opus_llama_prefix_bytes(const opus_config *cfg, int32_t P, int32_t Tp) {
+    if (check_cfg(cfg) != OPUS_OK) return -1;
+    if (P < 1 || Tp < 1 || P > cfg->max_batch || Tp > cfg->max_prompt + cfg->max_new_tokens) {
+        fail(OPUS_ESHAPE, "prefix_bytes: P=%d Tp=%d (1 .. max_batch=%d rows, 1 .. %d slots)", P, Tp, cfg->max_batch,
+             cfg->max_prompt + cfg->max_new_tokens);
+        return -1;
+    }
+    return 2 * prefix_snap_halfs(*cfg, P, Tp) * (int64_t)sizeof(half_t);
+}
+
+extern "C" int opus_llama_prefix_export(opus_ctx *c, int64_t epoch, int32_t R, int32_t T, void *d_k, void *d_v, int32_t *d_kstart,
+                                        void *stream) {
+    OPC(need_ready(c));
+    if (!d_k || !d_v) return fail(OPUS_EBADARG, "prefix_export: null pointer");
+    const opus_config &g = c->cfg;
+    if (!c->prefilled || epoch != c->epoch)
+        return fail(OPUS_ESTATE, "prefix_export: the epoch is not this context's current one (a later call prefilled or permuted the "
+                                 "cache, or it belongs to another context)");
+    if (R < 1 || R > g.max_batch || T < 1 || T > g.max_prompt + g.max_new_tokens)
+        return fail(OPUS_ESHAPE, "prefix_export: R=%d rows of T=%d slots (1 .. max_batch=%d, 1 .. %d)", R, T, g.max_batch,
+                    g.max_prompt + g.max_new_tokens);
+    hipStream_t s = (hipStream_t)stream;
+    c->phase = PH_OTHER;
+    KL(KC_OTHER, 4.0 * (double)prefix_snap_halfs(g, R, T) * sizeof(half_t),
+       launch_kv_export(c->kc, c->vc, c->cache_sl, c->cache_sb, c->cache_sh, g.dec_layers, R, g.dec_kv_heads, T, g.dec_head_dim,
+                        (half_t *)d_k, (half_t *)d_v, s));
+    if (d_kstart) HIPC(hipMemcpyAsync(d_kstart, c->d_kstart, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    return OPUS_OK;
+}
+
+// words of the behind pass's device tables: PrefixTables (+ workgroup table) | lens [R] | gather index [R]
+static int64_t behind_table_words(const opus_config &g) {
+    const int G = g.dec_heads / g.dec_kv_heads;
+    const int64_t nb = dec_rows_cap(g) * G / 128 + g.max_batch + 1;        // (attn_prefix_max_blocks for the largest pass)
+    return (int64_t)g.max_batch + 1 + 4 * (int64_t)g.max_batch + 2 * nb;
+}
+
+// The prefill of opus_llama_prefill_behind / opus_generate_scored_behind, after need_ready: checks, tables, kv_place, the suffix
+// pass (prefill()'s layer loop with continuation rows that also append to the cache), the rows' last positions, lm_head, state.
+struct BehindArgs {
+    const opus_prefix_snap *snap;
+    const int32_t *h_lens, *h_src;
+};
+static int prefill_behind(opus_ctx *c, hipStream_t s, const BehindArgs &b, const half_t *embeds, int R, int n) {
+    const opus_config &g = c->cfg;
+    if (!b.snap || !b.h_lens || !b.h_src || !embeds) return fail(OPUS_EBADARG, "prefill_behind: null pointer");
+    PrefixSrc ps;
+    OPC(resolve_prefix(c, "prefill_behind", b.snap, 0, 0, ps));
+    const int P = ps.P, Tp = ps.Tp, H = g.dec_dim, G = g.dec_heads / g.dec_kv_heads;
+    if (R < 1 || R > g.max_batch)
+        return fail(OPUS_ESHAPE, "prefill_behind: R=%d decoder rows, the context holds max_batch=%d", R, g.max_batch);
+    if (n < 1 || Tp + n > g.max_prompt)
+        return fail(OPUS_ESHAPE, "prefill_behind: prefix of %d slots + suffix of %d positions = %d, the context holds max_prompt=%d", Tp, n,
+                    Tp + n, g.max_prompt);
+    if ((int64_t)R * n > dec_rows_cap(g))
+        return fail(OPUS_ESHAPE, "prefill_behind: R x n = %d x %d suffix positions, the prefill buffers hold %lld", R, n,
+                    (long long)dec_rows_cap(g));
+    for (int r = 0; r < R; ++r) {
+        if (b.h_src[r] < 0 || b.h_src[r] >= P) return fail(OPUS_EBADARG, "prefill_behind: prefix row %d of row %d outside [0, %d)", b.h_src[r], r, P);
+        if (b.h_lens[r] < 1 || b.h_lens[r] > n) return fail(OPUS_ESHAPE, "prefill_behind: suffix length %d of row %d outside [1, %d]", b.h_lens[r], r, n);
+    }
+    if (!c->behind_tbl) HIPC(hipMalloc((void **)&c->behind_tbl, (size_t)behind_table_words(g) * sizeof(int32_t)));
+    PrefixTables t;
+    build_prefix_tables(g, ps.kst, Tp, b.h_src, R, n, t);
+    if (t.nblocks > attn_prefix_max_blocks(R, g.max_batch, G, n)) return fail(OPUS_EHIP, "prefill_behind: block table overflow");
+    const int o_lens = (int)t.w.size();
+    t.w.insert(t.w.end(), b.h_lens, b.h_lens + R);
+    const int o_last = (int)t.w.size();
+    std::vector<int32_t> nks(R);
+    for (int r = 0; r < R; ++r) {
+        t.w.push_back(r * n + b.h_lens[r] - 1);                               // the row's last real position in the pass
+        nks[r] = ps.kst[b.h_src[r]] + n - b.h_lens[r];                        // kstart' = kstart[p] + d_r
+    }
+    if ((int64_t)t.w.size() > behind_table_words(g)) return fail(OPUS_EHIP, "prefill_behind: table overflow");
+    int32_t *tbl = c->behind_tbl;
+    new_epoch(c);
+    c->prefilled = false;                                                     // (until the pass is enqueued whole)
+    c->cur_B = 0;
+    c->h_kstart.clear();
+    c->phase = PH_PREFILL;
+    HIPC(launch_upload_i32(t.w.data(), (int)t.w.size(), tbl, s));
+    HIPC(launch_upload_i32(nks.data(), R, c->d_kstart, s));
+    KvPlaceParams kp;
+    kp.snap_k = reinterpret_cast<const half_t *>(b.snap->d_k); kp.snap_v = reinterpret_cast<const half_t *>(b.snap->d_v);
+    kp.kstart = b.snap->d_kstart; kp.P = P; kp.Tp = Tp; kp.kc = c->kc; kp.vc = c->vc;
+    kp.cache_sl = c->cache_sl; kp.cache_sb = c->cache_sb; kp.cache_sh = c->cache_sh;
+    kp.list = tbl + t.list; kp.off = tbl + t.off; kp.new_kstart = c->d_kstart;
+    kp.layers = g.dec_layers; kp.nkv = g.dec_kv_heads; kp.hd = g.dec_head_dim;
+    double placed = 0.0, read = 0.0;                                          // slots written / read, for the launch's byte count
+    for (int r = 0; r < R; ++r) placed += Tp - ps.kst[b.h_src[r]];
+    for (int p = 0; p < P; ++p) read += t.w[t.off + p + 1] > t.w[t.off + p] ? Tp - ps.kst[p] : 0;
+    // timed under phase "other": opus_timing_get("other", "other") behind this call is the placement launch alone (its own
+    // dispatch timestamps), apart from the prefill phase's class totals
+    c->phase = PH_OTHER;
+    KL(KC_OTHER, (placed + read) * 2.0 * g.dec_layers * g.dec_kv_heads * g.dec_head_dim * sizeof(half_t), launch_kv_place(kp, s));
+    c->phase = PH_PREFILL;
+    ContRows cr;
+    cr.nkst = tbl + t.nkst;
+    cr.nblocks = t.nblocks;
+    cr.attn = prefix_params(c, tbl, t, Tp, n, c->d_qkv, nullptr, nullptr, c->d_ctx);
+    ps.apply(g, cr);
+    cr.app_lens = tbl + o_lens;
+    OPC(prefill(c, s, embeds, nullptr, R, n, true, &cr));
+    c->phase = PH_PREFILL;
+    // every position ran through the last layer (the continuation-row form keeps all rows): the rows' last real positions -> d_xl
+    KL(KC_OTHER, 8.0 * R * H + 4.0 * R, launch_gather_rows(c->d_x, tbl + o_last, R, (int64_t)R * n, H, c->d_xl, s));
+    if (g.dec_arch == 1) {
+        OPC(lm_head_opt(c, s, R));
+    } else {
+        ResidShadow none;
+        OPC(lm_head(c, s, none, R));
+    }
+    OPC(reset_step(c, s, Tp + n));
+    c->cur_B = R;
+    c->cur_T = Tp + n;
+    c->prefilled = true;
+    ++c->prefills_behind;
+    return OPUS_OK;
+}
+
+extern "C" int opus_llama_prefill_behind(opus_ctx *c, const opus_prefix_snap *snap, const void *d_embeds, int32_t R, int32_t n,
+                                         const int32_t *h_lens, const int32_t *h_src, float *d_last_logits, int64_t *epoch,
+                                         void *stream) {
+    OPC(need_ready(c));
+    hipStream_t s = (hipStream_t)stream;
+    OPC(prefill_behind(c, s, BehindArgs{snap, h_lens, h_src}, (const half_t *)d_embeds, R, n));
+    if (d_last_logits)
+        HIPC(hipMemcpyAsync(d_last_logits, c->d_logits, (size_t)R * c->cfg.dec_vocab * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (epoch) *epoch = c->epoch;
     return OPUS_OK;
 }
 
@@ -2201,12 +2443,15 @@ static int set_cons_start_div(opus_ctx *c, int32_t div, hipStream_t s) {
 
 static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mask, int32_t B, int32_t T, int32_t max_new,
                          const int32_t *eos_ids, int32_t n_eos, int32_t pad_id, float temperature, float top_p, uint64_t seed,
-                         int32_t *d_out_ids, int32_t *n_out, void *stream, const GenOutDesc *outs = nullptr, int32_t nret = 1) {
+                         int32_t *d_out_ids, int32_t *n_out, void *stream, const GenOutDesc *outs = nullptr, int32_t nret = 1,
+                         const BehindArgs *behind = nullptr) {
+    // behind (opus_generate_scored_behind): the B rows are suffixes of T right-padded positions behind a detached prefix (no mask)
     OPC(need_ready(c));
     if (temperature < 0.f || top_p <= 0.f || top_p > 1.f) return fail(OPUS_EBADARG, "generate: temperature >= 0 and 0 < top_p <= 1");
     c->samp_temp = temperature;
     c->samp_top_p = top_p;
-    OPC(check_prefill_args(c, d_embeds, d_mask, B, T));
+    if (!behind) OPC(check_prefill_args(c, d_embeds, d_mask, B, T));
+    else if (B < 1 || B > c->cfg.max_batch) return fail(OPUS_ESHAPE, "generate: B=%d decoder rows, the context holds max_batch=%d", B, c->cfg.max_batch);
     OPC(check_fanout(c, B, nret, "generate"));
     const int32_t BN = B * nret;             // decoder rows: the loop, its buffers and the captured step are those of a BN-row batch
     if (!d_out_ids || !n_out) return fail(OPUS_EBADARG, "generate_greedy: null pointer");
@@ -2241,8 +2486,9 @@ static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mas
     }
     HIPC(hipMemsetAsync(c->d_fin, 0, BN * sizeof(int32_t), s));
     HIPC(hipMemsetAsync(c->d_nunf, 0, (size_t)max_new * sizeof(int32_t), s));
-    OPC(prefill(c, s, (const half_t *)d_embeds, d_mask, B, T, false, nullptr, nret));
-    c->gen_outs = gen_outs;              // (the prefill's own launches are the same either way)
+    if (behind) OPC(prefill_behind(c, s, *behind, (const half_t *)d_embeds, B, T));
+    else OPC(prefill(c, s, (const half_t *)d_embeds, d_mask, B, T, false, nullptr, nret));
+    c->gen_outs = gen_outs;             // (the prefill's own launches are the same either way)
     struct GenOutsReset { opus_ctx *c; ~GenOutsReset() { c->gen_outs = 0; } } gen_outs_reset{c};
 
     // OPUS_NO_GRAPH=1: eager launches (rocprofv3 --pmc cannot collect counters through graph replays)
@@ -2559,6 +2805,23 @@ extern "C" int opus_generate_scored_fanout(opus_ctx *c, const void *d_embeds, co
     const GenOutDesc outs{d_token_logprobs, d_scores, d_logits, nullptr};
     return generate_impl(c, d_embeds, d_mask, B, T, max_new, eos_ids, n_eos, pad_id, temperature, temperature > 0.f ? top_p : 1.f,
                          temperature > 0.f ? seed : 0, d_out_ids, n_out, stream, &outs, nret);
+}
+
+/* opus_generate_scored with its prefill replaced by opus_llama_prefill_behind: R suffix rows of n right-padded positions behind the
+   rows h_src of a detached prefix.  Everything behind the prefill - the captured step and its cache key (R rows), EOS ids, stop
+   sequence, processors, constraint, outputs, the draws keyed by (seed, row, step) - is that of an R-row batch. */
+extern "C" int opus_generate_scored_behind(opus_ctx *c, const opus_prefix_snap *snap, const void *d_embeds, int32_t R, int32_t n,
+                                           const int32_t *h_lens, const int32_t *h_src, int32_t max_new, const int32_t *eos_ids,
+                                           int32_t n_eos, int32_t pad_id, float temperature, float top_p, uint64_t seed,
+                                           int32_t *d_out_ids, int32_t *n_out, float *d_token_logprobs, float *d_scores, float *d_logits,
+                                           void *stream) {
+    if (!c) return fail(OPUS_EBADARG, "ctx is null");
+    if (!snap || !h_lens || !h_src || !d_embeds) return fail(OPUS_EBADARG, "generate_scored_behind: null pointer");
+    if (!(temperature >= 0.f)) return fail(OPUS_EBADARG, "generate_scored_behind: temperature must be >= 0 (0 = greedy)");
+    const GenOutDesc outs{d_token_logprobs, d_scores, d_logits, nullptr};
+    const BehindArgs behind{snap, h_lens, h_src};
+    return generate_impl(c, d_embeds, nullptr, R, n, max_new, eos_ids, n_eos, pad_id, temperature, temperature > 0.f ? top_p : 1.f,
+                         temperature > 0.f ? seed : 0, d_out_ids, n_out, stream, &outs, 1, &behind);
 }
 
 /* Diagnostic: the fused arg-max / log-sum-exp pass of opus_generate_scored on fp32 logits [B, V] (B <= max_batch, any V >= 1):
@@ -3059,6 +3322,7 @@ extern "C" int64_t opus_stat(opus_ctx *c, const char *name) {
     if (!strcmp(name, "graphs_cached")) return (int64_t)c->graphs.size();
     if (!strcmp(name, "decode_steps")) return c->decode_steps;
     if (!strcmp(name, "w8_gemms")) return c->w8_gemms;
+    if (!strcmp(name, "prefills_behind")) return c->prefills_behind;
     return -1;
 }
 

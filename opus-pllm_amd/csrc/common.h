@@ -339,6 +339,31 @@ int attn_prefix_max_blocks(int R, int P, int G, int n);   // an upper bound of t
 // the cache slots of its prefix row, then to r, par[r], par[par[r]], ... (rows of this pass, the chain ends at -1).
 hipError_t launch_attn_prefix(const AttnPrefixParams &p, int nblocks, hipStream_t s);
 
+// kv_place.hip: the bandwidth kernels of detached prefixes (opus_llama_prefix_export, opus_llama_prefill_behind).  A snapshot holds
+// K (or V) of `rows` cache rows as [layers][rows][nkv][T][hd], slot 0 first; the live cache is kc / vc with strides cache_sl /
+// cache_sb / cache_sh (halfs).  hd is a multiple of 8 and every base 16-byte aligned: the copies move 16 bytes per lane.
+// export: snapshot <- rows 0 .. R - 1, slots 0 .. T - 1 of every layer of the cache (one launch, K and V)
+hipError_t launch_kv_export(const half_t *kc, const half_t *vc, int64_t cache_sl, int64_t cache_sb, int64_t cache_sh, int layers, int R,
+                            int nkv, int T, int hd, half_t *snap_k, half_t *snap_v, hipStream_t s);
+// place: the visible slots kstart[p] .. Tp - 1 of snapshot row p -> every decode row r of list[off[p] .. off[p + 1]) at slots
+// new_kstart[r] .. new_kstart[r] + Tp - kstart[p] - 1, all layers, K and V, one launch; each 16-byte piece is read once and stored
+// to all the rows of its prefix row.  Nothing else of the cache is written.
+struct KvPlaceParams {
+    const half_t *snap_k, *snap_v;
+    const int32_t *kstart;          // [P] device: first visible slot of every snapshot row
+    int P, Tp;
+    half_t *kc, *vc;
+    int64_t cache_sl, cache_sb, cache_sh;
+    const int32_t *list, *off;      // decode rows grouped by prefix row (PrefixTables)
+    const int32_t *new_kstart;      // [R] device: first visible slot of every decode row
+    int layers, nkv, hd;
+};
+hipError_t launch_kv_place(const KvPlaceParams &p, hipStream_t s);
+// append (one layer): rotated K and the V of the suffix positions t < lens[r] of the R rows in qkv ([R n][(nh + 2 nkv) hd]) -> cache
+// row r at slot Tp + (n - lens[r]) + t
+hipError_t launch_kv_append(const half_t *qkv, const int32_t *lens, int R, int n, int nh, int nkv, int hd, int Tp, half_t *kc, half_t *vc,
+                            int64_t cache_sb, int64_t cache_sh, hipStream_t s);
+
 // contact.hip: ESM-2 contact maps (opus_esm2_contacts_packed).  One layer's accumulation over token-packed proteins cu[B + 1]
 // (rows <cls> residues <eos>): Q / K rows of stride ld (head h at column h hd; q scaled and both rotated as the attention takes
 // them); A[sum n_b^2] (+)= sum_h w[h] P_h over the interior positions, rows[(cu[b] - 2 b + i) vld + c0 + h] = interior row sums

@@ -42,7 +42,7 @@ from opus_pllm_amd.prompt import (add_constraint_args, add_logits_processor_args
 
 def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperature=0.0, top_p=0.7, num_beams=1,
              use_input_embed=False, device=None, logits_out=None, stop_sequence=None, inflight=1, logprobs_out=None,
-             processors=None, num_return_sequences=1):
+             processors=None, num_return_sequences=1, share_prompt_head=False):
     """The batch loop of run_opus_ddp.py:88-134 over this rank's items -> [n, max_new] new ids (rows padded with eos).
 
     use_input_embed (two-stage pipeline): the `input_embed` vectors of the WHOLE shard go through the modality
@@ -60,7 +60,11 @@ def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperatu
     logits processors and of the token constraint (prefix_allowed_tokens_fn: one TokenTrie, built once, for every batch).
     num_return_sequences = N > 1 (--num_return_sequences): a call takes batch_size // N prompts and returns N rows for each
     (generate(num_return_sequences=N): one encode and one prefill per prompt); the result is [n N, max_new], item i's answers in
-    rows i N .. i N + N - 1, and the other outputs have n N rows too."""
+    rows i N .. i N + N - 1, and the other outputs have n N rows too.
+    share_prompt_head (--share_prompt_head): the longest leading id run that all the shard's prompts share in front of their
+    first placeholder (build_prompt's system text: tokenizer_seq_token tokenises it on its own, so the ids are identical) is
+    prefilled ONCE as a detached one-row prefix (cache_prefix(detach=True)) and every batch is generated behind it
+    (generate(prefix=...)): only the rest of each prompt is prefilled.  Other launch shapes than the plain call, so opt-in."""
     dev = device or model.device
     nret = int(num_return_sequences)
     if nret < 1:
@@ -71,6 +75,14 @@ def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperatu
     if use_input_embed and items:
         prot_all = model.project_dataset(torch.tensor([q["input_embed"] for q in items], dtype=torch.float32, device=dev))
     starts = list(range(0, len(items), batch_size))
+    head_len, head = 0, None
+    if share_prompt_head and items:
+        head_len = shared_head_length([opa.tokenizer_seq_token(build_prompt(q["instruction"], input_path), tokenizer,
+                                                               opa.DEFAULT_SEQ_TOKEN_INDEX) for q in items])
+        if head_len:
+            first = opa.tokenizer_seq_token(build_prompt(items[0]["instruction"], input_path), tokenizer, opa.DEFAULT_SEQ_TOKEN_INDEX)
+            with torch.inference_mode():
+                head = model.cache_prefix(torch.tensor([list(first[:head_len])], dtype=torch.long, device=dev), detach=True)
     outs = [None] * len(starts)
     last = [None] * len(starts)
     lps = [None] * len(starts)
@@ -82,11 +94,13 @@ def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperatu
         i = starts[j]
         batch = items[i:i + batch_size]
         prompts = [build_prompt(q["instruction"], input_path) for q in batch]
-        ids = [opa.tokenizer_seq_token(p, tokenizer, opa.DEFAULT_SEQ_TOKEN_INDEX, return_tensors="pt").to(dev) for p in prompts]
+        ids = [opa.tokenizer_seq_token(p, tokenizer, opa.DEFAULT_SEQ_TOKEN_INDEX, return_tensors="pt").to(dev)[head_len:] for p in prompts]
         ids = opa.left_pad_sequence(ids, padding_value=tokenizer.pad_token_id, batch_first=True)
         mask = ids != tokenizer.pad_token_id
         extra = {} if prot_all is None else {"protein_tokens": prot_all[i:i + len(batch)]}
         extra.update(processors or {})
+        if head is not None:                             # every row behind the one cached head (a detached handle: any context)
+            extra.update(prefix=head, prefix_rows=[0] * len(batch))
         if nret > 1:
             extra["num_return_sequences"] = nret
         if logprobs_out is not None:
@@ -137,6 +151,25 @@ def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperatu
     if logprobs_out is not None:
         logprobs_out.extend(lps)
     return torch.cat(outs) if outs else torch.empty((0, max_new), dtype=torch.long, device=dev)
+
+
+def shared_head_length(rows) -> int:
+    """Length of the longest leading id run that all `rows` (id lists) share, ending in front of every row's first placeholder and
+    leaving every row at least one id behind it."""
+    if not rows:
+        return 0
+    n = min(len(r) for r in rows) - 1
+    for r in rows:
+        r = list(r)
+        if opa.DEFAULT_SEQ_TOKEN_INDEX in r:
+            n = min(n, r.index(opa.DEFAULT_SEQ_TOKEN_INDEX))
+    first = list(rows[0])
+    for r in rows[1:]:
+        r, k = list(r), 0
+        while k < n and r[k] == first[k]:
+            k += 1
+        n = k
+    return max(n, 0)
 
 
 def prompts_per_call(batch_size: int, num_return_sequences: int) -> int:
@@ -242,7 +275,8 @@ def eval_model(args):
     local_ids = annotate(model, tokenizer, mine, args.input_path, args.batch_size, max_new, args.temperature, args.top_p,
                          args.num_beams, args.use_input_embed, dev, logits,
                          tokenizer.encode("###", add_special_tokens=False) if args.stop_at_hashes else None, inflight=args.inflight,
-                         logprobs_out=lps, processors=proc_kw, num_return_sequences=N)
+                         logprobs_out=lps, processors=proc_kw, num_return_sequences=N,
+                         share_prompt_head=bool(getattr(args, "share_prompt_head", False)))
     all_ids = odist.all_gather_ids(local_ids, tokenizer.eos_token_id)
     if lps is not None:         # [n, max_new] log-probabilities and [n] counted positions, in rank order
         loc_lp = torch.cat([x[0] for x in lps]) if lps else torch.empty((0, max_new), dtype=torch.float32, device=dev)
@@ -318,6 +352,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--inflight", type=int, default=2,
                    help="batches in flight per GPU (contexts sharing the weights, one host thread each): with 2, one batch's kernels "
                         "fill the other's launch gaps and ramps (+10 %% throughput at batch 64; same ids)")
+    p.add_argument("--share_prompt_head", action="store_true",
+                   help="opt-in: prefill the id run that all prompts of the shard share in front of the protein once (a detached "
+                        "prefix) and generate every batch behind it; not with --num_beams > 1")
     p.add_argument("--save_logprobs", action="store_true",
                    help="each saved item also gets `logprob` and `token_logprobs`: the log-probabilities of its generated tokens "
                         "(greedy or sampling; computed on the GPU in the decode loop)")

@@ -535,7 +535,16 @@ class OpusLlamaForCausalLM:
         `seq`, `seq_embedding` and `protein_tokens` carry B entries.  With num_beams=K >= N the N best finished hypotheses of
         every prompt come back best first ([B N, n], `sequences_scores` [B N]); the beams' prefill stays on B K rows.  Greedy
         search with N > 1, N > num_beams and N < 1 raise ValueError as transformers does; B N > max_batch raises OpusError.
-        N = 1 (or absent) is the call without the argument."""
+        N = 1 (or absent) is the call without the argument.
+        prefix=OpusPrefix (extension; cache_prefix()): `inputs` [R, n] are SUFFIX ids behind the cached prompt, left-padded or
+        unpadded with attention_mask as always; they may hold <seq> placeholders with seq / seq_embedding / protein_tokens.  Row r
+        continues prefix row prefix_rows[r] (any order, repeats; default the identity when R == prefix.rows).  The prefix is not
+        run again: its K / V are placed under the R decode rows (kv_place_kernel) and only the suffix positions are prefilled;
+        the decode loop, its graph and every option above act as for an R-row batch of the concatenated prompts.  A detached
+        handle (cache_prefix(detach=True) / OpusPrefix.detach()) can be used any number of times, also from new_context()
+        contexts; a live one is detached on the fly (one export) and is stale afterwards, as after any prefill.
+        num_return_sequences=N with sampling expands the rows on the host (row r N + j), so the suffix pass runs N times per
+        row.  num_beams > 1 raises NotImplementedError, an empty suffix row ValueError, a capacity violation OpusError -2."""
         return_dict = bool(kwargs.pop("return_dict_in_generate", False))
         want = {k: bool(kwargs.pop(k, False)) for k in ("output_scores", "output_logits", "output_token_logprobs",
                                                          "output_attentions", "output_hidden_states")}
@@ -546,6 +555,8 @@ class OpusLlamaForCausalLM:
         kwargs.pop("position_ids", None)
         protein_tokens = kwargs.pop("protein_tokens", None)
         attention_mask = kwargs.pop("attention_mask", None)
+        prefix = kwargs.pop("prefix", None)
+        prefix_rows = kwargs.pop("prefix_rows", None)
         if "inputs_embeds" in kwargs:
             raise NotImplementedError("`inputs_embeds` is not supported")
         do_sample = bool(kwargs.pop("do_sample", False))
@@ -611,6 +622,22 @@ class OpusLlamaForCausalLM:
             pad_id = eos[0] if eos else 0
         if inputs is None:
             raise ValueError("generate() needs input ids")
+        if prefix is not None:
+            if num_beams > 1:
+                raise NotImplementedError("generate(prefix=...) is built for greedy search and sampling, not for num_beams > 1")
+            if nret > 1 and constraint is not None and constraint.n_rows() is not None:
+                raise NotImplementedError("generate(prefix=..., num_return_sequences > 1) takes one TokenTrie for all rows, not "
+                                          "TokenTrie.per_row: the rows are expanded on the host")
+            embeds, behind = self._suffix_behind(prefix, prefix_rows, inputs, attention_mask, seq, seq_embedding, protein_tokens, nret)
+            if lproc is not None:              # min_length counts the whole prompt: the prefix's slots and the spliced suffix
+                pen, ngram, min_new, min_len, bad = lproc
+                if min_new is None:
+                    min_new = max((min_len or 0) - behind.Tp - int(embeds.shape[1]), 0)
+                lproc = (pen, ngram, min_new, bad)
+            self._set_logits_processors(lproc)
+            self._set_token_constraint(constraint)
+            outs = (want["output_token_logprobs"], want["output_scores"], want["output_logits"]) if return_dict else None
+            return self._greedy(embeds, None, max_new, eos, int(pad_id), sampler, outputs=outs, behind=behind)
         if num_beams <= 1 and nret > 1 and inputs.shape[0] * nret > self.cfg.max_batch:
             raise _cabi.OpusError(-2, f"num_return_sequences runs batch x num_return_sequences = {inputs.shape[0]} x {nret} decoder "
                                       f"rows: the context holds max_batch={self.cfg.max_batch}")
@@ -786,15 +813,18 @@ class OpusLlamaForCausalLM:
             self._leave()
         self._constraint = constraint
 
-    def _greedy(self, embeds, mask, max_new, eos, pad_id, sampler=None, outputs=None, nret: int = 1):
+    def _greedy(self, embeds, mask, max_new, eos, pad_id, sampler=None, outputs=None, nret: int = 1, behind=None):
         """outputs = (token_logprobs, scores, logits) flags: a GenerateDecoderOnlyOutput instead of the ids.
         nret > 1: the B prompts are prefilled once and decoded as B nret rows (opus_generate_scored_fanout); every result has
-        B nret rows.  nret == 1 takes the entries it always took."""
+        B nret rows.  nret == 1 takes the entries it always took.
+        behind (a _BehindCall; mask unused, nret 1): embeds are right-padded suffix rows behind a detached prefix
+        (opus_generate_scored_behind)."""
         P, T, _ = embeds.shape                           # P prompts, B decoder rows
         B = P * nret
         V = self.cfg.dec_vocab
         embeds = embeds.contiguous()
-        mask = mask.to(torch.uint8).contiguous()
+        if behind is None:
+            mask = mask.to(torch.uint8).contiguous()
         s = self._enter()
         with torch.cuda.stream(self._stream):
             # one persistent id buffer: its address is part of the captured decode graph's identity
@@ -818,7 +848,11 @@ class OpusLlamaForCausalLM:
                     lg = None                                   # greedy: the processed scores are the logits - one tensor
                 t, p, sd = (sampler[0], sampler[1], sampler[2]) if sampler is not None else (0.0, 1.0, 0)
                 ptr = lambda x: None if x is None else x.data_ptr()                          # noqa: E731
-                if nret > 1:
+                if behind is not None:
+                    _cabi.check(self._lib.opus_generate_scored_behind(self._ctx, behind.snap, embeds.data_ptr(), B, T, behind.lens,
+                                                                      behind.src, max_new, eos_arr, len(eos), pad_id, t, p, sd,
+                                                                      out.data_ptr(), C.byref(n_out), ptr(lp), ptr(sc), ptr(lg), s))
+                elif nret > 1:
                     _cabi.check(self._lib.opus_generate_scored_fanout(self._ctx, embeds.data_ptr(), mask.data_ptr(), P, T, nret, max_new,
                                                                       eos_arr, len(eos), pad_id, t, p, sd, out.data_ptr(),
                                                                       C.byref(n_out), ptr(lp), ptr(sc), ptr(lg), s))
@@ -826,6 +860,11 @@ class OpusLlamaForCausalLM:
                     _cabi.check(self._lib.opus_generate_scored(self._ctx, embeds.data_ptr(), mask.data_ptr(), B, T, max_new,
                                                                eos_arr, len(eos), pad_id, t, p, sd, out.data_ptr(), C.byref(n_out),
                                                                ptr(lp), ptr(sc), ptr(lg), s))
+            elif behind is not None:
+                t, p, sd = (sampler[0], sampler[1], sampler[2]) if sampler is not None else (0.0, 1.0, 0)
+                _cabi.check(self._lib.opus_generate_scored_behind(self._ctx, behind.snap, embeds.data_ptr(), B, T, behind.lens, behind.src,
+                                                                  max_new, eos_arr, len(eos), pad_id, t, p, sd, out.data_ptr(),
+                                                                  C.byref(n_out), None, None, None, s))
             elif nret > 1:                               # (sampling: greedy search takes no num_return_sequences)
                 _cabi.check(self._lib.opus_generate_scored_fanout(self._ctx, embeds.data_ptr(), mask.data_ptr(), P, T, nret, max_new,
                                                                   eos_arr, len(eos), pad_id, sampler[0], sampler[1], sampler[2],
@@ -1022,7 +1061,7 @@ class OpusLlamaForCausalLM:
     # ------------------------------------------------------------------ shared-prefix scoring
     @torch.no_grad()
     def cache_prefix(self, input_ids: torch.Tensor, seq=None, attention_mask: Optional[torch.Tensor] = None,
-                     seq_embedding=None, protein_tokens: Optional[torch.Tensor] = None) -> "OpusPrefix":
+                     seq_embedding=None, protein_tokens: Optional[torch.Tensor] = None, detach: bool = False) -> "OpusPrefix":
         """Prefills a prompt batch once and returns a handle that score_continuations() ranks continuations against.  The inputs
         are prepared exactly as generate() prepares them (inference-mode splice with `seq` / `seq_embedding` / `protein_tokens`;
         left-padded or unpadded rows): it IS a prefill, decode_logits() continues it as after prefill_logits().  The last slot of
@@ -1052,7 +1091,113 @@ class OpusLlamaForCausalLM:
             _cabi.check(self._lib.opus_llama_prefix(self._ctx, embeds.data_ptr(), mask.data_ptr(), B, T, None, last.data_ptr(),
                                                     C.byref(epoch), s))
         self._leave()
-        return OpusPrefix(self, epoch.value, last, mask.sum(dim=1).cpu())
+        handle = OpusPrefix(self, epoch.value, last, mask.sum(dim=1).cpu(), slots=T)
+        return handle.detach() if detach else handle
+
+    def export_cache(self, epoch: int, rows: int, slots: int):
+        """Copy-out of the live KV cache (opus_llama_prefix_export): rows 0 .. rows - 1, slots 0 .. slots - 1 of every layer as
+        (k, v, kstart) = ([layers, rows, kv heads, slots, head_dim] x 2 in the operand dtype, int32 [rows]).  `epoch`: the cache
+        epoch of the prefill that filled it (OpusPrefix._epoch, prefill_logits_behind); OpusError -6 when it is stale."""
+        cfg = self.cfg
+        s = self._enter()
+        with torch.cuda.stream(self._stream):
+            shape = (cfg.dec_layers, rows, cfg.dec_kv_heads, slots, cfg.dec_head_dim)
+            k = torch.empty(shape, dtype=_cabi.operand_dtype(), device=self.device)
+            v = torch.empty(shape, dtype=_cabi.operand_dtype(), device=self.device)
+            kst = torch.empty((rows,), dtype=torch.int32, device=self.device)
+            _cabi.check(self._lib.opus_llama_prefix_export(self._ctx, int(epoch), rows, slots, k.data_ptr(), v.data_ptr(),
+                                                           kst.data_ptr(), s))
+        self._leave()
+        torch.cuda.current_stream(self.device).synchronize()
+        return k, v, kst
+
+    def _usable_prefix(self, prefix: "OpusPrefix", detach: bool) -> "OpusPrefix":
+        """The handle a call behind `prefix` works with: a detached one as it is (any context of the same weights), a live one
+        detached on the fly when the call is going to overwrite the cache (detach)."""
+        if not isinstance(prefix, OpusPrefix):
+            raise TypeError("needs the OpusPrefix that cache_prefix() returned")
+        if prefix.detached:
+            if prefix._owner.weights is not self.weights or prefix._k.device != self.device:
+                raise ValueError("a detached prefix can be used from contexts of the same weights on the same device only")
+            return prefix
+        if detach:
+            if prefix._owner is not self:
+                raise _cabi.OpusError(-6, "the prefix belongs to another context: detach() it there first")
+            prefix.detach()
+        return prefix
+
+    def _suffix_behind(self, prefix, prefix_rows, inputs, attention_mask, seq, seq_embedding, protein_tokens, nret: int):
+        """generate(prefix=...)'s host side: strips the rows' padding, splices them right-padded, plans the offsets (prefix.py)
+        and returns (embeds [R nret, n, H], _BehindCall)."""
+        from .prefix import CapacityError, plan_prefill_behind
+        cfg = self.cfg
+        prefix = self._usable_prefix(prefix, detach=True)
+        ids = inputs.detach().cpu().long()
+        if ids.dim() != 2:
+            raise ValueError("generate(prefix=...) takes suffix ids [R, n]")
+        m = torch.ones_like(ids, dtype=torch.bool) if attention_mask is None else attention_mask.detach().cpu().bool()
+        rows = [ids[r][m[r]] for r in range(ids.shape[0])]
+        R = len(rows)
+        for r, row in enumerate(rows):
+            if row.numel() == 0:
+                raise ValueError(f"suffix row {r} is empty: every row needs at least one token behind the prefix")
+        if R * nret > cfg.max_batch:
+            raise _cabi.OpusError(-2, f"generate(prefix=...): {R * nret} decoder rows, the context holds max_batch={cfg.max_batch}")
+        width = max(int(row.numel()) for row in rows)
+        rp = torch.zeros((R, width), dtype=torch.long)
+        rm = torch.zeros((R, width), dtype=torch.bool)
+        for r, row in enumerate(rows):
+            rp[r, : row.numel()] = row
+            rm[r, : row.numel()] = True
+        if prefix_rows is None:
+            if R != prefix.rows:
+                raise ValueError(f"{R} suffix rows for {prefix.rows} prefix rows: pass prefix_rows")
+            src = np.arange(R, dtype=np.int64)
+        else:
+            src = np.asarray(torch.as_tensor(prefix_rows).cpu(), dtype=np.int64).reshape(-1)
+            if src.shape[0] != R:
+                raise ValueError(f"prefix_rows has {src.shape[0]} entries for {R} suffix rows")
+        has_seq = bool((rp == DEFAULT_SEQ_TOKEN_INDEX).any())
+        if has_seq and width == 1:             # (the multimodal preparation passes one-token rows through unspliced)
+            raise ValueError("a suffix that is the <seq> placeholder alone is not supported: put the protein into the prefix")
+        if has_seq:
+            _, _, mask, _, embeds, _ = self.prepare_inputs_labels_for_multimodal(
+                rp, None, rm, None, None, seq if seq is not None else (), seq_embedding, inference_mode=False,
+                protein_tokens=protein_tokens)
+        else:
+            dummy = torch.zeros((R, cfg.n_prot_tokens, cfg.dec_dim), dtype=_cabi.operand_dtype(), device=self.device)
+            embeds, mask, _ = self._splice(rp, rm, dummy, False)
+        lens = mask.to(torch.int64).sum(dim=1).cpu().numpy()
+        if nret > 1:                           # transformers' row layout: row r N + j is the j-th sample of row r
+            embeds = embeds.repeat_interleave(nret, dim=0)
+            lens, src = np.repeat(lens, nret), np.repeat(src, nret)
+        cc = _cabi.CConfig.from_config(cfg)
+        cap = int(self._lib.opus_llama_dec_rows_cap(C.byref(cc)))
+        try:
+            plan = plan_prefill_behind(prefix._kstart.cpu().numpy(), prefix.slots, src, lens, int(embeds.shape[1]), cfg.max_batch,
+                                       cfg.max_prompt, cap)
+        except CapacityError as e:
+            raise _cabi.OpusError(-2, str(e)) from None
+        embeds = embeds.to(self.device, _cabi.operand_dtype()).contiguous()
+        return embeds, _BehindCall(prefix, plan.lens, plan.src)
+
+    def prefill_logits_behind(self, prefix: "OpusPrefix", embeds: torch.Tensor, lens, prefix_rows=None):
+        """prefill_logits() behind a prefix (opus_llama_prefill_behind): embeds [R, n, H] right-padded suffix rows with `lens`
+        real positions each, row r behind prefix row prefix_rows[r].  Returns (last-position logits fp32 [R, V], cache epoch);
+        decode_logits() continues it, export_cache(epoch, ...) reads the cache back.  A live prefix is detached first."""
+        prefix = self._usable_prefix(prefix, detach=True)
+        R, n, _ = embeds.shape
+        src = np.arange(R) if prefix_rows is None else np.asarray(prefix_rows).reshape(-1)
+        call = _BehindCall(prefix, np.asarray(lens).reshape(-1), src)
+        embeds = embeds.to(self.device, _cabi.operand_dtype()).contiguous()
+        s = self._enter()
+        with torch.cuda.stream(self._stream):
+            logits = torch.empty((R, self.cfg.dec_vocab), dtype=torch.float32, device=self.device)
+            epoch = C.c_int64(0)
+            _cabi.check(self._lib.opus_llama_prefill_behind(self._ctx, call.snap, embeds.data_ptr(), R, n, call.lens, call.src,
+                                                            logits.data_ptr(), C.byref(epoch), s))
+        self._leave()
+        return logits, epoch.value
 
     @torch.no_grad()
     def score_continuations(self, prefix: "OpusPrefix", continuations, prefix_rows=None,
@@ -1066,6 +1211,7 @@ class OpusLlamaForCausalLM:
         cfg = self.cfg
         if not isinstance(prefix, OpusPrefix):
             raise TypeError("score_continuations() needs the OpusPrefix that cache_prefix() returned")
+        prefix = self._usable_prefix(prefix, detach=False)     # (a detached handle: read from its snapshot, never stale)
         if isinstance(continuations, torch.Tensor):
             ids = continuations.detach().cpu().long()
             if ids.dim() != 2:
@@ -1118,9 +1264,15 @@ class OpusLlamaForCausalLM:
             lp = torch.zeros((max(N, 1),), dtype=torch.float32, device=dev)
             h_lens = (C.c_int32 * R)(*lens_np.tolist())
             h_src = (C.c_int32 * R)(*src.tolist())
-            _cabi.check(self._lib.opus_llama_score_continuations(
-                self._ctx, embeds.data_ptr(), R, n, h_lens, h_src, prefix._last_rows.data_ptr(), prefix.rows, prefix._epoch,
-                d_tgt.data_ptr(), lp.data_ptr(), scratch.data_ptr(), n_scratch, s))
+            if prefix.detached:                # the same pass reading the snapshot: no epoch, the cache is not touched
+                snap = prefix._snap()
+                _cabi.check(self._lib.opus_llama_score_continuations_detached(
+                    self._ctx, C.byref(snap), embeds.data_ptr(), R, n, h_lens, h_src, prefix._last_rows.data_ptr(),
+                    d_tgt.data_ptr(), lp.data_ptr(), scratch.data_ptr(), n_scratch, s))
+            else:
+                _cabi.check(self._lib.opus_llama_score_continuations(
+                    self._ctx, embeds.data_ptr(), R, n, h_lens, h_src, prefix._last_rows.data_ptr(), prefix.rows, prefix._epoch,
+                    d_tgt.data_ptr(), lp.data_ptr(), scratch.data_ptr(), n_scratch, s))
             token_lp = torch.zeros((R, n), dtype=torch.float32, device=dev)
             token_lp[m.to(dev)] = lp[:N]
             logprob = token_lp.sum(dim=1)
@@ -1143,6 +1295,7 @@ class OpusLlamaForCausalLM:
         cfg = self.cfg
         if not isinstance(prefix, OpusPrefix):
             raise TypeError("score_trie() needs the OpusPrefix that cache_prefix() returned")
+        prefix = self._usable_prefix(prefix, detach=False)     # (a detached handle: read from its snapshot, never stale)
         if isinstance(trie, TokenTrie):
             tries = [trie] * prefix.rows
         elif isinstance(trie, PerRowTokenTrie):
@@ -1186,12 +1339,17 @@ class OpusLlamaForCausalLM:
                 emb = None
                 if ps.rows:
                     emb = self.model.embed_tokens(torch.from_numpy(ps.tok.astype(np.int64)).to(dev)).to(_cabi.operand_dtype()).contiguous()
-                _cabi.check(self._lib.opus_llama_score_tree(
-                    self._ctx, emb.data_ptr() if emb is not None else None, ps.rows, ptr(ps.prow), ptr(ps.parent), ptr(ps.depth),
-                    ps.score_src.size, ptr(ps.score_src), ps.edge_row.size, ptr(ps.edge_row), ptr(ps.edge_tok), ptr(ps.edge_slot),
-                    ps.stop_row.size, ptr(ps.stop_row), ptr(ps.stop_set), ptr(ps.stop_slot), n_ids, ptr(plan.stop_ids), n_sets,
-                    ptr(plan.stop_off), prefix._last_rows.data_ptr(), P, prefix._epoch, node_lp.data_ptr(),
-                    stop_node.data_ptr() if include_stop else None, P * (N + 1), scratch.data_ptr(), n_scratch, s))
+                head = (emb.data_ptr() if emb is not None else None, ps.rows, ptr(ps.prow), ptr(ps.parent), ptr(ps.depth),
+                        ps.score_src.size, ptr(ps.score_src), ps.edge_row.size, ptr(ps.edge_row), ptr(ps.edge_tok), ptr(ps.edge_slot),
+                        ps.stop_row.size, ptr(ps.stop_row), ptr(ps.stop_set), ptr(ps.stop_slot), n_ids, ptr(plan.stop_ids), n_sets,
+                        ptr(plan.stop_off), prefix._last_rows.data_ptr())
+                tail = (node_lp.data_ptr(), stop_node.data_ptr() if include_stop else None, P * (N + 1), scratch.data_ptr(),
+                        n_scratch, s)
+                if prefix.detached:            # the same pass reading the snapshot: no epoch, the cache is not touched
+                    snap = prefix._snap()
+                    _cabi.check(self._lib.opus_llama_score_tree_detached(self._ctx, C.byref(snap), *head, *tail))
+                else:
+                    _cabi.check(self._lib.opus_llama_score_tree(self._ctx, *head, P, prefix._epoch, *tail))
             d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)   # noqa: E731
             trie_of_row, member_node = d(plan.trie_of_row), d(plan.member_node)
             par, depth = d(plan.node_par), d(plan.node_depth)
@@ -1333,10 +1491,43 @@ class OpusPrefix:
     real token counts; the final residual row of every prompt's last position (fp32 [rows, hidden]) scores a continuation's first
     token.  Valid until the next call on the context that prefills or permutes its cache (the epoch check of the native side)."""
 
-    def __init__(self, owner, epoch: int, last_rows: torch.Tensor, lengths: torch.Tensor):
+    def __init__(self, owner, epoch: int, last_rows: torch.Tensor, lengths: torch.Tensor, slots: int = 0):
         self._owner, self._epoch, self._last_rows = owner, int(epoch), last_rows
         self.rows = int(last_rows.shape[0])
         self.lengths = lengths
+        self.slots = int(slots)          # Tp: cache slots per row (the padded prompt width)
+        self._k = self._v = self._kstart = self._h_kstart = None
+
+    @property
+    def detached(self) -> bool:
+        return self._k is not None
+
+    def detach(self) -> "OpusPrefix":
+        """Copies the rows' K and V of all layers out of the context's cache into tensors this handle owns
+        ([layers][rows][kv heads][slots][head_dim], operand dtype; beside them kstart [rows] and the fp32 last rows it already
+        keeps) and returns the handle.  A detached handle never goes stale, can be used any number of times by generate(prefix=),
+        score_continuations() and score_trie(), and by new_context() contexts of the same weights.  OpusError -6 when the live
+        handle is already stale; a second detach() is a no-op."""
+        if not self.detached:
+            k, v, kst = self._owner.export_cache(self._epoch, self.rows, self.slots)
+            h = kst.cpu().numpy().astype(np.int32)
+            self._k, self._v, self._kstart = k, v, kst
+            self._h_kstart = (C.c_int32 * self.rows)(*h.tolist())
+        return self
+
+    def _snap(self) -> "_cabi.CPrefixSnap":
+        return _cabi.CPrefixSnap(self._k.data_ptr(), self._v.data_ptr(), self._kstart.data_ptr(), self._h_kstart, self.rows, self.slots)
+
+
+class _BehindCall:
+    """Arguments of one opus_*_behind call (kept alive for its duration): the snapshot, the rows' lengths and prefix rows."""
+
+    def __init__(self, prefix: OpusPrefix, lens: np.ndarray, src: np.ndarray):
+        self.prefix, self.Tp = prefix, prefix.slots
+        self._struct = prefix._snap()
+        self.snap = C.byref(self._struct)
+        self.lens = (C.c_int32 * len(lens))(*[int(x) for x in lens])
+        self.src = (C.c_int32 * len(src))(*[int(x) for x in src])
 
 
 class ContinuationScores:
