@@ -361,6 +361,26 @@ int opus_generate_scored_fanout(opus_ctx *ctx, const void *d_embeds, const uint8
                                 float top_p, uint64_t seed, int32_t *d_out_ids, int32_t *n_out, float *d_token_logprobs,
                                 float *d_scores, float *d_logits, void *stream);
 
+/* opus_generate_scored with classifier-free guidance (generate(guidance_scale=g); transformers'
+ * UnbatchedClassifierFreeGuidanceLogitsProcessor) on paired rows.  d_embeds [2 P, T, dec_dim] / d_mask [2 P, T]: rows [0, P) the
+ * conditional prompts, rows [P, 2 P) their negative prompts, all left-padded to one length T.  One 2 P-row prefill; every step
+ * decodes 2 P rows, and its head works on the first P:
+ *   1. the raw outputs of the conditional rows are taken (d_logits, the log-sum-exp behind d_token_logprobs);
+ *   2. scores[b] = g ((l_c - lse_c) - (l_u - lse_u)) + (l_u - lse_u), l_u = row P + b, overwrites row b in fp32;
+ *   3. the logits processors, the token constraint, then temperature / top-k / top-p;
+ *   4. the arg-max or the draw (keyed by (seed, b, step)) on the P rows;
+ *   5. row P + b is fed the token chosen for row b (pad_id once row b has finished).
+ * EOS ids, the stop sequence, processor histories and constraint states (one start state, or P) exist for the P rows only.
+ * d_out_ids [P, max_new], d_token_logprobs [P, max_new] (raw, conditional), d_scores [max_new, P, V] (guided and processed),
+ * d_logits [max_new, P, V] (raw, conditional).  guidance_scale reaches the step through a device word: the captured step is that of
+ * a 2 P-row batch with "guided" in its identity, shared by every scale.  A guided call of P prompts costs about a plain call of
+ * 2 P rows.  OPUS_EBADARG: guidance_scale not finite; OPUS_ESHAPE: 2 P > max_batch, T > max_prompt.  Added within ABI 10 (a new
+ * symbol only). */
+int opus_generate_scored_guided(opus_ctx *ctx, const void *d_embeds, const uint8_t *d_mask, int32_t P, int32_t T, float guidance_scale,
+                                int32_t max_new, const int32_t *eos_ids, int32_t n_eos, int32_t pad_id, float temperature,
+                                float top_p, uint64_t seed, int32_t *d_out_ids, int32_t *n_out, float *d_token_logprobs,
+                                float *d_scores, float *d_logits, void *stream);
+
 /* Detached prefixes (added within ABI 10).  A snapshot is the K and V of a prefill's rows copied out of the context's cache into
  * memory the caller owns: d_k / d_v operand dtype [dec_layers][P][dec_kv_heads][Tp][dec_head_dim] (slot 0 first), d_kstart int32 [P]
  * (device) the first real slot of every row, h_kstart the same on the host.  It never goes stale, can be used any number of times
@@ -416,6 +436,11 @@ int opus_llama_score_tree_detached(opus_ctx *ctx, const opus_prefix_snap *snap, 
 /* Diagnostic: opus_generate_scored's fused arg-max / log-sum-exp pass on fp32 logits [B, V] (B <= max_batch, any V >= 1; rows
  * need no alignment): d_idx [B] the arg-max (lowest index among ties, bitwise what the greedy step picks), d_lse [B]. */
 int opus_debug_argmax_lse(opus_ctx *ctx, const float *d_logits, int32_t B, int32_t V, int32_t *d_idx, float *d_lse, void *stream);
+/* Diagnostic: the guidance launches of opus_generate_scored_guided alone on caller memory - fp32 logits [2 P, V] (any P >= 1, any
+ * V >= 1; rows need no alignment): rows [0, P) become g (lsm(l_b) - lsm(l_{P+b})) + lsm(l_{P+b}) with lsm(x) = (x - max x) -
+ * log(sum exp(x - max x)) in fp32 (g = 0 returns the partner rows' log-softmax as the kernel takes it); rows [P, 2 P) are not
+ * written.  Added within ABI 10. */
+int opus_debug_guidance(opus_ctx *ctx, float *d_logits, int32_t P, int32_t V, float guidance_scale, void *stream);
 
 /* generate()'s logits processors, transformers' semantics and order (GenerationMixin._get_logits_processor): the repetition
  * penalty, no_repeat_ngram_size, bad_words_ids, then min_new_tokens; under sampling the temperature / top-k / top-p warpers follow.
@@ -642,7 +667,7 @@ int64_t opus_stat(opus_ctx *ctx, const char *name);
  * belongs to, and its ALGORITHMIC bytes and FLOPs.  opus_timing_get sums the records since the last reset that match
  * kernel_class and phase ("*" = any); opus_timing_names returns "class,class,...;phase,phase,..." .  Classes and phases are
  * addressed by name, never by position.  Order of the lists: phases are append-only ("score" last); among the classes "xent"
- * stays the last entry, as published since opus_llama_forward, and a class added later ("contact", "constraint", "mlm", "logitproc") is
+ * stays the last entry, as published since opus_llama_forward, and a class added later ("contact", "constraint", "guidance", "mlm", "logitproc") is
  * listed in front of it ("logitproc" keeps its place next to "xent"). */
 int opus_timing_enable(opus_ctx *ctx, int32_t on);
 int opus_timing_reset(opus_ctx *ctx);

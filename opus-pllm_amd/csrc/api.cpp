@@ -122,6 +122,7 @@ struct opus_ctx {
         int outs = 0;                    // GEN_* flags of opus_generate_scored (the addresses come from the descriptor)
         bool lproc = false;              // logits processors on (their values come from the descriptor d_lproc)
         bool cons = false;               // token constraint on (its table comes from the descriptor d_cons)
+        bool guided = false;             // guidance on: the head works on B / 2 rows (the scale comes from the word d_gscale)
         uint64_t used = 0;
     };
     static constexpr int MAX_GRAPHS = 4;
@@ -158,6 +159,13 @@ struct opus_ctx {
     int32_t *d_cstate = nullptr, *d_cstep = nullptr;
     int32_t cons_n_start = 0, cons_max_id = -1;
     int32_t cons_start_div = 1;          // TokenConstraintDesc::start_div as the device descriptor holds it
+    // classifier-free guidance (opus_generate_scored_guided): while guid_on, rows [0, cur_B / 2) are the conditional prompts the
+    // head of the step works on and rows [cur_B / 2, cur_B) their negative prompts.  guid_mem (first use): the scale word the
+    // captured step reads, the part sums and the rows' maximum / log of the shifted sum / log-sum-exp [2 max_batch each]; guid_keep (first
+    // guided call with token log-probs): the raw conditional rows [max_batch / 2, V] the combine overwrites in d_logits
+    bool guid_on = false;
+    char *guid_mem = nullptr;
+    float *d_gscale = nullptr, *d_gdpsum = nullptr, *d_gmax = nullptr, *d_glog = nullptr, *d_glse = nullptr, *guid_keep = nullptr;
     int gemm_w8 = 0;                     // 1: this context's last GEMM streamed the FP8 panels (GemmParams::ran_w8)
     int64_t w8_gemms = 0;                // GEMMs issued on this context that did (opus_stat("w8_gemms"))
     int gemm_plan[GEMM_PLAN_WORDS] = {-1, -1, -1, -1, -1, -1, -1, -1};   // the launchers' report of this context's last GEMM (GemmParams::plan; opus_debug_gemm_plan)
@@ -420,6 +428,8 @@ extern "C" int opus_ctx_destroy(opus_ctx *c) {
     if (c->lproc_mem) (void)hipFree(c->lproc_mem);
     if (c->cons_tab) (void)hipFree(c->cons_tab);
     if (c->cons_mem) (void)hipFree(c->cons_mem);
+    if (c->guid_mem) (void)hipFree(c->guid_mem);
+    if (c->guid_keep) (void)hipFree(c->guid_keep);
     if (c->behind_tbl) (void)hipFree(c->behind_tbl);
     if (c->h_nunf) (void)hipHostFree(c->h_nunf);
     for (auto &e : c->poll_ev) if (e) (void)hipEventDestroy(e);
@@ -2342,6 +2352,31 @@ static int ensure_lproc_mem(opus_ctx *c) {
     return OPUS_OK;
 }
 
+// guidance: keep = the call also needs the copy of the raw conditional rows
+static int ensure_guid_mem(opus_ctx *c, bool keep) {
+    const size_t B = c->cfg.max_batch;
+    if (!c->guid_mem) {
+        const size_t rows = align_up(2 * B * sizeof(float));
+        const size_t o_ps = align_up(sizeof(float)), o_mx = o_ps + align_up(APART * B * sizeof(float)), o_lg = o_mx + rows,
+                     o_ls = o_lg + rows;
+        HIPC(hipMalloc((void **)&c->guid_mem, o_ls + rows));
+        c->d_gscale = reinterpret_cast<float *>(c->guid_mem);
+        c->d_gdpsum = reinterpret_cast<float *>(c->guid_mem + o_ps);
+        c->d_gmax = reinterpret_cast<float *>(c->guid_mem + o_mx);
+        c->d_glog = reinterpret_cast<float *>(c->guid_mem + o_lg);
+        c->d_glse = reinterpret_cast<float *>(c->guid_mem + o_ls);
+    }
+    if (keep && !c->guid_keep) HIPC(hipMalloc((void **)&c->guid_keep, align_up((B / 2) * (size_t)c->cfg.dec_vocab * sizeof(float))));
+    return OPUS_OK;
+}
+
+static int upload_guidance_scale(opus_ctx *c, float g, hipStream_t s) {
+    int32_t w;
+    memcpy(&w, &g, sizeof(w));
+    HIPC(launch_upload_i32(&w, 1, reinterpret_cast<int32_t *>(c->d_gscale), s));
+    return OPUS_OK;
+}
+
 // the setting's words through the kernel arguments (stream order, no host buffer outlives the call): the header and the used
 // offsets, then the used ids
 static int upload_lproc(opus_ctx *c, const LogitsProcDesc &h, hipStream_t s) {
@@ -2370,58 +2405,72 @@ static int upload_gen_desc(const GenOutDesc &h, GenOutDesc *d, hipStream_t s) {
 // descriptor) and the raw rows' log-sum-exp (GEN_LOGPROBS: one more pass over the logits); the kernel records the raw logit of every
 // history position, where the step kernel finds the chosen token's raw logit if a penalty changed it.  The selection, the scores
 // and the bookkeeping then run on the processed logits.
+//
+// Guidance on (c->guid_on): everything here works on the HB = cur_B / 2 conditional rows.  Behind the raw logits' copy and in front
+// of the processors, one log-sum-exp pass over all cur_B rows and the combine (guidance.hip) overwrite row b with the guided
+// scores of the pair (b, HB + b); the raw conditional log-sum-exp of that pass serves GEN_LOGPROBS, the chosen id's raw logit
+// comes from the combine's copy of the raw rows.  Behind the step kernel, row HB + b is given row b's token.
 static int argmax(opus_ctx *c, hipStream_t s, int max_new, int n_eos, int pad_id, int32_t *d_out) {
     c->phase = PH_DECODE;
     const opus_config &g = c->cfg;
     const int32_t *chosen = nullptr;
-    const bool proc = c->lproc_on || c->cons_on;            // the logits are edited in place: raw outputs first
+    const bool guid = c->guid_on;
+    const int HB = guid ? c->cur_B / 2 : c->cur_B;          // rows the head works on
+    const bool proc = c->lproc_on || c->cons_on || guid;    // the logits are edited in place: raw outputs first
     const bool lp = c->gen_outs & GEN_LOGPROBS, sc = c->gen_outs & (GEN_SCORES | GEN_LOGITS);
-    const size_t BV = (size_t)c->cur_B * g.dec_vocab;
+    const size_t BV = (size_t)HB * g.dec_vocab;
     if (proc) {
         if (c->gen_outs & GEN_LOGITS)
-            KL(KC_OTHER, 8.0 * BV, launch_gen_scores(c->d_logits, c->cur_B, g.dec_vocab, c->d_gen_raw, c->d_step, max_new, 0.f, 1.f,
+            KL(KC_OTHER, 8.0 * BV, launch_gen_scores(c->d_logits, HB, g.dec_vocab, c->d_gen_raw, c->d_step, max_new, 0.f, 1.f,
                                                      nullptr, nullptr, s));
-        if (lp) {
-            KL(KC_OTHER, 4.0 * BV, launch_argmax_lse_partial(c->d_logits, c->cur_B, g.dec_vocab, c->d_pval, c->d_pidx, c->d_gpsum, s));
-            KL(KC_OTHER, 512.0 * c->cur_B, launch_argmax_lse_final(c->d_pval, c->d_pidx, c->d_gpsum, c->cur_B, c->d_ridx, c->d_rlse, s));
+        if (guid) {
+            KL(KC_GUIDANCE, 8.0 * BV, launch_guidance_lse_partial(c->d_logits, 2 * HB, g.dec_vocab, c->d_pval, c->d_gdpsum, s));
+            KL(KC_GUIDANCE, 1024.0 * HB, launch_guidance_lse_final(c->d_pval, c->d_gdpsum, 2 * HB, c->d_gmax, c->d_glog, c->d_glse, s));
+            KL(KC_GUIDANCE, (lp ? 16.0 : 12.0) * BV,
+               launch_guidance_combine(c->d_logits, c->d_logits + BV, HB, g.dec_vocab, c->d_gmax, c->d_glog, c->d_gmax + HB,
+                                       c->d_glog + HB, c->d_gscale, lp ? c->guid_keep : nullptr, s));
+        } else if (lp) {
+            KL(KC_OTHER, 4.0 * BV, launch_argmax_lse_partial(c->d_logits, HB, g.dec_vocab, c->d_pval, c->d_pidx, c->d_gpsum, s));
+            KL(KC_OTHER, 512.0 * HB, launch_argmax_lse_final(c->d_pval, c->d_pidx, c->d_gpsum, HB, c->d_ridx, c->d_rlse, s));
         }
         if (c->lproc_on)
-            KL(KC_LOGITPROC, 12.0 * c->cur_B * max_new,
-               launch_logits_proc(c->d_logits, c->cur_B, g.dec_vocab, d_out, max_new, c->d_step, max_new, c->d_eos, n_eos, c->d_lproc,
-                                  lp ? c->d_rawh : nullptr, s));
+            KL(KC_LOGITPROC, 12.0 * HB * max_new,
+               launch_logits_proc(c->d_logits, HB, g.dec_vocab, d_out, max_new, c->d_step, max_new, c->d_eos, n_eos, c->d_lproc,
+                                  lp && !guid ? c->d_rawh : nullptr, s));
         if (c->cons_on)                      // behind min_new_tokens, in front of the warpers (transformers' order)
             KL(KC_CONSTRAINT, 4.0 * BV,
-               launch_token_constraint(c->d_logits, c->cur_B, g.dec_vocab, d_out, max_new, c->d_step, max_new, c->d_cons, s));
+               launch_token_constraint(c->d_logits, HB, g.dec_vocab, d_out, max_new, c->d_step, max_new, c->d_cons, s));
     }
     if (c->samp_temp > 0.f) {
-        KL(KC_OTHER, 4.0 * 4 * c->cur_B * g.dec_vocab,
-           launch_sample_select(c->d_logits, c->cur_B, g.dec_vocab, c->samp_temp, c->samp_top_p, c->samp_top_k, c->d_seed, c->d_step,
+        KL(KC_OTHER, 4.0 * 4 * HB * g.dec_vocab,
+           launch_sample_select(c->d_logits, HB, g.dec_vocab, c->samp_temp, c->samp_top_p, c->samp_top_k, c->d_seed, c->d_step,
                                 c->d_pval, c->d_pidx, c->d_probs, c->d_cand_i, c->d_cand_n, c->d_zpart, c->d_spart, c->d_chosen, nullptr,
                                 lp && !proc ? c->d_gpsum : nullptr, sc ? c->d_gthr : nullptr, s));
         chosen = c->d_chosen;
     } else if (lp && !proc) {
-        KL(KC_OTHER, 4.0 * c->cur_B * g.dec_vocab,
-           launch_argmax_lse_partial(c->d_logits, c->cur_B, g.dec_vocab, c->d_pval, c->d_pidx, c->d_gpsum, s));
+        KL(KC_OTHER, 4.0 * HB * g.dec_vocab,
+           launch_argmax_lse_partial(c->d_logits, HB, g.dec_vocab, c->d_pval, c->d_pidx, c->d_gpsum, s));
     } else {
-        KL(KC_OTHER, 4.0 * c->cur_B * g.dec_vocab, launch_argmax_partial(c->d_logits, c->cur_B, g.dec_vocab, c->d_pval, c->d_pidx, s));
+        KL(KC_OTHER, 4.0 * HB * g.dec_vocab, launch_argmax_partial(c->d_logits, HB, g.dec_vocab, c->d_pval, c->d_pidx, s));
     }
     if (proc ? (c->gen_outs & GEN_SCORES) != 0 : sc)
-        KL(KC_OTHER, 4.0 * c->cur_B * g.dec_vocab * (1 + ((c->gen_outs & GEN_SCORES) ? 1 : 0) + ((c->gen_outs & GEN_LOGITS) && !proc ? 1 : 0)),
-           launch_gen_scores(c->d_logits, c->cur_B, g.dec_vocab, proc ? c->d_gen_proc : c->d_gen, c->d_step, max_new, c->samp_temp,
+        KL(KC_OTHER, 4.0 * HB * g.dec_vocab * (1 + ((c->gen_outs & GEN_SCORES) ? 1 : 0) + ((c->gen_outs & GEN_LOGITS) && !proc ? 1 : 0)),
+           launch_gen_scores(c->d_logits, HB, g.dec_vocab, proc ? c->d_gen_proc : c->d_gen, c->d_step, max_new, c->samp_temp,
                              c->samp_top_p, c->d_pval, c->samp_temp > 0.f ? c->d_gthr : nullptr, s));
     if (lp && proc)
-        KL(KC_OTHER, 512.0 * c->cur_B + 8.0 * c->cur_B * max_new,
-           launch_argmax_rawlp_step(c->d_pval, c->d_pidx, c->d_rlse, c->lproc_on ? c->d_rawh : nullptr, chosen, c->cur_B, c->d_eos, n_eos, pad_id, c->d_fin, d_out,
-                                    max_new, c->d_step, c->d_next, c->d_nunf, c->d_stop, c->n_stop, c->d_logits, g.dec_vocab,
-                                    c->d_gen_proc, s));
+        KL(KC_OTHER, 512.0 * HB + 8.0 * HB * max_new,
+           launch_argmax_rawlp_step(c->d_pval, c->d_pidx, guid ? c->d_glse : c->d_rlse, c->lproc_on && !guid ? c->d_rawh : nullptr, chosen, HB, c->d_eos, n_eos, pad_id, c->d_fin, d_out,
+                                    max_new, c->d_step, c->d_next, c->d_nunf, c->d_stop, c->n_stop, guid ? c->guid_keep : c->d_logits,
+                                    g.dec_vocab, c->d_gen_proc, s));
     else if (lp)
-        KL(KC_OTHER, 512.0 * c->cur_B + 8.0 * c->cur_B,
-           launch_argmax_lse_step(c->d_pval, c->d_pidx, c->d_gpsum, chosen, c->cur_B, c->d_eos, n_eos, pad_id, c->d_fin, d_out, max_new,
+        KL(KC_OTHER, 512.0 * HB + 8.0 * HB,
+           launch_argmax_lse_step(c->d_pval, c->d_pidx, c->d_gpsum, chosen, HB, c->d_eos, n_eos, pad_id, c->d_fin, d_out, max_new,
                                   c->d_step, c->d_next, c->d_nunf, c->d_stop, c->n_stop, c->d_logits, g.dec_vocab, c->d_gen, s));
     else
-        KL(KC_OTHER, 512.0 * c->cur_B,
-           launch_argmax_step(c->d_pval, c->d_pidx, chosen, c->cur_B, c->d_eos, n_eos, pad_id, c->d_fin, d_out, max_new, c->d_step,
+        KL(KC_OTHER, 512.0 * HB,
+           launch_argmax_step(c->d_pval, c->d_pidx, chosen, HB, c->d_eos, n_eos, pad_id, c->d_fin, d_out, max_new, c->d_step,
                               c->d_next, c->d_nunf, c->d_stop, c->n_stop, s));
+    if (guid) KL(KC_GUIDANCE, 8.0 * HB, launch_guidance_pair_next(c->d_next, HB, s));
     return OPUS_OK;
 }
 
@@ -2444,7 +2493,8 @@ static int set_cons_start_div(opus_ctx *c, int32_t div, hipStream_t s) {
 static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mask, int32_t B, int32_t T, int32_t max_new,
                          const int32_t *eos_ids, int32_t n_eos, int32_t pad_id, float temperature, float top_p, uint64_t seed,
                          int32_t *d_out_ids, int32_t *n_out, void *stream, const GenOutDesc *outs = nullptr, int32_t nret = 1,
-                         const BehindArgs *behind = nullptr) {
+                         const BehindArgs *behind = nullptr, const float *guidance = nullptr) {
+    // guidance (opus_generate_scored_guided; nret 1, no behind): B = 2 P rows, the head of every step works on the first P
     // behind (opus_generate_scored_behind): the B rows are suffixes of T right-padded positions behind a detached prefix (no mask)
     OPC(need_ready(c));
     if (temperature < 0.f || top_p <= 0.f || top_p > 1.f) return fail(OPUS_EBADARG, "generate: temperature >= 0 and 0 < top_p <= 1");
@@ -2471,10 +2521,15 @@ static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mas
             HIPC(hipMemcpyAsync(c->d_gen, &c->h_gen, sizeof(GenOutDesc), hipMemcpyHostToDevice, s));
         }
     }
-    if (c->cons_on && c->cons_n_start != 1 && c->cons_n_start != B)
-        return fail(OPUS_ESHAPE, "generate: the token constraint has %d per-row start states, the batch %d rows", c->cons_n_start, B);
+    const int32_t HB = guidance ? B / 2 : B;                // rows (before the fan-out) with a state of their own
+    if (c->cons_on && c->cons_n_start != 1 && c->cons_n_start != HB)
+        return fail(OPUS_ESHAPE, "generate: the token constraint has %d per-row start states, the batch %d rows", c->cons_n_start, HB);
     if (c->cons_on) OPC(set_cons_start_div(c, nret, s));    // one start state per prompt: decoder row r starts at start[r / nret]
-    if (c->lproc_on || c->cons_on) {
+    if (guidance) {
+        OPC(ensure_guid_mem(c, gen_outs & GEN_LOGPROBS));
+        OPC(upload_guidance_scale(c, *guidance, s));
+    }
+    if (c->lproc_on || c->cons_on || guidance) {
         if (c->lproc_on && max_new > LP_MAX_HIST)
             return fail(OPUS_ESHAPE, "generate: logits processors keep a history of at most %d ids (max_new=%d)", LP_MAX_HIST, max_new);
         OPC(ensure_lproc_mem(c));
@@ -2489,14 +2544,15 @@ static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mas
     if (behind) OPC(prefill_behind(c, s, *behind, (const half_t *)d_embeds, B, T));
     else OPC(prefill(c, s, (const half_t *)d_embeds, d_mask, B, T, false, nullptr, nret));
     c->gen_outs = gen_outs;             // (the prefill's own launches are the same either way)
-    struct GenOutsReset { opus_ctx *c; ~GenOutsReset() { c->gen_outs = 0; } } gen_outs_reset{c};
+    c->guid_on = guidance != nullptr;
+    struct GenOutsReset { opus_ctx *c; ~GenOutsReset() { c->gen_outs = 0; c->guid_on = false; } } gen_outs_reset{c};
 
     // OPUS_NO_GRAPH=1: eager launches (rocprofv3 --pmc cannot collect counters through graph replays)
     const bool use_graph = s != nullptr && !c->timing && !getenv("OPUS_NO_GRAPH");
     auto find_graph = [&]() -> opus_ctx::GraphEntry * {
         for (auto &e : c->graphs)
             if (e.exec && e.B == BN && e.maxnew == max_new && e.pad == pad_id && e.neos == n_eos && e.out == d_out_ids &&
-                e.temp == temperature && e.top_p == top_p && e.outs == gen_outs && e.lproc == c->lproc_on && e.cons == c->cons_on) return &e;
+                e.temp == temperature && e.top_p == top_p && e.outs == gen_outs && e.lproc == c->lproc_on && e.cons == c->cons_on && e.guided == c->guid_on) return &e;
         return nullptr;
     };
     opus_ctx::GraphEntry *ge = use_graph ? find_graph() : nullptr;
@@ -2529,6 +2585,7 @@ static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mas
                 e.outs = gen_outs;
                 e.lproc = c->lproc_on;
                 e.cons = c->cons_on;
+                e.guided = c->guid_on;
                 if ((int)c->graphs.size() >= opus_ctx::MAX_GRAPHS) {           // least recently used out
                     size_t v = 0;
                     for (size_t k = 1; k < c->graphs.size(); ++k) if (c->graphs[k].used < c->graphs[v].used) v = k;
@@ -2805,6 +2862,50 @@ extern "C" int opus_generate_scored_fanout(opus_ctx *c, const void *d_embeds, co
     const GenOutDesc outs{d_token_logprobs, d_scores, d_logits, nullptr};
     return generate_impl(c, d_embeds, d_mask, B, T, max_new, eos_ids, n_eos, pad_id, temperature, temperature > 0.f ? top_p : 1.f,
                          temperature > 0.f ? seed : 0, d_out_ids, n_out, stream, &outs, nret);
+}
+
+/* opus_generate_scored with classifier-free guidance on paired rows: d_embeds [2 P, T, D] / d_mask [2 P, T] hold the P conditional
+   prompts, then their P negative prompts (left-padded to one length); one 2 P-row prefill, then the loop of a 2 P-row batch whose head
+   works on the first P rows (argmax()).  ids and outputs are P-row shaped.  The scale travels in a device word: only "guided"
+   enters the captured step's identity. */
+extern "C" int opus_generate_scored_guided(opus_ctx *c, const void *d_embeds, const uint8_t *d_mask, int32_t P, int32_t T,
+                                           float guidance_scale, int32_t max_new, const int32_t *eos_ids, int32_t n_eos, int32_t pad_id,
+                                           float temperature, float top_p, uint64_t seed, int32_t *d_out_ids, int32_t *n_out,
+                                           float *d_token_logprobs, float *d_scores, float *d_logits, void *stream) {
+    if (!c) return fail(OPUS_EBADARG, "ctx is null");
+    if (!(temperature >= 0.f)) return fail(OPUS_EBADARG, "generate_scored_guided: temperature must be >= 0 (0 = greedy)");
+    if (!std::isfinite(guidance_scale)) return fail(OPUS_EBADARG, "generate_scored_guided: guidance_scale must be a finite number");
+    if (P < 1 || 2 * (int64_t)P > c->cfg.max_batch)
+        return fail(OPUS_ESHAPE, "generate_scored_guided: 2 x P = 2 x %d decoder rows, the context holds max_batch=%d", P, c->cfg.max_batch);
+    const GenOutDesc outs{d_token_logprobs, d_scores, d_logits, nullptr};
+    return generate_impl(c, d_embeds, d_mask, 2 * P, T, max_new, eos_ids, n_eos, pad_id, temperature, temperature > 0.f ? top_p : 1.f,
+                         temperature > 0.f ? seed : 0, d_out_ids, n_out, stream, &outs, 1, nullptr, &guidance_scale);
+}
+
+/* Diagnostic: the guidance launches alone on caller memory - fp32 logits [2 P, V] (any P >= 1, any V >= 1, no alignment), rows
+   [0, P) overwritten with the guided scores of the pairs (b, P + b), rows [P, 2 P) untouched.  Pairs are taken max_batch at a time:
+   the log-sum-exp pass of the conditional rows, that of their partners, the combine. */
+extern "C" int opus_debug_guidance(opus_ctx *c, float *d_logits, int32_t P, int32_t V, float guidance_scale, void *stream) {
+    if (!c || !d_logits) return fail(OPUS_EBADARG, "debug_guidance: null pointer");
+    if (P < 1 || V < 1) return fail(OPUS_ESHAPE, "debug_guidance: P=%d V=%d", P, V);
+    if (!std::isfinite(guidance_scale)) return fail(OPUS_EBADARG, "debug_guidance: guidance_scale must be a finite number");
+    HIPC(hipSetDevice(c->device));
+    OPC(ensure_guid_mem(c, false));
+    hipStream_t s = (hipStream_t)stream;
+    c->phase = PH_OTHER;
+    OPC(upload_guidance_scale(c, guidance_scale, s));
+    const int Bm = c->cfg.max_batch;
+    for (int b0 = 0; b0 < P; b0 += Bm) {
+        const int n = P - b0 < Bm ? P - b0 : Bm;
+        float *cond = d_logits + (size_t)b0 * V, *unc = d_logits + ((size_t)P + b0) * V;
+        KL(KC_GUIDANCE, 4.0 * n * V, launch_guidance_lse_partial(cond, n, V, c->d_pval, c->d_gdpsum, s));
+        KL(KC_GUIDANCE, 512.0 * n, launch_guidance_lse_final(c->d_pval, c->d_gdpsum, n, c->d_gmax, c->d_glog, c->d_glse, s));
+        KL(KC_GUIDANCE, 4.0 * n * V, launch_guidance_lse_partial(unc, n, V, c->d_pval, c->d_gdpsum, s));
+        KL(KC_GUIDANCE, 512.0 * n, launch_guidance_lse_final(c->d_pval, c->d_gdpsum, n, c->d_gmax + Bm, c->d_glog + Bm, c->d_glse + Bm, s));
+        KL(KC_GUIDANCE, 12.0 * n * V,
+           launch_guidance_combine(cond, unc, n, V, c->d_gmax, c->d_glog, c->d_gmax + Bm, c->d_glog + Bm, c->d_gscale, nullptr, s));
+    }
+    return OPUS_OK;
 }
 
 /* opus_generate_scored with its prefill replaced by opus_llama_prefill_behind: R suffix rows of n right-padded positions behind the
@@ -3339,7 +3440,7 @@ extern "C" int opus_timing_reset(opus_ctx *c) {
     return OPUS_OK;
 }
 static const char *kclass_names[KC_COUNT] = {"gemm_skinny", "gemm_mid", "gemm_wide", "gemm_ring", "gemm_pp", "gemm_tile", "splitk_reduce",
-                                            "attn_prefill", "attn_decode", "norm", "other", "gemm_stream", "contact", "constraint", "mlm", "logitproc",
+                                            "attn_prefill", "attn_decode", "norm", "other", "gemm_stream", "contact", "constraint", "guidance", "mlm", "logitproc",
                                             "xent"};
 static const char *phase_names[PH_COUNT] = {"encode", "project", "splice", "prefill", "decode", "other", "score"};
 

@@ -52,7 +52,7 @@ int skinny_max_m();   // rows up to which the skinny kernel is used (default 4, 
 constexpr int MID_MAX_M = 64;   // (65..128 rows measured faster on the split-K tile kernel)
 // kernel classes of the per-launch timing (opus_timing_get): one per kernel family
 enum KClass { KC_SKINNY = 0, KC_MID, KC_WIDE, KC_RING, KC_PP, KC_TILE, KC_REDUCE, KC_ATTN_PREFILL, KC_ATTN_DECODE, KC_NORM,
-              KC_OTHER, KC_STREAM, KC_CONTACT, KC_CONSTRAINT, KC_MLM, KC_LOGITPROC, KC_XENT, KC_COUNT };
+              KC_OTHER, KC_STREAM, KC_CONTACT, KC_CONSTRAINT, KC_GUIDANCE, KC_MLM, KC_LOGITPROC, KC_XENT, KC_COUNT };
 // Ordering rule of the published class list (opus_timing_names, include/opus_pllm.h): "xent" stays its last entry, as published
 // since opus_llama_forward, and a class added later goes in front of it.  Classes are looked up by name, never by index.
 // phases of the path a launch belongs to (set by the entry points of api.cpp)
@@ -544,6 +544,14 @@ struct TokenConstraintDesc {
 // then -inf outside the state's allowed set.  logits == nullptr: the transition only.
 hipError_t launch_token_constraint(float *logits, int B, int V, const int32_t *hist, int64_t ld, const int32_t *step, int max_hist,
                                    const TokenConstraintDesc *desc, hipStream_t s);
+// guidance.hip (generate(guidance_scale=g)): the parts' maxima and sums of B rows (an order independent of the rows' alignment), from
+// them the rows' maximum, log(sum exp(l - max)) and log-sum-exp; rows cond[b] = g (lsm(cond[b]) - lsm(uncond[b])) + lsm(uncond[b]), lsm(x) = (x - max) - log, in place for n pairs of V-float
+// rows (any alignment), g one device float, keep (optional) [n, V] the raw conditional rows; and next[P + b] = next[b]
+hipError_t launch_guidance_lse_partial(const float *logits, int B, int V, float *pval, float *psum, hipStream_t s);
+hipError_t launch_guidance_lse_final(const float *pval, const float *psum, int B, float *rmax, float *rlog, float *rlse, hipStream_t s);
+hipError_t launch_guidance_combine(float *cond, const float *uncond, int n, int V, const float *max_c, const float *log_c,
+                                   const float *max_u, const float *log_u, const float *g, float *keep, hipStream_t s);
+hipError_t launch_guidance_pair_next(int32_t *next, int P, hipStream_t s);
 // beam.hip: best M of the K V continuations per batch row (log_softmax + running scores), cache rows of the surviving beams
 hipError_t launch_beam_topk(const float *logits, const float *run, int B, int K, int V, int M, float *lse, float *out_s,
                             int32_t *out_i, hipStream_t s);

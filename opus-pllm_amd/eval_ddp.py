@@ -42,7 +42,7 @@ from opus_pllm_amd.prompt import (add_constraint_args, add_logits_processor_args
 
 def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperature=0.0, top_p=0.7, num_beams=1,
              use_input_embed=False, device=None, logits_out=None, stop_sequence=None, inflight=1, logprobs_out=None,
-             processors=None, num_return_sequences=1, share_prompt_head=False):
+             processors=None, num_return_sequences=1, share_prompt_head=False, guidance_scale=None):
     """The batch loop of run_opus_ddp.py:88-134 over this rank's items -> [n, max_new] new ids (rows padded with eos).
 
     use_input_embed (two-stage pipeline): the `input_embed` vectors of the WHOLE shard go through the modality
@@ -64,13 +64,18 @@ def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperatu
     share_prompt_head (--share_prompt_head): the longest leading id run that all the shard's prompts share in front of their
     first placeholder (build_prompt's system text: tokenizer_seq_token tokenises it on its own, so the ids are identical) is
     prefilled ONCE as a detached one-row prefix (cache_prefix(detach=True)) and every batch is generated behind it
-    (generate(prefix=...)): only the rest of each prompt is prefilled.  Other launch shapes than the plain call, so opt-in."""
+    (generate(prefix=...)): only the rest of each prompt is prefilled.  Other launch shapes than the plain call, so opt-in.
+    guidance_scale = g (--guidance_scale; None or 1: off): classifier-free guidance against each prompt's protein-free twin
+    (generate(guidance_scale=g)); a call takes batch_size // 2 prompts, whose negative rows fill the other half of the batch."""
     dev = device or model.device
     nret = int(num_return_sequences)
     if nret < 1:
         raise ValueError(f"--num_return_sequences has to be at least 1 (got {nret})")
     if nret > 1:
         batch_size = prompts_per_call(batch_size, nret)
+    guided = guidance_scale is not None and float(guidance_scale) != 1.0
+    if guided:
+        batch_size = prompts_per_call(batch_size, 2)
     prot_all = None
     if use_input_embed and items:
         prot_all = model.project_dataset(torch.tensor([q["input_embed"] for q in items], dtype=torch.float32, device=dev))
@@ -103,6 +108,8 @@ def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperatu
             extra.update(prefix=head, prefix_rows=[0] * len(batch))
         if nret > 1:
             extra["num_return_sequences"] = nret
+        if guided:
+            extra["guidance_scale"] = float(guidance_scale)
         if logprobs_out is not None:
             extra.update(return_dict_in_generate=True, output_token_logprobs=True)
         with torch.inference_mode():
@@ -276,7 +283,8 @@ def eval_model(args):
                          args.num_beams, args.use_input_embed, dev, logits,
                          tokenizer.encode("###", add_special_tokens=False) if args.stop_at_hashes else None, inflight=args.inflight,
                          logprobs_out=lps, processors=proc_kw, num_return_sequences=N,
-                         share_prompt_head=bool(getattr(args, "share_prompt_head", False)))
+                         share_prompt_head=bool(getattr(args, "share_prompt_head", False)),
+                         guidance_scale=getattr(args, "guidance_scale", None))
     all_ids = odist.all_gather_ids(local_ids, tokenizer.eos_token_id)
     if lps is not None:         # [n, max_new] log-probabilities and [n] counted positions, in rank order
         loc_lp = torch.cat([x[0] for x in lps]) if lps else torch.empty((0, max_new), dtype=torch.float32, device=dev)
@@ -334,6 +342,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--num_return_sequences", type=int, default=1, metavar="N",
                    help="N answers per item from one run (sampling, or the N best of --num_beams): a call takes batch_size // N "
                         "prompts, prefilled once; items are saved with `generated_all` (N answers) beside `generated` (the first)")
+    p.add_argument("--guidance_scale", type=float, default=None, metavar="G",
+                   help="classifier-free guidance against each prompt's protein-free twin (the prompt without its <seq> "
+                        "placeholders): a call takes batch_size // 2 prompts and costs about a plain call of batch_size rows; "
+                        "greedy and sampling only")
     p.add_argument("--max_new_tokens", type=int, default=None)
     p.add_argument("--switch_projector_type", type=str, default="mlp2x_gelu")
     p.add_argument("--load-4bit", action="store_true")

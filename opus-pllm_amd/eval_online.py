@@ -37,6 +37,7 @@ def answer_once(model, tokenizer, instruction: str, seq: str, args, conv=conv_vi
                              do_sample=args.temperature > 0, temperature=args.temperature, top_p=args.top_p,
                              num_beams=args.num_beams, max_new_tokens=args.max_new_tokens, use_cache=True,
                              **logits_processor_kwargs(args),
+                             **({} if getattr(args, "guidance_scale", None) is None else dict(guidance_scale=args.guidance_scale)),
                              **({} if constraint is None else dict(prefix_allowed_tokens_fn=constraint)))
     text = tokenizer.batch_decode(out, skip_special_tokens=True)[0]
     return shown, seq, online_cut(text, conv.sep)
@@ -48,7 +49,8 @@ def eval_model(args):
     tokenizer, model, _ = load_pretrained_model(args.model_base_path, args.opus_pllm_weights_path, model_name,
                                                 args.load_8bit, args.load_4bit, switch_projector_type=args.switch_projector_type,
                                                 decoder_weights=getattr(args, "decoder_weights", None),
-                                                cstp_path=cstp_path, device="cuda:0", max_batch=max(1, args.num_beams),
+                                                cstp_path=cstp_path, device="cuda:0",
+                                                max_batch=max(1, args.num_beams, 2 if getattr(args, "guidance_scale", None) is not None else 1),
                                                 max_enc_tokens=args.max_residues + 2, max_prompt=args.max_prompt,
                                                 max_new_tokens=max(args.max_new_tokens, 1))
     constraint = token_constraint(args, tokenizer)
@@ -79,6 +81,8 @@ if __name__ == "__main__":
     p.add_argument("--top_p", type=float, default=0.7)
     p.add_argument("--num_beams", type=int, default=1)
     p.add_argument("--max_new_tokens", type=int, default=32)         # run_opus_online.py:101
+    p.add_argument("--guidance_scale", type=float, default=None, metavar="G",
+                   help="classifier-free guidance against the prompt without its protein (two decoder rows per answer)")
     p.add_argument("--switch_projector_type", type=str, default="mlp2x_gelu")
     p.add_argument("--load-4bit", action="store_true")
     p.add_argument("--decoder_weights", choices=("fp8",), default=None,

@@ -544,7 +544,22 @@ class OpusLlamaForCausalLM:
         handle (cache_prefix(detach=True) / OpusPrefix.detach()) can be used any number of times, also from new_context()
         contexts; a live one is detached on the fly (one export) and is stale afterwards, as after any prefill.
         num_return_sequences=N with sampling expands the rows on the host (row r N + j), so the suffix pass runs N times per
-        row.  num_beams > 1 raises NotImplementedError, an empty suffix row ValueError, a capacity violation OpusError -2."""
+        row.  num_beams > 1 raises NotImplementedError, an empty suffix row ValueError, a capacity violation OpusError -2.
+        guidance_scale=g (transformers' UnbatchedClassifierFreeGuidanceLogitsProcessor; greedy and sampling): classifier-free
+        guidance against a negative prompt.  A call of P prompts runs 2 P decoder rows - rows [0, P) the prompts as always, rows
+        [P, 2 P) the negative prompts, text only - so it costs about a plain call of 2 P rows.  Per step, in transformers' order:
+        scores = g (log_softmax(cond) - log_softmax(uncond)) + log_softmax(uncond) in fp32, then the logits processors, the
+        TokenTrie, temperature / top-k / top-p, the arg-max or the draw on the P rows; the negative row decodes the token chosen for
+        its prompt (pad ids once that row finished).  EOS ids, the stop sequence, processor histories and trie states
+        (TokenTrie.per_row of P tries) belong to the P rows; every output has P rows, `scores` the guided, processed scores,
+        `logits` and `token_logprobs` raw and conditional.  negative_prompt_ids [P, Tn] (+ negative_prompt_attention_mask;
+        left-padded or unpadded) is used as given and may hold no <seq> placeholder; None (an extension: transformers has no
+        default when it generates from embeddings) takes the call's own prompt with every <seq> placeholder dropped - the
+        protein-free twin - so the answer is contrasted with what the text alone would say.  Both sets are left-padded to one
+        length for the single 2 P-row prefill.  g None or 1 is the call without the argument (the negative prompt is ignored, as in
+        transformers).  g not a finite number, a negative prompt of another row count or with a placeholder raise ValueError;
+        2 P > max_batch or a padded length above max_prompt OpusError -2; num_beams > 1, num_return_sequences > 1 and prefix=
+        with guidance NotImplementedError."""
         return_dict = bool(kwargs.pop("return_dict_in_generate", False))
         want = {k: bool(kwargs.pop(k, False)) for k in ("output_scores", "output_logits", "output_token_logprobs",
                                                          "output_attentions", "output_hidden_states")}
@@ -557,6 +572,9 @@ class OpusLlamaForCausalLM:
         attention_mask = kwargs.pop("attention_mask", None)
         prefix = kwargs.pop("prefix", None)
         prefix_rows = kwargs.pop("prefix_rows", None)
+        guidance = _guidance_scale(kwargs.pop("guidance_scale", None))
+        neg_ids = kwargs.pop("negative_prompt_ids", None)
+        neg_mask = kwargs.pop("negative_prompt_attention_mask", None)
         if "inputs_embeds" in kwargs:
             raise NotImplementedError("`inputs_embeds` is not supported")
         do_sample = bool(kwargs.pop("do_sample", False))
@@ -622,6 +640,30 @@ class OpusLlamaForCausalLM:
             pad_id = eos[0] if eos else 0
         if inputs is None:
             raise ValueError("generate() needs input ids")
+        if guidance is not None:               # every check before the device is touched
+            if num_beams > 1:
+                raise NotImplementedError("guidance_scale is built for greedy search and sampling, not for num_beams > 1 "
+                                          "(transformers applies it to the beams' log-softmax scores)")
+            if nret > 1:
+                raise NotImplementedError("guidance_scale with num_return_sequences > 1 is not built: the fanned-out prefill has no "
+                                          "paired negative rows")
+            if prefix is not None:
+                raise NotImplementedError("guidance_scale with generate(prefix=...) is not built: a detached prefix holds no rows "
+                                          "for the negative prompts")
+            P = int(inputs.shape[0])
+            if neg_ids is None:
+                neg_ids, neg_mask = protein_free_twin(inputs, attention_mask)
+            else:
+                neg_ids, neg_mask = _explicit_negative_prompt(neg_ids, neg_mask, P)
+            max_len = int(getattr(getattr(self, "config", None), "tokenizer_model_max_length", None) or 0)
+            T_pad = max(spliced_length(inputs, attention_mask, self.cfg.n_prot_tokens, max_len),
+                        spliced_length(neg_ids, neg_mask, self.cfg.n_prot_tokens, max_len))
+            if 2 * P > self.cfg.max_batch:
+                raise _cabi.OpusError(-2, f"guidance_scale runs 2 x batch = 2 x {P} decoder rows: the context holds "
+                                          f"max_batch={self.cfg.max_batch}")
+            if T_pad > self.cfg.max_prompt:
+                raise _cabi.OpusError(-2, f"guidance_scale pads the prompts and the negative prompts to {T_pad} positions: the "
+                                          f"context holds max_prompt={self.cfg.max_prompt}")
         if prefix is not None:
             if num_beams > 1:
                 raise NotImplementedError("generate(prefix=...) is built for greedy search and sampling, not for num_beams > 1")
@@ -654,8 +696,17 @@ class OpusLlamaForCausalLM:
             if min_new is None:
                 min_new = max((min_len or 0) - int(embeds.shape[1]), 0)
             lproc = (pen, ngram, min_new, bad)
+        if guidance is not None:               # the negative rows through the text-only splice, both sets to one length
+            dummy = torch.zeros((neg_ids.shape[0], self.cfg.n_prot_tokens, self.cfg.dec_dim), dtype=_cabi.operand_dtype(),
+                                device=self.device)
+            n_embeds, n_mask, _ = self._splice(neg_ids, neg_mask, dummy, True)
+            with torch.cuda.stream(self._stream):
+                embeds, mask = pad_left_common(embeds, mask.to(torch.uint8), n_embeds, n_mask)
         self._set_logits_processors(lproc)
         self._set_token_constraint(constraint)
+        if guidance is not None:
+            outs = (want["output_token_logprobs"], want["output_scores"], want["output_logits"]) if return_dict else None
+            return self._greedy(embeds, mask, max_new, eos, int(pad_id), sampler, outputs=outs, guidance=guidance)
         if num_beams > 1:
             ids = self._beam_search(embeds, mask, max_new, eos, beam_pad, num_beams, sampler, nret)
             if not return_dict:
@@ -813,14 +864,19 @@ class OpusLlamaForCausalLM:
             self._leave()
         self._constraint = constraint
 
-    def _greedy(self, embeds, mask, max_new, eos, pad_id, sampler=None, outputs=None, nret: int = 1, behind=None):
+    def _greedy(self, embeds, mask, max_new, eos, pad_id, sampler=None, outputs=None, nret: int = 1, behind=None,
+                guidance: Optional[float] = None):
         """outputs = (token_logprobs, scores, logits) flags: a GenerateDecoderOnlyOutput instead of the ids.
         nret > 1: the B prompts are prefilled once and decoded as B nret rows (opus_generate_scored_fanout); every result has
         B nret rows.  nret == 1 takes the entries it always took.
         behind (a _BehindCall; mask unused, nret 1): embeds are right-padded suffix rows behind a detached prefix
-        (opus_generate_scored_behind)."""
+        (opus_generate_scored_behind).
+        guidance (nret 1, no behind): embeds / mask hold P conditional rows, then their P negative rows
+        (opus_generate_scored_guided); every result has P rows."""
         P, T, _ = embeds.shape                           # P prompts, B decoder rows
         B = P * nret
+        if guidance is not None:
+            P = B = P // 2                               # (rows with ids and outputs: the conditional half)
         V = self.cfg.dec_vocab
         embeds = embeds.contiguous()
         if behind is None:
@@ -844,11 +900,15 @@ class OpusLlamaForCausalLM:
                 sc = torch.empty((max_new, B, V), dtype=torch.float32, device=self.device) if want_sc else None
                 lg = torch.empty((max_new, B, V), dtype=torch.float32, device=self.device) if want_lg else None
                 if (sampler is None and sc is not None and lg is not None and getattr(self, "_lproc", None) is None
-                        and getattr(self, "_constraint", None) is None):
+                        and getattr(self, "_constraint", None) is None and guidance is None):
                     lg = None                                   # greedy: the processed scores are the logits - one tensor
                 t, p, sd = (sampler[0], sampler[1], sampler[2]) if sampler is not None else (0.0, 1.0, 0)
                 ptr = lambda x: None if x is None else x.data_ptr()                          # noqa: E731
-                if behind is not None:
+                if guidance is not None:
+                    _cabi.check(self._lib.opus_generate_scored_guided(self._ctx, embeds.data_ptr(), mask.data_ptr(), P, T, guidance,
+                                                                      max_new, eos_arr, len(eos), pad_id, t, p, sd, out.data_ptr(),
+                                                                      C.byref(n_out), ptr(lp), ptr(sc), ptr(lg), s))
+                elif behind is not None:
                     _cabi.check(self._lib.opus_generate_scored_behind(self._ctx, behind.snap, embeds.data_ptr(), B, T, behind.lens,
                                                                       behind.src, max_new, eos_arr, len(eos), pad_id, t, p, sd,
                                                                       out.data_ptr(), C.byref(n_out), ptr(lp), ptr(sc), ptr(lg), s))
@@ -860,6 +920,11 @@ class OpusLlamaForCausalLM:
                     _cabi.check(self._lib.opus_generate_scored(self._ctx, embeds.data_ptr(), mask.data_ptr(), B, T, max_new,
                                                                eos_arr, len(eos), pad_id, t, p, sd, out.data_ptr(), C.byref(n_out),
                                                                ptr(lp), ptr(sc), ptr(lg), s))
+            elif guidance is not None:
+                t, p, sd = (sampler[0], sampler[1], sampler[2]) if sampler is not None else (0.0, 1.0, 0)
+                _cabi.check(self._lib.opus_generate_scored_guided(self._ctx, embeds.data_ptr(), mask.data_ptr(), P, T, guidance, max_new,
+                                                                  eos_arr, len(eos), pad_id, t, p, sd, out.data_ptr(), C.byref(n_out),
+                                                                  None, None, None, s))
             elif behind is not None:
                 t, p, sd = (sampler[0], sampler[1], sampler[2]) if sampler is not None else (0.0, 1.0, 0)
                 _cabi.check(self._lib.opus_generate_scored_behind(self._ctx, behind.snap, embeds.data_ptr(), B, T, behind.lens, behind.src,
@@ -1558,6 +1623,82 @@ class TrieScores:
 
 # capacities of the processor kernel (include/opus_pllm.h, opus_set_logits_processors)
 LP_MAX_BAD, LP_MAX_BAD_LEN, LP_MAX_BAD_IDS = 256, 8, 1024
+
+
+def _guidance_scale(g) -> Optional[float]:
+    """generate(guidance_scale=g): None when guidance is off (g None or 1, as in transformers), else the finite float."""
+    if g is None:
+        return None
+    if isinstance(g, (bool, str)) or not isinstance(g, (int, float, np.integer, np.floating)) or not np.isfinite(float(g)):
+        raise ValueError(f"`guidance_scale` has to be a finite number (got {g!r})")
+    return None if float(g) == 1.0 else float(g)
+
+
+def _left_pack(rows: List[List[int]]):
+    """Lists of ids -> (ids int64 [P, T], mask bool [P, T]) on the CPU, left-padded with id 0 to the longest row."""
+    T = max(len(r) for r in rows)
+    ids = torch.zeros((len(rows), T), dtype=torch.int64)
+    mask = torch.zeros((len(rows), T), dtype=torch.bool)
+    for b, r in enumerate(rows):
+        if r:
+            ids[b, T - len(r):] = torch.tensor(r, dtype=torch.int64)
+            mask[b, T - len(r):] = True
+    return ids, mask
+
+
+def protein_free_twin(input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None):
+    """The default negative prompt of generate(guidance_scale=...): every row of the prompt with its masked-out positions and
+    every <seq> placeholder dropped, left-padded to the longest row -> (ids int64 [P, Tn], mask bool [P, Tn]) on the CPU."""
+    ids = input_ids.detach().to("cpu", torch.int64)
+    m = torch.ones_like(ids, dtype=torch.bool) if attention_mask is None else attention_mask.detach().to("cpu").bool()
+    if ids.ndim != 2 or m.shape != ids.shape:
+        raise ValueError(f"input ids [P, T] and attention_mask of the same shape (got {tuple(ids.shape)} and {tuple(m.shape)})")
+    rows = [[int(t) for t, k in zip(r.tolist(), mr.tolist()) if k and t != DEFAULT_SEQ_TOKEN_INDEX] for r, mr in zip(ids, m)]
+    for b, r in enumerate(rows):
+        if not r:
+            raise ValueError(f"row {b} of the prompt holds nothing but <seq> placeholders: its protein-free twin is empty "
+                             "(pass negative_prompt_ids)")
+    return _left_pack(rows)
+
+
+def _explicit_negative_prompt(neg_ids, neg_mask, P: int):
+    """negative_prompt_ids / negative_prompt_attention_mask as given, checked: P rows, no <seq> placeholder, no empty row."""
+    ids = torch.as_tensor(neg_ids).detach().to("cpu", torch.int64)
+    if ids.ndim != 2 or ids.shape[0] != P:
+        raise ValueError(f"`negative_prompt_ids` has to be [batch, Tn] with one row per prompt: got {tuple(ids.shape)} for "
+                         f"{P} prompts")
+    m = torch.ones_like(ids, dtype=torch.bool) if neg_mask is None else torch.as_tensor(neg_mask).detach().to("cpu").bool()
+    if m.shape != ids.shape:
+        raise ValueError(f"`negative_prompt_attention_mask` {tuple(m.shape)} does not match `negative_prompt_ids` {tuple(ids.shape)}")
+    if bool(((ids == DEFAULT_SEQ_TOKEN_INDEX) & m).any()):
+        raise ValueError("`negative_prompt_ids` may hold no <seq> placeholder: the negative rows are text only")
+    if bool((m.sum(dim=1) == 0).any()):
+        raise ValueError("`negative_prompt_ids` has an empty row")
+    return ids, m
+
+
+def spliced_length(input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor], n_prot_tokens: int, max_length: int = 0) -> int:
+    """Positions the longest row takes after the splice: its unmasked ids, every <seq> placeholder standing for n_prot_tokens
+    (cut at max_length when > 0, as the splice does)."""
+    ids = input_ids.detach().to("cpu", torch.int64)
+    m = torch.ones_like(ids, dtype=torch.bool) if attention_mask is None else attention_mask.detach().to("cpu").bool()
+    n = m.sum(dim=1) + (n_prot_tokens - 1) * ((ids == DEFAULT_SEQ_TOKEN_INDEX) & m).sum(dim=1)
+    T = int(n.max())
+    return min(T, max_length) if max_length > 0 else T
+
+
+def pad_left_common(a: torch.Tensor, a_mask: torch.Tensor, b: torch.Tensor, b_mask: torch.Tensor, fill=0):
+    """Two left-padded sets [P, Ta, ...] and [P, Tb, ...] with masks [P, Ta] / [P, Tb] -> one set [2 P, T, ...] and its mask
+    [2 P, T], T = max(Ta, Tb): the rows of `a`, then those of `b`, each moved to the right end, `fill` and mask 0 in front."""
+    T = max(a.shape[1], b.shape[1])
+    P = a.shape[0]
+    out = torch.full((P + b.shape[0], T) + tuple(a.shape[2:]), fill, dtype=a.dtype, device=a.device)
+    mask = torch.zeros((P + b.shape[0], T), dtype=a_mask.dtype, device=a_mask.device)
+    out[:P, T - a.shape[1]:] = a
+    out[P:, T - b.shape[1]:] = b.to(a.dtype)
+    mask[:P, T - a.shape[1]:] = a_mask
+    mask[P:, T - b.shape[1]:] = b_mask.to(a_mask.dtype)
+    return out, mask
 
 
 def _logits_processors(kwargs: dict, eos: Sequence[int], vocab: Optional[int]):
