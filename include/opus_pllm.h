@@ -647,6 +647,38 @@ int opus_beam_sample_topk(opus_ctx *ctx, const float *d_logits, const float *d_r
  * samples (transformers >= 5: None); the Python mirror's generate(top_k=...) defaults to 50 accordingly. */
 int opus_set_sampling_top_k(opus_ctx *ctx, int32_t k);
 
+/* Continuous batching (no reference counterpart; added within ABI 10): one live decode batch - a session - whose done rows are handed
+ * to new prompts while the other rows keep decoding.  Step t of a session writes every row's token to column t of d_ids int32
+ * [B, S] (S = max_new_tokens of the context: the session's step budget) and its K / V to cache slot T + t.  A row is done at the
+ * first step at which it emitted an EOS id, completed the stop sequence, or has emitted max_new tokens since its occupant began.
+ * opus_stream_begin: opus_generate_*'s checks, uploads and prefill (B rows, T left-padded positions); every row begins at step 0.
+ *   OPUS_EUNSUPPORTED while logits processors or a token constraint are set.
+ * opus_stream_run: at every step boundary t the host knows the rows' state as of step t - opus_stream_lag() (it never enqueues
+ *   more than that ahead) and returns - *t_out = t, h_end[r] (HOST, int32 [B]) = the step row r was done at, -1 if not (yet, as far
+ *   as known) - when every row is done, when t == t_max (at most S), or when t >= t_min and at least min_free rows are done;
+ *   otherwise it enqueues step t (from a captured graph of its own: the plain decode graphs are neither used nor evicted).  What it
+ *   returns is a function of the rows' end steps alone.
+ * opus_stream_refill (at the boundary opus_stream_run returned): rows h_rows[i] (n of them, each once) take the prompts that were
+ *   prefilled elsewhere: row h_src[i] of the detached snapshot, of h_len[i] = Tp - kstart slots, is placed at cache slots
+ *   [T + t - h_len[i], T + t) of the row, whose kstart moves there; row h_src[i] of d_last_logits (fp32 [snap rows, dec_vocab]) becomes
+ *   the row's logits; its flags are cleared, its occupant begins at step t, and id columns t - 8 .. t - 1 are set to -1 (the stop
+ *   sequence is matched against at most 8 ids back).  No other row is touched.  OPUS_ESHAPE when a prompt does not fit under T + t
+ *   slots or t + max_new > S.  Prefix handles of the context go stale.
+ * opus_stream_end synchronises, fills h_end (optional, HOST int32 [B]) with the rows' end steps as of the last enqueued step and
+ *   leaves the context as after opus_generate_*.  Any prefill on the context also ends a session. */
+int32_t opus_stream_lag(void);
+int opus_stream_begin(opus_ctx *ctx, const void *d_embeds, const uint8_t *d_mask, int32_t B, int32_t T, int32_t max_new,
+                      const int32_t *eos_ids, int32_t n_eos, int32_t pad_id, float temperature, float top_p, uint64_t seed,
+                      int32_t *d_ids, void *stream);
+int opus_stream_run(opus_ctx *ctx, int32_t t_min, int32_t min_free, int32_t t_max, int32_t *t_out, int32_t *h_end, void *stream);
+int opus_stream_refill(opus_ctx *ctx, const opus_prefix_snap *snap, int32_t n, const int32_t *h_rows, const int32_t *h_src,
+                       const float *d_last_logits, const int32_t *h_len, void *stream);
+int opus_stream_end(opus_ctx *ctx, int32_t *h_end, void *stream);
+/* Test support: synchronises `stream`; kstart, finished flags, start and end steps (HOST, int32 [B] each) of the open session's rows
+ * and the cache epoch (for opus_llama_prefix_export).  poison != 0: the whole KV cache is first filled with that byte. */
+int opus_debug_stream_state(opus_ctx *ctx, int32_t *h_kstart, int32_t *h_fin, int32_t *h_start, int32_t *h_end, int64_t *epoch,
+                            int32_t poison, void *stream);
+
 /* fp32 logits [B, dec_vocab] of the most recent prefill / decode step (device copy on `stream`): the payload of the
  * optional logits all-gather of SURVEY 8e (ids are what eval/run_opus_ddp.py:138 gathers). */
 int opus_last_logits(opus_ctx *ctx, float *d_out, int32_t B, void *stream);

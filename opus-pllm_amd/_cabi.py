@@ -74,6 +74,13 @@ SIGNATURES = {
     "opus_llama_score_continuations_detached": (C.c_int, [_P, _SNAP, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     "opus_llama_score_tree_detached": (C.c_int, [_P, _SNAP, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, C.c_int32, _P,
                                                  _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, _P]),
+    "opus_stream_lag": (C.c_int32, []),
+    "opus_stream_begin": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _I32P, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                    C.c_uint64, _P, _P]),
+    "opus_stream_run": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _I32P, _I32P, _P]),
+    "opus_stream_refill": (C.c_int, [_P, _SNAP, C.c_int32, _I32P, _I32P, _P, _I32P, _P]),
+    "opus_stream_end": (C.c_int, [_P, _I32P, _P]),
+    "opus_debug_stream_state": (C.c_int, [_P, _I32P, _I32P, _I32P, _I32P, C.POINTER(C.c_int64), C.c_int32, _P]),
     "opus_abi_version": (C.c_int, []),
     "opus_operand_dtype": (C.c_int, []),
     "opus_last_error": (C.c_char_p, []),

@@ -193,10 +193,32 @@ struct opus_ctx {
     // its own, made on first use for the largest pass the context can run
     int32_t *behind_tbl = nullptr;
     int64_t prefills_behind = 0;         // opus_stat("prefills_behind")
+    // continuous batching (opus_stream_*): one live decode batch whose done rows are refilled.  stream_mem (first use): start [B],
+    // poll [B + 1] (end steps + the count of rows not done), the refill's tables (new kstart per row, listed rows, their snapshot
+    // rows, kv_place's offsets and list).  h_poll (pinned): STREAM_RING copies of poll, one per step in flight.  The captured step
+    // of a session is an entry of its own (stream_graph), beside the plain graphs and never evicting one.
+    static constexpr int STREAM_LAG = POLL_LAG + 1, STREAM_RING = POLL_RING;
+    struct StreamState {
+        bool on = false;
+        int B = 0, T0 = 0, t = 0, max_new = 0, n_eos = 0, pad = 0;
+        int32_t *d_ids = nullptr;
+        float temp = 0.f, top_p = 1.f;
+        std::vector<int32_t> start;      // host copy of start[]
+    } st;
+    char *stream_mem = nullptr;
+    int32_t *d_sstart = nullptr, *d_spoll = nullptr, *d_snks = nullptr, *d_srows = nullptr, *d_ssrc = nullptr, *d_soff = nullptr,
+            *d_slist = nullptr;
+    int32_t *h_poll = nullptr;
+    GraphEntry stream_graph;
+    int stream_graph_budget = -1;        // max_new of the captured finish launch
+    int64_t stream_steps = 0, stream_refills = 0;   // opus_stat("stream_steps" / "stream_refills")
 };
 
 static std::atomic<int64_t> g_epoch{0};
-static void new_epoch(opus_ctx *c) { c->epoch = ++g_epoch; }
+static void new_epoch(opus_ctx *c) {     // (a call that prefills or permutes the cache also ends a continuous session)
+    c->epoch = ++g_epoch;
+    c->st.on = false;
+}
 
 // Continuation rows of opus_llama_score_continuations in the prefill's layer loop: B rows of T new positions behind a cached prefix.
 // No mask / kstart upload, no cache write, no decode state: rotary (learned positions for OPT) at Tp - kstart[p] + t through
@@ -414,6 +436,8 @@ static void drop_graphs(opus_ctx *c) {   // a captured step holds weight pointer
     for (auto &g : c->graphs)
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
     c->graphs.clear();
+    if (c->stream_graph.exec) (void)hipGraphExecDestroy(c->stream_graph.exec);
+    c->stream_graph = opus_ctx::GraphEntry();
 }
 
 extern "C" int opus_ctx_destroy(opus_ctx *c) {
@@ -432,6 +456,8 @@ extern "C" int opus_ctx_destroy(opus_ctx *c) {
     if (c->guid_keep) (void)hipFree(c->guid_keep);
     if (c->behind_tbl) (void)hipFree(c->behind_tbl);
     if (c->h_nunf) (void)hipHostFree(c->h_nunf);
+    if (c->stream_mem) (void)hipFree(c->stream_mem);
+    if (c->h_poll) (void)hipHostFree(c->h_poll);
     for (auto &e : c->poll_ev) if (e) (void)hipEventDestroy(e);
     delete c;
     return OPUS_OK;
@@ -2635,6 +2661,231 @@ extern "C" int opus_set_stop_sequence(opus_ctx *c, const int32_t *ids, int32_t n
     return OPUS_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ continuous batching
+// One live decode batch (a session) whose done rows are handed to new prompts: opus_stream_begin prefills the first rows,
+// opus_stream_run decodes until enough rows are done, opus_stream_refill places new prompts (prefilled elsewhere, a detached
+// snapshot + their last-position logits) under done rows, opus_stream_end closes the session.  Step t of a session writes column t
+// of the id buffer [B, S] (S = max_new_tokens of the context, the session's step budget) and cache slot T0 + t; a row's occupant
+// began at start[r].  The host looks at the rows' state STREAM_LAG steps behind what it enqueues (the event ring of generate_impl),
+// so a boundary's decision is a function of the rows' end steps only, never of how far the GPU happens to be.
+static int ensure_stream_mem(opus_ctx *c) {
+    if (c->stream_mem) return OPUS_OK;
+    const size_t B = c->cfg.max_batch;
+    const size_t words = 2 * B + 1 + 5 * B + 2;            // start | poll | nks, rows, src, off [B + 2], list (one upload)
+    HIPC(hipMalloc((void **)&c->stream_mem, words * sizeof(int32_t)));
+    HIPC(hipHostMalloc((void **)&c->h_poll, opus_ctx::STREAM_RING * (B + 1) * sizeof(int32_t), hipHostMallocDefault));
+    int32_t *w = reinterpret_cast<int32_t *>(c->stream_mem);
+    c->d_sstart = w;
+    c->d_spoll = w + B;
+    c->d_snks = w + 2 * B + 1;
+    c->d_srows = c->d_snks + B;
+    c->d_ssrc = c->d_srows + B;
+    c->d_soff = c->d_ssrc + B;
+    c->d_slist = c->d_soff + B + 2;
+    return OPUS_OK;
+}
+
+// one step of a session: the head of generate's step, the rows' budgets and end steps, the decode of the chosen tokens
+static int stream_body(opus_ctx *c, hipStream_t s) {
+    const opus_ctx::StreamState &st = c->st;
+    OPC(argmax(c, s, c->cfg.max_new_tokens, st.n_eos, st.pad, st.d_ids));
+    KL(KC_OTHER, 16.0 * st.B, launch_stream_finish(c->d_step, c->d_sstart, c->d_fin, c->d_spoll, st.B, st.max_new, s));
+    return decode_step(c, s, c->d_next);
+}
+
+extern "C" int32_t opus_stream_lag(void) { return opus_ctx::STREAM_LAG; }
+
+extern "C" int opus_stream_begin(opus_ctx *c, const void *d_embeds, const uint8_t *d_mask, int32_t B, int32_t T, int32_t max_new,
+                                 const int32_t *eos_ids, int32_t n_eos, int32_t pad_id, float temperature, float top_p, uint64_t seed,
+                                 int32_t *d_ids, void *stream) {
+    OPC(need_ready(c));
+    if (temperature < 0.f || top_p <= 0.f || top_p > 1.f) return fail(OPUS_EBADARG, "stream_begin: temperature >= 0 and 0 < top_p <= 1");
+    OPC(check_prefill_args(c, d_embeds, d_mask, B, T));
+    if (!d_ids) return fail(OPUS_EBADARG, "stream_begin: null pointer");
+    const opus_config &g = c->cfg;
+    if (max_new < 1 || max_new > g.max_new_tokens)
+        return fail(OPUS_ESHAPE, "stream_begin: max_new=%d exceeds the session's step budget max_new_tokens=%d", max_new, g.max_new_tokens);
+    if (n_eos < 0 || n_eos > 64 || (n_eos > 0 && !eos_ids)) return fail(OPUS_EBADARG, "stream_begin: eos list");
+    if (c->lproc_on || c->cons_on)
+        return fail(OPUS_EUNSUPPORTED, "stream_begin: logits processors and token constraints count steps from 0 for every row: not "
+                                       "built for rows that begin at a later step");
+    OPC(ensure_stream_mem(c));
+    hipStream_t s = (hipStream_t)stream;
+    c->samp_temp = temperature;
+    c->samp_top_p = top_p;
+    if (n_eos) HIPC(hipMemcpyAsync(c->d_eos, eos_ids, n_eos * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(c->d_seed, &seed, sizeof(seed), hipMemcpyHostToDevice, s));
+    HIPC(hipMemsetAsync(c->d_fin, 0, B * sizeof(int32_t), s));
+    HIPC(hipMemsetAsync(c->d_nunf, 0, (size_t)g.max_new_tokens * sizeof(int32_t), s));
+    OPC(prefill(c, s, (const half_t *)d_embeds, d_mask, B, T));
+    c->phase = PH_DECODE;
+    KL(KC_OTHER, 8.0 * B, launch_stream_reset(c->d_sstart, c->d_spoll, B, s));
+    c->gen_outs = 0;
+    c->guid_on = false;
+    opus_ctx::StreamState &st = c->st;
+    st.B = B; st.T0 = T; st.t = 0; st.max_new = max_new; st.n_eos = n_eos; st.pad = pad_id; st.d_ids = d_ids;
+    st.temp = temperature; st.top_p = top_p;
+    st.start.assign(B, 0);
+    st.on = true;
+    return OPUS_OK;
+}
+
+extern "C" int opus_stream_run(opus_ctx *c, int32_t t_min, int32_t min_free, int32_t t_max, int32_t *t_out, int32_t *h_end,
+                               void *stream) {
+    if (!c || !t_out || !h_end) return fail(OPUS_EBADARG, "stream_run: null pointer");
+    HIPC(hipSetDevice(c->device));
+    opus_ctx::StreamState &st = c->st;
+    if (!st.on) return fail(OPUS_ESTATE, "stream_run: no session is open (opus_stream_begin; a prefill on this context ends one)");
+    hipStream_t s = (hipStream_t)stream;
+    const int B = st.B, S = c->cfg.max_new_tokens;
+    constexpr int LAG = opus_ctx::STREAM_LAG, RING = opus_ctx::STREAM_RING;
+    if (t_max > S) t_max = S;
+    if (min_free < 1) min_free = 1;
+    const bool use_graph = s != nullptr && !c->timing && !getenv("OPUS_NO_GRAPH");
+    opus_ctx::GraphEntry &ge = c->stream_graph;
+    if (ge.exec && !(ge.B == B && ge.maxnew == S && ge.pad == st.pad && ge.neos == st.n_eos && ge.out == st.d_ids && ge.temp == st.temp &&
+                     ge.top_p == st.top_p && c->stream_graph_budget == st.max_new)) {
+        (void)hipGraphExecDestroy(ge.exec);
+        ge = opus_ctx::GraphEntry();
+    }
+    for (;;) {                                                      // (at most S + 1 boundaries: t grows by one per round)
+        const int t = st.t, sv = t - LAG;
+        int ndone = 0;
+        for (int r = 0; r < B; ++r) h_end[r] = -1;
+        if (sv >= 0) {
+            HIPC(hipEventSynchronize(c->poll_ev[sv % RING]));
+            const int32_t *p = c->h_poll + (size_t)(sv % RING) * (c->cfg.max_batch + 1);
+            for (int r = 0; r < B; ++r)
+                if (st.start[r] <= sv && p[r] >= 0) {               // (an earlier occupant's end step is not this row's)
+                    h_end[r] = p[r];
+                    ++ndone;
+                }
+        }
+        if (ndone == B || t >= t_max || (t >= t_min && ndone >= min_free)) {
+            *t_out = t;
+            return OPUS_OK;
+        }
+        if (!use_graph || (!ge.exec && t == 0)) {
+            OPC(stream_body(c, s));                                 // eager (the first step also warms lazily-set attributes)
+        } else {
+            if (!ge.exec) {
+                hipGraph_t graph = nullptr;
+                HIPC(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+                int rc = stream_body(c, s);
+                hipError_t ee = hipStreamEndCapture(s, &graph);
+                if (rc != OPUS_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+                if (ee != hipSuccess) return fail(OPUS_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(ee));
+                ee = hipGraphInstantiate(&ge.exec, graph, nullptr, nullptr, 0);
+                (void)hipGraphDestroy(graph);
+                if (ee != hipSuccess) { ge.exec = nullptr; return fail(OPUS_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(ee)); }
+                ++c->graph_instantiations;
+                ge.B = B; ge.maxnew = S; ge.pad = st.pad; ge.neos = st.n_eos; ge.temp = st.temp; ge.top_p = st.top_p; ge.out = st.d_ids;
+                c->stream_graph_budget = st.max_new;
+            }
+            ++c->graph_replays;
+            HIPC(hipGraphLaunch(ge.exec, s));
+        }
+        HIPC(hipMemcpyAsync(c->h_poll + (size_t)(t % RING) * (c->cfg.max_batch + 1), c->d_spoll, (size_t)(B + 1) * sizeof(int32_t),
+                            hipMemcpyDeviceToHost, s));
+        HIPC(hipEventRecord(c->poll_ev[t % RING], s));
+        ++st.t;
+        ++c->decode_steps;
+        ++c->stream_steps;
+    }
+}
+
+extern "C" int opus_stream_refill(opus_ctx *c, const opus_prefix_snap *snap, int32_t n, const int32_t *h_rows, const int32_t *h_src,
+                                  const float *d_last_logits, const int32_t *h_len, void *stream) {
+    OPC(need_ready(c));
+    opus_ctx::StreamState &st = c->st;
+    if (!st.on) return fail(OPUS_ESTATE, "stream_refill: no session is open");
+    if (!h_rows || !h_src || !d_last_logits || !h_len) return fail(OPUS_EBADARG, "stream_refill: null pointer");
+    const opus_config &g = c->cfg;
+    const int B = st.B, MB = g.max_batch, S = g.max_new_tokens, t = st.t, L = st.T0 + t;
+    PrefixSrc ps;
+    OPC(resolve_prefix(c, "stream_refill", snap, 0, 0, ps));
+    if (n < 1 || n > B) return fail(OPUS_ESHAPE, "stream_refill: %d rows listed, the session has %d", n, B);
+    if (t + st.max_new > S)
+        return fail(OPUS_ESHAPE, "stream_refill: a row that begins at step %d cannot end inside the session's %d steps (budget %d)", t, S,
+                    st.max_new);
+    if (d_last_logits == c->d_logits) return fail(OPUS_EBADARG, "stream_refill: the logits rows must come from another buffer");
+    std::vector<int32_t> w(5 * (size_t)MB + 2, 0), seen(B, 0);
+    int32_t *nks = w.data(), *rows = nks + MB, *src = rows + MB, *off = src + MB, *list = off + MB + 2;
+    for (int i = 0; i < n; ++i) {
+        const int r = h_rows[i], p = h_src[i];
+        if (r < 0 || r >= B || seen[r]) return fail(OPUS_EBADARG, "stream_refill: row %d outside [0, %d) or listed twice", r, B);
+        if (p < 0 || p >= ps.P) return fail(OPUS_EBADARG, "stream_refill: snapshot row %d of row %d outside [0, %d)", p, r, ps.P);
+        const int len = ps.Tp - ps.kst[p];
+        if (h_len[i] != len) return fail(OPUS_EBADARG, "stream_refill: row %d: length %d, the snapshot row holds %d slots", r, h_len[i], len);
+        if (len < 1 || len > L) return fail(OPUS_ESHAPE, "stream_refill: a prompt of %d slots does not fit under %d slots", len, L);
+        seen[r] = 1;
+        nks[r] = L - len;
+        rows[i] = r;
+        src[i] = p;
+    }
+    int k = 0;
+    for (int p = 0; p < ps.P; ++p) {                                // kv_place's grouping: the listed rows of every snapshot row
+        off[p] = k;
+        for (int i = 0; i < n; ++i)
+            if (h_src[i] == p) list[k++] = h_rows[i];
+    }
+    off[ps.P] = k;
+    hipStream_t s = (hipStream_t)stream;
+    new_epoch(c);                                                   // (prefix handles of this context are stale)
+    st.on = true;
+    c->h_kstart.clear();
+    c->phase = PH_OTHER;
+    HIPC(launch_upload_i32(w.data(), (int)w.size(), c->d_snks, s));
+    KvPlaceParams kp;
+    kp.snap_k = reinterpret_cast<const half_t *>(snap->d_k); kp.snap_v = reinterpret_cast<const half_t *>(snap->d_v);
+    kp.kstart = snap->d_kstart; kp.P = ps.P; kp.Tp = ps.Tp; kp.kc = c->kc; kp.vc = c->vc;
+    kp.cache_sl = c->cache_sl; kp.cache_sb = c->cache_sb; kp.cache_sh = c->cache_sh;
+    kp.list = c->d_slist; kp.off = c->d_soff; kp.new_kstart = c->d_snks;
+    kp.layers = g.dec_layers; kp.nkv = g.dec_kv_heads; kp.hd = g.dec_head_dim;
+    double slots = 0.0;
+    for (int i = 0; i < n; ++i) slots += h_len[i];
+    KL(KC_OTHER, 2.0 * slots * 2.0 * g.dec_layers * g.dec_kv_heads * g.dec_head_dim * sizeof(half_t), launch_kv_place(kp, s));
+    KL(KC_OTHER, 8.0 * n * g.dec_vocab,
+       launch_stream_refill(c->d_srows, c->d_ssrc, c->d_snks, n, d_last_logits, c->d_logits, g.dec_vocab, c->d_kstart, c->d_sstart,
+                            c->d_fin, c->d_spoll, st.d_ids, S, t, s));
+    for (int i = 0; i < n; ++i) st.start[h_rows[i]] = t;
+    ++c->stream_refills;
+    return OPUS_OK;
+}
+
+extern "C" int opus_stream_end(opus_ctx *c, int32_t *h_end, void *stream) {
+    if (!c) return fail(OPUS_EBADARG, "ctx is null");
+    HIPC(hipSetDevice(c->device));
+    if (!c->st.on) return fail(OPUS_ESTATE, "stream_end: no session is open");
+    c->st.on = false;
+    hipStream_t s = (hipStream_t)stream;
+    // the rows' end steps with every enqueued step complete (no lag: nothing is decided from them but what to harvest)
+    if (h_end) HIPC(hipMemcpyAsync(h_end, c->d_spoll, (size_t)c->st.B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    return handoff_check(c, s);                                     // (synchronises the stream)
+}
+
+// Test support: synchronises `stream` and copies the session's row words to the host - kstart, the finished flags, start and the
+// end steps [rows of the session each] - and the cache epoch.  poison != 0 first fills the whole KV cache with that byte.
+extern "C" int opus_debug_stream_state(opus_ctx *c, int32_t *h_kstart, int32_t *h_fin, int32_t *h_start, int32_t *h_end, int64_t *epoch,
+                                       int32_t poison, void *stream) {
+    if (!c || !h_kstart || !h_fin || !h_start || !h_end || !epoch) return fail(OPUS_EBADARG, "debug_stream_state: null pointer");
+    HIPC(hipSetDevice(c->device));
+    if (!c->st.on) return fail(OPUS_ESTATE, "debug_stream_state: no session is open");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t B = c->st.B, cache = (size_t)c->cache_sl * c->cfg.dec_layers * sizeof(half_t);
+    if (poison) {
+        HIPC(hipMemsetAsync(c->kc, poison & 255, cache, s));
+        HIPC(hipMemsetAsync(c->vc, poison & 255, cache, s));
+    }
+    HIPC(hipMemcpyAsync(h_kstart, c->d_kstart, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPC(hipMemcpyAsync(h_fin, c->d_fin, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPC(hipMemcpyAsync(h_start, c->d_sstart, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPC(hipMemcpyAsync(h_end, c->d_spoll, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    *epoch = c->epoch;
+    return OPUS_OK;
+}
+
 // A logits-processor setting from host values (opus_set_logits_processors / opus_debug_logits_process): checked against the
 // capacities; V > 0 also bounds the ids.
 static int make_lproc(LogitsProcDesc &d, float penalty, int32_t ngram, int32_t min_new, const int32_t *bad_ids, const int32_t *bad_off,
@@ -3424,6 +3675,9 @@ extern "C" int64_t opus_stat(opus_ctx *c, const char *name) {
     if (!strcmp(name, "decode_steps")) return c->decode_steps;
     if (!strcmp(name, "w8_gemms")) return c->w8_gemms;
     if (!strcmp(name, "prefills_behind")) return c->prefills_behind;
+    if (!strcmp(name, "stream_steps")) return c->stream_steps;
+    if (!strcmp(name, "stream_refills")) return c->stream_refills;
+    if (!strcmp(name, "stream_graph")) return c->stream_graph.exec ? 1 : 0;
     return -1;
 }
 

@@ -364,6 +364,18 @@ hipError_t launch_kv_place(const KvPlaceParams &p, hipStream_t s);
 hipError_t launch_kv_append(const half_t *qkv, const int32_t *lens, int R, int n, int nh, int nkv, int hd, int Tp, half_t *kc, half_t *vc,
                             int64_t cache_sb, int64_t cache_sh, hipStream_t s);
 
+// stream.hip: continuous batching (opus_stream_*).  start [B]: the step a row's occupant began at; poll [B + 1]: the rows' end steps
+// (-1: not done) and, in poll[B], the count of rows not done - what the host copies out behind every step.
+// finish (behind the step kernel of step t = step[0]): a row whose budget is used up (t + 1 - start[r] >= max_new) is marked
+// finished; the first step at which a row is done goes to poll[r]
+hipError_t launch_stream_finish(const int32_t *step, const int32_t *start, int32_t *fin, int32_t *poll, int B, int max_new, hipStream_t s);
+// refill (step boundary t): listed row i = decode row rows[i] takes row src[i] of logits_in [*, V], kstart nks[rows[i]], start t,
+// cleared fin / poll words and -1 in id columns t - 8 .. t - 1 (ids [B, S])
+hipError_t launch_stream_refill(const int32_t *rows, const int32_t *src, const int32_t *nks, int n, const float *logits_in, float *logits,
+                                int V, int32_t *kstart, int32_t *start, int32_t *fin, int32_t *poll, int32_t *ids, int S, int t,
+                                hipStream_t s);
+hipError_t launch_stream_reset(int32_t *start, int32_t *poll, int B, hipStream_t s);
+
 // contact.hip: ESM-2 contact maps (opus_esm2_contacts_packed).  One layer's accumulation over token-packed proteins cu[B + 1]
 // (rows <cls> residues <eos>): Q / K rows of stride ld (head h at column h hd; q scaled and both rotated as the attention takes
 // them); A[sum n_b^2] (+)= sum_h w[h] P_h over the interior positions, rows[(cu[b] - 2 b + i) vld + c0 + h] = interior row sums

@@ -160,6 +160,50 @@ def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperatu
     return torch.cat(outs) if outs else torch.empty((0, max_new), dtype=torch.long, device=dev)
 
 
+def annotate_continuous(model, tokenizer, items, input_path, max_new, temperature=0.0, top_p=1.0, use_input_embed=False,
+                        device=None, stop_sequence=None, slots=None, refill_min=None, stats_out=None):
+    """--continuous: the whole shard through ONE generate_continuous() call - a decode batch of `slots` rows whose finished rows
+    are handed to the next prompts - instead of a sequence of batches that each wait for their longest answer.  Returns what
+    annotate() returns, [n, max_new] padded with the EOS id; stats_out (a dict) receives the call's statistics."""
+    dev = device or model.device
+    if not items:
+        return torch.empty((0, max_new), dtype=torch.long, device=dev)
+    prompts = [opa.tokenizer_seq_token(build_prompt(q["instruction"], input_path), tokenizer, opa.DEFAULT_SEQ_TOKEN_INDEX,
+                                       return_tensors="pt") for q in items]
+    extra = {}
+    if use_input_embed:
+        extra["protein_tokens"] = model.project_dataset(torch.tensor([q["input_embed"] for q in items], dtype=torch.float32, device=dev))
+    with torch.inference_mode():
+        out = model.generate_continuous(prompts, [q["input"] for q in items], max_new_tokens=max_new,
+                                        pad_token_id=tokenizer.eos_token_id, slots=slots, refill_min=refill_min,
+                                        do_sample=temperature > 0, temperature=temperature, top_p=top_p,
+                                        stop_sequence=stop_sequence, return_dict_in_generate=True, **extra)
+    if stats_out is not None:
+        stats_out.update(out.stats)
+    full = torch.full((len(items), max_new), tokenizer.eos_token_id, dtype=torch.long)
+    for i, s in enumerate(out.sequences):
+        full[i, : len(s)] = s
+    return full.to(dev)
+
+
+def continuous_refusals(args):
+    """The options --continuous does not take (generate_continuous raises NotImplementedError for their arguments)."""
+    bad = []
+    if args.num_beams > 1:
+        bad.append("--num_beams")
+    if int(getattr(args, "num_return_sequences", 1) or 1) > 1:
+        bad.append("--num_return_sequences")
+    g = getattr(args, "guidance_scale", None)
+    if g is not None and float(g) != 1.0:
+        bad.append("--guidance_scale")
+    for flag in ("share_prompt_head", "save_logprobs", "dump_logits", "rank_terms", "allowed_terms"):
+        if getattr(args, flag, None):
+            bad.append("--" + flag)
+    if logits_processor_kwargs(args):
+        bad.append("the logits-processor options")
+    return bad
+
+
 def shared_head_length(rows) -> int:
     """Length of the longest leading id run that all `rows` (id lists) share, ending in front of every row's first placeholder and
     leaving every row at least one id behind it."""
@@ -254,6 +298,17 @@ def eval_model(args):
     if n_rank and not getattr(args, "allowed_terms", None):
         raise ValueError("--rank_terms needs --allowed_terms (the vocabulary to rank)")
     held = {}
+    continuous = bool(getattr(args, "continuous", False))
+    ctx_new, ctx_batch = max_new, args.batch_size * max(1, args.num_beams)
+    if continuous:
+        bad = continuous_refusals(args)
+        if bad:
+            raise ValueError("--continuous does not take " + ", ".join(bad))
+        # the context's max_new_tokens capacity is a session's step budget: a row can begin at any step that leaves it its budget
+        ctx_new = int(args.session_steps) if args.session_steps else 4 * max_new
+        if ctx_new < max_new:
+            raise ValueError(f"--session_steps {ctx_new} is below the token budget {max_new}")
+        ctx_batch = int(args.slots) if args.slots else args.batch_size
 
     def capacity(tok, cfg):
         need = prompt_capacity(tok, mine, args.input_path, cfg.n_prot_tokens)
@@ -265,8 +320,8 @@ def eval_model(args):
     tokenizer, model, _ = load_pretrained_model(args.model_base_path, args.opus_pllm_weights_path, model_name,
                                                 args.load_8bit, args.load_4bit, switch_projector_type=args.switch_projector_type,
                                                 decoder_weights=getattr(args, "decoder_weights", None),
-                                                cstp_path=cstp_path, device=f"cuda:{local}", max_batch=args.batch_size * max(1, args.num_beams),
-                                                max_enc_tokens=args.max_residues + 2, max_prompt=8, max_new_tokens=max_new,
+                                                cstp_path=cstp_path, device=f"cuda:{local}", max_batch=ctx_batch,
+                                                max_enc_tokens=args.max_residues + 2, max_prompt=8, max_new_tokens=ctx_new,
                                                 capacity_from=capacity)
     dev = torch.device("cuda", local)
     t0 = time.time()
@@ -279,12 +334,19 @@ def eval_model(args):
         proc_kw["prefix_allowed_tokens_fn"] = trie
     lps = [] if args.save_logprobs else None
     N = int(getattr(args, "num_return_sequences", 1) or 1)
-    local_ids = annotate(model, tokenizer, mine, args.input_path, args.batch_size, max_new, args.temperature, args.top_p,
-                         args.num_beams, args.use_input_embed, dev, logits,
-                         tokenizer.encode("###", add_special_tokens=False) if args.stop_at_hashes else None, inflight=args.inflight,
-                         logprobs_out=lps, processors=proc_kw, num_return_sequences=N,
-                         share_prompt_head=bool(getattr(args, "share_prompt_head", False)),
-                         guidance_scale=getattr(args, "guidance_scale", None))
+    stop_ids = tokenizer.encode("###", add_special_tokens=False) if args.stop_at_hashes else None
+    if continuous:              # the rank's whole shard in one call; the same fields are saved
+        cstats = {}
+        local_ids = annotate_continuous(model, tokenizer, mine, args.input_path, max_new, args.temperature, args.top_p,
+                                        args.use_input_embed, dev, stop_ids, slots=ctx_batch, refill_min=args.refill_min, stats_out=cstats)
+        if cstats:
+            print(f"rank {rank}: continuous {cstats}, occupancy {cstats['live_row_steps'] / max(cstats['slot_steps'], 1):.3f}")
+    else:
+        local_ids = annotate(model, tokenizer, mine, args.input_path, args.batch_size, max_new, args.temperature, args.top_p,
+                             args.num_beams, args.use_input_embed, dev, logits, stop_ids, inflight=args.inflight,
+                             logprobs_out=lps, processors=proc_kw, num_return_sequences=N,
+                             share_prompt_head=bool(getattr(args, "share_prompt_head", False)),
+                             guidance_scale=getattr(args, "guidance_scale", None))
     all_ids = odist.all_gather_ids(local_ids, tokenizer.eos_token_id)
     if lps is not None:         # [n, max_new] log-probabilities and [n] counted positions, in rank order
         loc_lp = torch.cat([x[0] for x in lps]) if lps else torch.empty((0, max_new), dtype=torch.float32, device=dev)
@@ -364,6 +426,17 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--inflight", type=int, default=2,
                    help="batches in flight per GPU (contexts sharing the weights, one host thread each): with 2, one batch's kernels "
                         "fill the other's launch gaps and ramps (+10 %% throughput at batch 64; same ids)")
+    p.add_argument("--continuous", action="store_true",
+                   help="opt-in: the rank's whole shard through one generate_continuous() call - finished decode rows are handed to "
+                        "the next prompts instead of waiting for the batch's longest answer; greedy and sampling only, not with "
+                        "--num_beams > 1, --num_return_sequences > 1, --guidance_scale, --share_prompt_head, --save_logprobs, "
+                        "--dump_logits, --allowed_terms or the logits-processor options")
+    p.add_argument("--slots", type=int, default=None, help="with --continuous: decode rows (default: --batch_size)")
+    p.add_argument("--refill_min", type=int, default=None,
+                   help="with --continuous: free rows a refill waits for (default: max(1, slots // 4))")
+    p.add_argument("--session_steps", type=int, default=None,
+                   help="with --continuous: decode steps one live batch may run, the context's max_new_tokens capacity "
+                        "(default: 4 x the token budget)")
     p.add_argument("--share_prompt_head", action="store_true",
                    help="opt-in: prefill the id run that all prompts of the shard share in front of the protein once (a detached "
                         "prefix) and generate every batch behind it; not with --num_beams > 1")

@@ -957,6 +957,102 @@ class OpusLlamaForCausalLM:
             res.n_tokens = counted_tokens(ids, eos, getattr(self, "_stop_ids", []))
         return res
 
+    # ------------------------------------------------------------------ continuous batching
+    _CONTINUOUS_UNSUPPORTED = ("guidance_scale", "negative_prompt_ids", "negative_prompt_attention_mask", "prefix", "prefix_rows",
+                               "prefix_allowed_tokens_fn", "repetition_penalty", "no_repeat_ngram_size", "bad_words_ids",
+                               "min_length", "min_new_tokens", "output_scores", "output_logits", "output_token_logprobs")
+
+    @torch.no_grad()
+    def generate_continuous(self, prompts, seqs=None, max_new_tokens: int = 32, eos_token_id=None, pad_token_id=None,
+                            slots: Optional[int] = None, refill_min: Optional[int] = None, do_sample: bool = False,
+                            temperature=None, top_p=None, top_k="default", seed=None, stop_sequence=None, seq_embedding=None,
+                            protein_tokens=None, return_dict_in_generate: bool = False, **kwargs):
+        """Answers N prompts through ONE decode batch of `slots` rows that is kept full: a row whose answer has ended (an EOS id,
+        the stop sequence, max_new_tokens ids) is handed to the next queued prompt while the other rows keep decoding, instead of
+        decoding pad ids until the batch's longest answer ends as generate() does.
+
+        prompts: N 1-D id tensors, unpadded, <seq> placeholders as in generate(); `seqs` / `seq_embedding` / `protein_tokens`
+        carry N entries (one protein per prompt).  Returns a list of N 1-D int64 tensors in input order: each prompt's new ids up
+        to and including its EOS id or the last id of the stop sequence, at most max_new_tokens - what generate() returns for that
+        row, without the pad tail.  return_dict_in_generate=True: an object with `sequences` (that list), `n_tokens` int64 [N]
+        and `stats`, a dict of sessions, decode_steps, refills, rows_refilled, live_row_steps, slot_steps (occupancy =
+        live_row_steps / slot_steps).
+
+        slots (default and at most cfg.max_batch): decode rows.  refill_min (default max(1, slots // 4)): rows that must be free
+        before a refill is worth its prefill; ignored when the queue could otherwise not progress.  The context's
+        max_new_tokens capacity S is a session's step budget: a row can only begin at a step t with t + max_new_tokens <= S, so
+        create the context with a few times the token budget (continuous.py holds the schedule).  New prompts are prefilled in
+        a helper context (new_context(), created on first use and kept) and their K / V placed under the free rows.
+
+        Greedy and sampling, EOS ids and the stop sequence.  Draws are keyed by (seed, decode row, session step), so the same
+        call twice gives the same ids, but a sampled run is NOT the generate() run of the same seed (a prompt's row and step
+        differ).  Greedy ids are generate()'s wherever the top-1 margin is decisive: a refilled row's K / V come from the same
+        prefill kernels, at other cache slots.  num_beams > 1, num_return_sequences > 1, guidance_scale, prefix=,
+        prefix_allowed_tokens_fn, the logits processors and output_scores / output_logits / output_token_logprobs raise
+        NotImplementedError; a capacity violation raises OpusError -2."""
+        from . import continuous as cont
+        for k in self._CONTINUOUS_UNSUPPORTED:
+            v = kwargs.pop(k, None)
+            if v is not None and v is not False and not (k == "repetition_penalty" and float(v) == 1.0) \
+                    and not (k in ("no_repeat_ngram_size", "min_length", "min_new_tokens") and int(v) == 0) \
+                    and not (k == "guidance_scale" and float(v) == 1.0):
+                raise NotImplementedError(f"generate_continuous({k}=...) is not built: {k} counts a row's steps from the start of "
+                                          "the decode batch, and a refilled row begins later")
+        for k in ("num_beams", "num_return_sequences"):
+            v = kwargs.pop(k, None)
+            if v is not None and int(v) > 1:
+                raise NotImplementedError(f"generate_continuous({k}={int(v)}) is not built: one decode row per prompt")
+        for k in ("use_cache", "position_ids", "attention_mask"):
+            kwargs.pop(k, None)
+        if kwargs:
+            raise TypeError(f"generate_continuous() got unexpected arguments {sorted(kwargs)}")
+        if prompts is None or len(prompts) == 0:
+            raise ValueError("generate_continuous() needs a list of prompts")
+        prompts = [torch.as_tensor(p).detach().to("cpu", torch.int64).reshape(-1) for p in prompts]
+        N = len(prompts)
+        for name, x in (("seqs", seqs), ("seq_embedding", seq_embedding), ("protein_tokens", protein_tokens)):
+            if x is not None and len(x) != N:
+                raise ValueError(f"`{name}` carries {len(x)} entries for {N} prompts")
+        cfg = self.cfg
+        max_new = int(max_new_tokens)
+        slots = cfg.max_batch if slots is None else int(slots)
+        max_len = int(getattr(getattr(self, "config", None), "tokenizer_model_max_length", None) or 0)
+        lens = [spliced_length(p[None], None, cfg.n_prot_tokens, max_len) for p in prompts]
+        bad = cont.check_capacity(lens, slots, max_new, cfg.max_new_tokens, cfg.max_prompt, cfg.max_batch)
+        if bad:
+            raise _cabi.OpusError(-2, "generate_continuous: " + bad)
+        g = self.generation_config
+        eos = g.eos_token_id if eos_token_id is None else eos_token_id
+        eos = [] if eos is None else ([int(eos)] if isinstance(eos, int) else [int(e) for e in eos])
+        pad_id = g.pad_token_id if pad_token_id is None else pad_token_id
+        pad_id = int(pad_id) if pad_id is not None else (eos[0] if eos else 0)
+        sampler = None
+        if do_sample:
+            t = 1.0 if temperature is None else float(temperature)
+            if not t > 0:
+                raise ValueError("`temperature` has to be a strictly positive float when do_sample=True")
+            k = self.default_top_k if isinstance(top_k, str) else (0 if top_k is None else int(top_k))
+            if k < 0:
+                raise ValueError("`top_k` has to be a non-negative integer (0 / None: no top-k filtering)")
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            sampler = (t, 1.0 if top_p is None else float(top_p), int(seed), k)
+        # ---- the device from here on
+        if self._lib.opus_stream_lag() != cont.LAG:
+            raise _cabi.OpusError(-101, "opus_stream_lag() differs from continuous.LAG")
+        self.set_stop_sequence(stop_sequence)
+        self._set_logits_processors(None)
+        self._set_token_constraint(None)
+        if sampler is not None:
+            self._set_top_k(sampler[3])
+        backend = _StreamBackend(self, prompts, lens, seqs, seq_embedding, protein_tokens, max_new, eos, pad_id, sampler, slots)
+        stats = cont.run_schedule(lens, slots, max_new, cfg.max_new_tokens, refill_min, backend)
+        stats.pop("placements", None)
+        out = backend.results()
+        if not return_dict_in_generate:
+            return out
+        return ContinuousOutput(sequences=out, n_tokens=torch.tensor([int(x.numel()) for x in out], dtype=torch.int64), stats=stats)
+
     def generate_from_tokens(self, d_tokens, d_lens, input_ids: torch.Tensor,
                              attention_mask: Optional[torch.Tensor], max_new_tokens: int, eos: Sequence[int] = (),
                              pad_token_id: int = 0, bucket_rows: Optional[Sequence[torch.Tensor]] = None,
@@ -1126,7 +1222,8 @@ class OpusLlamaForCausalLM:
     # ------------------------------------------------------------------ shared-prefix scoring
     @torch.no_grad()
     def cache_prefix(self, input_ids: torch.Tensor, seq=None, attention_mask: Optional[torch.Tensor] = None,
-                     seq_embedding=None, protein_tokens: Optional[torch.Tensor] = None, detach: bool = False) -> "OpusPrefix":
+                     seq_embedding=None, protein_tokens: Optional[torch.Tensor] = None, detach: bool = False,
+                     last_logits: bool = False) -> "OpusPrefix":
         """Prefills a prompt batch once and returns a handle that score_continuations() ranks continuations against.  The inputs
         are prepared exactly as generate() prepares them (inference-mode splice with `seq` / `seq_embedding` / `protein_tokens`;
         left-padded or unpadded rows): it IS a prefill, decode_logits() continues it as after prefill_logits().  The last slot of
@@ -1152,11 +1249,14 @@ class OpusLlamaForCausalLM:
         s = self._enter()
         with torch.cuda.stream(self._stream):
             last = torch.empty((B, H), dtype=torch.float32, device=self.device)
+            logits = torch.empty((B, self.cfg.dec_vocab), dtype=torch.float32, device=self.device) if last_logits else None
             epoch = C.c_int64(0)
-            _cabi.check(self._lib.opus_llama_prefix(self._ctx, embeds.data_ptr(), mask.data_ptr(), B, T, None, last.data_ptr(),
+            _cabi.check(self._lib.opus_llama_prefix(self._ctx, embeds.data_ptr(), mask.data_ptr(), B, T,
+                                                    None if logits is None else logits.data_ptr(), last.data_ptr(),
                                                     C.byref(epoch), s))
         self._leave()
         handle = OpusPrefix(self, epoch.value, last, mask.sum(dim=1).cpu(), slots=T)
+        handle.last_logits = logits          # (last_logits=True: the fp32 last-position logits [rows, V], what a refill hands on)
         return handle.detach() if detach else handle
 
     def export_cache(self, epoch: int, rows: int, slots: int):
@@ -1593,6 +1693,113 @@ class _BehindCall:
         self.snap = C.byref(self._struct)
         self.lens = (C.c_int32 * len(lens))(*[int(x) for x in lens])
         self.src = (C.c_int32 * len(src))(*[int(x) for x in src])
+
+
+def _take(x, group):
+    """Entries `group` of a per-prompt argument (None, a list or a tensor)."""
+    if x is None:
+        return None
+    if torch.is_tensor(x):
+        return x[torch.as_tensor(list(group), dtype=torch.long, device=x.device)]
+    picked = [x[p] for p in group]
+    return torch.stack(picked) if picked and torch.is_tensor(picked[0]) else picked
+
+
+class _StreamBackend:
+    """The device side of continuous.run_schedule(): sessions on the model's context (opus_stream_*), refill groups prefilled
+    in the model's helper context (cache_prefix(detach=True, last_logits=True))."""
+
+    def __init__(self, model, prompts, lens, seqs, seq_embedding, protein_tokens, max_new, eos, pad_id, sampler, slots):
+        self.m, self.prompts, self.lens = model, prompts, lens
+        self.seqs, self.seq_embedding, self.protein_tokens = seqs, seq_embedding, protein_tokens
+        self.max_new, self.eos, self.pad_id, self.sampler = max_new, eos, pad_id, sampler
+        self.dev: List[Optional[torch.Tensor]] = [None] * len(prompts)
+        cfg = model.cfg
+        with torch.cuda.stream(model._stream):
+            # one persistent id buffer [max_batch, S]: its address is part of the captured step's identity
+            if getattr(model, "_stream_ids", None) is None:
+                model._stream_ids = torch.empty((cfg.max_batch, cfg.max_new_tokens), dtype=torch.int32, device=model.device)
+        self.ids = model._stream_ids
+        self.B = 0
+
+    def _kw(self, group):
+        kw = dict(seq_embedding=_take(self.seq_embedding, group), protein_tokens=_take(self.protein_tokens, group))
+        seq = _take(self.seqs, group)
+        return seq, kw
+
+    def begin(self, prompts, T0):
+        m = self.m
+        ids, mask = _left_pack([self.prompts[p].tolist() for p in prompts])
+        seq, kw = self._kw(prompts)
+        if seq is not None or kw["seq_embedding"] is not None or kw["protein_tokens"] is not None:
+            _, _, mask, _, embeds, _ = m.prepare_inputs_labels_for_multimodal(ids, None, mask, None, None, seq if seq is not None else (),
+                                                                              kw["seq_embedding"], inference_mode=True,
+                                                                              protein_tokens=kw["protein_tokens"])
+        else:
+            dummy = torch.zeros((len(prompts), m.cfg.n_prot_tokens, m.cfg.dec_dim), dtype=_cabi.operand_dtype(), device=m.device)
+            embeds, mask, _ = m._splice(ids, mask, dummy, True)
+        if int(embeds.shape[1]) != T0:
+            raise RuntimeError(f"the splice gave {int(embeds.shape[1])} positions, the schedule planned {T0}")
+        embeds = embeds.contiguous()
+        mask = mask.to(m.device).to(torch.uint8).contiguous()
+        self.B = len(prompts)
+        t, p, sd = (self.sampler[0], self.sampler[1], self.sampler[2]) if self.sampler is not None else (0.0, 1.0, 0)
+        eos_arr = (C.c_int32 * max(1, len(self.eos)))(*self.eos)
+        s = m._enter()
+        with torch.cuda.stream(m._stream):
+            self.ids.fill_(self.pad_id)
+            _cabi.check(m._lib.opus_stream_begin(m._ctx, embeds.data_ptr(), mask.data_ptr(), self.B, T0, self.max_new, eos_arr,
+                                                 len(self.eos), self.pad_id, t, p, sd, self.ids.data_ptr(), s))
+        m._leave()
+
+    def run(self, t_min, min_free, t_max):
+        m = self.m
+        t_out, h_end = C.c_int32(0), (C.c_int32 * self.B)()
+        _cabi.check(m._lib.opus_stream_run(m._ctx, int(t_min), int(min_free), int(t_max), C.byref(t_out), h_end, m._stream.cuda_stream))
+        return t_out.value, list(h_end)
+
+    def harvest(self, prompt, row, start, end):
+        with torch.cuda.stream(self.m._stream):          # (stream-ordered in front of the refill that clears the row's tail)
+            self.dev[prompt] = self.ids[row, start:end + 1].clone()
+
+    def refill(self, assign, t, L):
+        m = self.m
+        if getattr(m, "_helper", None) is None:
+            m._helper = m.new_context()
+        group = [p for _, p in assign]
+        ids, mask = _left_pack([self.prompts[p].tolist() for p in group])
+        seq, kw = self._kw(group)
+        h = m._helper.cache_prefix(ids, seq=seq, attention_mask=mask, detach=True, last_logits=True, **kw)
+        n = len(group)
+        rows = (C.c_int32 * n)(*[r for r, _ in assign])
+        src = (C.c_int32 * n)(*range(n))
+        lens = (C.c_int32 * n)(*[self.lens[p] for p in group])
+        snap = h._snap()
+        s = m._enter()
+        for x in (h._k, h._v, h._kstart, h.last_logits):  # allocated on the helper's stream, read on this context's
+            x.record_stream(m._stream)
+        _cabi.check(m._lib.opus_stream_refill(m._ctx, C.byref(snap), n, rows, src, h.last_logits.data_ptr(), lens, s))
+        m._leave()
+
+    def finish(self):
+        m = self.m
+        h_end = (C.c_int32 * self.B)()
+        s = m._enter()
+        _cabi.check(m._lib.opus_stream_end(m._ctx, h_end, s))
+        m._leave()
+        return list(h_end)
+
+    def results(self):
+        self.m._stream.synchronize()
+        return [x.long().cpu() for x in self.dev]
+
+
+class ContinuousOutput:
+    """generate_continuous(return_dict_in_generate=True): `sequences` (N 1-D int64 tensors, input order), `n_tokens` int64 [N],
+    `stats` (sessions, decode_steps, refills, rows_refilled, live_row_steps, slot_steps)."""
+
+    def __init__(self, sequences, n_tokens, stats):
+        self.sequences, self.n_tokens, self.stats = sequences, n_tokens, stats
 
 
 class ContinuationScores:
