@@ -66,6 +66,29 @@ struct TimeRec {
     double bytes, flops;
 };
 
+// What decides which launches the head of a decode step makes (select_next) and with which scalar arguments: built once per call
+// (generate_impl) or session (opus_stream_begin), the settings of the setter entry points copied in.  What the launches read through
+// device descriptors and words (output addresses, processor values, constraint table, guidance scale, T0) is not part of it.
+struct StepPlan {
+    int rows = -1;                       // decoder rows
+    bool guided = false;                 // the rows are guided pairs: the head works on the first rows / 2 (the scale: the word d_gscale)
+    int stride = -1;                     // of the id matrix: the token budget (a session: the context's max_new_tokens)
+    int32_t *ids = nullptr;              // id buffer [head rows, stride]
+    int n_eos = -1, pad = 0;
+    float temp = 0.f, top_p = 1.f;       // temp 0: greedy
+    int top_k = 0, n_stop = 0;           // opus_set_sampling_top_k, opus_set_stop_sequence
+    int outs = 0;                        // GEN_* flags of opus_generate_scored (the addresses come from the descriptors)
+    bool lproc = false;                  // logits processors on (their values come from the descriptor d_lproc)
+    bool cons = false;                   // token constraint on (its table comes from the descriptor d_cons)
+    int budget = -1;                     // a session's token budget per row (the finish launch); -1: not a session
+};
+// "the same captured step": the key of the graph cache and of the session's slot
+static bool same_step(const StepPlan &a, const StepPlan &b) {
+    return a.rows == b.rows && a.guided == b.guided && a.stride == b.stride && a.ids == b.ids && a.n_eos == b.n_eos && a.pad == b.pad &&
+           a.temp == b.temp && a.top_p == b.top_p && a.top_k == b.top_k && a.n_stop == b.n_stop && a.outs == b.outs &&
+           a.lproc == b.lproc && a.cons == b.cons && a.budget == b.budget;
+}
+
 struct opus_ctx {
     opus_config cfg;
     int device = 0;
@@ -91,8 +114,6 @@ struct opus_ctx {
     int32_t *d_cand_i, *d_cand_n;
     uint64_t *d_seed;
     int32_t *d_chosen;
-    // sampling head (0 = greedy)
-    float samp_temp = 0.f, samp_top_p = 1.f;
     int samp_top_k = 0;                       // opus_set_sampling_top_k (0 = no TopKLogitsWarper)
     float *d_bthr = nullptr, *d_blse = nullptr;   // beam-sample: keep threshold and log-sum-exp per decoder row
     int64_t gemm_ws_bytes = 0;
@@ -111,18 +132,12 @@ struct opus_ctx {
     bool prefilled = false;
     // Graph cache for the decode iteration.  A captured step does NOT depend on the prompt length: T0 reaches its kernels through
     // the device word d_step[1] (d_step[0] = the step counter), so one instantiated graph serves every batch of a dataset whatever
-    // its T.  It does depend on the number of rows (grid sizes, kernel routing), the token budget (stride of the id matrix), the
-    // pad / EOS / sampling settings and the id buffer: a few entries are kept (a dataset's full batches + its short last batch),
-    // least recently used first out.
+    // its T.  It does depend on everything in the step's plan (the number of rows: grid sizes, kernel routing; the token budget:
+    // stride of the id matrix; the pad / EOS / sampling settings, the id buffer, the mode of the head): a few entries are kept (a
+    // dataset's full batches + its short last batch), least recently used first out.
     struct GraphEntry {
         hipGraphExec_t exec = nullptr;
-        int B = -1, maxnew = -1, pad = 0, neos = -1;
-        const int32_t *out = nullptr;
-        float temp = 0.f, top_p = 1.f;
-        int outs = 0;                    // GEN_* flags of opus_generate_scored (the addresses come from the descriptor)
-        bool lproc = false;              // logits processors on (their values come from the descriptor d_lproc)
-        bool cons = false;               // token constraint on (its table comes from the descriptor d_cons)
-        bool guided = false;             // guidance on: the head works on B / 2 rows (the scale comes from the word d_gscale)
+        StepPlan key;
         uint64_t used = 0;
     };
     static constexpr int MAX_GRAPHS = 4;
@@ -137,7 +152,6 @@ struct opus_ctx {
     GenOutDesc *d_gen = nullptr;
     GenOutDesc h_gen{};
     float *d_gpsum = nullptr, *d_gthr = nullptr;
-    int gen_outs = 0;                    // GEN_* flags of the running call (0: the plain step)
     // logits processors (opus_set_logits_processors): the host setting, uploaded in stream order by every generate call, and a
     // separate allocation made on first use - the device descriptor, the step word of opus_debug_logits_process, the output
     // descriptors split into raw (before the processors) and processed (after), the raw rows' log-sum-exp and the raw logits of the
@@ -159,11 +173,10 @@ struct opus_ctx {
     int32_t *d_cstate = nullptr, *d_cstep = nullptr;
     int32_t cons_n_start = 0, cons_max_id = -1;
     int32_t cons_start_div = 1;          // TokenConstraintDesc::start_div as the device descriptor holds it
-    // classifier-free guidance (opus_generate_scored_guided): while guid_on, rows [0, cur_B / 2) are the conditional prompts the
+    // classifier-free guidance (opus_generate_scored_guided; StepPlan::guided): rows [0, cur_B / 2) are the conditional prompts the
     // head of the step works on and rows [cur_B / 2, cur_B) their negative prompts.  guid_mem (first use): the scale word the
     // captured step reads, the part sums and the rows' maximum / log of the shifted sum / log-sum-exp [2 max_batch each]; guid_keep (first
     // guided call with token log-probs): the raw conditional rows [max_batch / 2, V] the combine overwrites in d_logits
-    bool guid_on = false;
     char *guid_mem = nullptr;
     float *d_gscale = nullptr, *d_gdpsum = nullptr, *d_gmax = nullptr, *d_glog = nullptr, *d_glse = nullptr, *guid_keep = nullptr;
     int gemm_w8 = 0;                     // 1: this context's last GEMM streamed the FP8 panels (GemmParams::ran_w8)
@@ -200,9 +213,8 @@ struct opus_ctx {
     static constexpr int STREAM_LAG = POLL_LAG + 1, STREAM_RING = POLL_RING;
     struct StreamState {
         bool on = false;
-        int B = 0, T0 = 0, t = 0, max_new = 0, n_eos = 0, pad = 0;
-        int32_t *d_ids = nullptr;
-        float temp = 0.f, top_p = 1.f;
+        int T0 = 0, t = 0;
+        StepPlan plan;                   // rows, budget, id buffer [rows, max_new_tokens] ... of the session's step
         std::vector<int32_t> start;      // host copy of start[]
     } st;
     char *stream_mem = nullptr;
@@ -210,7 +222,6 @@ struct opus_ctx {
             *d_slist = nullptr;
     int32_t *h_poll = nullptr;
     GraphEntry stream_graph;
-    int stream_graph_budget = -1;        // max_new of the captured finish launch
     int64_t stream_steps = 0, stream_refills = 0;   // opus_stat("stream_steps" / "stream_refills")
 };
 
@@ -2347,7 +2358,7 @@ extern "C" int opus_debug_attn_tree(opus_ctx *c, const void *d_qkv, const void *
     return debug_attn_prefix_run(c, "debug_attn_tree", d_qkv, d_k_hist, d_v_hist, d_kstart, P, Tp, R, 1, h_src, h_par, d_out, stream);
 }
 
-// opus_generate_scored's outputs (opus_ctx::gen_outs)
+// opus_generate_scored's outputs (StepPlan::outs)
 enum { GEN_LOGPROBS = 1, GEN_SCORES = 2, GEN_LOGITS = 4 };
 
 static int ensure_gen_mem(opus_ctx *c) {
@@ -2422,31 +2433,33 @@ static int upload_gen_desc(const GenOutDesc &h, GenOutDesc *d, hipStream_t s) {
     return OPUS_OK;
 }
 
-// next token per row: argmax (greedy) or temperature / top-p sampling, then the GenerationMixin bookkeeping.  With gen_outs set
+// next token per row: argmax (greedy) or temperature / top-p sampling, then the GenerationMixin bookkeeping.  With outputs asked for
 // (opus_generate_scored): the first pass also sums the parts' exponentials and the step kernel writes the chosen token's
 // log-probability (GEN_LOGPROBS), and / or the score writer copies the step's logits out (GEN_SCORES / GEN_LOGITS).
 //
-// Logits processors on (c->lproc_on): the processor kernel edits d_logits in place first, reading the history from d_out and the
+// Logits processors on (p.lproc): the processor kernel edits d_logits in place first, reading the history from d_out and the
 // setting from d_lproc.  The raw outputs are taken before it: the raw logits (GEN_LOGITS, through the raw half of the split output
 // descriptor) and the raw rows' log-sum-exp (GEN_LOGPROBS: one more pass over the logits); the kernel records the raw logit of every
 // history position, where the step kernel finds the chosen token's raw logit if a penalty changed it.  The selection, the scores
 // and the bookkeeping then run on the processed logits.
 //
-// Guidance on (c->guid_on): everything here works on the HB = cur_B / 2 conditional rows.  Behind the raw logits' copy and in front
-// of the processors, one log-sum-exp pass over all cur_B rows and the combine (guidance.hip) overwrite row b with the guided
+// Guidance on (p.guided): everything here works on the HB = rows / 2 conditional rows.  Behind the raw logits' copy and in front
+// of the processors, one log-sum-exp pass over all rows and the combine (guidance.hip) overwrite row b with the guided
 // scores of the pair (b, HB + b); the raw conditional log-sum-exp of that pass serves GEN_LOGPROBS, the chosen id's raw logit
 // comes from the combine's copy of the raw rows.  Behind the step kernel, row HB + b is given row b's token.
-static int argmax(opus_ctx *c, hipStream_t s, int max_new, int n_eos, int pad_id, int32_t *d_out) {
+static int select_next(opus_ctx *c, hipStream_t s, const StepPlan &p) {
+    const int max_new = p.stride, n_eos = p.n_eos, pad_id = p.pad;
+    int32_t *d_out = p.ids;
     c->phase = PH_DECODE;
     const opus_config &g = c->cfg;
     const int32_t *chosen = nullptr;
-    const bool guid = c->guid_on;
-    const int HB = guid ? c->cur_B / 2 : c->cur_B;          // rows the head works on
-    const bool proc = c->lproc_on || c->cons_on || guid;    // the logits are edited in place: raw outputs first
-    const bool lp = c->gen_outs & GEN_LOGPROBS, sc = c->gen_outs & (GEN_SCORES | GEN_LOGITS);
+    const bool guid = p.guided;
+    const int HB = guid ? p.rows / 2 : p.rows;      // rows the head works on
+    const bool proc = p.lproc || p.cons || guid;    // the logits are edited in place: raw outputs first
+    const bool lp = p.outs & GEN_LOGPROBS, sc = p.outs & (GEN_SCORES | GEN_LOGITS);
     const size_t BV = (size_t)HB * g.dec_vocab;
     if (proc) {
-        if (c->gen_outs & GEN_LOGITS)
+        if (p.outs & GEN_LOGITS)
             KL(KC_OTHER, 8.0 * BV, launch_gen_scores(c->d_logits, HB, g.dec_vocab, c->d_gen_raw, c->d_step, max_new, 0.f, 1.f,
                                                      nullptr, nullptr, s));
         if (guid) {
@@ -2459,17 +2472,17 @@ static int argmax(opus_ctx *c, hipStream_t s, int max_new, int n_eos, int pad_id
             KL(KC_OTHER, 4.0 * BV, launch_argmax_lse_partial(c->d_logits, HB, g.dec_vocab, c->d_pval, c->d_pidx, c->d_gpsum, s));
             KL(KC_OTHER, 512.0 * HB, launch_argmax_lse_final(c->d_pval, c->d_pidx, c->d_gpsum, HB, c->d_ridx, c->d_rlse, s));
         }
-        if (c->lproc_on)
+        if (p.lproc)
             KL(KC_LOGITPROC, 12.0 * HB * max_new,
                launch_logits_proc(c->d_logits, HB, g.dec_vocab, d_out, max_new, c->d_step, max_new, c->d_eos, n_eos, c->d_lproc,
                                   lp && !guid ? c->d_rawh : nullptr, s));
-        if (c->cons_on)                      // behind min_new_tokens, in front of the warpers (transformers' order)
+        if (p.cons)                          // behind min_new_tokens, in front of the warpers (transformers' order)
             KL(KC_CONSTRAINT, 4.0 * BV,
                launch_token_constraint(c->d_logits, HB, g.dec_vocab, d_out, max_new, c->d_step, max_new, c->d_cons, s));
     }
-    if (c->samp_temp > 0.f) {
+    if (p.temp > 0.f) {
         KL(KC_OTHER, 4.0 * 4 * HB * g.dec_vocab,
-           launch_sample_select(c->d_logits, HB, g.dec_vocab, c->samp_temp, c->samp_top_p, c->samp_top_k, c->d_seed, c->d_step,
+           launch_sample_select(c->d_logits, HB, g.dec_vocab, p.temp, p.top_p, p.top_k, c->d_seed, c->d_step,
                                 c->d_pval, c->d_pidx, c->d_probs, c->d_cand_i, c->d_cand_n, c->d_zpart, c->d_spart, c->d_chosen, nullptr,
                                 lp && !proc ? c->d_gpsum : nullptr, sc ? c->d_gthr : nullptr, s));
         chosen = c->d_chosen;
@@ -2479,32 +2492,64 @@ static int argmax(opus_ctx *c, hipStream_t s, int max_new, int n_eos, int pad_id
     } else {
         KL(KC_OTHER, 4.0 * HB * g.dec_vocab, launch_argmax_partial(c->d_logits, HB, g.dec_vocab, c->d_pval, c->d_pidx, s));
     }
-    if (proc ? (c->gen_outs & GEN_SCORES) != 0 : sc)
-        KL(KC_OTHER, 4.0 * HB * g.dec_vocab * (1 + ((c->gen_outs & GEN_SCORES) ? 1 : 0) + ((c->gen_outs & GEN_LOGITS) && !proc ? 1 : 0)),
-           launch_gen_scores(c->d_logits, HB, g.dec_vocab, proc ? c->d_gen_proc : c->d_gen, c->d_step, max_new, c->samp_temp,
-                             c->samp_top_p, c->d_pval, c->samp_temp > 0.f ? c->d_gthr : nullptr, s));
+    if (proc ? (p.outs & GEN_SCORES) != 0 : sc)
+        KL(KC_OTHER, 4.0 * HB * g.dec_vocab * (1 + ((p.outs & GEN_SCORES) ? 1 : 0) + ((p.outs & GEN_LOGITS) && !proc ? 1 : 0)),
+           launch_gen_scores(c->d_logits, HB, g.dec_vocab, proc ? c->d_gen_proc : c->d_gen, c->d_step, max_new, p.temp,
+                             p.top_p, c->d_pval, p.temp > 0.f ? c->d_gthr : nullptr, s));
     if (lp && proc)
         KL(KC_OTHER, 512.0 * HB + 8.0 * HB * max_new,
-           launch_argmax_rawlp_step(c->d_pval, c->d_pidx, guid ? c->d_glse : c->d_rlse, c->lproc_on && !guid ? c->d_rawh : nullptr, chosen, HB, c->d_eos, n_eos, pad_id, c->d_fin, d_out,
-                                    max_new, c->d_step, c->d_next, c->d_nunf, c->d_stop, c->n_stop, guid ? c->guid_keep : c->d_logits,
+           launch_argmax_rawlp_step(c->d_pval, c->d_pidx, guid ? c->d_glse : c->d_rlse, p.lproc && !guid ? c->d_rawh : nullptr, chosen, HB, c->d_eos, n_eos, pad_id, c->d_fin, d_out,
+                                    max_new, c->d_step, c->d_next, c->d_nunf, c->d_stop, p.n_stop, guid ? c->guid_keep : c->d_logits,
                                     g.dec_vocab, c->d_gen_proc, s));
     else if (lp)
         KL(KC_OTHER, 512.0 * HB + 8.0 * HB,
            launch_argmax_lse_step(c->d_pval, c->d_pidx, c->d_gpsum, chosen, HB, c->d_eos, n_eos, pad_id, c->d_fin, d_out, max_new,
-                                  c->d_step, c->d_next, c->d_nunf, c->d_stop, c->n_stop, c->d_logits, g.dec_vocab, c->d_gen, s));
+                                  c->d_step, c->d_next, c->d_nunf, c->d_stop, p.n_stop, c->d_logits, g.dec_vocab, c->d_gen, s));
     else
         KL(KC_OTHER, 512.0 * HB,
            launch_argmax_step(c->d_pval, c->d_pidx, chosen, HB, c->d_eos, n_eos, pad_id, c->d_fin, d_out, max_new, c->d_step,
-                              c->d_next, c->d_nunf, c->d_stop, c->n_stop, s));
+                              c->d_next, c->d_nunf, c->d_stop, p.n_stop, s));
     if (guid) KL(KC_GUIDANCE, 8.0 * HB, launch_guidance_pair_next(c->d_next, HB, s));
     return OPUS_OK;
 }
 
 // iteration body of the greedy loop: pick the next token from the current logits, then decode it.
-static int greedy_body(opus_ctx *c, hipStream_t s, int max_new, int n_eos, int pad_id, int32_t *d_out) {
-    const opus_config &g = c->cfg;
-    OPC(argmax(c, s, max_new, n_eos, pad_id, d_out));
+static int greedy_body(opus_ctx *c, hipStream_t s, const StepPlan &p) {
+    OPC(select_next(c, s, p));
     return decode_step(c, s, c->d_next);
+}
+
+// One step (greedy_body / stream_body) captured on s and instantiated into *exec.  The body's error wins over the capture's, a
+// half-made graph is destroyed, and only an exec that exists is counted.
+static int capture_step(opus_ctx *c, hipStream_t s, int (*body)(opus_ctx *, hipStream_t, const StepPlan &), const StepPlan &p,
+                        hipGraphExec_t *exec) {
+    hipGraph_t graph = nullptr;
+    HIPC(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    int rc = body(c, s, p);
+    hipError_t ee = hipStreamEndCapture(s, &graph);
+    if (rc != OPUS_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+    if (ee != hipSuccess) return fail(OPUS_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(ee));
+    ee = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    if (ee != hipSuccess) { *exec = nullptr; return fail(OPUS_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(ee)); }
+    ++c->graph_instantiations;
+    return OPUS_OK;
+}
+
+// What opus_generate_* and opus_stream_begin do alike in front of their prefill, under the caller's name: the checks of the
+// sampling settings, the token budget and the EOS list, the uploads of the EOS ids and the seed, the clears of the rows' finished
+// flags and of the steps' unfinished counts.  (seed: the caller's own word, the source of an asynchronous copy.)
+static int begin_generation(opus_ctx *c, const char *who, float temperature, float top_p, int32_t max_new, const int32_t *eos_ids,
+                            int32_t n_eos, const uint64_t *seed, int rows, int steps, hipStream_t s) {
+    if (temperature < 0.f || top_p <= 0.f || top_p > 1.f) return fail(OPUS_EBADARG, "%s: temperature >= 0 and 0 < top_p <= 1", who);
+    if (max_new < 1 || max_new > c->cfg.max_new_tokens)
+        return fail(OPUS_ESHAPE, "%s: max_new=%d exceeds max_new_tokens=%d", who, max_new, c->cfg.max_new_tokens);
+    if (n_eos < 0 || n_eos > 64 || (n_eos > 0 && !eos_ids)) return fail(OPUS_EBADARG, "%s: eos list", who);
+    if (n_eos) HIPC(hipMemcpyAsync(c->d_eos, eos_ids, n_eos * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(c->d_seed, seed, sizeof(*seed), hipMemcpyHostToDevice, s));
+    HIPC(hipMemsetAsync(c->d_fin, 0, rows * sizeof(int32_t), s));
+    HIPC(hipMemsetAsync(c->d_nunf, 0, (size_t)steps * sizeof(int32_t), s));
+    return OPUS_OK;
 }
 
 // TokenConstraintDesc::start_div of the device descriptor (uploaded only when it changes: the plain call launches nothing here)
@@ -2523,36 +2568,30 @@ static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mas
     // guidance (opus_generate_scored_guided; nret 1, no behind): B = 2 P rows, the head of every step works on the first P
     // behind (opus_generate_scored_behind): the B rows are suffixes of T right-padded positions behind a detached prefix (no mask)
     OPC(need_ready(c));
-    if (temperature < 0.f || top_p <= 0.f || top_p > 1.f) return fail(OPUS_EBADARG, "generate: temperature >= 0 and 0 < top_p <= 1");
-    c->samp_temp = temperature;
-    c->samp_top_p = top_p;
     if (!behind) OPC(check_prefill_args(c, d_embeds, d_mask, B, T));
     else if (B < 1 || B > c->cfg.max_batch) return fail(OPUS_ESHAPE, "generate: B=%d decoder rows, the context holds max_batch=%d", B, c->cfg.max_batch);
     OPC(check_fanout(c, B, nret, "generate"));
     const int32_t BN = B * nret;             // decoder rows: the loop, its buffers and the captured step are those of a BN-row batch
     if (!d_out_ids || !n_out) return fail(OPUS_EBADARG, "generate_greedy: null pointer");
-    if (max_new < 1 || max_new > c->cfg.max_new_tokens)
-        return fail(OPUS_ESHAPE, "generate_greedy: max_new=%d exceeds max_new_tokens=%d", max_new, c->cfg.max_new_tokens);
-    if (n_eos < 0 || n_eos > 64 || (n_eos > 0 && !eos_ids)) return fail(OPUS_EBADARG, "generate_greedy: eos list");
     hipStream_t s = (hipStream_t)stream;
     const opus_config &g = c->cfg;
-    if (n_eos) HIPC(hipMemcpyAsync(c->d_eos, eos_ids, n_eos * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPC(hipMemcpyAsync(c->d_seed, &seed, sizeof(seed), hipMemcpyHostToDevice, s));
-    int gen_outs = 0;
-    if (outs) {
-        gen_outs = (outs->token_lp ? GEN_LOGPROBS : 0) | (outs->scores ? GEN_SCORES : 0) | (outs->logits ? GEN_LOGITS : 0);
-        if (gen_outs) {
-            OPC(ensure_gen_mem(c));
-            c->h_gen = *outs;                // (a member: the source outlives the asynchronous copy)
-            HIPC(hipMemcpyAsync(c->d_gen, &c->h_gen, sizeof(GenOutDesc), hipMemcpyHostToDevice, s));
-        }
+    OPC(begin_generation(c, "generate_greedy", temperature, top_p, max_new, eos_ids, n_eos, &seed, BN, max_new, s));
+    StepPlan plan;
+    plan.rows = BN; plan.guided = guidance != nullptr; plan.stride = max_new; plan.ids = d_out_ids; plan.n_eos = n_eos; plan.pad = pad_id;
+    plan.temp = temperature; plan.top_p = top_p; plan.top_k = c->samp_top_k; plan.n_stop = c->n_stop;
+    plan.lproc = c->lproc_on; plan.cons = c->cons_on;
+    if (outs) plan.outs = (outs->token_lp ? GEN_LOGPROBS : 0) | (outs->scores ? GEN_SCORES : 0) | (outs->logits ? GEN_LOGITS : 0);
+    if (plan.outs) {
+        OPC(ensure_gen_mem(c));
+        c->h_gen = *outs;                    // (a member: the source outlives the asynchronous copy)
+        HIPC(hipMemcpyAsync(c->d_gen, &c->h_gen, sizeof(GenOutDesc), hipMemcpyHostToDevice, s));
     }
     const int32_t HB = guidance ? B / 2 : B;                // rows (before the fan-out) with a state of their own
     if (c->cons_on && c->cons_n_start != 1 && c->cons_n_start != HB)
         return fail(OPUS_ESHAPE, "generate: the token constraint has %d per-row start states, the batch %d rows", c->cons_n_start, HB);
     if (c->cons_on) OPC(set_cons_start_div(c, nret, s));    // one start state per prompt: decoder row r starts at start[r / nret]
     if (guidance) {
-        OPC(ensure_guid_mem(c, gen_outs & GEN_LOGPROBS));
+        OPC(ensure_guid_mem(c, plan.outs & GEN_LOGPROBS));
         OPC(upload_guidance_scale(c, *guidance, s));
     }
     if (c->lproc_on || c->cons_on || guidance) {
@@ -2560,58 +2599,37 @@ static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mas
             return fail(OPUS_ESHAPE, "generate: logits processors keep a history of at most %d ids (max_new=%d)", LP_MAX_HIST, max_new);
         OPC(ensure_lproc_mem(c));
         if (c->lproc_on) OPC(upload_lproc(c, c->h_lproc, s));
-        if (gen_outs) {                      // raw logits before the processors, the rest after them
+        if (plan.outs) {                     // raw logits before the processors, the rest after them
             OPC(upload_gen_desc(GenOutDesc{nullptr, nullptr, outs->logits, nullptr}, c->d_gen_raw, s));
             OPC(upload_gen_desc(GenOutDesc{outs->token_lp, outs->scores, nullptr, nullptr}, c->d_gen_proc, s));
         }
     }
-    HIPC(hipMemsetAsync(c->d_fin, 0, BN * sizeof(int32_t), s));
-    HIPC(hipMemsetAsync(c->d_nunf, 0, (size_t)max_new * sizeof(int32_t), s));
     if (behind) OPC(prefill_behind(c, s, *behind, (const half_t *)d_embeds, B, T));
     else OPC(prefill(c, s, (const half_t *)d_embeds, d_mask, B, T, false, nullptr, nret));
-    c->gen_outs = gen_outs;             // (the prefill's own launches are the same either way)
-    c->guid_on = guidance != nullptr;
-    struct GenOutsReset { opus_ctx *c; ~GenOutsReset() { c->gen_outs = 0; c->guid_on = false; } } gen_outs_reset{c};
 
     // OPUS_NO_GRAPH=1: eager launches (rocprofv3 --pmc cannot collect counters through graph replays)
     const bool use_graph = s != nullptr && !c->timing && !getenv("OPUS_NO_GRAPH");
-    auto find_graph = [&]() -> opus_ctx::GraphEntry * {
+    opus_ctx::GraphEntry *ge = nullptr;
+    if (use_graph)
         for (auto &e : c->graphs)
-            if (e.exec && e.B == BN && e.maxnew == max_new && e.pad == pad_id && e.neos == n_eos && e.out == d_out_ids &&
-                e.temp == temperature && e.top_p == top_p && e.outs == gen_outs && e.lproc == c->lproc_on && e.cons == c->cons_on && e.guided == c->guid_on) return &e;
-        return nullptr;
-    };
-    opus_ctx::GraphEntry *ge = use_graph ? find_graph() : nullptr;
+            if (e.exec && same_step(e.key, plan)) { ge = &e; break; }
     const bool same_graph = ge != nullptr;
     std::vector<int32_t> nunf(max_new, 1);
     int produced = 0;
     for (int i = 0; i < max_new; ++i) {
         if (i + 1 == max_new) {   // last token: no decode behind it
-            OPC(argmax(c, s, max_new, n_eos, pad_id, d_out_ids));
+            OPC(select_next(c, s, plan));
             produced = i + 1;
             break;
         }
         ++c->decode_steps;
         if (!use_graph || (i == 0 && !same_graph)) {
-            OPC(greedy_body(c, s, max_new, n_eos, pad_id, d_out_ids));   // eager (also warms lazily-set attributes)
+            OPC(greedy_body(c, s, plan));    // eager (also warms lazily-set attributes)
         } else {
             if (!ge) {
-                hipGraph_t graph = nullptr;
-                HIPC(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-                int rc = greedy_body(c, s, max_new, n_eos, pad_id, d_out_ids);
-                hipError_t ee = hipStreamEndCapture(s, &graph);
-                if (rc != OPUS_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-                if (ee != hipSuccess) return fail(OPUS_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(ee));
                 opus_ctx::GraphEntry e;
-                ee = hipGraphInstantiate(&e.exec, graph, nullptr, nullptr, 0);
-                (void)hipGraphDestroy(graph);
-                if (ee != hipSuccess) return fail(OPUS_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(ee));
-                ++c->graph_instantiations;
-                e.B = BN; e.maxnew = max_new; e.pad = pad_id; e.neos = n_eos; e.temp = temperature; e.top_p = top_p; e.out = d_out_ids;
-                e.outs = gen_outs;
-                e.lproc = c->lproc_on;
-                e.cons = c->cons_on;
-                e.guided = c->guid_on;
+                OPC(capture_step(c, s, greedy_body, plan, &e.exec));
+                e.key = plan;
                 if ((int)c->graphs.size() >= opus_ctx::MAX_GRAPHS) {           // least recently used out
                     size_t v = 0;
                     for (size_t k = 1; k < c->graphs.size(); ++k) if (c->graphs[k].used < c->graphs[v].used) v = k;
@@ -2631,7 +2649,7 @@ static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mas
         // i + 1 is enqueued the host waits for step i - 2's event (the GPU still has a step queued: no bubble) and stops when that
         // count is zero - at most 2 steps are decoded past the last row's EOS (rounds 1-4: a stream synchronisation every 8 steps,
         // up to 7 wasted steps).  Finished rows emit pad, so the ids are identical and n_out is computed exactly below.
-        if (n_eos > 0 || c->n_stop > 0) {
+        if (n_eos > 0 || plan.n_stop > 0) {
             HIPC(hipMemcpyAsync(c->h_nunf + i, c->d_nunf + i, sizeof(int32_t), hipMemcpyDeviceToHost, s));
             HIPC(hipEventRecord(c->poll_ev[i % opus_ctx::POLL_RING], s));
             if (i >= opus_ctx::POLL_LAG) {
@@ -2686,10 +2704,9 @@ static int ensure_stream_mem(opus_ctx *c) {
 }
 
 // one step of a session: the head of generate's step, the rows' budgets and end steps, the decode of the chosen tokens
-static int stream_body(opus_ctx *c, hipStream_t s) {
-    const opus_ctx::StreamState &st = c->st;
-    OPC(argmax(c, s, c->cfg.max_new_tokens, st.n_eos, st.pad, st.d_ids));
-    KL(KC_OTHER, 16.0 * st.B, launch_stream_finish(c->d_step, c->d_sstart, c->d_fin, c->d_spoll, st.B, st.max_new, s));
+static int stream_body(opus_ctx *c, hipStream_t s, const StepPlan &p) {
+    OPC(select_next(c, s, p));
+    KL(KC_OTHER, 16.0 * p.rows, launch_stream_finish(c->d_step, c->d_sstart, c->d_fin, c->d_spoll, p.rows, p.budget, s));
     return decode_step(c, s, c->d_next);
 }
 
@@ -2699,32 +2716,24 @@ extern "C" int opus_stream_begin(opus_ctx *c, const void *d_embeds, const uint8_
                                  const int32_t *eos_ids, int32_t n_eos, int32_t pad_id, float temperature, float top_p, uint64_t seed,
                                  int32_t *d_ids, void *stream) {
     OPC(need_ready(c));
-    if (temperature < 0.f || top_p <= 0.f || top_p > 1.f) return fail(OPUS_EBADARG, "stream_begin: temperature >= 0 and 0 < top_p <= 1");
     OPC(check_prefill_args(c, d_embeds, d_mask, B, T));
     if (!d_ids) return fail(OPUS_EBADARG, "stream_begin: null pointer");
     const opus_config &g = c->cfg;
-    if (max_new < 1 || max_new > g.max_new_tokens)
-        return fail(OPUS_ESHAPE, "stream_begin: max_new=%d exceeds the session's step budget max_new_tokens=%d", max_new, g.max_new_tokens);
-    if (n_eos < 0 || n_eos > 64 || (n_eos > 0 && !eos_ids)) return fail(OPUS_EBADARG, "stream_begin: eos list");
     if (c->lproc_on || c->cons_on)
         return fail(OPUS_EUNSUPPORTED, "stream_begin: logits processors and token constraints count steps from 0 for every row: not "
                                        "built for rows that begin at a later step");
     OPC(ensure_stream_mem(c));
     hipStream_t s = (hipStream_t)stream;
-    c->samp_temp = temperature;
-    c->samp_top_p = top_p;
-    if (n_eos) HIPC(hipMemcpyAsync(c->d_eos, eos_ids, n_eos * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPC(hipMemcpyAsync(c->d_seed, &seed, sizeof(seed), hipMemcpyHostToDevice, s));
-    HIPC(hipMemsetAsync(c->d_fin, 0, B * sizeof(int32_t), s));
-    HIPC(hipMemsetAsync(c->d_nunf, 0, (size_t)g.max_new_tokens * sizeof(int32_t), s));
+    OPC(begin_generation(c, "stream_begin", temperature, top_p, max_new, eos_ids, n_eos, &seed, B, g.max_new_tokens, s));
     OPC(prefill(c, s, (const half_t *)d_embeds, d_mask, B, T));
     c->phase = PH_DECODE;
     KL(KC_OTHER, 8.0 * B, launch_stream_reset(c->d_sstart, c->d_spoll, B, s));
-    c->gen_outs = 0;
-    c->guid_on = false;
     opus_ctx::StreamState &st = c->st;
-    st.B = B; st.T0 = T; st.t = 0; st.max_new = max_new; st.n_eos = n_eos; st.pad = pad_id; st.d_ids = d_ids;
-    st.temp = temperature; st.top_p = top_p;
+    st.T0 = T; st.t = 0;
+    st.plan = StepPlan();
+    st.plan.rows = B; st.plan.stride = g.max_new_tokens; st.plan.ids = d_ids; st.plan.n_eos = n_eos; st.plan.pad = pad_id;
+    st.plan.temp = temperature; st.plan.top_p = top_p; st.plan.top_k = c->samp_top_k; st.plan.n_stop = c->n_stop;
+    st.plan.budget = max_new;
     st.start.assign(B, 0);
     st.on = true;
     return OPUS_OK;
@@ -2737,14 +2746,13 @@ extern "C" int opus_stream_run(opus_ctx *c, int32_t t_min, int32_t min_free, int
     opus_ctx::StreamState &st = c->st;
     if (!st.on) return fail(OPUS_ESTATE, "stream_run: no session is open (opus_stream_begin; a prefill on this context ends one)");
     hipStream_t s = (hipStream_t)stream;
-    const int B = st.B, S = c->cfg.max_new_tokens;
+    const int B = st.plan.rows, S = c->cfg.max_new_tokens;
     constexpr int LAG = opus_ctx::STREAM_LAG, RING = opus_ctx::STREAM_RING;
     if (t_max > S) t_max = S;
     if (min_free < 1) min_free = 1;
     const bool use_graph = s != nullptr && !c->timing && !getenv("OPUS_NO_GRAPH");
     opus_ctx::GraphEntry &ge = c->stream_graph;
-    if (ge.exec && !(ge.B == B && ge.maxnew == S && ge.pad == st.pad && ge.neos == st.n_eos && ge.out == st.d_ids && ge.temp == st.temp &&
-                     ge.top_p == st.top_p && c->stream_graph_budget == st.max_new)) {
+    if (ge.exec && !same_step(ge.key, st.plan)) {
         (void)hipGraphExecDestroy(ge.exec);
         ge = opus_ctx::GraphEntry();
     }
@@ -2766,21 +2774,11 @@ extern "C" int opus_stream_run(opus_ctx *c, int32_t t_min, int32_t min_free, int
             return OPUS_OK;
         }
         if (!use_graph || (!ge.exec && t == 0)) {
-            OPC(stream_body(c, s));                                 // eager (the first step also warms lazily-set attributes)
+            OPC(stream_body(c, s, st.plan));                        // eager (the first step also warms lazily-set attributes)
         } else {
             if (!ge.exec) {
-                hipGraph_t graph = nullptr;
-                HIPC(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-                int rc = stream_body(c, s);
-                hipError_t ee = hipStreamEndCapture(s, &graph);
-                if (rc != OPUS_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-                if (ee != hipSuccess) return fail(OPUS_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(ee));
-                ee = hipGraphInstantiate(&ge.exec, graph, nullptr, nullptr, 0);
-                (void)hipGraphDestroy(graph);
-                if (ee != hipSuccess) { ge.exec = nullptr; return fail(OPUS_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(ee)); }
-                ++c->graph_instantiations;
-                ge.B = B; ge.maxnew = S; ge.pad = st.pad; ge.neos = st.n_eos; ge.temp = st.temp; ge.top_p = st.top_p; ge.out = st.d_ids;
-                c->stream_graph_budget = st.max_new;
+                OPC(capture_step(c, s, stream_body, st.plan, &ge.exec));
+                ge.key = st.plan;
             }
             ++c->graph_replays;
             HIPC(hipGraphLaunch(ge.exec, s));
@@ -2801,13 +2799,13 @@ extern "C" int opus_stream_refill(opus_ctx *c, const opus_prefix_snap *snap, int
     if (!st.on) return fail(OPUS_ESTATE, "stream_refill: no session is open");
     if (!h_rows || !h_src || !d_last_logits || !h_len) return fail(OPUS_EBADARG, "stream_refill: null pointer");
     const opus_config &g = c->cfg;
-    const int B = st.B, MB = g.max_batch, S = g.max_new_tokens, t = st.t, L = st.T0 + t;
+    const int B = st.plan.rows, MB = g.max_batch, S = g.max_new_tokens, t = st.t, L = st.T0 + t;
     PrefixSrc ps;
     OPC(resolve_prefix(c, "stream_refill", snap, 0, 0, ps));
     if (n < 1 || n > B) return fail(OPUS_ESHAPE, "stream_refill: %d rows listed, the session has %d", n, B);
-    if (t + st.max_new > S)
+    if (t + st.plan.budget > S)
         return fail(OPUS_ESHAPE, "stream_refill: a row that begins at step %d cannot end inside the session's %d steps (budget %d)", t, S,
-                    st.max_new);
+                    st.plan.budget);
     if (d_last_logits == c->d_logits) return fail(OPUS_EBADARG, "stream_refill: the logits rows must come from another buffer");
     std::vector<int32_t> w(5 * (size_t)MB + 2, 0), seen(B, 0);
     int32_t *nks = w.data(), *rows = nks + MB, *src = rows + MB, *off = src + MB, *list = off + MB + 2;
@@ -2847,7 +2845,7 @@ extern "C" int opus_stream_refill(opus_ctx *c, const opus_prefix_snap *snap, int
     KL(KC_OTHER, 2.0 * slots * 2.0 * g.dec_layers * g.dec_kv_heads * g.dec_head_dim * sizeof(half_t), launch_kv_place(kp, s));
     KL(KC_OTHER, 8.0 * n * g.dec_vocab,
        launch_stream_refill(c->d_srows, c->d_ssrc, c->d_snks, n, d_last_logits, c->d_logits, g.dec_vocab, c->d_kstart, c->d_sstart,
-                            c->d_fin, c->d_spoll, st.d_ids, S, t, s));
+                            c->d_fin, c->d_spoll, st.plan.ids, S, t, s));
     for (int i = 0; i < n; ++i) st.start[h_rows[i]] = t;
     ++c->stream_refills;
     return OPUS_OK;
@@ -2860,7 +2858,7 @@ extern "C" int opus_stream_end(opus_ctx *c, int32_t *h_end, void *stream) {
     c->st.on = false;
     hipStream_t s = (hipStream_t)stream;
     // the rows' end steps with every enqueued step complete (no lag: nothing is decided from them but what to harvest)
-    if (h_end) HIPC(hipMemcpyAsync(h_end, c->d_spoll, (size_t)c->st.B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (h_end) HIPC(hipMemcpyAsync(h_end, c->d_spoll, (size_t)c->st.plan.rows * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     return handoff_check(c, s);                                     // (synchronises the stream)
 }
 
@@ -2872,7 +2870,7 @@ extern "C" int opus_debug_stream_state(opus_ctx *c, int32_t *h_kstart, int32_t *
     HIPC(hipSetDevice(c->device));
     if (!c->st.on) return fail(OPUS_ESTATE, "debug_stream_state: no session is open");
     hipStream_t s = (hipStream_t)stream;
-    const size_t B = c->st.B, cache = (size_t)c->cache_sl * c->cfg.dec_layers * sizeof(half_t);
+    const size_t B = c->st.plan.rows, cache = (size_t)c->cache_sl * c->cfg.dec_layers * sizeof(half_t);
     if (poison) {
         HIPC(hipMemsetAsync(c->kc, poison & 255, cache, s));
         HIPC(hipMemsetAsync(c->vc, poison & 255, cache, s));
@@ -3117,7 +3115,7 @@ extern "C" int opus_generate_scored_fanout(opus_ctx *c, const void *d_embeds, co
 
 /* opus_generate_scored with classifier-free guidance on paired rows: d_embeds [2 P, T, D] / d_mask [2 P, T] hold the P conditional
    prompts, then their P negative prompts (left-padded to one length); one 2 P-row prefill, then the loop of a 2 P-row batch whose head
-   works on the first P rows (argmax()).  ids and outputs are P-row shaped.  The scale travels in a device word: only "guided"
+   works on the first P rows (select_next()).  ids and outputs are P-row shaped.  The scale travels in a device word: only "guided"
    enters the captured step's identity. */
 extern "C" int opus_generate_scored_guided(opus_ctx *c, const void *d_embeds, const uint8_t *d_mask, int32_t P, int32_t T,
                                            float guidance_scale, int32_t max_new, const int32_t *eos_ids, int32_t n_eos, int32_t pad_id,

@@ -868,7 +868,7 @@ class OpusLlamaForCausalLM:
                 guidance: Optional[float] = None):
         """outputs = (token_logprobs, scores, logits) flags: a GenerateDecoderOnlyOutput instead of the ids.
         nret > 1: the B prompts are prefilled once and decoded as B nret rows (opus_generate_scored_fanout); every result has
-        B nret rows.  nret == 1 takes the entries it always took.
+        B nret rows.
         behind (a _BehindCall; mask unused, nret 1): embeds are right-padded suffix rows behind a detached prefix
         (opus_generate_scored_behind).
         guidance (nret 1, no behind): embeds / mask hold P conditional rows, then their P negative rows
@@ -893,6 +893,7 @@ class OpusLlamaForCausalLM:
             eos_arr = (C.c_int32 * max(1, len(eos)))(*eos)
             if sampler is not None:
                 self._set_top_k(sampler[3] if len(sampler) > 3 else self.default_top_k)
+            lp = sc = lg = None
             if outputs is not None:
                 want_lp, want_sc, want_lg = outputs
                 # fresh caller-owned tensors every call: their addresses reach the captured step through a device descriptor
@@ -902,45 +903,19 @@ class OpusLlamaForCausalLM:
                 if (sampler is None and sc is not None and lg is not None and getattr(self, "_lproc", None) is None
                         and getattr(self, "_constraint", None) is None and guidance is None):
                     lg = None                                   # greedy: the processed scores are the logits - one tensor
-                t, p, sd = (sampler[0], sampler[1], sampler[2]) if sampler is not None else (0.0, 1.0, 0)
-                ptr = lambda x: None if x is None else x.data_ptr()                          # noqa: E731
-                if guidance is not None:
-                    _cabi.check(self._lib.opus_generate_scored_guided(self._ctx, embeds.data_ptr(), mask.data_ptr(), P, T, guidance,
-                                                                      max_new, eos_arr, len(eos), pad_id, t, p, sd, out.data_ptr(),
-                                                                      C.byref(n_out), ptr(lp), ptr(sc), ptr(lg), s))
-                elif behind is not None:
-                    _cabi.check(self._lib.opus_generate_scored_behind(self._ctx, behind.snap, embeds.data_ptr(), B, T, behind.lens,
-                                                                      behind.src, max_new, eos_arr, len(eos), pad_id, t, p, sd,
-                                                                      out.data_ptr(), C.byref(n_out), ptr(lp), ptr(sc), ptr(lg), s))
-                elif nret > 1:
-                    _cabi.check(self._lib.opus_generate_scored_fanout(self._ctx, embeds.data_ptr(), mask.data_ptr(), P, T, nret, max_new,
-                                                                      eos_arr, len(eos), pad_id, t, p, sd, out.data_ptr(),
-                                                                      C.byref(n_out), ptr(lp), ptr(sc), ptr(lg), s))
-                else:
-                    _cabi.check(self._lib.opus_generate_scored(self._ctx, embeds.data_ptr(), mask.data_ptr(), B, T, max_new,
-                                                               eos_arr, len(eos), pad_id, t, p, sd, out.data_ptr(), C.byref(n_out),
-                                                               ptr(lp), ptr(sc), ptr(lg), s))
-            elif guidance is not None:
-                t, p, sd = (sampler[0], sampler[1], sampler[2]) if sampler is not None else (0.0, 1.0, 0)
-                _cabi.check(self._lib.opus_generate_scored_guided(self._ctx, embeds.data_ptr(), mask.data_ptr(), P, T, guidance, max_new,
-                                                                  eos_arr, len(eos), pad_id, t, p, sd, out.data_ptr(), C.byref(n_out),
-                                                                  None, None, None, s))
+            # one entry per prefill; with no output pointers each is the plain call (the same launches and graph)
+            if guidance is not None:
+                entry, head = self._lib.opus_generate_scored_guided, (embeds.data_ptr(), mask.data_ptr(), P, T, guidance)
             elif behind is not None:
-                t, p, sd = (sampler[0], sampler[1], sampler[2]) if sampler is not None else (0.0, 1.0, 0)
-                _cabi.check(self._lib.opus_generate_scored_behind(self._ctx, behind.snap, embeds.data_ptr(), B, T, behind.lens, behind.src,
-                                                                  max_new, eos_arr, len(eos), pad_id, t, p, sd, out.data_ptr(),
-                                                                  C.byref(n_out), None, None, None, s))
+                entry, head = self._lib.opus_generate_scored_behind, (behind.snap, embeds.data_ptr(), B, T, behind.lens, behind.src)
             elif nret > 1:                               # (sampling: greedy search takes no num_return_sequences)
-                _cabi.check(self._lib.opus_generate_scored_fanout(self._ctx, embeds.data_ptr(), mask.data_ptr(), P, T, nret, max_new,
-                                                                  eos_arr, len(eos), pad_id, sampler[0], sampler[1], sampler[2],
-                                                                  out.data_ptr(), C.byref(n_out), None, None, None, s))
-            elif sampler is None:
-                _cabi.check(self._lib.opus_generate_greedy(self._ctx, embeds.data_ptr(), mask.data_ptr(), B, T, max_new,
-                                                           eos_arr, len(eos), pad_id, out.data_ptr(), C.byref(n_out), s))
+                entry, head = self._lib.opus_generate_scored_fanout, (embeds.data_ptr(), mask.data_ptr(), P, T, nret)
             else:
-                _cabi.check(self._lib.opus_generate_sample(self._ctx, embeds.data_ptr(), mask.data_ptr(), B, T, max_new,
-                                                           eos_arr, len(eos), pad_id, sampler[0], sampler[1], sampler[2],
-                                                           out.data_ptr(), C.byref(n_out), s))
+                entry, head = self._lib.opus_generate_scored, (embeds.data_ptr(), mask.data_ptr(), B, T)
+            t, p, sd = (sampler[0], sampler[1], sampler[2]) if sampler is not None else (0.0, 1.0, 0)
+            ptr = lambda x: None if x is None else x.data_ptr()                              # noqa: E731
+            _cabi.check(entry(self._ctx, *head, max_new, eos_arr, len(eos), pad_id, t, p, sd, out.data_ptr(), C.byref(n_out),
+                              ptr(lp), ptr(sc), ptr(lg), s))
         self._leave()
         n = n_out.value
         ids = out[:, :n].long()                          # (a copy: the id buffer is reused by the next call)

@@ -20,7 +20,11 @@ decoder 4096 / 32 / 8 / 128, FFN 14336, vocabulary 32768) on 64 proteins of 100-
 misc7 at 0 and 1, at batch 1, 4, 5, 16, 17 and 64 (skinny; stream with one panel; stream with k-parts; QKV slabs summed by the
 attention; tiled hand-offs), at batch 64 with no_stream = 1, forward(labels=...) on 2 rows, score_continuations() with 2 prefix
 rows x 3 continuations of 4 tokens, generate(num_return_sequences=3) at batch 2; and a two-layer decoder of the Vicuna-13B width
-(hidden 5120: the 5-panel stream plan) at batch 48, prefill + 1 decode step.
+(hidden 5120: the 5-panel stream plan) at batch 48, prefill + 1 decode step; and (--only heads) every mode of the head of the
+decode step on the micro model at 3 rows and 6 new tokens: greedy and sampling (top-p, top-k), each with all per-step outputs, the
+logits processors with and without outputs, a TokenTrie and a per-row one, guidance with and without token log-probs,
+num_return_sequences=3, prefix=, a stop sequence, an EOS id, and generate_continuous() with a refill (plus its step and refill
+counters).  The plain run of a case replays the captured step, the timing-mode run launches eagerly: both paths are covered.
 """
 from __future__ import annotations
 
@@ -37,7 +41,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lib", type=str, default=None, help="libopus_pllm.so to load instead of this tree's (OPUS_LIB_PATH)")
     ap.add_argument("--out", type=str, default=None, help="also write the lines to this file")
-    ap.add_argument("--only", choices=["all", "micro", "full", "wide"], default="all")
+    ap.add_argument("--only", choices=["all", "micro", "full", "wide", "heads"], default="all")
     args = ap.parse_args()
     if args.lib:
         os.environ["OPUS_LIB_PATH"] = os.path.abspath(args.lib)
@@ -60,8 +64,9 @@ def main():
     def knob(model, name, value):
         _cabi.check(_cabi.lib().opus_debug_knob(model._ctx, name.encode(), int(value)))
 
-    def census(name, model, case):
-        """case() -> {output name: tensor}; run plainly for the hashes, once more in timing mode for the launch counts"""
+    def census(name, model, case, stats=()):
+        """case() -> {output name: tensor}; run plainly for the hashes, once more in timing mode for the launch counts;
+        stats: opus_stat counters read behind both runs"""
         hashes = {k: sha(v) for k, v in case().items()}
         torch.cuda.synchronize(dev)
         model.timing(True)
@@ -75,7 +80,8 @@ def main():
                 if n:
                     launches[f"{k}/{p}"] = int(n)
         model.timing(False)
-        line = json.dumps(dict(config=name, sha256=hashes, launches=launches), sort_keys=True)
+        extra = dict(stats={k: model.stat(k) for k in stats}) if stats else {}
+        line = json.dumps(dict(config=name, sha256=hashes, launches=launches, **extra), sort_keys=True)
         print(line, flush=True)
         lines.append(line)
 
@@ -171,6 +177,69 @@ def main():
         ids = torch.tensor([synth.synth_prompt_ids(cfg.dec_vocab, i, n_text=41, seq_pos=5) for i in range(48)])
         census("vicuna_13b-width decoder B=48 prefill+decode", model,
                path(model, seqs, ids, torch.ones_like(ids, dtype=torch.bool), 0, steps=1, new_tokens=0))
+        del model
+        torch.cuda.empty_cache()
+
+    if args.only in ("all", "heads"):
+        cfg = opa.micro(max_batch=12, max_new_tokens=24)       # (9 rows for num_return_sequences, a session of 4 budgets)
+        model = make(cfg)
+        seqs = [synth.synth_protein(n, i) for i, n in enumerate((40, 21, 33))]
+        ids, mask = prompts(cfg, ((14, 5), (9, 2), (11, 7)), 2)
+        base = dict(attention_mask=mask, pad_token_id=2, eos_token_id=[], max_new_tokens=6)
+        samp = dict(do_sample=True, temperature=0.8, seed=5)
+        outs = dict(return_dict_in_generate=True, output_scores=True, output_logits=True, output_token_logprobs=True)
+
+        def gen(inputs=ids, proteins=seqs, **kw):
+            def case():
+                r = model.generate(inputs, proteins, **{**base, **kw})
+                if torch.is_tensor(r):
+                    return dict(generate_ids=r)
+                out = dict(generate_ids=r.sequences)
+                for k in ("scores", "logits"):
+                    if getattr(r, k, None) is not None:
+                        out[k] = torch.stack(list(getattr(r, k)))
+                for k in ("token_logprobs", "logprob", "n_tokens"):
+                    if getattr(r, k, None) is not None:
+                        out[k] = torch.as_tensor(getattr(r, k))
+                return out
+            return case
+
+        plain = model.generate(ids, seqs, **base).cpu()
+        procs = dict(repetition_penalty=1.3, no_repeat_ngram_size=2, bad_words_ids=[[int(plain[0, 0])], [int(plain[1, 1]), int(plain[1, 2])]],
+                     min_new_tokens=3, eos_token_id=[int(plain[2, 1])])
+        trie = lambda k: opa.TokenTrie([[5 + k, 6, 7], [5 + k, 8], [9, 10 + k, 11, 12]], end_token_id=3)   # noqa: E731
+        head = torch.tensor(synth.synth_prompt_ids(cfg.dec_vocab, 9, n_text=8, seq_pos=3))
+        tails = torch.tensor([[(7 + 13 * r + 5 * j) % cfg.dec_vocab for j in range(5)] for r in range(3)])
+        for name, case in (
+                ("greedy", gen()),
+                ("sampling top_p=0.9", gen(top_p=0.9, top_k=0, **samp)),
+                ("sampling top_k=5", gen(top_k=5, **samp)),
+                ("greedy + outputs", gen(**outs)),
+                ("sampling top_p=0.9 + outputs", gen(top_p=0.9, top_k=0, **samp, **outs)),
+                ("processors", gen(**procs)),
+                ("processors + token_logprobs + logits", gen(return_dict_in_generate=True, output_token_logprobs=True,
+                                                             output_logits=True, **procs)),
+                ("TokenTrie", gen(eos_token_id=[3], prefix_allowed_tokens_fn=trie(0))),
+                ("TokenTrie.per_row", gen(eos_token_id=[3], prefix_allowed_tokens_fn=opa.TokenTrie.per_row([trie(k) for k in range(3)]))),
+                ("guidance_scale=1.5", gen(guidance_scale=1.5)),
+                ("guidance_scale=1.5 + token_logprobs", gen(guidance_scale=1.5, return_dict_in_generate=True,
+                                                            output_token_logprobs=True)),
+                ("sampling num_return_sequences=3", gen(num_return_sequences=3, top_p=0.9, **samp)),
+                ("prefix= with prefix_rows", lambda: gen(tails, None, attention_mask=None, prefix_rows=[1, 0, 1],
+                                                         prefix=model.cache_prefix(torch.stack([head, head]), seq=seqs[:2],
+                                                                                   detach=True))()),
+                ("stop sequence", gen(stop_sequence=[int(plain[0, 1]), int(plain[0, 2])])),
+                ("eos_token_id", gen(eos_token_id=[int(plain[0, 1]), int(plain[1, 0]), int(plain[2, 1])]))):    # (every row ends by step 1)
+            census(f"heads {name}", model, case)
+
+        queue = [torch.tensor(synth.synth_prompt_ids(cfg.dec_vocab, i, n_text=8 + i, seq_pos=2)) for i in range(7)]
+        qseqs = [synth.synth_protein(20 + 3 * i, 50 + i) for i in range(7)]
+
+        def continuous():
+            r = model.generate_continuous(queue, qseqs, max_new_tokens=6, eos_token_id=[int(plain[0, 2]), int(plain[1, 3])],
+                                          pad_token_id=2, slots=3, refill_min=1, return_dict_in_generate=True)
+            return dict(sequences=torch.cat(r.sequences), n_tokens=r.n_tokens)
+        census("heads generate_continuous 7 prompts on 3 rows", model, continuous, stats=("stream_steps", "stream_refills"))
         del model
         torch.cuda.empty_cache()
 
