@@ -433,6 +433,48 @@ int opus_llama_score_tree_detached(opus_ctx *ctx, const opus_prefix_snap *snap, 
                                    const int32_t *h_stop_off, const float *d_last_rows, float *d_node_lp, float *d_stop_lp,
                                    int64_t n_slots, void *d_scratch, int64_t scratch_bytes, void *stream);
 
+/* Prompt-lookup decoding (generate(prompt_lookup_num_tokens=k); transformers' PromptLookupCandidateGenerator + assisted decoding,
+ * greedy and exact: the ids are those of opus_generate_greedy).  Added within ABI 10 (new symbols only).
+ *   History of row b: d_hist[b, 0 .. h_hist_len[b]) (int32 [B, Lh], device; the caller's prompt ids without padding, -1 at every
+ *     position a protein block was spliced into, then optionally -1 and a corpus to search) followed by the ids generated so far.
+ *   Draft: for m from min(max_ngram, len - 1) down to 1, the FIRST window start i with h[i .. i + m) == h[len - m .. len), i + m < len
+ *     and h[i + m] != -1; the draft is h[i + m .. min(i + m + k, len)), cut in front of a -1.  A window holding -1 never matches.
+ *   Pass: n = 1 + the longest draft of an unfinished row (cut to the token budget) positions per row - the last committed id, whose
+ *     K / V are not cached yet, then the draft (shorter drafts padded; the filler never counts as a match) - run through the
+ *     prefill's layer loop behind the context's own cache (attn_prefix_kernel; the weights stream through the decode-class GEMM
+ *     kernels, FP8 panels where bound), then the final norm and lm_head on all B n rows.  B (k + 1) <= max_batch, else OPUS_ESHAPE.
+ *   Acceptance in lockstep: y_j the arg-max at position j, m_b the longest accepted prefix of row b's draft, a = min m_b over the
+ *     unfinished rows; every row commits y_0 .. y_a and the step word advances by a + 1 (all rows stay at one cache slot).  An EOS id
+ *     or the stop sequence among a row's COMMITTED ids finishes it there; pad behind.  No unfinished row has a draft: a plain decode step.
+ * One stream synchronisation per pass.  stats (optional): {passes, plain steps, ids drafted, ids accepted}.  OPUS_EUNSUPPORTED with
+ * logits processors or a token constraint set on the context; max_ngram in [1, 8]; B <= 64. */
+int opus_generate_lookup(opus_ctx *ctx, const void *d_embeds, const uint8_t *d_mask, int32_t B, int32_t T, int32_t max_new,
+                         const int32_t *eos_ids, int32_t n_eos, int32_t pad_id, int32_t k, int32_t max_ngram, const int32_t *d_hist,
+                         int32_t Lh, const int32_t *h_hist_len, int32_t *d_out_ids, int32_t *n_out, int64_t *stats, void *stream);
+/* One verify pass with the caller's tokens on the current decode state (R = the rows of the last prefill, step word S): d_tokens
+ * int32 [R, n] (device; column 0 the token whose K / V are not cached yet, then the draft), d_draft_len int32 [R] (device) or NULL
+ * (n - 1 for every row).  Positions j = 0 .. n - 1 run at slots T0 + S + j; d_logits_all fp32 [R n, V] (row r n + j; optional),
+ * d_argmax int32 [R, n] (optional).  *a (HOST) = the lockstep acceptance; the step word advances by a + 1, so that
+ * opus_llama_decode_step or another verify step continues behind the accepted positions.  No ids are committed and no row ends.
+ * Synchronises `stream`.  OPUS_ESHAPE: R n > max_batch, S + n > max_new_tokens, R > 64; OPUS_ESTATE without a prefill. */
+int opus_llama_verify_step(opus_ctx *ctx, const int32_t *d_tokens, int32_t n, const int32_t *d_draft_len, float *d_logits_all,
+                           int32_t *d_argmax, int32_t *a, void *stream);
+/* Diagnostic: lookup_draft_kernel alone on R histories d_hist [R, Lh] of d_hist_len [R] ids (both device): d_draft int32 [R, k]
+ * (0 behind the draft), d_draft_len [R]. */
+int opus_debug_lookup_draft(opus_ctx *ctx, const int32_t *d_hist, int32_t Lh, const int32_t *d_hist_len, int32_t R, int32_t k,
+                            int32_t max_ngram, int32_t *d_draft, int32_t *d_draft_len, void *stream);
+/* Diagnostic: the projection buffer as the last attention launch of the context read it - operand dtype [rows, (heads + 2 kv) hd],
+ * q | k | v of the LAST layer, q and k rotated (behind opus_llama_verify_step: row r n + j = position j of row r). */
+int opus_debug_last_qkv(opus_ctx *ctx, void *d_out, int32_t rows, void *stream);
+/* Diagnostic: lookup_accept_kernel alone. d_argmax / d_tokens int32 [R, n], d_draft_len [R] or NULL, the id matrix d_ids [R, stride],
+ * d_fin [R], the step word d_step [1], d_next [R], d_nunf [stride] (all device, updated in place); pre = 1: a verify pass (commit at
+ * columns step + 1 .., step += a + 1), pre = 0: behind a plain step (n = 1, commit at column step).  eos_ids / stop_ids: HOST arrays.
+ * h_words (HOST) [4] = {a, rows unfinished, step word, ids drafted by unfinished rows}.  Synchronises `stream`. */
+int opus_debug_lookup_accept(opus_ctx *ctx, const int32_t *d_argmax, const int32_t *d_tokens, const int32_t *d_draft_len, int32_t R,
+                             int32_t n, int32_t pre, int32_t *d_ids, int32_t stride, int32_t *d_fin, int32_t *d_step,
+                             const int32_t *eos_ids, int32_t n_eos, int32_t pad_id, const int32_t *stop_ids, int32_t n_stop,
+                             int32_t *d_next, int32_t *d_nunf, int32_t *h_words, void *stream);
+
 /* Diagnostic: opus_generate_scored's fused arg-max / log-sum-exp pass on fp32 logits [B, V] (B <= max_batch, any V >= 1; rows
  * need no alignment): d_idx [B] the arg-max (lowest index among ties, bitwise what the greedy step picks), d_lse [B]. */
 int opus_debug_argmax_lse(opus_ctx *ctx, const float *d_logits, int32_t B, int32_t V, int32_t *d_idx, float *d_lse, void *stream);

@@ -74,6 +74,13 @@ SIGNATURES = {
     "opus_llama_score_continuations_detached": (C.c_int, [_P, _SNAP, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     "opus_llama_score_tree_detached": (C.c_int, [_P, _SNAP, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, C.c_int32, _P,
                                                  _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, _P]),
+    "opus_generate_lookup": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _I32P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,
+                                       C.c_int32, _I32P, _P, _I32P, C.POINTER(C.c_int64), _P]),
+    "opus_llama_verify_step": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _I32P, _P]),
+    "opus_debug_last_qkv": (C.c_int, [_P, _P, C.c_int32, _P]),
+    "opus_debug_lookup_draft": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "opus_debug_lookup_accept": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _I32P, C.c_int32,
+                                           C.c_int32, _I32P, C.c_int32, _P, _P, _I32P, _P]),
     "opus_stream_lag": (C.c_int32, []),
     "opus_stream_begin": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _I32P, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                     C.c_uint64, _P, _P]),

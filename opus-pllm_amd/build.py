@@ -18,7 +18,7 @@ SRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "lib", "libopus_pllm.so")
 LIB_BF16 = os.path.join(HERE, "lib", "libopus_pllm_bf16.so")      # the same sources with -DOPUS_BF16 (csrc/common.h)
-SOURCES = ["gemm.hip", "gemm_stream.hip", "norm.hip", "elementwise.hip", "attn_prefill.hip", "attn_prefix.hip", "kv_place.hip", "stream.hip", "attn_decode.hip", "beam.hip", "score.hip", "contact.hip", "mlm.hip", "logits_proc.hip", "constraint.hip", "guidance.hip", "quant.hip", "api.cpp"]
+SOURCES = ["gemm.hip", "gemm_stream.hip", "norm.hip", "elementwise.hip", "attn_prefill.hip", "attn_prefix.hip", "kv_place.hip", "stream.hip", "attn_decode.hip", "beam.hip", "score.hip", "contact.hip", "mlm.hip", "logits_proc.hip", "constraint.hip", "guidance.hip", "quant.hip", "lookup.hip", "api.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-Wno-unused-variable", "-Wno-unused-but-set-variable"]

@@ -223,6 +223,16 @@ struct opus_ctx {
     int32_t *h_poll = nullptr;
     GraphEntry stream_graph;
     int64_t stream_steps = 0, stream_refills = 0;   // opus_stat("stream_steps" / "stream_refills")
+    // prompt-lookup decoding (opus_generate_lookup / opus_llama_verify_step).  lk_mem (first use): the token matrix of a pass
+    // [max_batch] (row b: the last committed id, then the draft), the rows' draft lengths, history lengths and arg-maxes
+    // [max_batch each], the EOS / stop ids of opus_debug_lookup_accept, the pass's words {a, unfinished, step, drafted, longest draft}.
+    // h_lk (pinned): the words the host reads once per pass.  lk_kstart: host copy of kstart of the prefill of epoch lk_epoch.
+    char *lk_mem = nullptr;
+    int32_t *d_lk_tok = nullptr, *d_lk_dlen = nullptr, *d_lk_hlen = nullptr, *d_lk_arg = nullptr, *d_lk_ids = nullptr, *d_lk_words = nullptr;
+    int32_t *h_lk = nullptr;
+    std::vector<int32_t> lk_kstart;
+    int64_t lk_epoch = -1;
+    int64_t lookup_passes = 0;           // opus_stat("lookup_passes")
 };
 
 static std::atomic<int64_t> g_epoch{0};
@@ -246,6 +256,8 @@ struct ContRows {
     // opus_llama_prefill_behind: the rows' rotated K and V of positions t < app_lens[b] (device, [B]) are also appended to cache
     // row b at slot attn.Tp + (T - app_lens[b]) + t
     const int32_t *app_lens = nullptr;
+    // a verify pass of prompt-lookup decoding: the per-layer GEMMs ask for the FP8 panels as the decode step does, phase "decode"
+    bool w8 = false;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -469,6 +481,8 @@ extern "C" int opus_ctx_destroy(opus_ctx *c) {
     if (c->h_nunf) (void)hipHostFree(c->h_nunf);
     if (c->stream_mem) (void)hipFree(c->stream_mem);
     if (c->h_poll) (void)hipHostFree(c->h_poll);
+    if (c->lk_mem) (void)hipFree(c->lk_mem);
+    if (c->h_lk) (void)hipHostFree(c->h_lk);
     for (auto &e : c->poll_ev) if (e) (void)hipEventDestroy(e);
     delete c;
     return OPUS_OK;
@@ -1432,6 +1446,7 @@ static int decode_step_opt(opus_ctx *c, hipStream_t s) {
 static int prefill(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8_t *mask, int B, int T, bool all_rows = false,
                    const ContRows *cont = nullptr, int nret = 1) {
     c->phase = cont && !cont->app_lens ? PH_SCORE : PH_PREFILL;      // (rows that append to the cache: opus_llama_prefill_behind)
+    if (cont && cont->w8) c->phase = PH_DECODE;                      // (a verify pass of the decode loop)
     if (cont) {
         all_rows = true;
     } else {
@@ -1462,12 +1477,15 @@ static int prefill(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8
     };
     ResidShadow sh;
     GemmGot got;
+    const bool w8 = cont && cont->w8;                                // (false: every ask below is what it was)
+    auto ask8 = [&](GemmAsk a, const uint8_t *q, const int8_t *e) { return w8 ? a.w8(q, e) : a; };
     for (int l = 0; l < g.dec_layers; ++l) {
         const DecLayer &L = c->dec[l];
         if (have_stat && qkv_pp) {
             OPC(gemm(c, s, c->d_xn, H, L.wqkv, M, QKV, H, L.bqkv, EPI_NONE, nullptr, c->d_qkv, QKV, 0, GemmAsk().ln_consume(c->d_stat, nullptr)));
         } else {
-            OPC(gemm_norm(c, s, sh, c->d_x, g.dec_rms_eps, c->d_xn, L.wqkv, M, QKV, H, EPI_NONE, c->d_qkv, QKV, 0, L.bqkv));
+            OPC(gemm_norm(c, s, sh, c->d_x, g.dec_rms_eps, c->d_xn, L.wqkv, M, QKV, H, EPI_NONE, c->d_qkv, QKV, 0, L.bqkv,
+                          ask8(GemmAsk(), L.q8_qkv, L.e8_qkv)));
         }
         OPC(attn_prefill(c, s, l, B, T, cont, nret));
         if (l + 1 == g.dec_layers && T > 1 && !all_rows && !g_knobs.misc[7]) {
@@ -1490,17 +1508,18 @@ static int prefill(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8
         GemmAsk wo;
         if (gu_pp) wo.ln_produce(c->d_part, c->d_xn);
         else if (fuse_rows() && M <= 96) wo.copy16(c->d_xn);      // (d_ssq holds 128 rows)
-        OPC(gemm(c, s, c->d_ctx, QD, L.wo, M, H, QD, nullptr, EPI_NONE, c->d_x, c->d_x, H, 1, wo, &got));
+        OPC(gemm(c, s, c->d_ctx, QD, L.wo, M, H, QD, nullptr, EPI_NONE, c->d_x, c->d_x, H, 1, ask8(wo, L.q8_o, L.e8_o), &got));
         sh.produced(c->d_x, got);
         have_stat = got.ln_done != 0;
         if (have_stat) {
             OPC(finalize());
             OPC(gemm(c, s, c->d_xn, H, L.wgu, M, 2 * F, H, nullptr, EPI_SILU_GU16, nullptr, c->d_act, F, 0, GemmAsk().ln_consume(c->d_stat, nullptr)));
         } else {
-            OPC(gemm_norm(c, s, sh, c->d_x, g.dec_rms_eps, c->d_xn, L.wgu, M, 2 * F, H, EPI_SILU_GU16, c->d_act, F, 0));
+            OPC(gemm_norm(c, s, sh, c->d_x, g.dec_rms_eps, c->d_xn, L.wgu, M, 2 * F, H, EPI_SILU_GU16, c->d_act, F, 0, nullptr,
+                          ask8(GemmAsk(), L.q8_gu, L.e8_gu)));
         }
         const bool next_pp = qkv_pp && l + 1 < g.dec_layers;
-        OPC(gemm(c, s, c->d_act, F, L.wd, M, H, F, nullptr, EPI_NONE, c->d_x, c->d_x, H, 1, GemmAsk().ln_produce(next_pp ? c->d_part : nullptr, c->d_xn), &got));
+        OPC(gemm(c, s, c->d_act, F, L.wd, M, H, F, nullptr, EPI_NONE, c->d_x, c->d_x, H, 1, ask8(GemmAsk().ln_produce(next_pp ? c->d_part : nullptr, c->d_xn), L.q8_d, L.e8_d), &got));
         have_stat = got.ln_done != 0;
         if (have_stat) OPC(finalize());
     }
@@ -3174,6 +3193,251 @@ extern "C" int opus_generate_scored_behind(opus_ctx *c, const opus_prefix_snap *
                          temperature > 0.f ? seed : 0, d_out_ids, n_out, stream, &outs, 1, &behind);
 }
 
+// ------------------------------------------------------------------------------------------------ prompt-lookup decoding
+// generate(prompt_lookup_num_tokens=k): per pass the rows' n-gram drafts (lookup_draft_kernel) are verified by ONE run of the
+// layer loop on R n positions - prefill() with continuation rows behind the context's OWN cache (source rows the identity, Tp the
+// host's mirror of T0 + step, every row appends its n positions) - then the final norm and lm_head on all R n rows, the arg-max and
+// lookup_accept_kernel, which commits a + 1 ids per row in lockstep and advances the step word.  The host reads the pass's words
+// back once (one synchronisation per pass, as beam search).  Slots beyond Tp + a keep the K / V of rejected positions: finite
+// values no kernel reads, because attn_decode_kernel and attn_prefix_kernel select the visible slots by index (a slot past the
+// end is never loaded in the first, is staged as zeros and set to -inf by a select in the second) and the next pass or step
+// overwrites them before the end moves past them.
+static int ensure_lookup_mem(opus_ctx *c) {
+    if (c->lk_mem) return OPUS_OK;
+    const size_t B = c->cfg.max_batch, row = align_up(B * sizeof(int32_t));
+    HIPC(hipMalloc((void **)&c->lk_mem, 4 * row + align_up(80 * sizeof(int32_t)) + align_up(8 * sizeof(int32_t))));
+    HIPC(hipMemset(c->lk_mem, 0, 4 * row + align_up(80 * sizeof(int32_t)) + align_up(8 * sizeof(int32_t))));
+    c->d_lk_tok = reinterpret_cast<int32_t *>(c->lk_mem);
+    c->d_lk_dlen = reinterpret_cast<int32_t *>(c->lk_mem + row);
+    c->d_lk_hlen = reinterpret_cast<int32_t *>(c->lk_mem + 2 * row);
+    c->d_lk_arg = reinterpret_cast<int32_t *>(c->lk_mem + 3 * row);
+    c->d_lk_ids = reinterpret_cast<int32_t *>(c->lk_mem + 4 * row);
+    c->d_lk_words = reinterpret_cast<int32_t *>(c->lk_mem + 4 * row + align_up(80 * sizeof(int32_t)));
+    HIPC(hipHostMalloc((void **)&c->h_lk, 8 * sizeof(int32_t), hipHostMallocDefault));
+    return OPUS_OK;
+}
+
+// host copy of the current prefill's kstart (the pass's rotary positions and attention tables are built on the host)
+static int lookup_kstart(opus_ctx *c, hipStream_t s) {
+    if (c->lk_epoch == c->epoch && (int)c->lk_kstart.size() == c->cur_B) return OPUS_OK;
+    c->lk_kstart.assign((size_t)c->cur_B, 0);
+    HIPC(hipMemcpyAsync(c->lk_kstart.data(), c->d_kstart, (size_t)c->cur_B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    c->lk_epoch = c->epoch;
+    return OPUS_OK;
+}
+
+// One verify pass on the current decode state: tokens x [R, ld_x] (n columns used) at slots Tp .. Tp + n - 1 of every row; leaves
+// the logits of all R n positions in d_logits (row r n + j) and the positions' K / V in the cache.  The step word is not touched.
+static int verify_pass(opus_ctx *c, hipStream_t s, const int32_t *x, int ld_x, int n, int Tp) {
+    const opus_config &g = c->cfg;
+    const int R = c->cur_B, M = R * n, H = g.dec_dim, V = g.dec_vocab, G = g.dec_heads / g.dec_kv_heads;
+    if (!c->behind_tbl) HIPC(hipMalloc((void **)&c->behind_tbl, (size_t)behind_table_words(g) * sizeof(int32_t)));
+    std::vector<int32_t> src((size_t)R);
+    for (int r = 0; r < R; ++r) src[r] = r;
+    PrefixTables t;
+    build_prefix_tables(g, c->lk_kstart, Tp, src.data(), R, n, t);
+    if (t.nblocks > attn_prefix_max_blocks(R, g.max_batch, G, n)) return fail(OPUS_EHIP, "verify pass: block table overflow");
+    const int o_lens = (int)t.w.size();
+    t.w.insert(t.w.end(), (size_t)R, n);                                      // every row appends all its n positions
+    if ((int64_t)t.w.size() > behind_table_words(g)) return fail(OPUS_EHIP, "verify pass: table overflow");
+    int32_t *tbl = c->behind_tbl;
+    c->phase = PH_DECODE;
+    HIPC(launch_upload_i32(t.w.data(), (int)t.w.size(), tbl, s));
+    // the input rows in the operand type, staged in d_xn (prefill() reads them into d_x before its first GEMM writes d_xn)
+    KL(KC_OTHER, 4.0 * M * H, launch_lookup_embed(x, ld_x, R, n, c->dec_emb, H, V, c->d_xn, s));
+    ContRows cr;
+    cr.nkst = tbl + t.nkst;
+    cr.nblocks = t.nblocks;
+    cr.attn = prefix_params(c, tbl, t, Tp, n, c->d_qkv, nullptr, nullptr, c->d_ctx);
+    cr.app_lens = tbl + o_lens;
+    cr.w8 = true;
+    OPC(prefill(c, s, c->d_xn, nullptr, R, n, true, &cr));
+    c->phase = PH_DECODE;
+    if (g.dec_arch == 1) {
+        KL(KC_NORM, 6.0 * M * H, launch_layernorm(c->d_x, c->dec_lnfw, c->dec_lnfb, g.dec_rms_eps, M, H, c->d_xn, nullptr, s));
+        OPC(gemm(c, s, c->d_xn, H, c->lm_head, M, V, H, nullptr, EPI_NONE, nullptr, c->d_logits, V, 1));
+    } else {
+        ResidShadow none;
+        OPC(gemm_norm(c, s, none, c->d_x, g.dec_rms_eps, c->d_xn, c->lm_head, M, V, H, EPI_NONE, c->d_logits, V, 1));
+    }
+    ++c->lookup_passes;
+    return OPUS_OK;
+}
+
+// arg-max of the first `rows` rows of d_logits -> out [rows]
+static int lookup_argmax(opus_ctx *c, hipStream_t s, int rows, int32_t *out) {
+    const int V = c->cfg.dec_vocab;
+    KL(KC_OTHER, 4.0 * rows * V, launch_argmax_partial(c->d_logits, rows, V, c->d_pval, c->d_pidx, s));
+    KL(KC_OTHER, 512.0 * rows, launch_lookup_argmax(c->d_pval, c->d_pidx, rows, out, s));
+    return OPUS_OK;
+}
+
+// the pass's words -> pinned host memory, one synchronisation
+static int lookup_words(opus_ctx *c, hipStream_t s, int nwords) {
+    HIPC(hipMemcpyAsync(c->h_lk, c->d_lk_words, (size_t)nwords * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    return OPUS_OK;
+}
+
+static int check_lookup_state(opus_ctx *c, const char *who) {
+    if (!c->prefilled) return fail(OPUS_ESTATE, "%s before prefill", who);
+    if (c->st.on) return fail(OPUS_ESTATE, "%s: a continuous session is open on this context", who);
+    if (c->cur_B > 64) return fail(OPUS_ESHAPE, "%s: %d decoder rows (at most 64)", who, c->cur_B);
+    return OPUS_OK;
+}
+
+extern "C" int opus_llama_verify_step(opus_ctx *c, const int32_t *d_tokens, int32_t n, const int32_t *d_draft_len, float *d_logits_all,
+                                      int32_t *d_argmax, int32_t *a, void *stream) {
+    OPC(need_ready(c));
+    OPC(check_lookup_state(c, "verify_step"));
+    if (!d_tokens || !a) return fail(OPUS_EBADARG, "verify_step: null pointer");
+    const opus_config &g = c->cfg;
+    const int R = c->cur_B;
+    if (n < 1 || (int64_t)R * n > g.max_batch)
+        return fail(OPUS_ESHAPE, "verify_step: R x n = %d x %d logits rows, the context holds max_batch=%d", R, n, g.max_batch);
+    hipStream_t s = (hipStream_t)stream;
+    OPC(ensure_lookup_mem(c));
+    int32_t st = 0;
+    HIPC(hipMemcpyAsync(&st, c->d_step, sizeof(st), hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    if (st < 0 || st + n > g.max_new_tokens)
+        return fail(OPUS_ESHAPE, "verify_step: %d steps + %d positions, the KV cache holds max_new_tokens=%d behind the prompt", st, n,
+                    g.max_new_tokens);
+    OPC(lookup_kstart(c, s));
+    OPC(verify_pass(c, s, d_tokens, n, n, c->cur_T + st));
+    int32_t *arg = d_argmax ? d_argmax : c->d_lk_arg;
+    OPC(lookup_argmax(c, s, R * n, arg));
+    LookupAcceptParams p{};
+    p.y = arg; p.x = d_tokens; p.ld_x = n; p.draft_len = d_draft_len; p.R = R; p.n = n; p.pre = 1;
+    p.step = c->d_step; p.words = c->d_lk_words;
+    KL(KC_OTHER, 8.0 * R * n, launch_lookup_accept(p, s));
+    if (d_logits_all)
+        HIPC(hipMemcpyAsync(d_logits_all, c->d_logits, (size_t)R * n * g.dec_vocab * sizeof(float), hipMemcpyDeviceToDevice, s));
+    OPC(lookup_words(c, s, 4));
+    *a = c->h_lk[0];
+    return handoff_check(c, s);
+}
+
+extern "C" int opus_generate_lookup(opus_ctx *c, const void *d_embeds, const uint8_t *d_mask, int32_t B, int32_t T, int32_t max_new,
+                                    const int32_t *eos_ids, int32_t n_eos, int32_t pad_id, int32_t k, int32_t max_ngram,
+                                    const int32_t *d_hist, int32_t Lh, const int32_t *h_hist_len, int32_t *d_out_ids, int32_t *n_out,
+                                    int64_t *stats, void *stream) {
+    OPC(need_ready(c));
+    OPC(check_prefill_args(c, d_embeds, d_mask, B, T));
+    if (!d_out_ids || !n_out || !d_hist || !h_hist_len) return fail(OPUS_EBADARG, "generate_lookup: null pointer");
+    const opus_config &g = c->cfg;
+    if (k < 1 || B > 64 || (int64_t)B * (k + 1) > g.max_batch)
+        return fail(OPUS_ESHAPE, "generate_lookup: a pass of B x (k + 1) = %d x %d logits rows needs max_batch >= %d (the context holds %d; "
+                                 "at most 64 rows)", B, k + 1, B * (k + 1), g.max_batch);
+    if (max_ngram < 1 || max_ngram > lookup_max_ngram())
+        return fail(OPUS_EBADARG, "generate_lookup: max_matching_ngram_size=%d outside [1, %d]", max_ngram, lookup_max_ngram());
+    if (Lh < 1) return fail(OPUS_EBADARG, "generate_lookup: history stride %d", Lh);
+    for (int b = 0; b < B; ++b)
+        if (h_hist_len[b] < 0 || h_hist_len[b] > Lh) return fail(OPUS_EBADARG, "generate_lookup: history length %d of row %d outside [0, %d]", h_hist_len[b], b, Lh);
+    if (c->lproc_on || c->cons_on)
+        return fail(OPUS_EUNSUPPORTED, "generate_lookup: logits processors / a token constraint are set on this context");
+    hipStream_t s = (hipStream_t)stream;
+    OPC(ensure_lookup_mem(c));
+    const uint64_t seed = 0;
+    OPC(begin_generation(c, "generate_lookup", 0.f, 1.f, max_new, eos_ids, n_eos, &seed, B, max_new, s));
+    OPC(prefill(c, s, (const half_t *)d_embeds, d_mask, B, T));
+    HIPC(launch_upload_i32(h_hist_len, B, c->d_lk_hlen, s));
+    OPC(lookup_kstart(c, s));                                                 // (synchronises: the uploads above are done)
+    int64_t passes = 0, plain = 0, drafted = 0, accepted = 0;
+    LookupAcceptParams p{};
+    p.y = c->d_lk_arg; p.x = c->d_lk_tok; p.ld_x = k + 1; p.draft_len = c->d_lk_dlen; p.R = B;
+    p.ids = d_out_ids; p.stride = max_new; p.fin = c->d_fin; p.eos = c->d_eos; p.stop = c->d_stop; p.n_eos = n_eos; p.n_stop = c->n_stop;
+    p.pad = pad_id; p.step = c->d_step; p.next = c->d_next; p.n_unf = c->d_nunf; p.words = c->d_lk_words; p.max_len = c->d_lk_words + 4;
+    // behind every commit: the next pass's token matrix (the last committed id | the draft) and the longest draft, then the words
+    auto commit = [&](int n, int pre) -> int {
+        c->phase = PH_DECODE;
+        OPC(lookup_argmax(c, s, B * n, c->d_lk_arg));
+        p.n = n; p.pre = pre;
+        KL(KC_OTHER, 8.0 * B * n, launch_lookup_accept(p, s));
+        KL(KC_OTHER, 4.0 * B * (Lh + max_new), launch_lookup_draft(d_hist, Lh, c->d_lk_hlen, d_out_ids, max_new, c->d_step, 1, c->d_fin, B, k,
+                                                                   max_ngram, pad_id, c->d_lk_tok + 1, k + 1, c->d_lk_tok, c->d_lk_dlen,
+                                                                   c->d_lk_words + 4, s));
+        return lookup_words(c, s, 5);
+    };
+    // x for a plain step's commit: column 0 of the token matrix is not compared (n = 1)
+    OPC(commit(1, 0));                                                        // the first id, from the prefill's logits
+    int S = 0;
+    while (S + 1 < max_new && c->h_lk[1] > 0) {
+        const int n = std::min(1 + c->h_lk[4], max_new - 1 - S);
+        ++c->decode_steps;
+        if (n <= 1) {                                                         // no unfinished row has a draft: one plain decode step
+            OPC(decode_step(c, s, c->d_next));
+            OPC(commit(1, 0));
+            ++plain;
+        } else {
+            OPC(verify_pass(c, s, c->d_lk_tok, k + 1, n, T + S));
+            OPC(commit(n, 1));
+            ++passes;
+            drafted += c->h_lk[3];
+            accepted += c->h_lk[0];
+        }
+        S = c->h_lk[2];
+    }
+    const int produced = S + 1;
+    std::vector<int32_t> nunf((size_t)produced, 1);
+    HIPC(hipMemcpyAsync(nunf.data(), c->d_nunf, (size_t)produced * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    OPC(handoff_check(c, s));                                                 // (synchronises the stream)
+    int nn = produced;
+    for (int q = 0; q < produced; ++q) if (nunf[q] == 0) { nn = q + 1; break; }
+    *n_out = nn;
+    if (stats) { stats[0] = passes; stats[1] = plain; stats[2] = drafted; stats[3] = accepted; }
+    return OPUS_OK;
+}
+
+extern "C" int opus_debug_lookup_draft(opus_ctx *c, const int32_t *d_hist, int32_t Lh, const int32_t *d_hist_len, int32_t R, int32_t k,
+                                       int32_t max_ngram, int32_t *d_draft, int32_t *d_draft_len, void *stream) {
+    if (!c) return fail(OPUS_EBADARG, "ctx is null");
+    if (!d_hist || !d_hist_len || !d_draft || !d_draft_len) return fail(OPUS_EBADARG, "debug_lookup_draft: null pointer");
+    if (R < 1 || k < 1 || Lh < 1 || max_ngram < 1 || max_ngram > lookup_max_ngram())
+        return fail(OPUS_EBADARG, "debug_lookup_draft: R=%d k=%d Lh=%d max_ngram=%d (at most %d)", R, k, Lh, max_ngram, lookup_max_ngram());
+    HIPC(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    KL(KC_OTHER, 4.0 * R * Lh, launch_lookup_draft(d_hist, Lh, d_hist_len, nullptr, 0, nullptr, 0, nullptr, R, k, max_ngram, 0, d_draft, k,
+                                                    nullptr, d_draft_len, nullptr, s));
+    return OPUS_OK;
+}
+
+extern "C" int opus_debug_last_qkv(opus_ctx *c, void *d_out, int32_t rows, void *stream) {
+    if (!c || !d_out) return fail(OPUS_EBADARG, "debug_last_qkv: null pointer");
+    const opus_config &g = c->cfg;
+    if (rows < 1 || rows > dec_rows_cap(g)) return fail(OPUS_ESHAPE, "debug_last_qkv: rows=%d (1 .. %lld)", rows, (long long)dec_rows_cap(g));
+    HIPC(hipSetDevice(c->device));
+    const size_t QKV = (size_t)(g.dec_heads + 2 * g.dec_kv_heads) * g.dec_head_dim;
+    HIPC(hipMemcpyAsync(d_out, c->d_qkv, (size_t)rows * QKV * sizeof(half_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return OPUS_OK;
+}
+
+extern "C" int opus_debug_lookup_accept(opus_ctx *c, const int32_t *d_argmax, const int32_t *d_tokens, const int32_t *d_draft_len, int32_t R,
+                                        int32_t n, int32_t pre, int32_t *d_ids, int32_t stride, int32_t *d_fin, int32_t *d_step,
+                                        const int32_t *eos_ids, int32_t n_eos, int32_t pad_id, const int32_t *stop_ids, int32_t n_stop,
+                                        int32_t *d_next, int32_t *d_nunf, int32_t *h_words, void *stream) {
+    if (!c) return fail(OPUS_EBADARG, "ctx is null");
+    if (!d_argmax || !d_tokens || !d_ids || !d_fin || !d_step || !d_next || !d_nunf || !h_words)
+        return fail(OPUS_EBADARG, "debug_lookup_accept: null pointer");
+    if (R < 1 || R > 64 || n < 1 || stride < 1 || n_eos < 0 || n_eos > 64 || n_stop < 0 || n_stop > 8 || (pre != 0 && pre != 1) ||
+        (pre == 0 && n != 1) || (n_eos && !eos_ids) || (n_stop && !stop_ids))
+        return fail(OPUS_EBADARG, "debug_lookup_accept: R=%d n=%d stride=%d n_eos=%d n_stop=%d pre=%d", R, n, stride, n_eos, n_stop, pre);
+    HIPC(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    OPC(ensure_lookup_mem(c));
+    if (n_eos) HIPC(launch_upload_i32(eos_ids, n_eos, c->d_lk_ids, s));
+    if (n_stop) HIPC(launch_upload_i32(stop_ids, n_stop, c->d_lk_ids + 64, s));
+    LookupAcceptParams p{};
+    p.y = d_argmax; p.x = d_tokens; p.ld_x = n; p.draft_len = d_draft_len; p.R = R; p.n = n; p.pre = pre; p.ids = d_ids; p.stride = stride;
+    p.fin = d_fin; p.eos = c->d_lk_ids; p.stop = c->d_lk_ids + 64; p.n_eos = n_eos; p.n_stop = n_stop; p.pad = pad_id; p.step = d_step;
+    p.next = d_next; p.n_unf = d_nunf; p.words = c->d_lk_words;
+    KL(KC_OTHER, 8.0 * R * n, launch_lookup_accept(p, s));
+    OPC(lookup_words(c, s, 4));
+    for (int i = 0; i < 4; ++i) h_words[i] = c->h_lk[i];
+    return OPUS_OK;
+}
+
 /* Diagnostic: the fused arg-max / log-sum-exp pass of opus_generate_scored on fp32 logits [B, V] (B <= max_batch, any V >= 1):
    d_idx [B] (the arg-max argmax_partial gives: lowest index among ties), d_lse [B]. */
 extern "C" int opus_debug_argmax_lse(opus_ctx *c, const float *d_logits, int32_t B, int32_t V, int32_t *d_idx, float *d_lse,
@@ -3676,6 +3940,7 @@ extern "C" int64_t opus_stat(opus_ctx *c, const char *name) {
     if (!strcmp(name, "stream_steps")) return c->stream_steps;
     if (!strcmp(name, "stream_refills")) return c->stream_refills;
     if (!strcmp(name, "stream_graph")) return c->stream_graph.exec ? 1 : 0;
+    if (!strcmp(name, "lookup_passes")) return c->lookup_passes;
     return -1;
 }
 

@@ -577,6 +577,33 @@ hipError_t launch_kv_gather_rows(half_t *cache, half_t *tmp, const int32_t *idx,
 hipError_t launch_upload_i32(const int32_t *h, int n, int32_t *dst, hipStream_t s);   // host ints -> device through kernel arguments
 hipError_t launch_mask_to_kstart(const uint8_t *mask, int B, int T, int32_t *kstart, hipStream_t s);
 
+// lookup.hip : prompt-lookup decoding - the n-gram draft, the verify pass's input rows, acceptance and commit in lockstep
+struct LookupAcceptParams {
+    const int32_t *y;           // [R, n] arg-max of every position of the pass
+    const int32_t *x;           // [R, ld_x] the tokens fed: column 0 the last committed token, columns 1 .. the draft
+    int ld_x;
+    const int32_t *draft_len;   // [R] or nullptr (n - 1 for every row)
+    int R, n;
+    int pre;                    // 1: a verify pass (commit behind the step word, advance it by a + 1); 0: behind a plain step (n = 1)
+    int32_t *ids;               // [R, stride] id matrix or nullptr (opus_llama_verify_step: no commit, no end of a row)
+    int stride;
+    int32_t *fin;               // [R] finished flags or nullptr
+    const int32_t *eos, *stop;
+    int n_eos, n_stop, pad;
+    int32_t *step;              // the step word
+    int32_t *next;              // [R] the last committed token of every row or nullptr
+    int32_t *n_unf;             // [stride] rows unfinished behind every column or nullptr
+    int32_t *words;             // {a, rows unfinished, step word, ids drafted by unfinished rows}
+    int32_t *max_len;           // zeroed for the next draft launch, or nullptr
+};
+hipError_t launch_lookup_draft(const int32_t *hist, int ld_hist, const int32_t *hist_len, const int32_t *ids, int ld_ids,
+                               const int32_t *step, int gen_add, const int32_t *fin, int R, int k, int max_ngram, int filler,
+                               int32_t *draft, int ld_draft, int32_t *first, int32_t *draft_len, int32_t *max_len, hipStream_t s);
+hipError_t launch_lookup_embed(const int32_t *tok, int ld_tok, int R, int n, const half_t *emb, int H, int V, half_t *x, hipStream_t s);
+hipError_t launch_lookup_argmax(const float *pval, const int32_t *pidx, int rows, int32_t *out, hipStream_t s);
+hipError_t launch_lookup_accept(const LookupAcceptParams &p, hipStream_t s);
+int lookup_max_ngram();
+
 // attn_decode.hip : rope(q,k at the new slot) + cache append + single-query attention
 struct AttnDecodeParams {
     const half_t *qkv;          // [B][(nh + 2 nkv) hd] fp16 projection output of the new tokens, or nullptr when slabs != nullptr

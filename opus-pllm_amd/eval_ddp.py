@@ -36,8 +36,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import opus_pllm_amd as opa                                                    # noqa: E402
 from opus_pllm_amd import dist as odist                                        # noqa: E402
 from opus_pllm_amd.builder import load_pretrained_model, return_cstp_path      # noqa: E402
-from opus_pllm_amd.prompt import (add_constraint_args, add_logits_processor_args, after_process_output,  # noqa: E402
-                                  build_prompt, logits_processor_kwargs, max_new_tokens_for, token_constraint)
+from opus_pllm_amd.prompt import (add_constraint_args, add_logits_processor_args, add_lookup_args, after_process_output,  # noqa: E402
+                                  build_prompt, logits_processor_kwargs, lookup_kwargs, max_new_tokens_for, token_constraint)
 
 
 def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperature=0.0, top_p=0.7, num_beams=1,
@@ -309,6 +309,11 @@ def eval_model(args):
         if ctx_new < max_new:
             raise ValueError(f"--session_steps {ctx_new} is below the token budget {max_new}")
         ctx_batch = int(args.slots) if args.slots else args.batch_size
+    lookup_kw = lookup_kwargs(args)
+    if lookup_kw:                                     # a verify pass holds batch x (K + 1) logits rows
+        if continuous:
+            raise ValueError("--continuous does not take --prompt_lookup_num_tokens")
+        ctx_batch = max(ctx_batch, args.batch_size * (lookup_kw["prompt_lookup_num_tokens"] + 1))
 
     def capacity(tok, cfg):
         need = prompt_capacity(tok, mine, args.input_path, cfg.n_prot_tokens)
@@ -329,6 +334,7 @@ def eval_model(args):
         return _eval_ranked_terms(args, qs, mine, tokenizer, model, held["trie"], n_rank, dev, rank, world, t0)
     logits = [] if args.dump_logits else None
     proc_kw = logits_processor_kwargs(args)
+    proc_kw.update(lookup_kw)
     trie = token_constraint(args, tokenizer)          # --allowed_terms: built once, uploaded once per context
     if trie is not None:
         proc_kw["prefix_allowed_tokens_fn"] = trie
@@ -451,6 +457,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--rank_with_stop", action="store_true",
                    help="with --rank_terms: add the log-probability of ending the answer right behind the term")
     add_logits_processor_args(p)
+    add_lookup_args(p)
     add_constraint_args(p)
     return p
 

@@ -559,7 +559,17 @@ class OpusLlamaForCausalLM:
         length for the single 2 P-row prefill.  g None or 1 is the call without the argument (the negative prompt is ignored, as in
         transformers).  g not a finite number, a negative prompt of another row count or with a placeholder raise ValueError;
         2 P > max_batch or a padded length above max_prompt OpusError -2; num_beams > 1, num_return_sequences > 1 and prefix=
-        with guidance NotImplementedError."""
+        with guidance NotImplementedError.
+        prompt_lookup_num_tokens=k (transformers' prompt-lookup decoding; greedy search only, exact: the ids are those of the call
+        without it): per pass every row drafts up to k ids by n-gram lookup in its own history (max_matching_ngram_size, default
+        2: transformers' PromptLookupCandidateGenerator rule) and one pass of the decoder verifies all drafts, 1 + the longest
+        draft positions per row; the rows accept in lockstep (the shortest accepted prefix over the unfinished rows), so a pass
+        emits 1 + a ids per row for about the cost of one decode step.  The history is the text prompt (protein blocks are
+        never matched), the ids generated so far and lookup_ids (extension: [B, L] ids or B id lists searched like the prompt -
+        a retrieved annotation, an earlier answer, a term list).  batch x (k + 1) <= max_batch, else ValueError.  With
+        return_dict_in_generate the result carries `stats` (LookupStats: passes, plain_steps, drafted, accepted).  do_sample,
+        num_beams > 1, num_return_sequences > 1, guidance_scale, prefix=, the logits processors, a TokenTrie and the output_*
+        flags raise NotImplementedError.  k None or 0 is the call without the argument."""
         return_dict = bool(kwargs.pop("return_dict_in_generate", False))
         want = {k: bool(kwargs.pop(k, False)) for k in ("output_scores", "output_logits", "output_token_logprobs",
                                                          "output_attentions", "output_hidden_states")}
@@ -575,6 +585,10 @@ class OpusLlamaForCausalLM:
         guidance = _guidance_scale(kwargs.pop("guidance_scale", None))
         neg_ids = kwargs.pop("negative_prompt_ids", None)
         neg_mask = kwargs.pop("negative_prompt_attention_mask", None)
+        lookup_k = kwargs.pop("prompt_lookup_num_tokens", None)
+        lookup_k = int(lookup_k) if lookup_k else 0                      # (None / 0: the call without the argument)
+        lookup_m = kwargs.pop("max_matching_ngram_size", None)
+        lookup_ids = kwargs.pop("lookup_ids", None)
         if "inputs_embeds" in kwargs:
             raise NotImplementedError("`inputs_embeds` is not supported")
         do_sample = bool(kwargs.pop("do_sample", False))
@@ -640,6 +654,12 @@ class OpusLlamaForCausalLM:
             pad_id = eos[0] if eos else 0
         if inputs is None:
             raise ValueError("generate() needs input ids")
+        if lookup_k:                           # every check before the device is touched
+            lookup_m = _check_lookup(lookup_k, lookup_m, int(inputs.shape[0]), self.cfg.max_batch, do_sample=do_sample,
+                                     num_beams=num_beams, nret=nret, guidance=guidance, prefix=prefix, lproc=lproc,
+                                     constraint=constraint, outputs=return_dict and any(
+                                         want[k] for k in ("output_scores", "output_logits", "output_token_logprobs")))
+            lookup_hist = lookup_history(inputs, attention_mask, lookup_ids, self.cfg.n_prot_tokens)
         if guidance is not None:               # every check before the device is touched
             if num_beams > 1:
                 raise NotImplementedError("guidance_scale is built for greedy search and sampling, not for num_beams > 1 "
@@ -704,6 +724,13 @@ class OpusLlamaForCausalLM:
                 embeds, mask = pad_left_common(embeds, mask.to(torch.uint8), n_embeds, n_mask)
         self._set_logits_processors(lproc)
         self._set_token_constraint(constraint)
+        if lookup_k:
+            ids, stats = self._lookup(embeds, mask, max_new, eos, int(pad_id), lookup_k, lookup_m, lookup_hist)
+            if not return_dict:
+                return ids
+            res = GenerateDecoderOnlyOutput(sequences=ids)
+            res.stats = stats
+            return res
         if guidance is not None:
             outs = (want["output_token_logprobs"], want["output_scores"], want["output_logits"]) if return_dict else None
             return self._greedy(embeds, mask, max_new, eos, int(pad_id), sampler, outputs=outs, guidance=guidance)
@@ -931,6 +958,54 @@ class OpusLlamaForCausalLM:
             res.logprob = res.token_logprobs.sum(dim=1)
             res.n_tokens = counted_tokens(ids, eos, getattr(self, "_stop_ids", []))
         return res
+
+    # ------------------------------------------------------------------ prompt-lookup decoding
+    def _lookup(self, embeds, mask, max_new, eos, pad_id, k: int, max_ngram: int, hist):
+        """generate(prompt_lookup_num_tokens=k) behind the splice: opus_generate_lookup on the rows' histories (lookup_history).
+        Returns (new ids [B, n], LookupStats)."""
+        B, T, _ = embeds.shape
+        embeds = embeds.contiguous()
+        mask = mask.to(torch.uint8).contiguous()
+        rows, lens = hist
+        s = self._enter()
+        with torch.cuda.stream(self._stream):
+            if getattr(self, "_out_ids", None) is None or self._out_ids.shape[0] < B or self._out_ids.shape[1] < max_new:
+                self._out_ids = torch.empty((max(B, self.cfg.max_batch), max(max_new, self.cfg.max_new_tokens)),
+                                            dtype=torch.int32, device=self.device)
+            out = self._out_ids.view(-1)[: B * max_new].view(B, max_new)
+            out.fill_(pad_id)
+            d_hist = torch.from_numpy(rows).to(self.device)
+            n_out = C.c_int32(0)
+            eos_arr = (C.c_int32 * max(1, len(eos)))(*eos)
+            len_arr = (C.c_int32 * B)(*[int(v) for v in lens])
+            stats = (C.c_int64 * 4)()
+            _cabi.check(self._lib.opus_generate_lookup(self._ctx, embeds.data_ptr(), mask.data_ptr(), B, T, max_new, eos_arr, len(eos),
+                                                       pad_id, k, max_ngram, d_hist.data_ptr(), rows.shape[1], len_arr,
+                                                       out.data_ptr(), C.byref(n_out), stats, s))
+        self._leave()
+        return out[:, :n_out.value].long(), LookupStats(*[int(v) for v in stats])
+
+    def verify_step(self, tokens: torch.Tensor, draft_len: Optional[torch.Tensor] = None, return_logits: bool = True):
+        """One verify pass on the current decode state (behind prefill_logits() / decode_logits() / an earlier verify_step):
+        tokens int [R, n] - column 0 the token whose K / V are not cached yet, then a draft of draft_len[r] ids (None: n - 1).
+        Returns (logits fp32 [R, n, V] or None, argmax int32 [R, n], a): position j holds the model's prediction behind
+        tokens[:, : j + 1]; a is the lockstep acceptance (the shortest accepted draft prefix over the rows), and the decode
+        state has advanced by a + 1 positions.  R n <= max_batch."""
+        tokens = tokens.to(self.device, torch.int32).contiguous()
+        R, n = tokens.shape
+        if draft_len is not None:
+            draft_len = draft_len.to(self.device, torch.int32).contiguous()
+        s = self._enter()
+        with torch.cuda.stream(self._stream):
+            logits = torch.empty((R, n, self.cfg.dec_vocab), dtype=torch.float32, device=self.device) if return_logits else None
+            arg = torch.empty((R, n), dtype=torch.int32, device=self.device)
+            a = C.c_int32(0)
+            _cabi.check(self._lib.opus_llama_verify_step(self._ctx, tokens.data_ptr(), n,
+                                                         None if draft_len is None else draft_len.data_ptr(),
+                                                         None if logits is None else logits.data_ptr(), arg.data_ptr(),
+                                                         C.byref(a), s))
+        self._leave()
+        return logits, arg, a.value
 
     # ------------------------------------------------------------------ continuous batching
     _CONTINUOUS_UNSUPPORTED = ("guidance_scale", "negative_prompt_ids", "negative_prompt_attention_mask", "prefix", "prefix_rows",
@@ -1805,6 +1880,86 @@ class TrieScores:
 
 # capacities of the processor kernel (include/opus_pllm.h, opus_set_logits_processors)
 LP_MAX_BAD, LP_MAX_BAD_LEN, LP_MAX_BAD_IDS = 256, 8, 1024
+
+
+class LookupStats:
+    """What a generate(prompt_lookup_num_tokens=k) call did: verify passes, plain decode steps, ids drafted (by unfinished rows,
+    over all passes) and ids accepted (the lockstep a, summed over the passes)."""
+
+    def __init__(self, passes: int = 0, plain_steps: int = 0, drafted: int = 0, accepted: int = 0):
+        self.passes, self.plain_steps, self.drafted, self.accepted = passes, plain_steps, drafted, accepted
+
+    def __repr__(self):
+        return (f"LookupStats(passes={self.passes}, plain_steps={self.plain_steps}, drafted={self.drafted}, "
+                f"accepted={self.accepted})")
+
+
+LOOKUP_MAX_NGRAM = 8           # csrc/lookup.hip LK_MAX_NGRAM
+
+
+def _check_lookup(k: int, max_ngram, B: int, max_batch: int, *, do_sample=False, num_beams=1, nret=1, guidance=None, prefix=None,
+                  lproc=None, constraint=None, outputs=False) -> int:
+    """The argument checks of generate(prompt_lookup_num_tokens=k); returns max_matching_ngram_size (default 2)."""
+    if k < 0:
+        raise ValueError(f"`prompt_lookup_num_tokens` has to be a positive integer (got {k})")
+    m = 2 if max_ngram is None else int(max_ngram)
+    if not 1 <= m <= LOOKUP_MAX_NGRAM:
+        raise ValueError(f"`max_matching_ngram_size` has to lie in [1, {LOOKUP_MAX_NGRAM}] (got {m})")
+    why = "prompt_lookup_num_tokens is built for greedy search, where the verified ids are exactly those of plain generate(): "
+    if do_sample:
+        raise NotImplementedError(why + "do_sample=True needs speculative sampling, which is not built")
+    if num_beams > 1:
+        raise NotImplementedError(why + "num_beams > 1 would have to verify every beam's draft")
+    if nret > 1:
+        raise NotImplementedError(why + "num_return_sequences > 1 exists for sampling and beams only")
+    if guidance is not None:
+        raise NotImplementedError(why + "guidance_scale pairs every row with a negative row, whose pass rows are not built")
+    if prefix is not None:
+        raise NotImplementedError(why + "generate(prefix=...) starts from a detached cache, whose history the draft does not see")
+    if lproc is not None:
+        raise NotImplementedError(why + "the logits processors (repetition_penalty, no_repeat_ngram_size, bad_words_ids, "
+                                        "min_length / min_new_tokens) would have to run on every position of a pass")
+    if constraint is not None:
+        raise NotImplementedError(why + "a TokenTrie's automaton would have to step through every position of a pass")
+    if outputs:
+        raise NotImplementedError(why + "output_scores / output_logits / output_token_logprobs are not collected from the passes")
+    if B * (k + 1) > max_batch or B > 64:
+        raise ValueError(f"prompt_lookup_num_tokens={k} verifies batch x (k + 1) = {B} x {k + 1} positions per pass: it needs a "
+                         f"context with max_batch >= {B * (k + 1)} (this one holds max_batch={max_batch}) and at most 64 rows")
+    return m
+
+
+def lookup_history(input_ids, attention_mask=None, lookup_ids=None, n_prot_tokens: int = 1):
+    """The rows' searchable histories for prompt-lookup drafts: (int32 array [B, L], lengths [B]).  Row b: its prompt ids without
+    the padding, -1 at every position a protein block is spliced into, then - with lookup_ids ([B, L'] ids or a list of B id
+    lists; negative ids are dropped) - one -1 and that corpus."""
+    ids = np.asarray(input_ids.cpu() if hasattr(input_ids, "cpu") else input_ids).astype(np.int64)
+    B = ids.shape[0]
+    m = None if attention_mask is None else np.asarray(attention_mask.cpu() if hasattr(attention_mask, "cpu") else attention_mask).astype(bool)
+    if lookup_ids is not None:
+        if hasattr(lookup_ids, "cpu"):
+            lookup_ids = lookup_ids.cpu().tolist()
+        if len(lookup_ids) != B:
+            raise ValueError(f"`lookup_ids` holds {len(lookup_ids)} rows, the batch {B}")
+    rows = []
+    for b in range(B):
+        h = []
+        for j in range(ids.shape[1]):
+            if m is not None and not m[b, j]:
+                continue
+            t = int(ids[b, j])
+            h.extend([-1] * n_prot_tokens if t == DEFAULT_SEQ_TOKEN_INDEX else [t])
+        if lookup_ids is not None:
+            corpus = [int(t) for t in lookup_ids[b] if int(t) >= 0]
+            if corpus:
+                h.append(-1)
+                h.extend(corpus)
+        rows.append(h)
+    L = max(1, max(len(h) for h in rows))
+    out = np.full((B, L), -1, dtype=np.int32)
+    for b, h in enumerate(rows):
+        out[b, :len(h)] = h
+    return out, np.asarray([len(h) for h in rows], dtype=np.int32)
 
 
 def _guidance_scale(g) -> Optional[float]:

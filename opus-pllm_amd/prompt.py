@@ -132,6 +132,26 @@ def logits_processor_kwargs(args) -> dict:
     return {k: getattr(args, k) for k in names if getattr(args, k, None) is not None}
 
 
+def add_lookup_args(p) -> None:
+    """The drivers' prompt-lookup decoding (generate(prompt_lookup_num_tokens=K); greedy search only, off by default)."""
+    p.add_argument("--prompt_lookup_num_tokens", type=int, default=None,
+                   help="draft up to K ids per step by n-gram lookup in the prompt and the answer so far, verified in one pass "
+                        "(greedy search only; the ids are unchanged); needs max_batch >= batch x (K + 1)")
+    p.add_argument("--max_matching_ngram_size", type=int, default=None,
+                   help="with --prompt_lookup_num_tokens: the longest n-gram matched (default 2)")
+
+
+def lookup_kwargs(args) -> dict:
+    """generate() keywords of add_lookup_args' options (unset or 0: none)."""
+    k = getattr(args, "prompt_lookup_num_tokens", None)
+    if not k:
+        return {}
+    kw = {"prompt_lookup_num_tokens": int(k)}
+    if getattr(args, "max_matching_ngram_size", None) is not None:
+        kw["max_matching_ngram_size"] = int(args.max_matching_ngram_size)
+    return kw
+
+
 def add_constraint_args(p) -> None:
     """The drivers' constrained decoding: answers from a closed vocabulary (generate(prefix_allowed_tokens_fn=TokenTrie))."""
     p.add_argument("--allowed_terms", type=str, default=None,
