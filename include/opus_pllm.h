@@ -48,7 +48,10 @@ enum opus_status {
 
 /* OPUS_F8E4M3 (OCP e4m3fn codes) and OPUS_I8: the FP8 form of the decoder-layer weights only (opus_quantize_fp8); added within
  * ABI 10 (new values only). */
-enum opus_dtype { OPUS_F16 = 0, OPUS_F32 = 1, OPUS_I32 = 2, OPUS_I64 = 3, OPUS_U8 = 4, OPUS_F8E4M3 = 5, OPUS_I8 = 6 };
+/* OPUS_F4E2M1X2 (two OCP e2m1 codes per byte, the lower k in the low nibble) and OPUS_E8M0 (power-of-two scale bytes): the MXFP4
+ * form of the decoder-layer weights only (opus_quantize_mxfp4); added within ABI 10 (new values only). */
+enum opus_dtype { OPUS_F16 = 0, OPUS_F32 = 1, OPUS_I32 = 2, OPUS_I64 = 3, OPUS_U8 = 4, OPUS_F8E4M3 = 5, OPUS_I8 = 6,
+                  OPUS_F4E2M1X2 = 7, OPUS_E8M0 = 8 };
 
 /* Shapes of the path.  The reference hard-codes or threads these through a global class
  * (model/builder.py:24-28, protein_projector/builder.py:7-13, protein_mlp/builder.py:11-15,
@@ -127,6 +130,26 @@ int opus_tile_weight(const void *d_src, void *d_dst, int64_t N, int64_t K, void 
  * weight-streaming kernels: skinny at 1 .. 4 rows; stream, wide and mid at 5 .. 64 rows) then stream half the bytes of the same numbers; every other launch reads the fp16 tensor.
  * Synchronises `stream`.  OPUS_EBADARG when a weight is not finite (the outputs are then not to be used).  Added within ABI 10. */
 int opus_quantize_fp8(const void *d_src, int64_t N, int64_t K, void *d_q8, void *d_e8, void *d_dq, void *stream);
+
+/* MXFP4 decoder weights (OCP MX v1.0: e2m1 elements, one e8m0 scale per 32 consecutive k of a row; 4.25 bits per weight).  Like
+ * FP8 a decode-throughput option and a different model, not a capacity option: the operand-type tensors stay bound.  Quantises
+ * one decoder-layer weight after all load-time fusion and before tiling: row-major W[N,K] in the operand type (N % 16 == 0,
+ * K % 64 == 0) ->
+ *   d_s4  N K / 32 bytes  scale byte e + 127 of block (n, kb = k / 32), e = floor(log2(absmax_block)) - 2 (never below -120; 0 for
+ *                         an all-zero block), in scale panels: block (p = n / 16, c = k / 64) is the 32 B at ((p K / 64) + c) 32,
+ *                         row n = 16 p + li owns bytes 2 li (kb even) and 2 li + 1 (kb odd)
+ *   d_q4  N K / 2 bytes   e2m1 codes, magnitude RNE(min(|W| 2^-e, 6)) over {0, 0.5, 1, 1.5, 2, 3, 4, 6} (ties to the even code),
+ *                         sign in bit 3, two per byte with the lower k in the low nibble, in code panels: block (p, c) is the 512 B
+ *                         at ((p K / 64) + c) 512; lane g 16 + li owns 8 bytes, bytes 0..3 = k 64 c + 8 g + 0..7, bytes 4..7 =
+ *                         k 64 c + 32 + 8 g + 0..7.  A code whose value q 2^e would be subnormal in the operand type is +0, and so
+ *                         is a negative zero
+ *   d_dq  (optional)      q 2^e in the operand type, row-major [N,K], exact; may be d_src (in place)
+ * Bind q4 / s4 as "dec.{l}.{wqkv,wo,wgu,wd}.q4" (OPUS_F4E2M1X2 [N,K/2]) / ".s4" (OPUS_E8M0 [N,K/32]) beside the panel-tiled dq
+ * bound under the usual name (Llama / Qwen2 layers; both tensors of a projection or neither, and not beside its FP8 form): the
+ * decode step's GEMMs that have an MXFP4 form (the kernels that have an FP8 form) then stream 0.27 of the bytes of the same
+ * numbers; every other launch reads the operand-type tensor.  Synchronises `stream`.  OPUS_EBADARG when a weight is not finite
+ * (the outputs are then not to be used).  Added within ABI 10. */
+int opus_quantize_mxfp4(const void *d_src, int64_t N, int64_t K, void *d_q4, void *d_s4, void *d_dq, void *stream);
 
 /* Rows E1-E4: ProteinSeqEmbeddingExtractor.get_protein_seq_embeddings (cstp_v3/modelling.py:37-57):
  * tokens int32 [B,T] (<cls> seq <eos>, pad = 1), lens int32 [B] (incl. <cls>,<eos>) ->
@@ -567,6 +590,11 @@ int opus_debug_gemm_plan(opus_ctx *ctx, int32_t *plan);
 int opus_debug_gemm_w8(opus_ctx *ctx, int32_t form, const void *d_A, const void *d_W, const void *d_q8, const void *d_e8,
                        const float *d_bias, const float *d_residual, void *d_C, int32_t M, int32_t N, int32_t K, int32_t epi,
                        int32_t out_f32, float eps, int32_t *ks, int32_t *ran_w8, void *stream);
+/* opus_debug_gemm_w8 with the MXFP4 form of W (opus_quantize_mxfp4: d_q4, d_s4) in the place of the FP8 form; *ran_w4 (HOST) = 1
+ * when the routed kernel streamed the MXFP4 panels.  Added within ABI 10 (a new symbol only). */
+int opus_debug_gemm_w4(opus_ctx *ctx, int32_t form, const void *d_A, const void *d_W, const void *d_q4, const void *d_s4,
+                       const float *d_bias, const float *d_residual, void *d_C, int32_t M, int32_t N, int32_t K, int32_t epi,
+                       int32_t out_f32, float eps, int32_t *ks, int32_t *ran_w4, void *stream);
 /* Process-wide tuning knob of the benchmarks / parity tests (no reference counterpart): "no_stream" = 1 routes the narrow
  * GEMMs of the batched decode step through the round-2 split-K kernels instead of gemm_stream_kernel; "pp_gm" = tile rows
  * per rasterisation group of the big tiled GEMM; "debug_a_tiled" = 1: opus_debug_gemm takes A in fragment order; "no_ln_fusion" = 1: stand-alone normalisation kernels
@@ -732,7 +760,7 @@ int opus_last_logits(opus_ctx *ctx, float *d_out, int32_t B, void *stream);
  * launched from a graph.  "graphs_cached".  "decode_steps": decode steps the generate loops enqueued - with an EOS id or a stop
  * sequence the loop polls the rows' state with a bounded run-ahead and stops at most 2 steps after the last row finished (HF stops
  * at once; the extra steps emit pad ids only, the returned ids and n_out are exact).  "w8_gemms": GEMMs issued on this context
- * (eagerly or while a graph was captured; replays are not counted) whose kernel streamed the FP8 panels. */
+ * (eagerly or while a graph was captured; replays are not counted) whose kernel streamed the FP8 panels.  "w4_gemms": the same for the MXFP4 panels. */
 int64_t opus_stat(opus_ctx *ctx, const char *name);
 
 /* Measurement support (bench.py).  With timing enabled (off by default; decode runs eagerly instead of from the

@@ -20,6 +20,7 @@ ABI_VERSION = 10
 
 OPUS_F16, OPUS_F32, OPUS_I32, OPUS_I64, OPUS_U8 = 0, 1, 2, 3, 4      # (OPUS_F16 = the build's 16-bit operand type)
 OPUS_F8E4M3, OPUS_I8 = 5, 6                                          # FP8 decoder weights: the panels' codes, the row exponents
+OPUS_F4E2M1X2, OPUS_E8M0 = 7, 8                                      # MXFP4 decoder weights: packed e2m1 pairs, the block scales
 
 
 def operand_dtype():
@@ -102,6 +103,9 @@ SIGNATURES = {
     "opus_tile_weight": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P]),
     "opus_quantize_fp8": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P]),
     "opus_debug_gemm_w8": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
+    "opus_quantize_mxfp4": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P]),
+    "opus_debug_gemm_w4": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
     "opus_esm2_encode": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
     "opus_esm2_encode_packed": (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.c_int32, _P, _P]),

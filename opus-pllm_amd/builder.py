@@ -344,10 +344,13 @@ def load_pretrained_model(model_base_path, adapter_path, model_name, load_8bit=F
     CUDA-only library, out of scope): the weights are loaded unquantised in fp16 and a warning says so.
     decoder_weights=None | "fp8" | "fp8_dequantized": "fp8" quantises the decoder layers' projections to e4m3 with a power-of-two
     scale per output row; the decode step's weight-streaming kernels read the FP8 panels, everything else computes with the dequantised
-    fp16 tensors (the same numbers); model.decoder_weight_format reports it.
+    fp16 tensors (the same numbers); model.decoder_weight_format reports it.  "mxfp4" | "mxfp4_dequantized": the same with OCP
+    MXFP4 (e2m1 codes, one power-of-two scale per 32 consecutive k of a row; 4.25 bits per weight streamed by the decode step) -
+    uncalibrated round-to-nearest with ~11 % relative rms error per row, i.e. a different model, and like "fp8" it costs memory.
     """
     if load_8bit or load_4bit:
-        warnings.warn("NF4 / int8 loading is not built for MI355X (bitsandbytes is CUDA-only): loading unquantised fp16")
+        warnings.warn("NF4 / int8 loading is not built for MI355X (bitsandbytes is CUDA-only): loading unquantised fp16 "
+                      "(decoder_weights=\"mxfp4\" is the 4-bit decode option that is built: OCP MXFP4, not NF4)")
     # decoder_weights="fp8": the decoder layers' projections also as FP8 panels for the decode step (weights.DeviceWeights._fp8) -
     # a decode-throughput option that costs memory (the operand-type tensors stay); None: unquantised
     decoder_weights = kwargs.pop("decoder_weights", None)

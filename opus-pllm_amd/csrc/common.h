@@ -138,6 +138,51 @@ __device__ __forceinline__ float exp2_i8(int e) { return __builtin_bit_cast(floa
 // zeroed by the caller) is set when a weight is not finite
 hipError_t launch_quantize_fp8(const half_t *src, int64_t N, int64_t K, uint8_t *q8, int8_t *e8, half_t *dq, int *bad, hipStream_t s);
 
+// MXFP4 decoder weights (quant.hip, DESIGN section 4 "MXFP4 panels").  W[N][K] as OCP e2m1 codes (sign in bit 3, two per byte, the
+// lower k in the low nibble) with one e8m0 scale byte per 32 consecutive k of a row.
+// Code panels: block (p = n / 16, c = k / 64) is the 512 B at ((p K / 64) + c) 512; lane g 16 + li (n = 16 p + li) owns 8 bytes,
+// bytes 0 .. 3 = k 64 c + 8 g + 0 .. 7 (the first k-step of the chunk), bytes 4 .. 7 = k 64 c + 32 + 8 g + 0 .. 7 (the second):
+// one wave-wide 8-B load is 512 B of contiguous HBM.  Scale panels: block (p, c) is the 32 B at ((p K / 64) + c) 32, row li owns
+// bytes 2 li (the first k-step's scale) and 2 li + 1 (the second's): one 2-B load per lane, 32 B of contiguous HBM per wave.
+// mx4_code_off: the byte that holds element (n, k) (nibble k & 1); mx4_scale_off: the byte of (n, block kb = k / 32).
+__host__ __device__ __forceinline__ int64_t mx4_code_off(int64_t n, int64_t k, int64_t K) {
+    return ((n >> 4) * (K >> 6) + (k >> 6)) * 512 + ((((k & 31) >> 3) << 4) + (n & 15)) * 8 + ((k & 63) >> 5) * 4 + ((k & 7) >> 1);
+}
+__host__ __device__ __forceinline__ int64_t mx4_scale_off(int64_t n, int64_t kb, int64_t K) {
+    return ((n >> 4) * (K >> 6) + (kb >> 1)) * 32 + (n & 15) * 2 + (kb & 1);
+}
+constexpr int W4_EXP_MIN = W8_EXP_MIN;      // floor of the block exponents: the scale byte e + 127 is never 0 (nor 255)
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+// 16 e2m1 codes (one lane's 8 bytes of an MXFP4 code block) and the two scale bytes of (row, chunk) in the low 16 bits of s2 ->
+// the two B operands of the chunk: v_cvt_scalef32_pk_{f16,bf16}_fp4 multiplies by the fp32 whose exponent byte is the scale and
+// whose mantissa is zero, so the results ARE the dequantised weights (normal numbers of the operand type or zero, by the
+// quantiser's flush rule)
+__device__ __forceinline__ void mx4x16_to_h8(u32x2 q, uint32_t s2, h8 &lo, h8 &hi) {
+    const float s0 = __builtin_bit_cast(float, (s2 & 0xffu) << 23), s1 = __builtin_bit_cast(float, (s2 & 0xff00u) << 15);
+#ifdef OPUS_BF16
+#define OPUS_CVT_FP4(w, sc, sel) __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4((w), (sc), sel)
+#else
+#define OPUS_CVT_FP4(w, sc, sel) __builtin_amdgcn_cvt_scalef32_pk_f16_fp4((w), (sc), sel)
+#endif
+    const h2 a0 = OPUS_CVT_FP4(q[0], s0, 0), a1 = OPUS_CVT_FP4(q[0], s0, 1), a2 = OPUS_CVT_FP4(q[0], s0, 2), a3 = OPUS_CVT_FP4(q[0], s0, 3);
+    const h2 b0 = OPUS_CVT_FP4(q[1], s1, 0), b1 = OPUS_CVT_FP4(q[1], s1, 1), b2 = OPUS_CVT_FP4(q[1], s1, 2), b3 = OPUS_CVT_FP4(q[1], s1, 3);
+#undef OPUS_CVT_FP4
+    lo = h8{a0[0], a0[1], a1[0], a1[1], a2[0], a2[1], a3[0], a3[1]};
+    hi = h8{b0[0], b0[1], b1[0], b1[1], b2[0], b2[1], b3[0], b3[1]};
+}
+// One lane's share of an MXFP4 16-row x 64-k weight block in registers, the lane's base pointers into the code and scale panels,
+// the load of chunk c and the conversion to the two B operands (gemm_skinny_kernel's W4 form)
+struct mx4reg { u32x2 q; uint32_t s; };
+struct mx4ptr { const uint8_t *q, *s; };
+__device__ __forceinline__ mx4reg q_load(mx4ptr qp, int64_t c) {
+    return mx4reg{__builtin_nontemporal_load(reinterpret_cast<const u32x2 *>(qp.q + c * 512)),
+                  __builtin_nontemporal_load(reinterpret_cast<const uint16_t *>(qp.s + c * 32))};
+}
+__device__ __forceinline__ void q_to_h8(mx4reg q, h8 &lo, h8 &hi) { mx4x16_to_h8(q.q, q.s, lo, hi); }
+// quant.hip: q4 (code panels, N K / 2 bytes), s4 (scale panels, N K / 32 bytes), dq (operand type, row-major [N, K]; may be null or
+// src) from row-major src [N, K]; *bad (device, zeroed by the caller) is set when a weight is not finite
+hipError_t launch_quantize_mxfp4(const half_t *src, int64_t N, int64_t K, uint8_t *q4, uint8_t *s4, half_t *dq, int *bad, hipStream_t s);
+
 constexpr int HANDOFF_WORDS = 1024, HANDOFF_ERR = 1023;
 constexpr int HANDOFF_SPIN_LIMIT = 1 << 19;   // polls (s_sleep(4) + one L2 round trip each: >= 0.3 s) before a waiter gives up
 
@@ -227,6 +272,11 @@ struct GemmParams {
     const uint8_t *q8 = nullptr;
     const int8_t *e8 = nullptr;
     int *ran_w8 = nullptr;
+    // MXFP4 form of W (mx4_code_off / mx4_scale_off panels, the same values as W): as q8 / e8 - a kernel that has a W4 instantiation
+    // streams these instead of W and sets *ran_w4 (HOST) = 1.  At most one of the two forms is offered.
+    const uint8_t *q4 = nullptr;
+    const uint8_t *s4 = nullptr;
+    int *ran_w4 = nullptr;
 };
 constexpr int PP_PLAN_WORDS = 5;
 enum PpTail { PP_TAIL_NONE = 0, PP_TAIL_PAIR = 1, PP_TAIL_REDUCE = 2 };

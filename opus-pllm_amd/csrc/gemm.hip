@@ -80,8 +80,12 @@ __device__ __forceinline__ float silu(float x) { return x * __builtin_amdgcn_rcp
 // W8 (MT = 1): the weights come from the FP8 panels p.q8 - one 16-B load per lane and chunk instead of two, converted exactly to
 // the operand type in front of the MFMA (fp8x16_to_h8) - and the fp32 sums of column n are multiplied by 2^e8[n] in the epilogue,
 // ahead of the norm scale, bias, activation and residual.  Everything else - k-parts, rotation, staging, reduction - is the same.
-template <int MT, int EPI, bool NORM, bool ALDS, bool W8 = false>
+// W4 (MT = 1): the same loop on the MXFP4 panels p.q4 / p.s4 - per lane and chunk one 8-B load of codes and one 2-B load of the two
+// scale bytes, the scaled conversion in front of the MFMA (mx4x16_to_h8) - with nothing left for the epilogue: the converted
+// values are the dequantised operands.
+template <int MT, int EPI, bool NORM, bool ALDS, bool W8 = false, bool W4 = false>
 __global__ __launch_bounds__(1024) void gemm_skinny_kernel(GemmParams p) {
+    static_assert(!(W8 && W4), "one quantised form at a time");
     extern __shared__ __attribute__((aligned(16))) float red[];
     OPUS_ARGS_ONE_BATCH(p);
     constexpr int PB = EPI == EPI_SILU_GU16 ? 2 : 1;
@@ -109,7 +113,129 @@ __global__ __launch_bounds__(1024) void gemm_skinny_kernel(GemmParams p) {
 #pragma unroll
     for (int i = 0; i < MT; ++i) { acc[i] = f4{0.f, 0.f, 0.f, 0.f}; ssq[i] = 0.f; }
 
-    if constexpr (W8) {
+    if constexpr (W4) {   // (the FP8 loop below with the MXFP4 registers, loads and conversion)
+        static_assert(!W4 || MT == 1, "the MXFP4 form is built for M <= 16");
+        constexpr int U = (NORM && !ALDS) ? 2 : 4;           // (four chunks of fp32 activations + the conversions: past 128 VGPRs)
+        // one lane's share of a chunk in registers (8 code bytes, 2 scale bytes), where it comes from, its load and conversion
+        typedef mx4reg qreg_t;
+        const mx4ptr qp{p.q4 + ((int64_t)panel * chunks) * 512 + lane * 8, p.s4 + ((int64_t)panel * chunks) * 32 + li * 2};
+        // (the rotated k-range of the LDS-staged form, as below)
+        const int nck = c1 - c0;
+        const int rot = (ALDS && !p.no_rot && nck >= 2) ? (int)((wave * 3u) % (unsigned)nck) : 0;
+        auto phys = [&](int c) { const int q = c + rot; return q < c1 ? q : q - nck; };
+        auto qload = [&](qreg_t (&q)[U], int c) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (c + u < c1) q[u] = q_load(qp, phys(c + u));
+                else q[u] = qreg_t{};
+            }
+        };
+        if constexpr (ALDS) {
+            qreg_t qA[U], qB[U];
+            qload(qA, c0);                                  // weights first: HBM latency covers the staging
+            const int nthr = blockDim.x;
+            for (int m = 0; m < p.M; ++m) {
+                if (NORM) {
+                    const float4 *src = reinterpret_cast<const float4 *>(p.Af + (int64_t)m * p.lda);
+                    float s = 0.f;
+                    for (int i = tid; i < (p.K >> 2); i += nthr) {
+                        const float4 v = src[i];
+                        s += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+                        *reinterpret_cast<h4 *>(xs + (int64_t)m * p.K + 4 * i) = h4{(half_t)v.x, (half_t)v.y, (half_t)v.z, (half_t)v.w};
+                    }
+#pragma unroll
+                    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+                    if (lane == 0) wss[m * 16 + wave] = s;
+                } else {
+                    const h8 *src = reinterpret_cast<const h8 *>(p.A + (int64_t)m * p.lda);
+                    for (int i = tid; i < (p.K >> 3); i += nthr)
+                        *reinterpret_cast<h8 *>(xs + (int64_t)m * p.K + 8 * i) = src[i];
+                }
+            }
+            __syncthreads();
+            const int mr = li < p.M ? li : p.M - 1;          // rows >= M duplicate the last row: never stored
+            const h8 *xr = reinterpret_cast<const h8 *>(xs + (int64_t)mr * p.K + g * 8);
+            auto compute = [&](const qreg_t (&q)[U], int c) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int cc = phys(c + u < c1 ? c + u : c1 - 1);
+                    const h8 al = xr[cc * 8], ah = xr[cc * 8 + 4];
+                    h8 wl, wh;
+                    q_to_h8(q[u], wl, wh);
+                    acc[0] = mfma16(al, wl, acc[0]);
+                    acc[0] = mfma16(ah, wh, acc[0]);
+                }
+            };
+            for (int c = c0; c < c1; c += 2 * U) {
+                if (c + U < c1) qload(qB, c + U);
+                compute(qA, c);
+                if (c + U < c1) {
+                    if (c + 2 * U < c1) qload(qA, c + 2 * U);
+                    compute(qB, c + U);
+                }
+            }
+        } else {
+            // A rows through a buffer descriptor (rows >= M read as zeros), as the fp16 form below
+            constexpr int ESZ = NORM ? 4 : 2;
+            const __amdgpu_buffer_rsrc_t arsrc = __builtin_amdgcn_make_buffer_rsrc(
+                NORM ? (void *)p.Af : (void *)p.A, 0, (int)((int64_t)((p.M - 1) * p.lda + p.K) * ESZ), 0x00020000);
+            const int aoff = li < p.M ? (int)((li * p.lda + g * 8) * ESZ) : 0x40000000;
+            struct ARaw { u32x4 v[NORM ? 4 : 2]; };
+            auto load_a = [&](int c, ARaw &r) {
+                const int o = aoff + c * 64 * ESZ;
+                if (NORM) {
+                    r.v[0] = __builtin_amdgcn_raw_buffer_load_b128(arsrc, o, 0, 0);
+                    r.v[1] = __builtin_amdgcn_raw_buffer_load_b128(arsrc, o + 16, 0, 0);
+                    r.v[2] = __builtin_amdgcn_raw_buffer_load_b128(arsrc, o + 128, 0, 0);
+                    r.v[3] = __builtin_amdgcn_raw_buffer_load_b128(arsrc, o + 144, 0, 0);
+                } else {
+                    r.v[0] = __builtin_amdgcn_raw_buffer_load_b128(arsrc, o, 0, 0);
+                    r.v[1] = __builtin_amdgcn_raw_buffer_load_b128(arsrc, o + 64, 0, 0);
+                }
+            };
+            auto conv_a = [&](const ARaw &r, h8 &lo, h8 &hi) {
+                if (NORM) {
+                    const float4 a0 = __builtin_bit_cast(float4, r.v[0]), a1 = __builtin_bit_cast(float4, r.v[1]);
+                    const float4 b0 = __builtin_bit_cast(float4, r.v[2]), b1 = __builtin_bit_cast(float4, r.v[3]);
+                    ssq[0] += (a0.x * a0.x + a0.y * a0.y) + (a0.z * a0.z + a0.w * a0.w) + (a1.x * a1.x + a1.y * a1.y) +
+                              (a1.z * a1.z + a1.w * a1.w) + (b0.x * b0.x + b0.y * b0.y) + (b0.z * b0.z + b0.w * b0.w) +
+                              (b1.x * b1.x + b1.y * b1.y) + (b1.z * b1.z + b1.w * b1.w);
+                    lo = h8{(half_t)a0.x, (half_t)a0.y, (half_t)a0.z, (half_t)a0.w, (half_t)a1.x, (half_t)a1.y, (half_t)a1.z, (half_t)a1.w};
+                    hi = h8{(half_t)b0.x, (half_t)b0.y, (half_t)b0.z, (half_t)b0.w, (half_t)b1.x, (half_t)b1.y, (half_t)b1.z, (half_t)b1.w};
+                } else {
+                    lo = __builtin_bit_cast(h8, r.v[0]);
+                    hi = __builtin_bit_cast(h8, r.v[1]);
+                }
+            };
+            auto step = [&](qreg_t q, const ARaw &r) {
+                h8 al, ah, wl, wh;
+                conv_a(r, al, ah);
+                q_to_h8(q, wl, wh);
+                acc[0] = mfma16(al, wl, acc[0]);
+                acc[0] = mfma16(ah, wh, acc[0]);
+            };
+            int c = c0;
+            for (; c + U <= c1; c += U) {
+                qreg_t q[U];
+                ARaw ar[U];
+                qload(q, c);
+#pragma unroll
+                for (int u = 0; u < U; ++u) load_a(c + u, ar[u]);
+#pragma unroll
+                for (int u = 0; u < U; ++u) step(q[u], ar[u]);
+            }
+            for (; c < c1; ++c) {
+                const qreg_t q = q_load(qp, c);
+                ARaw ar;
+                load_a(c, ar);
+                step(q, ar);
+            }
+            if (NORM) {   // row m's squares sit in the 4 lanes (li = m, g = 0..3)
+                ssq[0] += __shfl_xor(ssq[0], 16, 64);
+                ssq[0] += __shfl_xor(ssq[0], 32, 64);
+            }
+        }
+    } else if constexpr (W8) {
         static_assert(!W8 || MT == 1, "the FP8 form is built for M <= 16");
         constexpr int U = (NORM && !ALDS) ? 2 : 4;           // (four chunks of fp32 activations + the conversions: past 128 VGPRs)
         const uint8_t *qp = p.q8 + ((int64_t)panel * chunks) * 1024 + lane * 16;
@@ -648,6 +774,16 @@ static hipError_t launch_skinny_t(const GemmParams &p, hipStream_t s) {
     const size_t lds = (size_t)W * MT * (256 + 16) * sizeof(float) + 256 * sizeof(float) +
                        (ALDS ? (size_t)p.M * p.K * sizeof(half_t) : 0);
     if constexpr (MT == 1) {
+        if (p.q4 && p.s4) {     // the MXFP4 form of the same launch: same grid, same workgroup, same LDS
+            if (lds > 48 * 1024) {
+                hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_skinny_kernel<1, EPI, NORM, ALDS, false, true>), lds);
+                if (ea != hipSuccess) return ea;
+            }
+            gemm_plan_set(p, KC_SKINNY, MT, 0, 0, ALDS ? 1 : 0, 0, 1, GC_NONE);
+            if (p.ran_w4) *p.ran_w4 = 1;
+            OPUS_LAUNCH(KC_SKINNY, (gemm_skinny_kernel<1, EPI, NORM, ALDS, false, true>), dim3(groups), dim3(64 * W), lds, s, p);
+            return hipGetLastError();
+        }
         if (p.q8 && p.e8) {     // the FP8 form of the same launch: same grid, same workgroup, same LDS
             if (lds > 48 * 1024) {
                 hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_skinny_kernel<1, EPI, NORM, ALDS, true>), lds);
@@ -692,8 +828,12 @@ static hipError_t launch_skinny_e(const GemmParams &p, hipStream_t s) {
 // sum(h^2); splitk_reduce_kernel combines them in a fixed order.
 // W8: the register sets hold one 16-B load per chunk from the FP8 panels p.q8, converted exactly in front of the MFMAs; the wave's
 // tile is multiplied by its columns' 2^e8 behind the main loop (ahead of the slabs, the norm scale and the gate / up exchange).
-template <int MT, int EPI, bool NORM, bool W8 = false>
+// W4: the register sets hold the lane's 8 code bytes and the 2 scale bytes of (row, chunk) from the MXFP4 panels p.q4 / p.s4 - two
+// loads per chunk, as the fp16 form - and the scaled conversion in front of the MFMAs yields the dequantised operands themselves:
+// nothing is left to do behind the main loop.
+template <int MT, int EPI, bool NORM, bool W8 = false, bool W4 = false>
 __global__ __launch_bounds__(256) void gemm_mid_kernel(GemmParams p, int ksplit) {
+    static_assert(!(W8 && W4), "one quantised form at a time");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int MP = 16 * MT;
     // 64-k chunks per LDS stage (one barrier each): deeper stages pay while the fp32/fp16 staging
@@ -767,13 +907,25 @@ __global__ __launch_bounds__(256) void gemm_mid_kernel(GemmParams p, int ksplit)
 #pragma unroll
     for (int i = 0; i < MT; ++i) acc[i] = f4{0.f, 0.f, 0.f, 0.f};
     // weights: two NAMED register sets of one stage each (runtime-indexed arrays would go to scratch)
-    typedef std::conditional_t<W8, u32x4, h8> wreg_t;               // (W8: the lane's 16 code bytes in wl, wh unused)
-    wreg_t wlA[CH], whA[CH], wlB[CH], whB[CH];
+    typedef std::conditional_t<W4, u32x2, std::conditional_t<W8, u32x4, h8>> wreg_t;   // (W8: the lane's 16 code bytes in wl, wh unused;
+    typedef std::conditional_t<W4, uint32_t, wreg_t> wreg2_t;                          //  W4: its 8 code bytes in wl, the 2 scale bytes in wh)
+    wreg_t wlA[CH], wlB[CH];
+    wreg2_t whA[CH], whB[CH];
     const uint8_t *qp = W8 ? p.q8 + ((int64_t)panel * chunks) * 1024 + lane * 16 : nullptr;
-    auto w_load = [&](wreg_t (&wl)[CH], wreg_t (&wh)[CH], int c) {
+    const uint8_t *q4p = W4 ? p.q4 + ((int64_t)panel * chunks) * 512 + lane * 8 : nullptr;
+    const uint8_t *s4p = W4 ? p.s4 + ((int64_t)panel * chunks) * 32 + li * 2 : nullptr;
+    auto w_load = [&](wreg_t (&wl)[CH], wreg2_t (&wh)[CH], int c) {
 #pragma unroll
         for (int u = 0; u < CH; ++u) {
-            if constexpr (W8) {
+            if constexpr (W4) {
+                if (c + u < c1) {
+                    wl[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x2 *>(q4p + (int64_t)(c + u) * 512));
+                    wh[u] = __builtin_nontemporal_load(reinterpret_cast<const uint16_t *>(s4p + (int64_t)(c + u) * 32));
+                } else {
+                    wl[u] = u32x2{0, 0};
+                    wh[u] = 0;
+                }
+            } else if constexpr (W8) {
                 if (c + u < c1) wl[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(qp + (int64_t)(c + u) * 1024));
                 else wl[u] = u32x4{0, 0, 0, 0};
             } else if (c + u < c1) {
@@ -786,12 +938,14 @@ __global__ __launch_bounds__(256) void gemm_mid_kernel(GemmParams p, int ksplit)
             }
         }
     };
-    auto compute = [&](const wreg_t (&wl)[CH], const wreg_t (&wh)[CH], int buf) {
+    auto compute = [&](const wreg_t (&wl)[CH], const wreg2_t (&wh)[CH], int buf) {
         const char *base = smem + buf * STAGE;
 #pragma unroll
         for (int u = 0; u < CH; ++u) {
             h8 w0, w1;
-            if constexpr (W8) {
+            if constexpr (W4) {
+                mx4x16_to_h8(wl[u], wh[u], w0, w1);
+            } else if constexpr (W8) {
                 fp8x16_to_h8(wl[u], w0, w1);
             } else {
                 w0 = wl[u];
@@ -2175,8 +2329,11 @@ hipError_t launch_splitk_reduce(const GemmParams &p, int ks, hipStream_t s) {
 // W8: the ring holds one 16-B register per chunk from the FP8 panels p.q8 instead of two (LPC loads per chunk in the vmcnt
 // arithmetic below), converted exactly in front of the MFMAs; the wave's tile is multiplied by its columns' 2^e8 behind the main loop,
 // ahead of the slabs / the row scale / the gate-up exchange.
-template <int MT, int EPI, bool W8 = false>
+// W4: the ring holds the lane's 8 code bytes and the 2 scale bytes of (row, chunk) from the MXFP4 panels p.q4 / p.s4 - two loads per
+// chunk, the fp16 form's vmcnt arithmetic - and the scaled conversion in front of the MFMAs yields the dequantised operands.
+template <int MT, int EPI, bool W8 = false, bool W4 = false>
 __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p, int ksplit) {
+    static_assert(!(W8 && W4), "one quantised form at a time");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     OPUS_ARGS_ONE_BATCH(p);
     constexpr int MP = 16 * MT;
@@ -2198,6 +2355,8 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p, int ksplit
     const int c0 = kpart_begin(chunks, ky, ksplit), c1 = kpart_begin(chunks, ky + 1, ksplit);
     const half_t *wp = p.W + ((int64_t)panel * chunks) * 1024 + lane * 8;
     const uint8_t *qp = W8 ? p.q8 + ((int64_t)panel * chunks) * 1024 + lane * 16 : nullptr;
+    const uint8_t *q4p = W4 ? p.q4 + ((int64_t)panel * chunks) * 512 + lane * 8 : nullptr;
+    const uint8_t *s4p = W4 ? p.s4 + ((int64_t)panel * chunks) * 32 + li * 2 : nullptr;
 
     typedef const __attribute__((address_space(1))) void *gptr_t;
     typedef __attribute__((address_space(3))) void *lptr_t;
@@ -2237,9 +2396,14 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p, int ksplit
     constexpr int U = 4;                                            // weight ring: 4 chunks = 8 KB per wave (8 measured slower)
     h8 wl[U], wh[U];
     u32x4 wq[U];                                                    // (W8: the ring; wl / wh are then unused)
+    u32x2 w4q[U];                                                   // (W4: the ring - the codes and, zero-extended, the 2 scale bytes)
+    uint32_t w4s[U];
     auto w_load = [&](int u, int c) {
         if (c < c1) {
-            if constexpr (W8) {
+            if constexpr (W4) {
+                w4q[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x2 *>(q4p + (int64_t)phys(c) * 512));
+                w4s[u] = __builtin_nontemporal_load(reinterpret_cast<const uint16_t *>(s4p + (int64_t)phys(c) * 32));
+            } else if constexpr (W8) {
                 wq[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(qp + (int64_t)phys(c) * 1024));
             } else {
                 const h8 *ptr = reinterpret_cast<const h8 *>(wp + (int64_t)phys(c) * 1024);
@@ -2265,16 +2429,26 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p, int ksplit
     };                                                                  //  LDS fragment reads can be scheduled around it)
     auto ld_q = [&](u32x4 &q, const uint8_t *ptr) { asm volatile("global_load_dwordx4 %0, %1, off nt" : "=&v"(q) : "v"(ptr)); };
     // chunk cn into ring slot u / the compiler fence on slot u / the counted wait on slot u / the chunk's MFMAs
+    auto ld_q4 = [&](u32x2 &q, uint32_t &sc, const uint8_t *qptr, const uint8_t *sptr) {
+        asm volatile("global_load_dwordx2 %0, %2, off nt\n\tglobal_load_ushort %1, %3, off nt" : "=&v"(q), "=&v"(sc) : "v"(qptr), "v"(sptr));
+    };
     auto ring_load = [&](int u, int cn) {
-        if constexpr (W8) ld_q(wq[u], qp + (int64_t)cn * 1024);
+        if constexpr (W4) ld_q4(w4q[u], w4s[u], q4p + (int64_t)cn * 512, s4p + (int64_t)cn * 32);
+        else if constexpr (W8) ld_q(wq[u], qp + (int64_t)cn * 1024);
         else ld_nt(wl[u], wh[u], wp + (int64_t)cn * 1024);
     };
     auto ring_pin = [&](int u) {
-        if constexpr (W8) asm volatile("" : "+v"(wq[u]));
+        if constexpr (W4) asm volatile("" : "+v"(w4q[u]), "+v"(w4s[u]));
+        else if constexpr (W8) asm volatile("" : "+v"(wq[u]));
         else asm volatile("" : "+v"(wl[u]), "+v"(wh[u]));
     };
     auto ring_mul = [&](int u, int i, h8 a0, h8 a1) {
-        if constexpr (W8) {
+        if constexpr (W4) {
+            h8 w0, w1;
+            mx4x16_to_h8(w4q[u], w4s[u], w0, w1);
+            acc[i] = mfma16(w0, a0, acc[i]);   // C^T tile
+            acc[i] = mfma16(w1, a1, acc[i]);
+        } else if constexpr (W8) {
             h8 w0, w1;
             fp8x16_to_h8(wq[u], w0, w1);
             acc[i] = mfma16(w0, a0, acc[i]);   // C^T tile
@@ -2326,7 +2500,10 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p, int ksplit
             if (u8 + 1 < SC) read_chunk(u8 + 1, fa[(u8 + 1) & 1]);
             // younger than this chunk's pair (requested U chunks ago): the U-1 later refills, plus this stage's PW DMA
             // requests when the pair was requested before them (first U chunks of the stage)
-            if constexpr (W8) {
+            if constexpr (W4) {
+                if (u8 < U) asm volatile("s_waitcnt vmcnt(%2)" : "+v"(w4q[u]), "+v"(w4s[u]) : "n"(LPC * (U - 1) + PWN));
+                else asm volatile("s_waitcnt vmcnt(%2)" : "+v"(w4q[u]), "+v"(w4s[u]) : "n"(LPC * (U - 1)));
+            } else if constexpr (W8) {
                 if (u8 < U) asm volatile("s_waitcnt vmcnt(%1)" : "+v"(wq[u]) : "n"(LPC * (U - 1) + PWN));
                 else asm volatile("s_waitcnt vmcnt(%1)" : "+v"(wq[u]) : "n"(LPC * (U - 1)));
             } else {
@@ -2443,10 +2620,11 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p, int ksplit
 //  panels make 256 workgroups instead of 224 (what an [8 gate | 8 up] panel layout would allow with the pair product done across
 //  lanes): 41.8 vs 42.4 us on the 28672-column shape (-1.4 %; lm_head 207 vs 197 us), timing only.  0.6 us per layer is not
 //  worth a second copy of every gate / up weight: the 224-workgroup grid costs less than the sweep's 256-vs-224 pure-stream gap.)
-template <int MT, int EPI, bool W8 = false>
+template <int MT, int EPI, bool W8 = false, bool W4 = false>
 static hipError_t launch_wide(const GemmParams &p, hipStream_t s) {
-    if constexpr (!W8) {              // the FP8 form of the same launch: same grid, LDS, k-parts
+    if constexpr (!W8 && !W4) {       // the FP8 / MXFP4 form of the same launch: same grid, LDS, k-parts
         if (p.q8 && p.e8) return launch_wide<MT, EPI, true>(p, s);
+        if (p.q4 && p.s4) return launch_wide<MT, EPI, false, true>(p, s);
     }
     const int blocks = cdiv((p.N + 15) >> 4, 8), chunks = p.K / 64;
     int ks = 1;
@@ -2460,16 +2638,17 @@ static hipError_t launch_wide(const GemmParams &p, hipStream_t s) {
     }
     if (p.ks_out) *p.ks_out = ks;
     const int lds = 2 * (MT <= 4 ? 8 : 4) * 16 * MT * 128 + 16 * MT * (int)sizeof(float);   // two stages + the rows' 1 / rms
-    hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_wide_kernel<MT, EPI, W8>), lds);
+    hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_wide_kernel<MT, EPI, W8, W4>), lds);
     if (ea != hipSuccess) return ea;
     gemm_plan_set(p, KC_WIDE, MT, 0, 0, 0, 0, ks, ks == 1 ? GC_NONE : GC_SLABS);   // (launch_reduce names the reduce it takes)
     if (W8 && p.ran_w8) *p.ran_w8 = 1;
+    if (W4 && p.ran_w4) *p.ran_w4 = 1;
     if (ks > 1 && p.row_ssq) {       // k-parts leave raw slabs: the row scale is applied by whoever combines them, not here
         GemmParams q = p;
         q.row_ssq = nullptr;
-        OPUS_LAUNCH(KC_WIDE, (gemm_wide_kernel<MT, EPI, W8>), dim3(blocks, ks), dim3(512), lds, s, q, ks);
+        OPUS_LAUNCH(KC_WIDE, (gemm_wide_kernel<MT, EPI, W8, W4>), dim3(blocks, ks), dim3(512), lds, s, q, ks);
     } else {
-        OPUS_LAUNCH(KC_WIDE, (gemm_wide_kernel<MT, EPI, W8>), dim3(blocks, ks), dim3(512), lds, s, p, ks);
+        OPUS_LAUNCH(KC_WIDE, (gemm_wide_kernel<MT, EPI, W8, W4>), dim3(blocks, ks), dim3(512), lds, s, p, ks);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || ks == 1 || p.slab_only) return e;
@@ -2477,10 +2656,11 @@ static hipError_t launch_wide(const GemmParams &p, hipStream_t s) {
 }
 
 
-template <int MT, int EPI, bool NORM, bool W8 = false>
+template <int MT, int EPI, bool NORM, bool W8 = false, bool W4 = false>
 static hipError_t launch_mid_t(const GemmParams &p, hipStream_t s) {
-    if constexpr (!W8 && MT <= 4) {   // the FP8 form of the same launch (MT = 6 / 8: beyond MID_MAX_M, never launched)
+    if constexpr (!W8 && !W4 && MT <= 4) {   // the FP8 / MXFP4 form of the same launch (MT = 6 / 8: beyond MID_MAX_M, never launched)
         if (p.q8 && p.e8) return launch_mid_t<MT, EPI, NORM, true>(p, s);
+        if (p.q4 && p.s4) return launch_mid_t<MT, EPI, NORM, false, true>(p, s);
     }
     const int blocks = cdiv((p.N + 15) >> 4, 4), chunks = p.K / 64;
     // k-parts: enough workgroups for ~8 waves per CU, at least 4 chunks each, slabs within the workspace
@@ -2495,13 +2675,14 @@ static hipError_t launch_mid_t(const GemmParams &p, hipStream_t s) {
     constexpr int CH = MT <= 2 ? 4 : 1;
     const size_t lds = 2 * CH * 16 * MT * 128 + 16 * MT * sizeof(float) + 2 * MT * 4 * 64 * sizeof(float);
     if (lds > 48 * 1024) {
-        hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_mid_kernel<MT, EPI, NORM, W8>), lds);
+        hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_mid_kernel<MT, EPI, NORM, W8, W4>), lds);
         if (ea != hipSuccess) return ea;
     }
     if (p.row_ssq && ks == 1) return hipErrorInvalidValue;            // only the split-K reduce applies a row scale here
     gemm_plan_set(p, KC_MID, MT, 0, 0, 0, 0, ks, GC_NONE);
     if (W8 && p.ran_w8) *p.ran_w8 = 1;
-    OPUS_LAUNCH(KC_MID, (gemm_mid_kernel<MT, EPI, NORM, W8>), dim3(blocks, ks), dim3(256), lds, s, p, ks);
+    if (W4 && p.ran_w4) *p.ran_w4 = 1;
+    OPUS_LAUNCH(KC_MID, (gemm_mid_kernel<MT, EPI, NORM, W8, W4>), dim3(blocks, ks), dim3(256), lds, s, p, ks);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || ks == 1) return e;
     return launch_reduce<EPI>(p, ks, s);

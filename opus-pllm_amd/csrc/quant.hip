@@ -107,4 +107,78 @@ hipError_t launch_quantize_fp8(const half_t *src, int64_t N, int64_t K, uint8_t 
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------ MXFP4
+// Load-time MXFP4 quantiser ("MXFP4 panels"; tests/w4_ref.py is the CPU twin).  A block is 32 consecutive k of
+// one row:
+//   s4   the e8m0 scale byte e + 127, e = floor(log2(absmax_block)) - 2 read off the fp32 exponent field of absmax_block (the OCP
+//        MX v1.0 rule: the largest e2m1 value is 1.5 2^2); never below W4_EXP_MIN; 0 for an all-zero block (and for an absmax below
+//        the smallest normal fp32: bf16 only)
+//   q4   e2m1 codes, magnitude RNE(min(|w| 2^-e, 6)) over {0, 0.5, 1, 1.5, 2, 3, 4, 6} with ties to the even code, sign in bit 3,
+//        two per byte (the lower k in the low nibble), in the code panels (mx4_code_off); a code whose value q 2^e would be
+//        subnormal in the operand type is +0, and so is a negative zero
+//   dq   q 2^e in the operand type, row-major (exact: 2 significant bits, normal by the rule above, at most 1.5 2^(e + 2) <= absmax)
+// All of it in integer arithmetic on the fp32 bits of the weights.  A non-finite weight sets *bad; its block's codes are +0.
+//
+// One thread per 8 consecutive k of a row (16 B of W in, 4 B of codes and 16 B of dq out); the four threads of a block are four
+// neighbouring lanes of one wave (K % 64 == 0, so N K / 8 is a multiple of 128: whole waves leave at the bounds check).
+__global__ __launch_bounds__(256) void mxfp4_quantize_kernel(const half_t *src, int64_t N, int64_t K,   // (dq may be src: no restrict)
+                                                             uint8_t *__restrict__ q4, uint8_t *__restrict__ s4, half_t *dq,
+                                                             int *__restrict__ bad) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N * (K >> 3)) return;
+    const int64_t n = i / (K >> 3), k = (i % (K >> 3)) * 8;
+    const h8 w = *reinterpret_cast<const h8 *>(src + n * K + k);
+    uint32_t mag[8], mx = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        mag[j] = __builtin_bit_cast(uint32_t, (float)w[j]) & 0x7fffffffu;
+        mx = mag[j] > mx ? mag[j] : mx;                       // (non-negative floats order as their bits)
+    }
+#pragma unroll
+    for (int o = 1; o <= 2; o <<= 1) {                        // the block's four lanes
+        const uint32_t other = (uint32_t)__shfl_xor((int)mx, o, 64);
+        mx = other > mx ? other : mx;
+    }
+    const bool nonfinite = mx >= 0x7f800000u;                 // inf or NaN somewhere in the block
+    int e = 0;
+    if (mx >= 0x00800000u) {
+        e = (int)(mx >> 23) - 127 - 2;
+        e = e < W4_EXP_MIN ? W4_EXP_MIN : e;
+    }
+    if (nonfinite) { *bad = 1; e = 0; }
+    h8 d;
+    uint32_t codes = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        // v = |w| 2^-e as fp32 bits (exact: the exponent field moves); below the smallest normal fp32 it rounds to 0 anyway
+        const int ex = (int)(mag[j] >> 23);
+        uint32_t m = 0;
+        if (!nonfinite && ex > 0 && ex - e > 0) {
+            const uint32_t v = mag[j] - ((uint32_t)e << 23);
+            // nearest of the 8 magnitudes, ties to the even code: (0.25, 0.75) -> 0.5, [0.75, 1.25] -> 1, (1.25, 1.75) -> 1.5,
+            // [1.75, 2.5] -> 2, (2.5, 3.5) -> 3, [3.5, 5] -> 4, above 5 -> 6 (saturating)
+            m = (v > 0x3e800000u) + (v >= 0x3f400000u) + (v > 0x3fa00000u) + (v >= 0x3fe00000u) + (v > 0x40200000u) +
+                (v >= 0x40600000u) + (v > 0x40a00000u);
+        }
+        const int xq = m == 1 ? -1 : (int)(m >> 1) - 1;      // binary exponent of the magnitude (m > 0)
+        if (m == 0 || xq + e < OPERAND_MIN_EXP) m = 0;        // zero, or subnormal in the operand type: +0
+        uint32_t vb = 0, code = 0;
+        if (m) {
+            const uint32_t sign = __builtin_bit_cast(uint32_t, (float)w[j]) >> 31;
+            code = m | (sign << 3);
+            vb = (sign << 31) | ((uint32_t)(xq + e + 127) << 23) | ((m >= 2 && (m & 1)) ? 0x400000u : 0u);
+        }
+        d[j] = (half_t)__builtin_bit_cast(float, vb);
+        codes |= code << (4 * j);
+    }
+    *reinterpret_cast<uint32_t *>(q4 + mx4_code_off(n, k, K)) = codes;
+    if ((k & 31) == 0) s4[mx4_scale_off(n, k >> 5, K)] = (uint8_t)(e + 127);
+    if (dq) *reinterpret_cast<h8 *>(dq + n * K + k) = d;
+}
+
+hipError_t launch_quantize_mxfp4(const half_t *src, int64_t N, int64_t K, uint8_t *q4, uint8_t *s4, half_t *dq, int *bad, hipStream_t s) {
+    hipLaunchKernelGGL(mxfp4_quantize_kernel, dim3(cdiv(N * (K >> 3), 256)), dim3(256), 0, s, src, N, K, q4, s4, dq, bad);
+    return hipGetLastError();
+}
+
 }  // namespace opus

@@ -417,8 +417,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--max_new_tokens", type=int, default=None)
     p.add_argument("--switch_projector_type", type=str, default="mlp2x_gelu")
     p.add_argument("--load-4bit", action="store_true")
-    p.add_argument("--decoder_weights", choices=("fp8",), default=None,
-                   help="fp8: decoder-layer weights also as e4m3 panels for the decode step (faster decode, 1.5x the memory of those weights)")
+    p.add_argument("--decoder_weights", choices=("fp8", "mxfp4"), default=None,
+                   help="fp8 / mxfp4: decoder-layer weights also as e4m3 / MXFP4 panels for the decode step (faster decode, 1.5x / 1.27x "
+                        "the memory of those weights; mxfp4 is uncalibrated 4-bit rounding: a different model)")
     p.add_argument("--load-8bit", action="store_true")
     p.add_argument("--batch_size", type=int, default=8)          # hard-coded 8 in the reference (:75)
     p.add_argument("--max_residues", type=int, default=1024)

@@ -113,7 +113,8 @@ class OpusLlamaForCausalLM:
     @property
     def decoder_weight_format(self) -> str:
         """What the decoder layers' projections are bound as: "fp16" / "bf16" (the build's operand type, unquantised), "fp8" (FP8
-        panels for the decode step beside the dequantised operand-type tensors) or "fp8_dequantized" (those tensors alone)."""
+        panels for the decode step beside the dequantised operand-type tensors), "fp8_dequantized" (those tensors alone), "mxfp4" or
+        "mxfp4_dequantized" (the same with MXFP4 code and scale panels)."""
         return self.weights.decoder_weight_format
 
     def __del__(self):

@@ -173,7 +173,34 @@ def untile_fp8(q8: torch.Tensor) -> torch.Tensor:
     return q8.reshape(N // 16, K // 64, 4, 16, 2, 8).permute(0, 3, 1, 4, 2, 5).reshape(N, K).contiguous()
 
 
+def quantize_mxfp4(t: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Row-major operand-type [N,K] on the GPU -> (q4 uint8 [N,K/2]: packed e2m1 codes in the MXFP4 code panels, s4 uint8 [N,K/32]:
+    the e8m0 block scales in the scale panels, dq: q 2^e in the operand type, row-major) via opus_quantize_mxfp4.  Raises OpusError
+    when a weight is not finite."""
+    assert t.is_cuda and t.dtype == _cabi.operand_dtype() and t.dim() == 2 and t.is_contiguous()
+    N, K = t.shape
+    q4 = torch.empty((N, K // 2), dtype=torch.uint8, device=t.device)
+    s4 = torch.empty((N, K // 32), dtype=torch.uint8, device=t.device)
+    dq = torch.empty_like(t)
+    with torch.cuda.device(t.device):
+        _cabi.check(_cabi.lib().opus_quantize_mxfp4(t.data_ptr(), N, K, q4.data_ptr(), s4.data_ptr(), dq.data_ptr(),
+                                                    torch.cuda.current_stream(t.device).cuda_stream))
+    return q4, s4, dq
+
+
+def untile_mxfp4(q4: torch.Tensor, s4: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """MXFP4 code panels [N,K/2] and scale panels [N,K/32] -> (the codes 0 .. 15 row-major uint8 [N,K], the scale bytes row-major
+    uint8 [N,K/32]) (host-side index arithmetic; tests and debugging only)."""
+    N, K = q4.shape[0], q4.shape[1] * 2
+    b = q4.reshape(N // 16, K // 64, 4, 16, 2, 4)
+    codes = torch.stack((b & 15, b >> 4), dim=-1).reshape(N // 16, K // 64, 4, 16, 2, 8)
+    codes = codes.permute(0, 3, 1, 4, 2, 5).reshape(N, K).contiguous()
+    scales = s4.reshape(N // 16, K // 64, 16, 2).permute(0, 2, 1, 3).reshape(N, K // 32).contiguous()
+    return codes, scales
+
+
 DECODER_WEIGHT_FORMATS = (None, "fp8", "fp8_dequantized")
+DECODER_WEIGHT_FORMATS_MX = ("mxfp4", "mxfp4_dequantized")       # OCP MXFP4 (e2m1 codes, one e8m0 scale per 32 k of a row)
 
 
 def fp8_names(cfg: OpusConfig) -> List[str]:
@@ -189,7 +216,7 @@ class DeviceWeights:
     def __init__(self, cfg: OpusConfig, device: torch.device):
         self.cfg = cfg
         self.device = device
-        self.decoder_weights: Optional[str] = None       # None | "fp8" | "fp8_dequantized" (from_canonical / synthetic)
+        self.decoder_weights: Optional[str] = None       # None | "fp8" | "fp8_dequantized" | "mxfp4" | "mxfp4_dequantized" (from_canonical / synthetic)
         self.tensors: Dict[str, torch.Tensor] = {}
         # optional tensors bound beside the fused ones (the ESM-2 contact head: enc.contact.weight fp32 [enc_layers * enc_heads],
         # enc.contact.bias fp32 [1]; the ESM-2 masked-LM head: enc.lm.*); opus_weights_ready does not need them
@@ -251,7 +278,7 @@ class DeviceWeights:
 
         `lora` maps a canonical weight name to (A [r,in], B [out,r], alpha, r): merged into that weight
         first, W += (alpha / r) B A, as peft merge_and_unload does at model/builder.py:107-109 (row L1).
-        `decoder_weights`: None, "fp8" or "fp8_dequantized" (_fp8 below).
+        `decoder_weights`: None, "fp8" or "fp8_dequantized" (_fp8 below), "mxfp4" or "mxfp4_dequantized" (_mxfp4).
         """
         self = cls(cfg, torch.device(device))
         self._set_decoder_weights(decoder_weights)
@@ -297,8 +324,8 @@ class DeviceWeights:
         return self
 
     def _set_decoder_weights(self, decoder_weights: Optional[str]) -> None:
-        if decoder_weights not in DECODER_WEIGHT_FORMATS:
-            raise ValueError(f"decoder_weights={decoder_weights!r}: one of {DECODER_WEIGHT_FORMATS}")
+        if decoder_weights not in DECODER_WEIGHT_FORMATS + DECODER_WEIGHT_FORMATS_MX:
+            raise ValueError(f"decoder_weights={decoder_weights!r}: one of {DECODER_WEIGHT_FORMATS + DECODER_WEIGHT_FORMATS_MX}")
         self.decoder_weights = decoder_weights
         self._fp8_names = set(fp8_names(self.cfg)) if decoder_weights else set()
 
@@ -309,9 +336,23 @@ class DeviceWeights:
         launch without an FP8 kernel compute with the same numbers.  "fp8" also keeps the codes and exponents, bound as
         `name`.q8 / .e8 for the decode step (Llama / Qwen2; OPT / Galactica run on the dequantised tensors); "fp8_dequantized"
         keeps the dequantised tensors alone (the comparison model)."""
+        if self.decoder_weights in DECODER_WEIGHT_FORMATS_MX:
+            return self._mxfp4(name, t)
         q8, e8, dq = quantize_fp8(t.contiguous())
         if self.decoder_weights == "fp8" and self.cfg.dec_arch == 0:
             self.tensors[name + ".q8"], self.tensors[name + ".e8"] = q8, e8
+        return dq
+
+    def _mxfp4(self, name: str, t: torch.Tensor) -> torch.Tensor:
+        """The MXFP4 form of the fused decoder-layer weight `name`, at the same point of the load as _fp8: e2m1 codes with one
+        power-of-two scale per 32 consecutive k of a row (csrc/quant.hip).  Returns the dequantised weights (exact in the operand
+        type), which take the weight's place.  "mxfp4" also keeps the code and scale panels, bound as `name`.q4 / .s4 for the
+        decode step (Llama / Qwen2; OPT / Galactica run on the dequantised tensors); "mxfp4_dequantized" keeps the dequantised
+        tensors alone (the comparison model).  Uncalibrated round-to-nearest: ~11 % relative rms error per row on Gaussian
+        weights - a different model, and a decode-throughput option that ADDS 0.27 x the decoder-layer weights in memory."""
+        q4, s4, dq = quantize_mxfp4(t.contiguous())
+        if self.decoder_weights == "mxfp4" and self.cfg.dec_arch == 0:
+            self.tensors[name + ".q4"], self.tensors[name + ".s4"] = q4, s4
         return dq
 
     @property
@@ -337,7 +378,7 @@ class DeviceWeights:
                   mlm_head: bool = False, decoder_weights: Optional[str] = None) -> "DeviceWeights":
         """Fill the fused tensors on the GPU with the deterministic synthetic model (synth.py twin); contact_head: also the
         synthetic contact regression (synth.contact_head); mlm_head: also the synthetic masked-LM head (synth.mlm_head);
-        decoder_weights: None, "fp8" or "fp8_dequantized" (_fp8)."""
+        decoder_weights: None, "fp8" or "fp8_dequantized" (_fp8), "mxfp4" or "mxfp4_dequantized" (_mxfp4)."""
         self = cls(cfg, torch.device(device))
         self._set_decoder_weights(decoder_weights)
         lib = _cabi.lib()
@@ -392,10 +433,12 @@ class DeviceWeights:
     def bind(self, ctx) -> None:
         lib = _cabi.lib()
         codes = {torch.uint8: _cabi.OPUS_F8E4M3, torch.int8: _cabi.OPUS_I8}            # (the FP8 panels and their row exponents)
+        mx = {".q4": _cabi.OPUS_F4E2M1X2, ".s4": _cabi.OPUS_E8M0}                      # (the MXFP4 code and scale panels: uint8 both)
         for name, t in list(self.tensors.items()) + list(self.extra.items()):
             shape = (C.c_int64 * t.dim())(*t.shape)
             _cabi.check(lib.opus_bind_weight(ctx, name.encode(), t.data_ptr(),
-                                             _cabi.OPUS_F16 if t.dtype == _cabi.operand_dtype() else codes.get(t.dtype, _cabi.OPUS_F32),
+                                             _cabi.OPUS_F16 if t.dtype == _cabi.operand_dtype() else
+                                             mx[name[-3:]] if name[-3:] in mx else codes.get(t.dtype, _cabi.OPUS_F32),
                                              t.dim(), shape))
         _cabi.check(lib.opus_weights_ready(ctx))
 
