@@ -351,7 +351,7 @@ def load_pretrained_model(model_base_path, adapter_path, model_name, load_8bit=F
     if load_8bit or load_4bit:
         warnings.warn("NF4 / int8 loading is not built for MI355X (bitsandbytes is CUDA-only): loading unquantised fp16 "
                       "(decoder_weights=\"mxfp4\" is the 4-bit decode option that is built: OCP MXFP4, not NF4)")
-    # decoder_weights="fp8": the decoder layers' projections also as FP8 panels for the decode step (weights.DeviceWeights._fp8) -
+    # decoder_weights="fp8": the decoder layers' projections also as FP8 panels for the decode step (weights.DeviceWeights._quantize) -
     # a decode-throughput option that costs memory (the operand-type tensors stay); None: unquantised
     decoder_weights = kwargs.pop("decoder_weights", None)
     rank = accelerator.process_index if accelerator is not None else int(os.environ.get("LOCAL_RANK", "0"))

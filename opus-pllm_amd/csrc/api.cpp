@@ -51,14 +51,10 @@ struct EncLayer {   // the LayerNorm weights are folded into wqkv / w1 and the b
 struct DecLayer {   // arch 0: RMSNorm weights are folded into wqkv / wgu (and dec.lnf into lm_head) at load time
     const half_t *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wd = nullptr;
     const float *bqkv = nullptr;                      // Qwen2 q/k/v bias, OPT bias
-    // optional FP8 form of the four projections (dec.{l}.{wqkv,wo,wgu,wd}.q8 / .e8: the same values as the fp16 tensors, which
-    // then hold the dequantised weights); null: not bound.  Read by the decode step's GEMMs only (GemmAsk::w8).
-    const uint8_t *q8_qkv = nullptr, *q8_o = nullptr, *q8_gu = nullptr, *q8_d = nullptr;
-    const int8_t *e8_qkv = nullptr, *e8_o = nullptr, *e8_gu = nullptr, *e8_d = nullptr;
-    // optional MXFP4 form (dec.{l}.{wqkv,wo,wgu,wd}.q4 / .s4: code panels and scale panels, again the same values as the fp16
-    // tensors); a projection is bound in at most one quantised form (GemmAsk::w4)
-    const uint8_t *q4_qkv = nullptr, *q4_o = nullptr, *q4_gu = nullptr, *q4_d = nullptr;
-    const uint8_t *s4_qkv = nullptr, *s4_o = nullptr, *s4_gu = nullptr, *s4_d = nullptr;
+    // optional quantised form of the four projections (WQ_FORMATS: dec.{l}.{wqkv,wo,wgu,wd}.q8 / .e8 or .q4 / .s4 - the same
+    // values as the fp16 tensors, which then hold the dequantised weights); empty: not bound.  Read by the decode step's GEMMs
+    // only (GemmAsk::quant).
+    QuantW wq_qkv, wq_o, wq_gu, wq_d;
     // arch 1 (OPT / Galactica): LayerNorm affine parameters, fc1 / fc2 and the remaining biases
     const half_t *w1 = nullptr, *w2 = nullptr;
     const float *bo = nullptr, *b1 = nullptr, *b2 = nullptr, *ln1w = nullptr, *ln1b = nullptr, *ln2w = nullptr, *ln2b = nullptr;
@@ -183,10 +179,8 @@ struct opus_ctx {
     // guided call with token log-probs): the raw conditional rows [max_batch / 2, V] the combine overwrites in d_logits
     char *guid_mem = nullptr;
     float *d_gscale = nullptr, *d_gdpsum = nullptr, *d_gmax = nullptr, *d_glog = nullptr, *d_glse = nullptr, *guid_keep = nullptr;
-    int gemm_w8 = 0;                     // 1: this context's last GEMM streamed the FP8 panels (GemmParams::ran_w8)
-    int64_t w8_gemms = 0;                // GEMMs issued on this context that did (opus_stat("w8_gemms"))
-    int gemm_w4 = 0;                     // the same for the MXFP4 panels (GemmParams::ran_w4, opus_stat("w4_gemms"))
-    int64_t w4_gemms = 0;
+    int gemm_wq = WQ_NONE;               // the quantised format this context's last GEMM streamed (GemmParams::ran_wq)
+    int64_t wq_gemms[WQ_COUNT] = {};     // GEMMs issued on this context per streamed format (opus_stat("w8_gemms"), "w4_gemms")
     int gemm_plan[GEMM_PLAN_WORDS] = {-1, -1, -1, -1, -1, -1, -1, -1};   // the launchers' report of this context's last GEMM (GemmParams::plan; opus_debug_gemm_plan)
     // row-scale fusion (GemmParams::ssq_out / row_ssq): the rows' sums of squares, written by the GEMM that is asked for the fp16
     // copy of its output (GemmAsk::xh) and read by the one that scales its rows (GemmAsk::rs_on)
@@ -495,14 +489,30 @@ extern "C" int opus_ctx_destroy(opus_ctx *c) {
 }
 
 // ------------------------------------------------------------------------------------------------ weights
+// The quantised forms a decoder projection W [N, K] may be bound in: the suffix and dtype of the code tensor [N, K / codes_kdiv]
+// and of the scale tensor ([N, K / scales_kdiv]; scales_kdiv 0: one scale per row, [N]).
+struct WqFormat {
+    int fmt;
+    const char *name;
+    const char *codes_sfx; int codes_dtype; int64_t codes_kdiv;
+    const char *scales_sfx; int scales_dtype; int64_t scales_kdiv;
+};
+static const WqFormat WQ_FORMATS[] = {
+    {WQ_FP8, "FP8", ".q8", OPUS_F8E4M3, 1, ".e8", OPUS_I8, 0},
+    {WQ_MXFP4, "MXFP4", ".q4", OPUS_F4E2M1X2, 2, ".s4", OPUS_E8M0, 32},
+};
+
 extern "C" int opus_bind_weight(opus_ctx *c, const char *name, const void *d_ptr, int dtype, int ndim,
                                 const int64_t *shape) {
     if (!c || !name || !d_ptr || !shape) return fail(OPUS_EBADARG, "null argument");
     if (ndim < 1 || ndim > 4) return fail(OPUS_EBADARG, "ndim %d", ndim);
     const size_t nlen = strlen(name);
-    const bool is_q8 = nlen > 3 && !strcmp(name + nlen - 3, ".q8"), is_e8 = nlen > 3 && !strcmp(name + nlen - 3, ".e8");
-    const bool is_q4 = nlen > 3 && !strcmp(name + nlen - 3, ".q4"), is_s4 = nlen > 3 && !strcmp(name + nlen - 3, ".s4");
-    if (is_q4 ? dtype != OPUS_F4E2M1X2 : is_s4 ? dtype != OPUS_E8M0 : is_q8 ? dtype != OPUS_F8E4M3 : is_e8 ? dtype != OPUS_I8 : (dtype != OPUS_F16 && dtype != OPUS_F32))
+    int want = -1;                       // the dtype that the name's suffix asks for (-1: an ordinary weight)
+    for (const WqFormat &f : WQ_FORMATS) {
+        if (nlen > 3 && !strcmp(name + nlen - 3, f.codes_sfx)) want = f.codes_dtype;
+        if (nlen > 3 && !strcmp(name + nlen - 3, f.scales_sfx)) want = f.scales_dtype;
+    }
+    if (want >= 0 ? dtype != want : (dtype != OPUS_F16 && dtype != OPUS_F32))
         return fail(OPUS_EBADARG, "weights are fp16 or fp32 (FP8 panels '*.q8': e4m3, their row exponents '*.e8': int8; MXFP4 code panels "
                                   "'*.q4': packed e2m1 pairs, their scale panels '*.s4': e8m0)");
     if (((uintptr_t)d_ptr) & 15) return fail(OPUS_EBADARG, "%s: pointer must be 16-byte aligned", name);
@@ -595,30 +605,22 @@ extern "C" int opus_weights_ready(opus_ctx *c) {
         if (g.dec_qkv_bias) GW(p + "bqkv", OPUS_F32, (std::vector<int64_t>{QKV}), L.bqkv);
         GW(p + "wgu", OPUS_F16, (std::vector<int64_t>{2 * F, H}), L.wgu);
         GW(p + "wd", OPUS_F16, (std::vector<int64_t>{H, F}), L.wd);
-        // the optional FP8 form, per projection: both tensors or neither
-        const struct { const char *n; int64_t N, K; const uint8_t **q; const int8_t **e; } w8[4] = {
-            {"wqkv", QKV, H, &L.q8_qkv, &L.e8_qkv}, {"wo", H, QD, &L.q8_o, &L.e8_o},
-            {"wgu", 2 * F, H, &L.q8_gu, &L.e8_gu}, {"wd", H, F, &L.q8_d, &L.e8_d}};
-        for (const auto &t : w8) {
-            *t.q = nullptr; *t.e = nullptr;
-            const bool hq = c->w.count(p + t.n + ".q8") != 0, he = c->w.count(p + t.n + ".e8") != 0;
-            if (!hq && !he) continue;
-            if (t.N % 16 || t.K % 64) return fail(OPUS_ESHAPE, "weight '%s%s.q8': FP8 panels need N %% 16 == 0 and K %% 64 == 0", p.c_str(), t.n);
-            GW(p + t.n + ".q8", OPUS_F8E4M3, (std::vector<int64_t>{t.N, t.K}), *t.q);
-            GW(p + t.n + ".e8", OPUS_I8, (std::vector<int64_t>{t.N}), *t.e);
-        }
-        // the optional MXFP4 form, per projection: both tensors or neither, and not beside the FP8 form
-        const struct { const char *n; int64_t N, K; const uint8_t **q, **sc; } w4[4] = {
-            {"wqkv", QKV, H, &L.q4_qkv, &L.s4_qkv}, {"wo", H, QD, &L.q4_o, &L.s4_o},
-            {"wgu", 2 * F, H, &L.q4_gu, &L.s4_gu}, {"wd", H, F, &L.q4_d, &L.s4_d}};
-        for (const auto &t : w4) {
-            *t.q = nullptr; *t.sc = nullptr;
-            const bool hq = c->w.count(p + t.n + ".q4") != 0, hs = c->w.count(p + t.n + ".s4") != 0;
-            if (!hq && !hs) continue;
-            if (t.N % 16 || t.K % 64) return fail(OPUS_ESHAPE, "weight '%s%s.q4': MXFP4 panels need N %% 16 == 0 and K %% 64 == 0", p.c_str(), t.n);
-            if (c->w.count(p + t.n + ".q8")) return fail(OPUS_EBADARG, "weight '%s%s': bound as FP8 and as MXFP4 panels", p.c_str(), t.n);
-            GW(p + t.n + ".q4", OPUS_F4E2M1X2, (std::vector<int64_t>{t.N, t.K / 2}), *t.q);
-            GW(p + t.n + ".s4", OPUS_E8M0, (std::vector<int64_t>{t.N, t.K / 32}), *t.sc);
+        // the optional quantised form, per projection: both tensors of a format or neither, and one format at the most
+        const struct { const char *n; int64_t N, K; QuantW *q; } proj[4] = {
+            {"wqkv", QKV, H, &L.wq_qkv}, {"wo", H, QD, &L.wq_o}, {"wgu", 2 * F, H, &L.wq_gu}, {"wd", H, F, &L.wq_d}};
+        for (const auto &t : proj) {
+            *t.q = QuantW{};
+            const char *bound = nullptr;
+            for (const WqFormat &f : WQ_FORMATS) {
+                const std::string cn = p + t.n + f.codes_sfx, sn = p + t.n + f.scales_sfx;
+                if (!c->w.count(cn) && !c->w.count(sn)) continue;
+                if (t.N % 16 || t.K % 64) return fail(OPUS_ESHAPE, "weight '%s': %s panels need N %% 16 == 0 and K %% 64 == 0", cn.c_str(), f.name);
+                if (bound) return fail(OPUS_EBADARG, "weight '%s%s': bound as %s and as %s panels", p.c_str(), t.n, bound, f.name);
+                GW(cn, f.codes_dtype, (std::vector<int64_t>{t.N, t.K / f.codes_kdiv}), t.q->codes);
+                GW(sn, f.scales_dtype, (f.scales_kdiv ? std::vector<int64_t>{t.N, t.K / f.scales_kdiv} : std::vector<int64_t>{t.N}), t.q->scales);
+                t.q->fmt = f.fmt;
+                bound = f.name;
+            }
         }
     }
     if (g.dec_arch == 1) {
@@ -685,8 +687,8 @@ struct GemmAsk {
     int force_wide = 0, slab_only = 0;   // route a narrow output through the wide kernel / leave raw k-part slabs
     int a_tiled = 0, c_tiled = 0;        // A is read / the fp16 output is written in fragment order
     int *pp_plan = nullptr;              // (HOST) launch_pp reports its plan here
-    const uint8_t *q8 = nullptr;         // FP8 form of W (GemmParams::q8 / e8): streamed by a kernel that has a W8 instantiation,
-    const int8_t *e8 = nullptr;          //   ignored by every other one (W holds the same values)
+    QuantW wq;                           // quantised form of W (GemmParams::wq): streamed by a kernel that has an instantiation
+                                         //   for its format, ignored by every other one (W holds the same values)
     // setters; a null first pointer leaves that request unasked
     GemmAsk &copy16(half_t *dst, bool tiled = false) { xh = dst; xh_tiled = dst && tiled; return *this; }
     GemmAsk &scale_rows(float eps, int nblk) { rs_on = true; rs_eps = eps; rs_nblk = nblk; return *this; }
@@ -700,9 +702,7 @@ struct GemmAsk {
     GemmAsk &tiled_a(int on) { a_tiled = on; return *this; }
     GemmAsk &tiled_c(int on) { c_tiled = on; return *this; }
     GemmAsk &report_pp(int *plan) { pp_plan = plan; return *this; }
-    GemmAsk &w8(const uint8_t *q, const int8_t *e) { if (q && e) { q8 = q; e8 = e; } return *this; }
-    const uint8_t *q4 = nullptr, *s4 = nullptr;      // MXFP4 form of W (GemmParams::q4 / s4), on the same terms
-    GemmAsk &w4(const uint8_t *q, const uint8_t *sc) { if (q && sc) { q4 = q; s4 = sc; } return *this; }
+    GemmAsk &quant(const QuantW &q) { if (q.fmt != WQ_NONE && q.codes && q.scales) wq = q; return *this; }
 };
 // What the launch reports back: the row-scale producer's copy was written (ssq_nblk blocks of sums of squares per row), the rotary
 // ran in the epilogue, the norm partials were written; ks > 1: that many raw k-part slabs were left (slab_only).
@@ -732,10 +732,8 @@ static int gemm_any(opus_ctx *c, hipStream_t s, const half_t *A, const float *Af
     p.pp_plan = ask.pp_plan;
     for (int i = 0; i < GEMM_PLAN_WORDS; ++i) c->gemm_plan[i] = -1;
     p.plan = c->gemm_plan;
-    c->gemm_w8 = 0;
-    p.q8 = ask.q8; p.e8 = ask.e8; p.ran_w8 = &c->gemm_w8;
-    c->gemm_w4 = 0;
-    p.q4 = ask.q4; p.s4 = ask.s4; p.ran_w4 = &c->gemm_w4;
+    c->gemm_wq = WQ_NONE;
+    p.wq = ask.wq; p.ran_wq = &c->gemm_wq;
     p.a_tiled = ask.a_tiled; p.xh_tiled = ask.xh_tiled; p.c_tiled = ask.c_tiled;
     const int nout = epi == EPI_SILU_GU16 ? N / 2 : N;
     // algorithmic bytes: the weights once + activations in + result out (+ the residual read)
@@ -748,8 +746,7 @@ static int gemm_any(opus_ctx *c, hipStream_t s, const half_t *A, const float *Af
         e = launch_gemm(p, s, &klass);
     }
     if (e != hipSuccess) return fail(OPUS_EHIP, "gemm M=%d N=%d K=%d failed: %s", M, N, K, hipGetErrorString(e));
-    c->w8_gemms += c->gemm_w8;
-    c->w4_gemms += c->gemm_w4;
+    if (c->gemm_wq != WQ_NONE) ++c->wq_gemms[c->gemm_wq];
     return OPUS_OK;
 }
 static int gemm(opus_ctx *c, hipStream_t s, const half_t *A, int64_t lda, const half_t *W, int M, int N, int K,
@@ -841,46 +838,45 @@ extern "C" int opus_tile_weight(const void *d_src, void *d_dst, int64_t N, int64
     return OPUS_OK;
 }
 
-// FP8 form of one decoder-layer weight (csrc/quant.hip): row-major W[N, K] in the operand type -> q8 (FP8 panels, N K bytes),
-// e8 (int8 [N]) and, when d_dq is not null, the dequantised weights (operand type, row-major [N, K]; may be d_src itself).
-// Synchronises the stream: a weight that is not finite is reported (OPUS_EBADARG) and the outputs are not to be used.
-extern "C" int opus_quantize_fp8(const void *d_src, int64_t N, int64_t K, void *d_q8, void *d_e8, void *d_dq, void *stream) {
-    if (!d_src || !d_q8 || !d_e8) return fail(OPUS_EBADARG, "quantize_fp8: null pointer");
-    if (N < 16 || K < 64 || N % 16 || K % 64) return fail(OPUS_ESHAPE, "quantize_fp8: N %% 16 == 0 and K %% 64 == 0 required");
-    if ((((uintptr_t)d_src) | ((uintptr_t)d_q8) | ((uintptr_t)d_dq)) & 15) return fail(OPUS_EBADARG, "quantize_fp8: pointers must be 16-byte aligned");
+// Quantised form of one decoder-layer weight (csrc/quant.hip): the checks, the `bad` word, the synchronisation and the error
+// reporting of opus_quantize_fp8 / opus_quantize_mxfp4; `launch(d_bad, s)` starts the format's kernel, `aligned` are the pointers
+// that must be 16-byte aligned.
+template <class Launch>
+static int quantize_any(const char *who, const void *d_src, int64_t N, int64_t K, const void *d_codes, const void *d_scales,
+                        uintptr_t aligned, void *stream, Launch launch) {
+    if (!d_src || !d_codes || !d_scales) return fail(OPUS_EBADARG, "%s: null pointer", who);
+    if (N < 16 || K < 64 || N % 16 || K % 64) return fail(OPUS_ESHAPE, "%s: N %% 16 == 0 and K %% 64 == 0 required", who);
+    if (aligned & 15) return fail(OPUS_EBADARG, "%s: pointers must be 16-byte aligned", who);
     hipStream_t s = (hipStream_t)stream;
     int *d_bad = nullptr;
     HIPC(hipMalloc(&d_bad, sizeof(int)));
     int bad = 0;
     hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(int), s);
-    if (e == hipSuccess) e = launch_quantize_fp8((const half_t *)d_src, N, K, (uint8_t *)d_q8, (int8_t *)d_e8, (half_t *)d_dq, d_bad, s);
+    if (e == hipSuccess) e = launch(d_bad, s);
     if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     (void)hipFree(d_bad);
-    if (e != hipSuccess) return fail(OPUS_EHIP, "quantize_fp8 failed: %s", hipGetErrorString(e));
-    if (bad) return fail(OPUS_EBADARG, "quantize_fp8: the weight holds a value that is not finite");
+    if (e != hipSuccess) return fail(OPUS_EHIP, "%s failed: %s", who, hipGetErrorString(e));
+    if (bad) return fail(OPUS_EBADARG, "%s: the weight holds a value that is not finite", who);
     return OPUS_OK;
 }
 
-// MXFP4 form of one decoder-layer weight (csrc/quant.hip): row-major W[N, K] in the operand type -> q4 (code panels, N K / 2
-// bytes), s4 (scale panels, N K / 32 bytes) and, when d_dq is not null, the dequantised weights (operand type, row-major [N, K];
-// may be d_src itself).  Synchronises the stream, as opus_quantize_fp8.
+// FP8: row-major W[N, K] in the operand type -> q8 (FP8 panels, N K bytes), e8 (int8 [N]) and, when d_dq is not null, the
+// dequantised weights (operand type, row-major [N, K]; may be d_src itself).
+// Synchronises the stream: a weight that is not finite is reported (OPUS_EBADARG) and the outputs are not to be used.
+extern "C" int opus_quantize_fp8(const void *d_src, int64_t N, int64_t K, void *d_q8, void *d_e8, void *d_dq, void *stream) {
+    return quantize_any("quantize_fp8", d_src, N, K, d_q8, d_e8, (uintptr_t)d_src | (uintptr_t)d_q8 | (uintptr_t)d_dq, stream,
+                        [&](int *d_bad, hipStream_t s) {
+        return launch_quantize_fp8((const half_t *)d_src, N, K, (uint8_t *)d_q8, (int8_t *)d_e8, (half_t *)d_dq, d_bad, s);
+    });
+}
+
+// MXFP4: -> q4 (code panels, N K / 2 bytes), s4 (scale panels, N K / 32 bytes) and the dequantised weights, on the same terms.
 extern "C" int opus_quantize_mxfp4(const void *d_src, int64_t N, int64_t K, void *d_q4, void *d_s4, void *d_dq, void *stream) {
-    if (!d_src || !d_q4 || !d_s4) return fail(OPUS_EBADARG, "quantize_mxfp4: null pointer");
-    if (N < 16 || K < 64 || N % 16 || K % 64) return fail(OPUS_ESHAPE, "quantize_mxfp4: N %% 16 == 0 and K %% 64 == 0 required");
-    if ((((uintptr_t)d_src) | ((uintptr_t)d_q4) | ((uintptr_t)d_s4) | ((uintptr_t)d_dq)) & 15) return fail(OPUS_EBADARG, "quantize_mxfp4: pointers must be 16-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    int *d_bad = nullptr;
-    HIPC(hipMalloc(&d_bad, sizeof(int)));
-    int bad = 0;
-    hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(int), s);
-    if (e == hipSuccess) e = launch_quantize_mxfp4((const half_t *)d_src, N, K, (uint8_t *)d_q4, (uint8_t *)d_s4, (half_t *)d_dq, d_bad, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(d_bad);
-    if (e != hipSuccess) return fail(OPUS_EHIP, "quantize_mxfp4 failed: %s", hipGetErrorString(e));
-    if (bad) return fail(OPUS_EBADARG, "quantize_mxfp4: the weight holds a value that is not finite");
-    return OPUS_OK;
+    return quantize_any("quantize_mxfp4", d_src, N, K, d_q4, d_s4,
+                        (uintptr_t)d_src | (uintptr_t)d_q4 | (uintptr_t)d_s4 | (uintptr_t)d_dq, stream, [&](int *d_bad, hipStream_t s) {
+        return launch_quantize_mxfp4((const half_t *)d_src, N, K, (uint8_t *)d_q4, (uint8_t *)d_s4, (half_t *)d_dq, d_bad, s);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ encoder
@@ -1525,14 +1521,14 @@ static int prefill(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8
     ResidShadow sh;
     GemmGot got;
     const bool w8 = cont && cont->w8;                                // (false: every ask below is what it was)
-    auto ask8 = [&](GemmAsk a, const uint8_t *q, const int8_t *e, const uint8_t *q4, const uint8_t *s4) { return w8 ? a.w8(q, e).w4(q4, s4) : a; };
+    auto ask8 = [&](GemmAsk a, const QuantW &q) { return w8 ? a.quant(q) : a; };
     for (int l = 0; l < g.dec_layers; ++l) {
         const DecLayer &L = c->dec[l];
         if (have_stat && qkv_pp) {
             OPC(gemm(c, s, c->d_xn, H, L.wqkv, M, QKV, H, L.bqkv, EPI_NONE, nullptr, c->d_qkv, QKV, 0, GemmAsk().ln_consume(c->d_stat, nullptr)));
         } else {
             OPC(gemm_norm(c, s, sh, c->d_x, g.dec_rms_eps, c->d_xn, L.wqkv, M, QKV, H, EPI_NONE, c->d_qkv, QKV, 0, L.bqkv,
-                          ask8(GemmAsk(), L.q8_qkv, L.e8_qkv, L.q4_qkv, L.s4_qkv)));
+                          ask8(GemmAsk(), L.wq_qkv)));
         }
         OPC(attn_prefill(c, s, l, B, T, cont, nret));
         if (l + 1 == g.dec_layers && T > 1 && !all_rows && !g_knobs.misc[7]) {
@@ -1555,7 +1551,7 @@ static int prefill(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8
         GemmAsk wo;
         if (gu_pp) wo.ln_produce(c->d_part, c->d_xn);
         else if (fuse_rows() && M <= 96) wo.copy16(c->d_xn);      // (d_ssq holds 128 rows)
-        OPC(gemm(c, s, c->d_ctx, QD, L.wo, M, H, QD, nullptr, EPI_NONE, c->d_x, c->d_x, H, 1, ask8(wo, L.q8_o, L.e8_o, L.q4_o, L.s4_o), &got));
+        OPC(gemm(c, s, c->d_ctx, QD, L.wo, M, H, QD, nullptr, EPI_NONE, c->d_x, c->d_x, H, 1, ask8(wo, L.wq_o), &got));
         sh.produced(c->d_x, got);
         have_stat = got.ln_done != 0;
         if (have_stat) {
@@ -1563,10 +1559,10 @@ static int prefill(opus_ctx *c, hipStream_t s, const half_t *embeds, const uint8
             OPC(gemm(c, s, c->d_xn, H, L.wgu, M, 2 * F, H, nullptr, EPI_SILU_GU16, nullptr, c->d_act, F, 0, GemmAsk().ln_consume(c->d_stat, nullptr)));
         } else {
             OPC(gemm_norm(c, s, sh, c->d_x, g.dec_rms_eps, c->d_xn, L.wgu, M, 2 * F, H, EPI_SILU_GU16, c->d_act, F, 0, nullptr,
-                          ask8(GemmAsk(), L.q8_gu, L.e8_gu, L.q4_gu, L.s4_gu)));
+                          ask8(GemmAsk(), L.wq_gu)));
         }
         const bool next_pp = qkv_pp && l + 1 < g.dec_layers;
-        OPC(gemm(c, s, c->d_act, F, L.wd, M, H, F, nullptr, EPI_NONE, c->d_x, c->d_x, H, 1, ask8(GemmAsk().ln_produce(next_pp ? c->d_part : nullptr, c->d_xn), L.q8_d, L.e8_d, L.q4_d, L.s4_d), &got));
+        OPC(gemm(c, s, c->d_act, F, L.wd, M, H, F, nullptr, EPI_NONE, c->d_x, c->d_x, H, 1, ask8(GemmAsk().ln_produce(next_pp ? c->d_part : nullptr, c->d_xn), L.wq_d), &got));
         have_stat = got.ln_done != 0;
         if (have_stat) OPC(finalize());
     }
@@ -1608,22 +1604,22 @@ static int decode_step(opus_ctx *c, hipStream_t s, const int32_t *d_tok) {
             // kernel sums them, applies the RMSNorm row scale and the bias on the fly - no norm launch, no reduce launch
             sh.xh_src = nullptr;
             OPC(gemm(c, s, c->d_xln, H, L.wqkv, B, QKV, H, L.bqkv, EPI_NONE, nullptr, c->d_qkv, QKV, 0,
-                     GemmAsk().slabs().scale_rows(g.dec_rms_eps, sh.ssq_nblk).tiled_a(sh.xln_tiled).w8(L.q8_qkv, L.e8_qkv).w4(L.q4_qkv, L.s4_qkv), &got));
+                     GemmAsk().slabs().scale_rows(g.dec_rms_eps, sh.ssq_nblk).tiled_a(sh.xln_tiled).quant(L.wq_qkv), &got));
             OPC(attn_decode(c, s, sh, l, B, T, got.ks > 1 ? got.ks : 0, L.bqkv, wo_tiled ? 1 : 0));
         } else {
             OPC(gemm_norm(c, s, sh, c->d_xl, g.dec_rms_eps, c->d_xln, L.wqkv, B, QKV, H, EPI_NONE, c->d_qkv, QKV, 0, L.bqkv,
-                          GemmAsk().w8(L.q8_qkv, L.e8_qkv).w4(L.q4_qkv, L.s4_qkv)));
+                          GemmAsk().quant(L.wq_qkv)));
             OPC(attn_decode(c, s, sh, l, B, T, 0, nullptr, wo_tiled ? 1 : 0));
         }
         // (the copy row-major: the gate/up kernel stages it by LDS-DMA)
-        OPC(gemm(c, s, c->d_ctx, QD, L.wo, B, H, QD, nullptr, EPI_NONE, c->d_xl, c->d_xl, H, 1, GemmAsk().copy16(copy_xl).tiled_a(wo_tiled).w8(L.q8_o, L.e8_o).w4(L.q4_o, L.s4_o), &got));
+        OPC(gemm(c, s, c->d_ctx, QD, L.wo, B, H, QD, nullptr, EPI_NONE, c->d_xl, c->d_xl, H, 1, GemmAsk().copy16(copy_xl).tiled_a(wo_tiled).quant(L.wq_o), &got));
         sh.produced(c->d_xl, got);
         // the gate / up kernel writes silu(g) u in fragment order when the down projection will read it that way (only the wide
         // kernel - the row-scale form of gemm_norm - writes that layout)
         const bool act_tiled = down_tiled && sh.xh_src == c->d_xl && gemm_goes_wide(B, 2 * F);
-        OPC(gemm_norm(c, s, sh, c->d_xl, g.dec_rms_eps, c->d_xln, L.wgu, B, 2 * F, H, EPI_SILU_GU16, c->d_act, F, 0, nullptr, GemmAsk().tiled_c(act_tiled).w8(L.q8_gu, L.e8_gu).w4(L.q4_gu, L.s4_gu)));
+        OPC(gemm_norm(c, s, sh, c->d_xl, g.dec_rms_eps, c->d_xln, L.wgu, B, 2 * F, H, EPI_SILU_GU16, c->d_act, F, 0, nullptr, GemmAsk().tiled_c(act_tiled).quant(L.wq_gu)));
         const bool next_tiled = qkv_tiled && l + 1 < g.dec_layers;      // (the last layer's fp16(x) feeds lm_head: row-major)
-        OPC(gemm(c, s, c->d_act, F, L.wd, B, H, F, nullptr, EPI_NONE, c->d_xl, c->d_xl, H, 1, GemmAsk().copy16(copy_xl, next_tiled).tiled_a(act_tiled).w8(L.q8_d, L.e8_d).w4(L.q4_d, L.s4_d), &got));
+        OPC(gemm(c, s, c->d_act, F, L.wd, B, H, F, nullptr, EPI_NONE, c->d_xl, c->d_xl, H, 1, GemmAsk().copy16(copy_xl, next_tiled).tiled_a(act_tiled).quant(L.wq_d), &got));
         sh.produced(c->d_xl, got, next_tiled);
     }
     OPC(lm_head(c, s, sh, B));
@@ -3648,61 +3644,57 @@ extern "C" int opus_debug_gemm_slabs(opus_ctx *c, const void *A, const void *W, 
 }
 
 // opus_debug_gemm (form 0: A in the operand type), opus_debug_gemm_norm (form 1: A fp32, eps) or opus_debug_gemm_slabs (form 2:
-// d_C = the slab buffer, *ks) with the FP8 form of W offered beside it, as decode_step() offers it: *ran_w8 (HOST) = 1 when the
-// routed kernel streamed the FP8 panels, 0 when it has no such form and read W.
-// (debug_gemm_wq: the body shared with opus_debug_gemm_w4 - `w8` carries whichever quantised form is offered, *ran is the
-// context's flag of that form)
-static int debug_gemm_wq(opus_ctx *c, int32_t form, const void *A, const void *W, const GemmAsk &w8, const int *ran,
+// d_C = the slab buffer, *ks) with the quantised form `q` of W offered beside it, as decode_step() offers it: *ran (HOST) = 1 when
+// the routed kernel streamed the quantised panels, 0 when it has no such form and read W.  `who`: the entry point, for the messages.
+static int debug_gemm_wq(const char *who, opus_ctx *c, int32_t form, const void *A, const void *W, const QuantW &q,
                          const float *bias, const float *residual, void *Cp, int32_t M, int32_t N, int32_t K, int32_t epi,
-                         int32_t out_f32, float eps, int32_t *ks, int32_t *ran_w8, void *stream) {
-    if (form != 2 && !Cp) return fail(OPUS_EBADARG, "debug_gemm_wq: null pointer");
-    if (M < 1 || N < 1 || K < 64 || K % 64) return fail(OPUS_ESHAPE, "debug_gemm_w8: K must be a positive multiple of 64");
-    if (epi < 0 || epi > 2 || (epi == 2 && N % 32)) return fail(OPUS_EBADARG, "debug_gemm_w8: epilogue");
+                         int32_t out_f32, float eps, int32_t *ks, int32_t *ran, void *stream) {
+    if (!c || !A || !W || !q.codes || !q.scales || !ran || (form != 2 && !Cp)) return fail(OPUS_EBADARG, "%s: null pointer", who);
+    if (form < 0 || form > 2) return fail(OPUS_EBADARG, "%s: form 0, 1 or 2", who);
+    if (M < 1 || N < 1 || K < 64 || K % 64) return fail(OPUS_ESHAPE, "%s: K must be a positive multiple of 64", who);
+    if (epi < 0 || epi > 2 || (epi == 2 && N % 32)) return fail(OPUS_EBADARG, "%s: epilogue", who);
     HIPC(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const int nout = epi == EPI_SILU_GU16 ? N / 2 : N;
-    *ran_w8 = 0;
+    const GemmAsk ask = GemmAsk().quant(q);
+    *ran = 0;
     if (form == 0) {
         OPC(gemm(c, s, (const half_t *)A, K, (const half_t *)W, M, N, K, bias, epi, residual, Cp, nout, out_f32,
-                 GemmAsk(w8).tiled_a(g_knobs.debug_a_tiled)));
+                 GemmAsk(ask).tiled_a(g_knobs.debug_a_tiled)));
     } else if (form == 1) {
-        if (M > MID_MAX_M) return fail(OPUS_ESHAPE, "debug_gemm_w8: the fused norm takes M <= 64");
-        if (epi == 1 || bias || residual) return fail(OPUS_EBADARG, "debug_gemm_w8: the fused norm takes epilogue 0 or 2, no bias, no residual");
-        OPC(gemm_any(c, s, nullptr, (const float *)A, eps, K, (const half_t *)W, M, N, K, nullptr, epi, nullptr, Cp, nout, out_f32, w8));
+        if (M > MID_MAX_M) return fail(OPUS_ESHAPE, "%s: the fused norm takes M <= 64", who);
+        if (epi == 1 || bias || residual) return fail(OPUS_EBADARG, "%s: the fused norm takes epilogue 0 or 2, no bias, no residual", who);
+        OPC(gemm_any(c, s, nullptr, (const float *)A, eps, K, (const half_t *)W, M, N, K, nullptr, epi, nullptr, Cp, nout, out_f32, ask));
     } else {
-        if (!ks || epi != 0 || N < 16) return fail(OPUS_EBADARG, "debug_gemm_w8: the slab form takes ks, the plain epilogue and N >= 16");
+        if (!ks || epi != 0 || N < 16) return fail(OPUS_EBADARG, "%s: the slab form takes ks, the plain epilogue and N >= 16", who);
         const opus_config &g = c->cfg;
         const int64_t QKVd = (int64_t)(g.dec_heads + 2 * g.dec_kv_heads) * g.dec_head_dim;
-        if ((int64_t)M * N > (int64_t)g.max_batch * g.max_prompt * QKVd) return fail(OPUS_ESHAPE, "debug_gemm_w8: M * N exceeds the scratch");
+        if ((int64_t)M * N > (int64_t)g.max_batch * g.max_prompt * QKVd) return fail(OPUS_ESHAPE, "%s: M * N exceeds the scratch", who);
         GemmGot got;
         OPC(gemm(c, s, (const half_t *)A, K, (const half_t *)W, M, N, K, nullptr, EPI_NONE, nullptr, c->d_qkv, N, 0,
-                 GemmAsk(w8).slabs().tiled_a(g_knobs.debug_a_tiled), &got));
+                 GemmAsk(ask).slabs().tiled_a(g_knobs.debug_a_tiled), &got));
         *ks = got.ks;
         if (got.ks > 1 && Cp)
             HIPC(hipMemcpyAsync(Cp, c->gemm_ws, (size_t)got.ks * M * N * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
-    *ran_w8 = *ran;
+    *ran = c->gemm_wq == q.fmt;
     return OPUS_OK;
 }
+// The FP8 form of W (opus_quantize_fp8: d_q8, d_e8)
 extern "C" int opus_debug_gemm_w8(opus_ctx *c, int32_t form, const void *A, const void *W, const void *q8, const void *e8,
                                   const float *bias, const float *residual, void *Cp, int32_t M, int32_t N, int32_t K, int32_t epi,
-                                  int32_t out_f32, float eps, int32_t *ks, int32_t *ran_w8, void *stream) {
-    if (!c || !A || !W || !q8 || !e8 || !ran_w8) return fail(OPUS_EBADARG, "debug_gemm_w8: null pointer");
-    if (form < 0 || form > 2) return fail(OPUS_EBADARG, "debug_gemm_w8: form 0, 1 or 2");
+                                  int32_t out_f32, float eps, int32_t *ks, int32_t *ran, void *stream) {
     if ((((uintptr_t)q8) & 15) || (((uintptr_t)e8) & 3)) return fail(OPUS_EBADARG, "debug_gemm_w8: d_q8 must be 16-byte, d_e8 4-byte aligned");
-    return debug_gemm_wq(c, form, A, W, GemmAsk().w8((const uint8_t *)q8, (const int8_t *)e8), &c->gemm_w8, bias, residual, Cp, M, N, K,
-                         epi, out_f32, eps, ks, ran_w8, stream);
+    return debug_gemm_wq("debug_gemm_w8", c, form, A, W, QuantW{WQ_FP8, (const uint8_t *)q8, e8}, bias, residual, Cp, M, N, K,
+                         epi, out_f32, eps, ks, ran, stream);
 }
-// The same with the MXFP4 form of W (opus_quantize_mxfp4: d_q4, d_s4): *ran_w4 (HOST) = 1 when the routed kernel streamed the
-// MXFP4 panels, 0 when it has no such form and read W.
+// The MXFP4 form of W (opus_quantize_mxfp4: d_q4, d_s4)
 extern "C" int opus_debug_gemm_w4(opus_ctx *c, int32_t form, const void *A, const void *W, const void *q4, const void *s4,
                                   const float *bias, const float *residual, void *Cp, int32_t M, int32_t N, int32_t K, int32_t epi,
-                                  int32_t out_f32, float eps, int32_t *ks, int32_t *ran_w4, void *stream) {
-    if (!c || !A || !W || !q4 || !s4 || !ran_w4) return fail(OPUS_EBADARG, "debug_gemm_w4: null pointer");
-    if (form < 0 || form > 2) return fail(OPUS_EBADARG, "debug_gemm_w4: form 0, 1 or 2");
+                                  int32_t out_f32, float eps, int32_t *ks, int32_t *ran, void *stream) {
     if ((((uintptr_t)q4) & 15) || (((uintptr_t)s4) & 15)) return fail(OPUS_EBADARG, "debug_gemm_w4: d_q4 and d_s4 must be 16-byte aligned");
-    return debug_gemm_wq(c, form, A, W, GemmAsk().w4((const uint8_t *)q4, (const uint8_t *)s4), &c->gemm_w4, bias, residual, Cp, M, N, K,
-                         epi, out_f32, eps, ks, ran_w4, stream);
+    return debug_gemm_wq("debug_gemm_w4", c, form, A, W, QuantW{WQ_MXFP4, (const uint8_t *)q4, s4}, bias, residual, Cp, M, N, K,
+                         epi, out_f32, eps, ks, ran, stream);
 }
 
 // What the launchers launched for the last GEMM issued on this context (opus_debug_gemm, opus_debug_gemm_norm,
@@ -4000,8 +3992,8 @@ extern "C" int64_t opus_stat(opus_ctx *c, const char *name) {
     if (!strcmp(name, "graph_replays")) return c->graph_replays;
     if (!strcmp(name, "graphs_cached")) return (int64_t)c->graphs.size();
     if (!strcmp(name, "decode_steps")) return c->decode_steps;
-    if (!strcmp(name, "w8_gemms")) return c->w8_gemms;
-    if (!strcmp(name, "w4_gemms")) return c->w4_gemms;
+    if (!strcmp(name, "w8_gemms")) return c->wq_gemms[WQ_FP8];
+    if (!strcmp(name, "w4_gemms")) return c->wq_gemms[WQ_MXFP4];
     if (!strcmp(name, "prefills_behind")) return c->prefills_behind;
     if (!strcmp(name, "stream_steps")) return c->stream_steps;
     if (!strcmp(name, "stream_refills")) return c->stream_refills;

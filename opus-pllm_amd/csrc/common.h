@@ -186,6 +186,17 @@ hipError_t launch_quantize_mxfp4(const half_t *src, int64_t N, int64_t K, uint8_
 constexpr int HANDOFF_WORDS = 1024, HANDOFF_ERR = 1023;
 constexpr int HANDOFF_SPIN_LIMIT = 1 << 19;   // polls (s_sleep(4) + one L2 round trip each: >= 0.3 s) before a waiter gives up
 
+// Which quantised form of a weight matrix, if any, and where it lives (device pointers).  WQ_FP8: codes = fp8_tiled_off panels,
+// scales = one int8 exponent per row.  WQ_MXFP4: codes = mx4_code_off panels, scales = mx4_scale_off panels of e8m0 bytes.
+// fmt != WQ_NONE means both pointers are set.  Plain data on purpose: the kernels cast `scales` where they read it - a member
+// function called on the kernel argument (its `this`) cost gemm_skinny_kernel's LDS-staged FP8 instantiations 4 VGPRs.
+enum WeightQuant { WQ_NONE = 0, WQ_FP8 = 1, WQ_MXFP4 = 2, WQ_COUNT };
+struct QuantW {
+    int fmt = WQ_NONE;
+    const uint8_t *codes = nullptr;
+    const void *scales = nullptr;
+};
+
 struct GemmParams {
     const half_t *A;        // fp16 activations [M,K] (row-major, lda), or
     const float *Af;        // fp32 residual stream [M,K]: fused RMSNorm (skinny kernel only), else nullptr
@@ -267,16 +278,10 @@ struct GemmParams {
     // of the ring kernel (else 0), [4] the skinny kernel's ALDS flag (else 0), [5] the stream kernel's P (else 0), [6] k-parts over
     // workgroups (gemm_pp_kernel: per tail tile; 1: K is not cut), [7] how the k-parts become the output (GemmCombine)
     int *plan = nullptr;
-    // FP8 form of W (fp8_tiled_off panels + one exponent per row, the same values as W): a kernel that has a W8 instantiation
-    // streams these instead of W and sets *ran_w8 (HOST) = 1; every other kernel reads W as ever and leaves *ran_w8 alone
-    const uint8_t *q8 = nullptr;
-    const int8_t *e8 = nullptr;
-    int *ran_w8 = nullptr;
-    // MXFP4 form of W (mx4_code_off / mx4_scale_off panels, the same values as W): as q8 / e8 - a kernel that has a W4 instantiation
-    // streams these instead of W and sets *ran_w4 (HOST) = 1.  At most one of the two forms is offered.
-    const uint8_t *q4 = nullptr;
-    const uint8_t *s4 = nullptr;
-    int *ran_w4 = nullptr;
+    // Quantised form of W (the same values as W): a kernel that has an instantiation for wq.fmt streams it instead of W and sets
+    // *ran_wq (HOST) = wq.fmt; every other kernel reads W as ever and leaves *ran_wq alone
+    QuantW wq;
+    int *ran_wq = nullptr;
 };
 constexpr int PP_PLAN_WORDS = 5;
 enum PpTail { PP_TAIL_NONE = 0, PP_TAIL_PAIR = 1, PP_TAIL_REDUCE = 2 };

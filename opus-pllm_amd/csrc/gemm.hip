@@ -77,15 +77,14 @@ __device__ __forceinline__ float silu(float x) { return x * __builtin_amdgcn_rcp
 // !ALDS (16 < M <= 64 or huge K): A fragments come through a buffer descriptor (rows >= M read as
 // zeros without a branch), NORM accumulates sum(h^2) from those same loads.
 //
-// W8 (MT = 1): the weights come from the FP8 panels p.q8 - one 16-B load per lane and chunk instead of two, converted exactly to
-// the operand type in front of the MFMA (fp8x16_to_h8) - and the fp32 sums of column n are multiplied by 2^e8[n] in the epilogue,
+// WQ_FP8 (MT = 1): the weights come from the FP8 panels p.wq.codes - one 16-B load per lane and chunk instead of two, converted exactly to
+// the operand type in front of the MFMA (fp8x16_to_h8) - and the fp32 sums of column n are multiplied by 2^e[n] (p.wq.scales) in the epilogue,
 // ahead of the norm scale, bias, activation and residual.  Everything else - k-parts, rotation, staging, reduction - is the same.
-// W4 (MT = 1): the same loop on the MXFP4 panels p.q4 / p.s4 - per lane and chunk one 8-B load of codes and one 2-B load of the two
+// WQ_MXFP4 (MT = 1): the same loop on the MXFP4 panels p.wq.codes / p.wq.scales - per lane and chunk one 8-B load of codes and one 2-B load of the two
 // scale bytes, the scaled conversion in front of the MFMA (mx4x16_to_h8) - with nothing left for the epilogue: the converted
 // values are the dequantised operands.
-template <int MT, int EPI, bool NORM, bool ALDS, bool W8 = false, bool W4 = false>
+template <int MT, int EPI, bool NORM, bool ALDS, int WQ = WQ_NONE>
 __global__ __launch_bounds__(1024) void gemm_skinny_kernel(GemmParams p) {
-    static_assert(!(W8 && W4), "one quantised form at a time");
     extern __shared__ __attribute__((aligned(16))) float red[];
     OPUS_ARGS_ONE_BATCH(p);
     constexpr int PB = EPI == EPI_SILU_GU16 ? 2 : 1;
@@ -113,12 +112,12 @@ __global__ __launch_bounds__(1024) void gemm_skinny_kernel(GemmParams p) {
 #pragma unroll
     for (int i = 0; i < MT; ++i) { acc[i] = f4{0.f, 0.f, 0.f, 0.f}; ssq[i] = 0.f; }
 
-    if constexpr (W4) {   // (the FP8 loop below with the MXFP4 registers, loads and conversion)
-        static_assert(!W4 || MT == 1, "the MXFP4 form is built for M <= 16");
+    if constexpr (WQ == WQ_MXFP4) {   // (the FP8 loop below with the MXFP4 registers, loads and conversion)
+        static_assert(WQ != WQ_MXFP4 || MT == 1, "the MXFP4 form is built for M <= 16");
         constexpr int U = (NORM && !ALDS) ? 2 : 4;           // (four chunks of fp32 activations + the conversions: past 128 VGPRs)
         // one lane's share of a chunk in registers (8 code bytes, 2 scale bytes), where it comes from, its load and conversion
         typedef mx4reg qreg_t;
-        const mx4ptr qp{p.q4 + ((int64_t)panel * chunks) * 512 + lane * 8, p.s4 + ((int64_t)panel * chunks) * 32 + li * 2};
+        const mx4ptr qp{p.wq.codes + ((int64_t)panel * chunks) * 512 + lane * 8, static_cast<const uint8_t *>(p.wq.scales) + ((int64_t)panel * chunks) * 32 + li * 2};
         // (the rotated k-range of the LDS-staged form, as below)
         const int nck = c1 - c0;
         const int rot = (ALDS && !p.no_rot && nck >= 2) ? (int)((wave * 3u) % (unsigned)nck) : 0;
@@ -235,10 +234,10 @@ __global__ __launch_bounds__(1024) void gemm_skinny_kernel(GemmParams p) {
                 ssq[0] += __shfl_xor(ssq[0], 32, 64);
             }
         }
-    } else if constexpr (W8) {
-        static_assert(!W8 || MT == 1, "the FP8 form is built for M <= 16");
+    } else if constexpr (WQ == WQ_FP8) {
+        static_assert(WQ != WQ_FP8 || MT == 1, "the FP8 form is built for M <= 16");
         constexpr int U = (NORM && !ALDS) ? 2 : 4;           // (four chunks of fp32 activations + the conversions: past 128 VGPRs)
-        const uint8_t *qp = p.q8 + ((int64_t)panel * chunks) * 1024 + lane * 16;
+        const uint8_t *qp = p.wq.codes + ((int64_t)panel * chunks) * 1024 + lane * 16;
         // (the rotated k-range of the LDS-staged form, as below)
         const int nck = c1 - c0;
         const int rot = (ALDS && !p.no_rot && nck >= 2) ? (int)((wave * 3u) % (unsigned)nck) : 0;
@@ -556,9 +555,9 @@ __global__ __launch_bounds__(1024) void gemm_skinny_kernel(GemmParams p) {
             }
             const int n = n0 + li;
             if (n >= p.N) continue;
-            if constexpr (W8) {                               // the row exponents (exact: a power of two on an fp32 sum)
-                acc[i][r] *= exp2_i8(p.e8[n]);
-                if (EPI == EPI_SILU_GU16) up[i][r] *= exp2_i8(p.e8[n + 16]);
+            if constexpr (WQ == WQ_FP8) {                               // the row exponents (exact: a power of two on an fp32 sum)
+                acc[i][r] *= exp2_i8(static_cast<const int8_t *>(p.wq.scales)[n]);
+                if (EPI == EPI_SILU_GU16) up[i][r] *= exp2_i8(static_cast<const int8_t *>(p.wq.scales)[n + 16]);
             }
             float v;
             int no;
@@ -756,6 +755,18 @@ __global__ __launch_bounds__(256) void gemm_tile_kernel(GemmParams p, int tiles_
 }
 
 // ------------------------------------------------------------------------------------------------
+template <int MT, int EPI, bool NORM, bool ALDS, int WQ>
+static hipError_t launch_skinny_wq(const GemmParams &p, int groups, int W, size_t lds, hipStream_t s) {
+    if (lds > 48 * 1024) {
+        hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_skinny_kernel<MT, EPI, NORM, ALDS, WQ>), lds);
+        if (ea != hipSuccess) return ea;
+    }
+    gemm_plan_set(p, KC_SKINNY, MT, 0, 0, ALDS ? 1 : 0, 0, 1, GC_NONE);
+    if (WQ != WQ_NONE && p.ran_wq) *p.ran_wq = WQ;
+    OPUS_LAUNCH(KC_SKINNY, (gemm_skinny_kernel<MT, EPI, NORM, ALDS, WQ>), dim3(groups), dim3(64 * W), lds, s, p);
+    return hipGetLastError();
+}
+
 template <int MT, int EPI, bool NORM, bool ALDS>
 static hipError_t launch_skinny_t(const GemmParams &p, hipStream_t s) {
     constexpr int PB = EPI == EPI_SILU_GU16 ? 2 : 1;
@@ -773,35 +784,13 @@ static hipError_t launch_skinny_t(const GemmParams &p, hipStream_t s) {
     W = wpp * PB;
     const size_t lds = (size_t)W * MT * (256 + 16) * sizeof(float) + 256 * sizeof(float) +
                        (ALDS ? (size_t)p.M * p.K * sizeof(half_t) : 0);
-    if constexpr (MT == 1) {
-        if (p.q4 && p.s4) {     // the MXFP4 form of the same launch: same grid, same workgroup, same LDS
-            if (lds > 48 * 1024) {
-                hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_skinny_kernel<1, EPI, NORM, ALDS, false, true>), lds);
-                if (ea != hipSuccess) return ea;
-            }
-            gemm_plan_set(p, KC_SKINNY, MT, 0, 0, ALDS ? 1 : 0, 0, 1, GC_NONE);
-            if (p.ran_w4) *p.ran_w4 = 1;
-            OPUS_LAUNCH(KC_SKINNY, (gemm_skinny_kernel<1, EPI, NORM, ALDS, false, true>), dim3(groups), dim3(64 * W), lds, s, p);
-            return hipGetLastError();
-        }
-        if (p.q8 && p.e8) {     // the FP8 form of the same launch: same grid, same workgroup, same LDS
-            if (lds > 48 * 1024) {
-                hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_skinny_kernel<1, EPI, NORM, ALDS, true>), lds);
-                if (ea != hipSuccess) return ea;
-            }
-            gemm_plan_set(p, KC_SKINNY, MT, 0, 0, ALDS ? 1 : 0, 0, 1, GC_NONE);
-            if (p.ran_w8) *p.ran_w8 = 1;
-            OPUS_LAUNCH(KC_SKINNY, (gemm_skinny_kernel<1, EPI, NORM, ALDS, true>), dim3(groups), dim3(64 * W), lds, s, p);
-            return hipGetLastError();
+    if constexpr (MT == 1) {   // the quantised form of the same launch: same grid, same workgroup, same LDS
+        switch (p.wq.fmt) {
+            case WQ_FP8: return launch_skinny_wq<MT, EPI, NORM, ALDS, WQ_FP8>(p, groups, W, lds, s);
+            case WQ_MXFP4: return launch_skinny_wq<MT, EPI, NORM, ALDS, WQ_MXFP4>(p, groups, W, lds, s);
         }
     }
-    if (lds > 48 * 1024) {
-        hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_skinny_kernel<MT, EPI, NORM, ALDS>), lds);
-        if (ea != hipSuccess) return ea;
-    }
-    gemm_plan_set(p, KC_SKINNY, MT, 0, 0, ALDS ? 1 : 0, 0, 1, GC_NONE);
-    OPUS_LAUNCH(KC_SKINNY, (gemm_skinny_kernel<MT, EPI, NORM, ALDS>), dim3(groups), dim3(64 * W), lds, s, p);
-    return hipGetLastError();
+    return launch_skinny_wq<MT, EPI, NORM, ALDS, WQ_NONE>(p, groups, W, lds, s);
 }
 
 template <int EPI, bool NORM>
@@ -826,14 +815,13 @@ static hipError_t launch_skinny_e(const GemmParams &p, hipStream_t s) {
 // (non-temporal, 8 KB in flight per wave).  Accumulators are C^T tiles (16-B epilogue accesses).
 // k-parts (gridDim.y > 1, chosen when N is too small to fill the chip) write fp32 slabs + partial
 // sum(h^2); splitk_reduce_kernel combines them in a fixed order.
-// W8: the register sets hold one 16-B load per chunk from the FP8 panels p.q8, converted exactly in front of the MFMAs; the wave's
-// tile is multiplied by its columns' 2^e8 behind the main loop (ahead of the slabs, the norm scale and the gate / up exchange).
-// W4: the register sets hold the lane's 8 code bytes and the 2 scale bytes of (row, chunk) from the MXFP4 panels p.q4 / p.s4 - two
+// WQ_FP8: the register sets hold one 16-B load per chunk from the FP8 panels p.wq.codes, converted exactly in front of the MFMAs; the wave's
+// tile is multiplied by its columns' 2^e (p.wq.scales) behind the main loop (ahead of the slabs, the norm scale and the gate / up exchange).
+// WQ_MXFP4: the register sets hold the lane's 8 code bytes and the 2 scale bytes of (row, chunk) from the MXFP4 panels p.wq.codes / p.wq.scales - two
 // loads per chunk, as the fp16 form - and the scaled conversion in front of the MFMAs yields the dequantised operands themselves:
 // nothing is left to do behind the main loop.
-template <int MT, int EPI, bool NORM, bool W8 = false, bool W4 = false>
+template <int MT, int EPI, bool NORM, int WQ = WQ_NONE>
 __global__ __launch_bounds__(256) void gemm_mid_kernel(GemmParams p, int ksplit) {
-    static_assert(!(W8 && W4), "one quantised form at a time");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int MP = 16 * MT;
     // 64-k chunks per LDS stage (one barrier each): deeper stages pay while the fp32/fp16 staging
@@ -907,17 +895,17 @@ __global__ __launch_bounds__(256) void gemm_mid_kernel(GemmParams p, int ksplit)
 #pragma unroll
     for (int i = 0; i < MT; ++i) acc[i] = f4{0.f, 0.f, 0.f, 0.f};
     // weights: two NAMED register sets of one stage each (runtime-indexed arrays would go to scratch)
-    typedef std::conditional_t<W4, u32x2, std::conditional_t<W8, u32x4, h8>> wreg_t;   // (W8: the lane's 16 code bytes in wl, wh unused;
-    typedef std::conditional_t<W4, uint32_t, wreg_t> wreg2_t;                          //  W4: its 8 code bytes in wl, the 2 scale bytes in wh)
+    typedef std::conditional_t<WQ == WQ_MXFP4, u32x2, std::conditional_t<WQ == WQ_FP8, u32x4, h8>> wreg_t;   // (WQ_FP8: the lane's 16 code bytes in wl, wh unused;
+    typedef std::conditional_t<WQ == WQ_MXFP4, uint32_t, wreg_t> wreg2_t;                          //  WQ_MXFP4: its 8 code bytes in wl, the 2 scale bytes in wh)
     wreg_t wlA[CH], wlB[CH];
     wreg2_t whA[CH], whB[CH];
-    const uint8_t *qp = W8 ? p.q8 + ((int64_t)panel * chunks) * 1024 + lane * 16 : nullptr;
-    const uint8_t *q4p = W4 ? p.q4 + ((int64_t)panel * chunks) * 512 + lane * 8 : nullptr;
-    const uint8_t *s4p = W4 ? p.s4 + ((int64_t)panel * chunks) * 32 + li * 2 : nullptr;
+    const uint8_t *qp = WQ == WQ_FP8 ? p.wq.codes + ((int64_t)panel * chunks) * 1024 + lane * 16 : nullptr;
+    const uint8_t *q4p = WQ == WQ_MXFP4 ? p.wq.codes + ((int64_t)panel * chunks) * 512 + lane * 8 : nullptr;
+    const uint8_t *s4p = WQ == WQ_MXFP4 ? static_cast<const uint8_t *>(p.wq.scales) + ((int64_t)panel * chunks) * 32 + li * 2 : nullptr;
     auto w_load = [&](wreg_t (&wl)[CH], wreg2_t (&wh)[CH], int c) {
 #pragma unroll
         for (int u = 0; u < CH; ++u) {
-            if constexpr (W4) {
+            if constexpr (WQ == WQ_MXFP4) {
                 if (c + u < c1) {
                     wl[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x2 *>(q4p + (int64_t)(c + u) * 512));
                     wh[u] = __builtin_nontemporal_load(reinterpret_cast<const uint16_t *>(s4p + (int64_t)(c + u) * 32));
@@ -925,7 +913,7 @@ __global__ __launch_bounds__(256) void gemm_mid_kernel(GemmParams p, int ksplit)
                     wl[u] = u32x2{0, 0};
                     wh[u] = 0;
                 }
-            } else if constexpr (W8) {
+            } else if constexpr (WQ == WQ_FP8) {
                 if (c + u < c1) wl[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(qp + (int64_t)(c + u) * 1024));
                 else wl[u] = u32x4{0, 0, 0, 0};
             } else if (c + u < c1) {
@@ -943,9 +931,9 @@ __global__ __launch_bounds__(256) void gemm_mid_kernel(GemmParams p, int ksplit)
 #pragma unroll
         for (int u = 0; u < CH; ++u) {
             h8 w0, w1;
-            if constexpr (W4) {
+            if constexpr (WQ == WQ_MXFP4) {
                 mx4x16_to_h8(wl[u], wh[u], w0, w1);
-            } else if constexpr (W8) {
+            } else if constexpr (WQ == WQ_FP8) {
                 fp8x16_to_h8(wl[u], w0, w1);
             } else {
                 w0 = wl[u];
@@ -979,8 +967,8 @@ __global__ __launch_bounds__(256) void gemm_mid_kernel(GemmParams p, int ksplit)
         }
     }
 
-    if constexpr (W8) {   // this lane's four columns n = 16 panel + 4 g + r: the row exponents (exact: powers of two on fp32 sums)
-        const uint32_t e4 = *reinterpret_cast<const uint32_t *>(p.e8 + panel * 16 + 4 * g);
+    if constexpr (WQ == WQ_FP8) {   // this lane's four columns n = 16 panel + 4 g + r: the row exponents (exact: powers of two on fp32 sums)
+        const uint32_t e4 = *reinterpret_cast<const uint32_t *>(static_cast<const int8_t *>(p.wq.scales) + panel * 16 + 4 * g);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float sc = exp2_i8((int)(int8_t)(e4 >> (8 * r)));
@@ -2326,14 +2314,13 @@ hipError_t launch_splitk_reduce(const GemmParams &p, int ks, hipStream_t s) {
 // weights and nothing waits on a barrier for 64 MFMAs at a time.  vmcnt counts LDS-DMA and register loads
 // together in issue order: the stage's DMA is issued before the 16 weight loads of the stage, of which at
 // most 8 are still in flight at the end, so `s_waitcnt vmcnt(8)` retires the DMA without draining the ring.
-// W8: the ring holds one 16-B register per chunk from the FP8 panels p.q8 instead of two (LPC loads per chunk in the vmcnt
-// arithmetic below), converted exactly in front of the MFMAs; the wave's tile is multiplied by its columns' 2^e8 behind the main loop,
+// WQ_FP8: the ring holds one 16-B register per chunk from the FP8 panels p.wq.codes instead of two (LPC loads per chunk in the vmcnt
+// arithmetic below), converted exactly in front of the MFMAs; the wave's tile is multiplied by its columns' 2^e (p.wq.scales) behind the main loop,
 // ahead of the slabs / the row scale / the gate-up exchange.
-// W4: the ring holds the lane's 8 code bytes and the 2 scale bytes of (row, chunk) from the MXFP4 panels p.q4 / p.s4 - two loads per
+// WQ_MXFP4: the ring holds the lane's 8 code bytes and the 2 scale bytes of (row, chunk) from the MXFP4 panels p.wq.codes / p.wq.scales - two loads per
 // chunk, the fp16 form's vmcnt arithmetic - and the scaled conversion in front of the MFMAs yields the dequantised operands.
-template <int MT, int EPI, bool W8 = false, bool W4 = false>
+template <int MT, int EPI, int WQ = WQ_NONE>
 __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p, int ksplit) {
-    static_assert(!(W8 && W4), "one quantised form at a time");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     OPUS_ARGS_ONE_BATCH(p);
     constexpr int MP = 16 * MT;
@@ -2342,7 +2329,7 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p, int ksplit
     constexpr int STAGE = SC * CIMG;
     constexpr int NPIECE = SC * MP / 8;                              // 1-KB DMA pieces per stage (8 rows x 128 B)
     constexpr int PW = NPIECE / 8;                                   // per wave (MT = 2: 4, MT = 4: 8)
-    constexpr int LPC = W8 ? 1 : 2;                                  // weight loads per chunk and lane
+    constexpr int LPC = WQ == WQ_FP8 ? 1 : 2;                          // weight loads per chunk and lane
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, li = lane & 15;
@@ -2354,9 +2341,9 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p, int ksplit
     const int ky = blockIdx.y;
     const int c0 = kpart_begin(chunks, ky, ksplit), c1 = kpart_begin(chunks, ky + 1, ksplit);
     const half_t *wp = p.W + ((int64_t)panel * chunks) * 1024 + lane * 8;
-    const uint8_t *qp = W8 ? p.q8 + ((int64_t)panel * chunks) * 1024 + lane * 16 : nullptr;
-    const uint8_t *q4p = W4 ? p.q4 + ((int64_t)panel * chunks) * 512 + lane * 8 : nullptr;
-    const uint8_t *s4p = W4 ? p.s4 + ((int64_t)panel * chunks) * 32 + li * 2 : nullptr;
+    const uint8_t *qp = WQ == WQ_FP8 ? p.wq.codes + ((int64_t)panel * chunks) * 1024 + lane * 16 : nullptr;
+    const uint8_t *q4p = WQ == WQ_MXFP4 ? p.wq.codes + ((int64_t)panel * chunks) * 512 + lane * 8 : nullptr;
+    const uint8_t *s4p = WQ == WQ_MXFP4 ? static_cast<const uint8_t *>(p.wq.scales) + ((int64_t)panel * chunks) * 32 + li * 2 : nullptr;
 
     typedef const __attribute__((address_space(1))) void *gptr_t;
     typedef __attribute__((address_space(3))) void *lptr_t;
@@ -2395,15 +2382,15 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p, int ksplit
     for (int i = 0; i < MT; ++i) acc[i] = f4{0.f, 0.f, 0.f, 0.f};
     constexpr int U = 4;                                            // weight ring: 4 chunks = 8 KB per wave (8 measured slower)
     h8 wl[U], wh[U];
-    u32x4 wq[U];                                                    // (W8: the ring; wl / wh are then unused)
-    u32x2 w4q[U];                                                   // (W4: the ring - the codes and, zero-extended, the 2 scale bytes)
+    u32x4 wq[U];                                                    // (WQ_FP8: the ring; wl / wh are then unused)
+    u32x2 w4q[U];                                                   // (WQ_MXFP4: the ring - the codes and, zero-extended, the 2 scale bytes)
     uint32_t w4s[U];
     auto w_load = [&](int u, int c) {
         if (c < c1) {
-            if constexpr (W4) {
+            if constexpr (WQ == WQ_MXFP4) {
                 w4q[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x2 *>(q4p + (int64_t)phys(c) * 512));
                 w4s[u] = __builtin_nontemporal_load(reinterpret_cast<const uint16_t *>(s4p + (int64_t)phys(c) * 32));
-            } else if constexpr (W8) {
+            } else if constexpr (WQ == WQ_FP8) {
                 wq[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(qp + (int64_t)phys(c) * 1024));
             } else {
                 const h8 *ptr = reinterpret_cast<const h8 *>(wp + (int64_t)phys(c) * 1024);
@@ -2433,22 +2420,22 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p, int ksplit
         asm volatile("global_load_dwordx2 %0, %2, off nt\n\tglobal_load_ushort %1, %3, off nt" : "=&v"(q), "=&v"(sc) : "v"(qptr), "v"(sptr));
     };
     auto ring_load = [&](int u, int cn) {
-        if constexpr (W4) ld_q4(w4q[u], w4s[u], q4p + (int64_t)cn * 512, s4p + (int64_t)cn * 32);
-        else if constexpr (W8) ld_q(wq[u], qp + (int64_t)cn * 1024);
+        if constexpr (WQ == WQ_MXFP4) ld_q4(w4q[u], w4s[u], q4p + (int64_t)cn * 512, s4p + (int64_t)cn * 32);
+        else if constexpr (WQ == WQ_FP8) ld_q(wq[u], qp + (int64_t)cn * 1024);
         else ld_nt(wl[u], wh[u], wp + (int64_t)cn * 1024);
     };
     auto ring_pin = [&](int u) {
-        if constexpr (W4) asm volatile("" : "+v"(w4q[u]), "+v"(w4s[u]));
-        else if constexpr (W8) asm volatile("" : "+v"(wq[u]));
+        if constexpr (WQ == WQ_MXFP4) asm volatile("" : "+v"(w4q[u]), "+v"(w4s[u]));
+        else if constexpr (WQ == WQ_FP8) asm volatile("" : "+v"(wq[u]));
         else asm volatile("" : "+v"(wl[u]), "+v"(wh[u]));
     };
     auto ring_mul = [&](int u, int i, h8 a0, h8 a1) {
-        if constexpr (W4) {
+        if constexpr (WQ == WQ_MXFP4) {
             h8 w0, w1;
             mx4x16_to_h8(w4q[u], w4s[u], w0, w1);
             acc[i] = mfma16(w0, a0, acc[i]);   // C^T tile
             acc[i] = mfma16(w1, a1, acc[i]);
-        } else if constexpr (W8) {
+        } else if constexpr (WQ == WQ_FP8) {
             h8 w0, w1;
             fp8x16_to_h8(wq[u], w0, w1);
             acc[i] = mfma16(w0, a0, acc[i]);   // C^T tile
@@ -2500,10 +2487,10 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p, int ksplit
             if (u8 + 1 < SC) read_chunk(u8 + 1, fa[(u8 + 1) & 1]);
             // younger than this chunk's pair (requested U chunks ago): the U-1 later refills, plus this stage's PW DMA
             // requests when the pair was requested before them (first U chunks of the stage)
-            if constexpr (W4) {
+            if constexpr (WQ == WQ_MXFP4) {
                 if (u8 < U) asm volatile("s_waitcnt vmcnt(%2)" : "+v"(w4q[u]), "+v"(w4s[u]) : "n"(LPC * (U - 1) + PWN));
                 else asm volatile("s_waitcnt vmcnt(%2)" : "+v"(w4q[u]), "+v"(w4s[u]) : "n"(LPC * (U - 1)));
-            } else if constexpr (W8) {
+            } else if constexpr (WQ == WQ_FP8) {
                 if (u8 < U) asm volatile("s_waitcnt vmcnt(%1)" : "+v"(wq[u]) : "n"(LPC * (U - 1) + PWN));
                 else asm volatile("s_waitcnt vmcnt(%1)" : "+v"(wq[u]) : "n"(LPC * (U - 1)));
             } else {
@@ -2548,8 +2535,8 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p, int ksplit
         }
     }
 
-    if constexpr (W8) {   // this lane's four columns n = 16 panel + 4 g + r: the row exponents (exact: powers of two on fp32 sums)
-        const uint32_t e4 = *reinterpret_cast<const uint32_t *>(p.e8 + panel * 16 + 4 * g);
+    if constexpr (WQ == WQ_FP8) {   // this lane's four columns n = 16 panel + 4 g + r: the row exponents (exact: powers of two on fp32 sums)
+        const uint32_t e4 = *reinterpret_cast<const uint32_t *>(static_cast<const int8_t *>(p.wq.scales) + panel * 16 + 4 * g);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float sc = exp2_i8((int)(int8_t)(e4 >> (8 * r)));
@@ -2620,11 +2607,13 @@ __global__ __launch_bounds__(512) void gemm_wide_kernel(GemmParams p, int ksplit
 //  panels make 256 workgroups instead of 224 (what an [8 gate | 8 up] panel layout would allow with the pair product done across
 //  lanes): 41.8 vs 42.4 us on the 28672-column shape (-1.4 %; lm_head 207 vs 197 us), timing only.  0.6 us per layer is not
 //  worth a second copy of every gate / up weight: the 224-workgroup grid costs less than the sweep's 256-vs-224 pure-stream gap.)
-template <int MT, int EPI, bool W8 = false, bool W4 = false>
+template <int MT, int EPI, int WQ = WQ_NONE>
 static hipError_t launch_wide(const GemmParams &p, hipStream_t s) {
-    if constexpr (!W8 && !W4) {       // the FP8 / MXFP4 form of the same launch: same grid, LDS, k-parts
-        if (p.q8 && p.e8) return launch_wide<MT, EPI, true>(p, s);
-        if (p.q4 && p.s4) return launch_wide<MT, EPI, false, true>(p, s);
+    if constexpr (WQ == WQ_NONE) {       // the quantised form of the same launch: same grid, LDS, k-parts
+        switch (p.wq.fmt) {
+            case WQ_FP8: return launch_wide<MT, EPI, WQ_FP8>(p, s);
+            case WQ_MXFP4: return launch_wide<MT, EPI, WQ_MXFP4>(p, s);
+        }
     }
     const int blocks = cdiv((p.N + 15) >> 4, 8), chunks = p.K / 64;
     int ks = 1;
@@ -2638,17 +2627,16 @@ static hipError_t launch_wide(const GemmParams &p, hipStream_t s) {
     }
     if (p.ks_out) *p.ks_out = ks;
     const int lds = 2 * (MT <= 4 ? 8 : 4) * 16 * MT * 128 + 16 * MT * (int)sizeof(float);   // two stages + the rows' 1 / rms
-    hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_wide_kernel<MT, EPI, W8, W4>), lds);
+    hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_wide_kernel<MT, EPI, WQ>), lds);
     if (ea != hipSuccess) return ea;
     gemm_plan_set(p, KC_WIDE, MT, 0, 0, 0, 0, ks, ks == 1 ? GC_NONE : GC_SLABS);   // (launch_reduce names the reduce it takes)
-    if (W8 && p.ran_w8) *p.ran_w8 = 1;
-    if (W4 && p.ran_w4) *p.ran_w4 = 1;
+    if (WQ != WQ_NONE && p.ran_wq) *p.ran_wq = WQ;
     if (ks > 1 && p.row_ssq) {       // k-parts leave raw slabs: the row scale is applied by whoever combines them, not here
         GemmParams q = p;
         q.row_ssq = nullptr;
-        OPUS_LAUNCH(KC_WIDE, (gemm_wide_kernel<MT, EPI, W8, W4>), dim3(blocks, ks), dim3(512), lds, s, q, ks);
+        OPUS_LAUNCH(KC_WIDE, (gemm_wide_kernel<MT, EPI, WQ>), dim3(blocks, ks), dim3(512), lds, s, q, ks);
     } else {
-        OPUS_LAUNCH(KC_WIDE, (gemm_wide_kernel<MT, EPI, W8, W4>), dim3(blocks, ks), dim3(512), lds, s, p, ks);
+        OPUS_LAUNCH(KC_WIDE, (gemm_wide_kernel<MT, EPI, WQ>), dim3(blocks, ks), dim3(512), lds, s, p, ks);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || ks == 1 || p.slab_only) return e;
@@ -2656,11 +2644,13 @@ static hipError_t launch_wide(const GemmParams &p, hipStream_t s) {
 }
 
 
-template <int MT, int EPI, bool NORM, bool W8 = false, bool W4 = false>
+template <int MT, int EPI, bool NORM, int WQ = WQ_NONE>
 static hipError_t launch_mid_t(const GemmParams &p, hipStream_t s) {
-    if constexpr (!W8 && !W4 && MT <= 4) {   // the FP8 / MXFP4 form of the same launch (MT = 6 / 8: beyond MID_MAX_M, never launched)
-        if (p.q8 && p.e8) return launch_mid_t<MT, EPI, NORM, true>(p, s);
-        if (p.q4 && p.s4) return launch_mid_t<MT, EPI, NORM, false, true>(p, s);
+    if constexpr (WQ == WQ_NONE && MT <= 4) {   // the quantised form of the same launch (MT = 6 / 8: beyond MID_MAX_M, never launched)
+        switch (p.wq.fmt) {
+            case WQ_FP8: return launch_mid_t<MT, EPI, NORM, WQ_FP8>(p, s);
+            case WQ_MXFP4: return launch_mid_t<MT, EPI, NORM, WQ_MXFP4>(p, s);
+        }
     }
     const int blocks = cdiv((p.N + 15) >> 4, 4), chunks = p.K / 64;
     // k-parts: enough workgroups for ~8 waves per CU, at least 4 chunks each, slabs within the workspace
@@ -2675,14 +2665,13 @@ static hipError_t launch_mid_t(const GemmParams &p, hipStream_t s) {
     constexpr int CH = MT <= 2 ? 4 : 1;
     const size_t lds = 2 * CH * 16 * MT * 128 + 16 * MT * sizeof(float) + 2 * MT * 4 * 64 * sizeof(float);
     if (lds > 48 * 1024) {
-        hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_mid_kernel<MT, EPI, NORM, W8, W4>), lds);
+        hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_mid_kernel<MT, EPI, NORM, WQ>), lds);
         if (ea != hipSuccess) return ea;
     }
     if (p.row_ssq && ks == 1) return hipErrorInvalidValue;            // only the split-K reduce applies a row scale here
     gemm_plan_set(p, KC_MID, MT, 0, 0, 0, 0, ks, GC_NONE);
-    if (W8 && p.ran_w8) *p.ran_w8 = 1;
-    if (W4 && p.ran_w4) *p.ran_w4 = 1;
-    OPUS_LAUNCH(KC_MID, (gemm_mid_kernel<MT, EPI, NORM, W8, W4>), dim3(blocks, ks), dim3(256), lds, s, p, ks);
+    if (WQ != WQ_NONE && p.ran_wq) *p.ran_wq = WQ;
+    OPUS_LAUNCH(KC_MID, (gemm_mid_kernel<MT, EPI, NORM, WQ>), dim3(blocks, ks), dim3(256), lds, s, p, ks);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || ks == 1) return e;
     return launch_reduce<EPI>(p, ks, s);

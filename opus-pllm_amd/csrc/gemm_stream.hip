@@ -45,15 +45,15 @@ __device__ __forceinline__ float gelu_erf_s(float x) {   // same arithmetic as g
 }
 
 // MT row tiles of 16, P panels per workgroup, NT threads, U chunk sets in flight per wave
-// W8: the weight blocks come from the FP8 panels p.q8 (1 KB per block: one 16-B load per lane, converted exactly to the operand
-// type in front of the MFMA) and every wave multiplies its partial tiles by the columns' 2^e8 before the combine, so the slabs,
-// the in-launch combine, the split-K reduce and the attention kernel that sums raw slabs all see the sums they see today.
-// W4: the weight blocks come from the MXFP4 panels p.q4 / p.s4 (512 B of codes + 32 B of scales per block: per lane one 8-B and one
-// 2-B load, the fp16 form's two loads) and the scaled conversion in front of the MFMA yields the dequantised operands themselves:
-// the partial tiles need no scaling.
-template <int MT, int P, int NT, int U, int EPI, bool W8 = false, bool W4 = false>
+// WQ_FP8: the weight blocks come from the FP8 panels p.wq.codes (1 KB per block: one 16-B load per lane, converted exactly to the
+// operand type in front of the MFMA) and every wave multiplies its partial tiles by the columns' 2^e (p.wq.scales) before the
+// combine, so the slabs, the in-launch combine, the split-K reduce and the attention kernel that sums raw slabs all see the sums
+// they see today.
+// WQ_MXFP4: the weight blocks come from the MXFP4 panels p.wq.codes / p.wq.scales (512 B of codes + 32 B of scales per block: per
+// lane one 8-B and one 2-B load, the fp16 form's two loads) and the scaled conversion in front of the MFMA yields the dequantised
+// operands themselves: the partial tiles need no scaling.
+template <int MT, int P, int NT, int U, int EPI, int WQ = WQ_NONE>
 __global__ __launch_bounds__(NT) void gemm_stream_kernel(GemmParams p, int ksplit) {
-    static_assert(!(W8 && W4), "one quantised form at a time");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // Every kernel argument the main path reads, fetched in ONE scalar batch: left to itself the compiler loads the 330-byte
     // argument block piecemeal - six dependent scalar round trips before the first weight load was issued (OPUS_STREAM_TRACE's
@@ -99,23 +99,23 @@ __global__ __launch_bounds__(NT) void gemm_stream_kernel(GemmParams p, int kspli
     const int rot = (p.no_rot || nsteps < 2) ? 0 : (int)((blockIdx.x * 3u + (unsigned)ky) % (unsigned)nsteps);
 
     typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-    std::conditional_t<W8, u32x4, h8> wr[U][P][W8 ? 1 : 2];
-    u32x2 w4q[U][P];                         // (W4: the lane's 8 code bytes and, zero-extended, the 2 scale bytes; wr is then unused)
+    std::conditional_t<WQ == WQ_FP8, u32x4, h8> wr[U][P][WQ == WQ_FP8 ? 1 : 2];
+    u32x2 w4q[U][P];                         // (WQ_MXFP4: the lane's 8 code bytes and, zero-extended, the 2 scale bytes; wr is then unused)
     uint32_t w4s[U][P];
     const uint8_t *q4p[P], *s4p[P];
-    if constexpr (W4) {
-        asm volatile("" ::"s"(p.q4), "s"(p.s4));
+    if constexpr (WQ == WQ_MXFP4) {
+        asm volatile("" ::"s"(p.wq.codes), "s"(p.wq.scales));
 #pragma unroll
         for (int j = 0; j < P; ++j) {
-            q4p[j] = p.q4 + ((int64_t)(panel0 + j) * chunks) * 512 + lane * 8;
-            s4p[j] = p.s4 + ((int64_t)(panel0 + j) * chunks) * 32 + (lane & 15) * 2;
+            q4p[j] = p.wq.codes + ((int64_t)(panel0 + j) * chunks) * 512 + lane * 8;
+            s4p[j] = static_cast<const uint8_t *>(p.wq.scales) + ((int64_t)(panel0 + j) * chunks) * 32 + (lane & 15) * 2;
         }
     }
     const uint8_t *qp[P];
-    if constexpr (W8) {
-        asm volatile("" ::"s"(p.q8), "s"(p.e8));
+    if constexpr (WQ == WQ_FP8) {
+        asm volatile("" ::"s"(p.wq.codes), "s"(p.wq.scales));
 #pragma unroll
-        for (int j = 0; j < P; ++j) qp[j] = p.q8 + ((int64_t)(panel0 + j) * chunks) * 1024 + lane * 16;
+        for (int j = 0; j < P; ++j) qp[j] = p.wq.codes + ((int64_t)(panel0 + j) * chunks) * 1024 + lane * 16;
     }
     u4 ar[U][MT][2];
     f4 acc[P][MT];
@@ -135,10 +135,10 @@ __global__ __launch_bounds__(NT) void gemm_stream_kernel(GemmParams p, int kspli
         c = c < c1 ? c : c1 - 1;             // ragged last step: a harmless re-read, skipped by compute()
 #pragma unroll
         for (int j = 0; j < P; ++j) {
-            if constexpr (W4) {
+            if constexpr (WQ == WQ_MXFP4) {
                 w4q[u][j] = __builtin_nontemporal_load(reinterpret_cast<const u32x2 *>(q4p[j] + (int64_t)c * 512));
                 w4s[u][j] = __builtin_nontemporal_load(reinterpret_cast<const uint16_t *>(s4p[j] + (int64_t)c * 32));
-            } else if constexpr (W8) {
+            } else if constexpr (WQ == WQ_FP8) {
                 wr[u][j][0] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(qp[j] + (int64_t)c * 1024));
             } else {
                 const h8 *ptr = reinterpret_cast<const h8 *>(wp[j] + (int64_t)c * 1024);
@@ -158,9 +158,9 @@ __global__ __launch_bounds__(NT) void gemm_stream_kernel(GemmParams p, int kspli
 #pragma unroll
         for (int j = 0; j < P; ++j) {
             h8 w0, w1;
-            if constexpr (W4) {
+            if constexpr (WQ == WQ_MXFP4) {
                 mx4x16_to_h8(w4q[u][j], w4s[u][j], w0, w1);
-            } else if constexpr (W8) {
+            } else if constexpr (WQ == WQ_FP8) {
                 fp8x16_to_h8(wr[u][j][0], w0, w1);
             } else {
                 w0 = wr[u][j][0];
@@ -197,10 +197,10 @@ __global__ __launch_bounds__(NT) void gemm_stream_kernel(GemmParams p, int kspli
     }
     if (p.trace && tid == 0) p.trace[wg * 8 + 2] = wall_clock64();
 
-    if constexpr (W8) {   // this lane's four columns n = 16 (panel0 + j) + 4 g + r: the row exponents (exact: powers of two on fp32 sums)
+    if constexpr (WQ == WQ_FP8) {   // this lane's four columns n = 16 (panel0 + j) + 4 g + r: the row exponents (exact: powers of two on fp32 sums)
 #pragma unroll
         for (int j = 0; j < P; ++j) {
-            const uint32_t e4 = *reinterpret_cast<const uint32_t *>(p.e8 + (panel0 + j) * 16 + 4 * g);
+            const uint32_t e4 = *reinterpret_cast<const uint32_t *>(static_cast<const int8_t *>(p.wq.scales) + (panel0 + j) * 16 + 4 * g);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float sc = exp2_i8((int)(int8_t)(e4 >> (8 * r)));
@@ -397,16 +397,18 @@ bool gemm_stream_ok(const GemmParams &p) {
     return gemm_stream_would(p.M, p.N, p.K, p.slab_only, p.a_tiled, p.row_ssq != nullptr, p.ws_bytes);
 }
 
-template <int MT, int P, int NT, int U, int EPI, bool W8 = false, bool W4 = false>
+template <int MT, int P, int NT, int U, int EPI, int WQ = WQ_NONE>
 static hipError_t launch_stream_t(const GemmParams &p_in, const StreamPlan &pl, hipStream_t s) {
-    if constexpr (!W8 && !W4) {   // the FP8 / MXFP4 form of the same launch: same plan, grid, LDS and combine
-        if (p_in.q8 && p_in.e8) return launch_stream_t<MT, P, NT, U, EPI, true>(p_in, pl, s);
-        if (p_in.q4 && p_in.s4) return launch_stream_t<MT, P, NT, U, EPI, false, true>(p_in, pl, s);
+    if constexpr (WQ == WQ_NONE) {   // the quantised form of the same launch: same plan, grid, LDS and combine
+        switch (p_in.wq.fmt) {
+            case WQ_FP8: return launch_stream_t<MT, P, NT, U, EPI, WQ_FP8>(p_in, pl, s);
+            case WQ_MXFP4: return launch_stream_t<MT, P, NT, U, EPI, WQ_MXFP4>(p_in, pl, s);
+        }
     }
     GemmParams p = p_in;
     constexpr int NW = NT / 64;
     const size_t lds = (size_t)NW * P * MT * 1024 + 16;      // partial tiles + the "last arriver" word of the in-launch combine
-    hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_stream_kernel<MT, P, NT, U, EPI, W8, W4>), lds);
+    hipError_t ea = ensure_dyn_lds(reinterpret_cast<const void *>(&gemm_stream_kernel<MT, P, NT, U, EPI, WQ>), lds);
     if (ea != hipSuccess) return ea;
     const int npanels = p.N >> 4;
     // k-parts with a finished output: combined inside the launch by the workgroup that arrives last (no reduce launch)
@@ -431,7 +433,7 @@ static hipError_t launch_stream_t(const GemmParams &p_in, const StreamPlan &pl, 
             GemmParams q = p;
             q.trace = tb;
             for (int rep = 0; rep < 3; ++rep)      // (the third launch is reported: code and activations warm, weights from HBM if > caches)
-                hipLaunchKernelGGL((gemm_stream_kernel<MT, P, NT, U, EPI, W8, W4>), dim3(npanels / P, pl.ks), dim3(NT), lds, s, q, pl.ks);
+                hipLaunchKernelGGL((gemm_stream_kernel<MT, P, NT, U, EPI, WQ>), dim3(npanels / P, pl.ks), dim3(NT), lds, s, q, pl.ks);
             (void)hipStreamSynchronize(s);
             std::vector<long long> h((size_t)nwg * 8);
             (void)hipMemcpy(h.data(), tb, h.size() * sizeof(long long), hipMemcpyDeviceToHost);
@@ -461,9 +463,8 @@ static hipError_t launch_stream_t(const GemmParams &p_in, const StreamPlan &pl, 
     }
     if (pl.ks & (pl.ks - 1)) return hipErrorInvalidValue;               // (the kernel cuts K with a shift)
     gemm_plan_set(p_in, KC_STREAM, MT, 0, 0, 0, P, pl.ks, pl.ks == 1 ? GC_NONE : combine ? GC_IN_LAUNCH : GC_SLABS);   // (launch_splitk_reduce names its reduce)
-    if (W8 && p.ran_w8) *p.ran_w8 = 1;
-    if (W4 && p.ran_w4) *p.ran_w4 = 1;
-    OPUS_LAUNCH(KC_STREAM, (gemm_stream_kernel<MT, P, NT, U, EPI, W8, W4>), dim3(npanels / P, pl.ks), dim3(NT), lds, s, p, pl.ks);
+    if (WQ != WQ_NONE && p.ran_wq) *p.ran_wq = WQ;
+    OPUS_LAUNCH(KC_STREAM, (gemm_stream_kernel<MT, P, NT, U, EPI, WQ>), dim3(npanels / P, pl.ks), dim3(NT), lds, s, p, pl.ks);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || pl.ks == 1 || p_in.slab_only || combine) return e;
     return launch_splitk_reduce(p_in, pl.ks, s);                      // (applies bias / residual / row scale, writes xh_out + sums of squares)

@@ -29,7 +29,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Tuple
+from typing import Callable, Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -153,18 +153,24 @@ def untile_weight(t: torch.Tensor) -> torch.Tensor:
     return t.reshape(N // 16, K // 64, 2, 4, 16, 8).permute(0, 4, 1, 2, 3, 5).reshape(N, K).contiguous()
 
 
+def _quantize_via(entry: str, t: torch.Tensor, codes_cols: int, scales_shape: Tuple[int, ...], scales_dtype: torch.dtype):
+    """(codes uint8 [N, codes_cols], scales, dq: the dequantised weights in the operand type, row-major) of a row-major
+    operand-type [N,K] on the GPU via the library's `entry`.  Raises OpusError when a weight is not finite."""
+    assert t.is_cuda and t.dtype == _cabi.operand_dtype() and t.dim() == 2 and t.is_contiguous()
+    N, K = t.shape
+    codes = torch.empty((N, codes_cols), dtype=torch.uint8, device=t.device)
+    scales = torch.empty(scales_shape, dtype=scales_dtype, device=t.device)
+    dq = torch.empty_like(t)
+    with torch.cuda.device(t.device):
+        _cabi.check(getattr(_cabi.lib(), entry)(t.data_ptr(), N, K, codes.data_ptr(), scales.data_ptr(), dq.data_ptr(),
+                                                torch.cuda.current_stream(t.device).cuda_stream))
+    return codes, scales, dq
+
+
 def quantize_fp8(t: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Row-major operand-type [N,K] on the GPU -> (q8 uint8 [N,K]: e4m3fn codes in the FP8 panel layout, e8 int8 [N]: the row
     exponents, dq: q 2^e in the operand type, row-major) via opus_quantize_fp8.  Raises OpusError when a weight is not finite."""
-    assert t.is_cuda and t.dtype == _cabi.operand_dtype() and t.dim() == 2 and t.is_contiguous()
-    N, K = t.shape
-    q8 = torch.empty((N, K), dtype=torch.uint8, device=t.device)
-    e8 = torch.empty((N,), dtype=torch.int8, device=t.device)
-    dq = torch.empty_like(t)
-    with torch.cuda.device(t.device):
-        _cabi.check(_cabi.lib().opus_quantize_fp8(t.data_ptr(), N, K, q8.data_ptr(), e8.data_ptr(), dq.data_ptr(),
-                                                  torch.cuda.current_stream(t.device).cuda_stream))
-    return q8, e8, dq
+    return _quantize_via("opus_quantize_fp8", t, t.shape[1], (t.shape[0],), torch.int8)
 
 
 def untile_fp8(q8: torch.Tensor) -> torch.Tensor:
@@ -177,15 +183,7 @@ def quantize_mxfp4(t: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.T
     """Row-major operand-type [N,K] on the GPU -> (q4 uint8 [N,K/2]: packed e2m1 codes in the MXFP4 code panels, s4 uint8 [N,K/32]:
     the e8m0 block scales in the scale panels, dq: q 2^e in the operand type, row-major) via opus_quantize_mxfp4.  Raises OpusError
     when a weight is not finite."""
-    assert t.is_cuda and t.dtype == _cabi.operand_dtype() and t.dim() == 2 and t.is_contiguous()
-    N, K = t.shape
-    q4 = torch.empty((N, K // 2), dtype=torch.uint8, device=t.device)
-    s4 = torch.empty((N, K // 32), dtype=torch.uint8, device=t.device)
-    dq = torch.empty_like(t)
-    with torch.cuda.device(t.device):
-        _cabi.check(_cabi.lib().opus_quantize_mxfp4(t.data_ptr(), N, K, q4.data_ptr(), s4.data_ptr(), dq.data_ptr(),
-                                                    torch.cuda.current_stream(t.device).cuda_stream))
-    return q4, s4, dq
+    return _quantize_via("opus_quantize_mxfp4", t, t.shape[1] // 2, (t.shape[0], t.shape[1] // 32), torch.uint8)
 
 
 def untile_mxfp4(q4: torch.Tensor, s4: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -199,13 +197,28 @@ def untile_mxfp4(q4: torch.Tensor, s4: torch.Tensor) -> Tuple[torch.Tensor, torc
     return codes, scales
 
 
-DECODER_WEIGHT_FORMATS = (None, "fp8", "fp8_dequantized")
-DECODER_WEIGHT_FORMATS_MX = ("mxfp4", "mxfp4_dequantized")       # OCP MXFP4 (e2m1 codes, one e8m0 scale per 32 k of a row)
+@dataclass(frozen=True)
+class WeightFormat:
+    """One quantised form of the decoder layers' projections: `quantize(t)` -> (codes, scales, dequantised weights), the suffixes
+    the code and scale tensors are bound under with their _cabi dtype codes, and the two values of `decoder_weights` that select
+    it - `keyword` keeps the panels for the decode step, `keyword_dequantized` the dequantised tensors alone."""
+    quantize: Callable[[torch.Tensor], Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]
+    suffixes: Tuple[Tuple[str, int], Tuple[str, int]]
+    keyword: str
+    keyword_dequantized: str
 
 
-def fp8_names(cfg: OpusConfig) -> List[str]:
-    """The fused tensors decoder_weights="fp8" quantises: the four projections of every decoder layer (lm_head, the embeddings,
-    the encoder and the projectors stay as they are)."""
+WEIGHT_FORMATS = (
+    WeightFormat(quantize_fp8, ((".q8", _cabi.OPUS_F8E4M3), (".e8", _cabi.OPUS_I8)), "fp8", "fp8_dequantized"),
+    # OCP MXFP4 (e2m1 codes, one e8m0 scale per 32 k of a row)
+    WeightFormat(quantize_mxfp4, ((".q4", _cabi.OPUS_F4E2M1X2), (".s4", _cabi.OPUS_E8M0)), "mxfp4", "mxfp4_dequantized"),
+)
+DECODER_WEIGHT_FORMATS = (None,) + tuple(k for f in WEIGHT_FORMATS for k in (f.keyword, f.keyword_dequantized))
+
+
+def quantized_names(cfg: OpusConfig) -> List[str]:
+    """The fused tensors a quantised `decoder_weights` format quantises: the four projections of every decoder layer (lm_head, the
+    embeddings, the encoder and the projectors stay as they are)."""
     mats = ("wqkv", "wo", "w1", "w2") if cfg.dec_arch == 1 else ("wqkv", "wo", "wgu", "wd")
     return [f"dec.{l}.{m}" for l in range(cfg.dec_layers) for m in mats]
 
@@ -278,7 +291,7 @@ class DeviceWeights:
 
         `lora` maps a canonical weight name to (A [r,in], B [out,r], alpha, r): merged into that weight
         first, W += (alpha / r) B A, as peft merge_and_unload does at model/builder.py:107-109 (row L1).
-        `decoder_weights`: None, "fp8" or "fp8_dequantized" (_fp8 below), "mxfp4" or "mxfp4_dequantized" (_mxfp4).
+        `decoder_weights`: one of DECODER_WEIGHT_FORMATS (_quantize below).
         """
         self = cls(cfg, torch.device(device))
         self._set_decoder_weights(decoder_weights)
@@ -311,8 +324,8 @@ class DeviceWeights:
                     folded_vec[f.name] = t.float() @ get(wanted[f.name], torch.float32)
                 if f.fold is not None:
                     t.copy_((t.float() * get(f.fold, torch.float32)[None, :]).to(_cabi.operand_dtype()))
-                if f.name in self._fp8_names:
-                    t = self._fp8(f.name, t)
+                if f.name in self._quantized_names:
+                    t = self._quantize(f.name, t)
                 if f.tiled:
                     self.tensors[f.name] = tile_weight(t)
             self._derive(spec, None, None, folded_vec)
@@ -324,35 +337,26 @@ class DeviceWeights:
         return self
 
     def _set_decoder_weights(self, decoder_weights: Optional[str]) -> None:
-        if decoder_weights not in DECODER_WEIGHT_FORMATS + DECODER_WEIGHT_FORMATS_MX:
-            raise ValueError(f"decoder_weights={decoder_weights!r}: one of {DECODER_WEIGHT_FORMATS + DECODER_WEIGHT_FORMATS_MX}")
+        if decoder_weights not in DECODER_WEIGHT_FORMATS:
+            raise ValueError(f"decoder_weights={decoder_weights!r}: one of {DECODER_WEIGHT_FORMATS}")
         self.decoder_weights = decoder_weights
-        self._fp8_names = set(fp8_names(self.cfg)) if decoder_weights else set()
+        self._quantized_names = set(quantized_names(self.cfg)) if decoder_weights else set()
 
-    def _fp8(self, name: str, t: torch.Tensor) -> torch.Tensor:
-        """The FP8 form of the fused decoder-layer weight `name` (row-major, after LoRA merge, concatenation / interleave and norm
-        fold, before tiling): per-row power-of-two exponent + e4m3fn codes (csrc/quant.hip).  Returns the dequantised weights
-        (exactly representable in the operand type), which take the weight's place, so prefill, forward, scoring and every decode
-        launch without an FP8 kernel compute with the same numbers.  "fp8" also keeps the codes and exponents, bound as
-        `name`.q8 / .e8 for the decode step (Llama / Qwen2; OPT / Galactica run on the dequantised tensors); "fp8_dequantized"
-        keeps the dequantised tensors alone (the comparison model)."""
-        if self.decoder_weights in DECODER_WEIGHT_FORMATS_MX:
-            return self._mxfp4(name, t)
-        q8, e8, dq = quantize_fp8(t.contiguous())
-        if self.decoder_weights == "fp8" and self.cfg.dec_arch == 0:
-            self.tensors[name + ".q8"], self.tensors[name + ".e8"] = q8, e8
-        return dq
-
-    def _mxfp4(self, name: str, t: torch.Tensor) -> torch.Tensor:
-        """The MXFP4 form of the fused decoder-layer weight `name`, at the same point of the load as _fp8: e2m1 codes with one
-        power-of-two scale per 32 consecutive k of a row (csrc/quant.hip).  Returns the dequantised weights (exact in the operand
-        type), which take the weight's place.  "mxfp4" also keeps the code and scale panels, bound as `name`.q4 / .s4 for the
-        decode step (Llama / Qwen2; OPT / Galactica run on the dequantised tensors); "mxfp4_dequantized" keeps the dequantised
-        tensors alone (the comparison model).  Uncalibrated round-to-nearest: ~11 % relative rms error per row on Gaussian
-        weights - a different model, and a decode-throughput option that ADDS 0.27 x the decoder-layer weights in memory."""
-        q4, s4, dq = quantize_mxfp4(t.contiguous())
-        if self.decoder_weights == "mxfp4" and self.cfg.dec_arch == 0:
-            self.tensors[name + ".q4"], self.tensors[name + ".s4"] = q4, s4
+    def _quantize(self, name: str, t: torch.Tensor) -> torch.Tensor:
+        """The quantised form (self.decoder_weights, a row of WEIGHT_FORMATS) of the fused decoder-layer weight `name` (row-major,
+        after LoRA merge, concatenation / interleave and norm fold, before tiling), csrc/quant.hip.  FP8: per-row power-of-two
+        exponent + e4m3fn codes.  MXFP4: e2m1 codes with one power-of-two scale per 32 consecutive k of a row.  Returns the
+        dequantised weights (exactly representable in the operand type), which take the weight's place, so prefill, forward,
+        scoring and every decode launch without a kernel for the format compute with the same numbers.  The panels-kept keyword
+        ("fp8", "mxfp4") also keeps the codes and scales, bound as `name` + the format's suffixes (.q8 / .e8, .q4 / .s4) for the
+        decode step (Llama / Qwen2; OPT / Galactica run on the dequantised tensors); the "_dequantized" keyword keeps the
+        dequantised tensors alone (the comparison model).
+        MXFP4 is uncalibrated round-to-nearest: ~11 % relative rms error per row on Gaussian weights - a different model, and a
+        decode-throughput option that ADDS 0.27 x the decoder-layer weights in memory."""
+        fmt = next(f for f in WEIGHT_FORMATS if self.decoder_weights in (f.keyword, f.keyword_dequantized))
+        codes, scales, dq = fmt.quantize(t.contiguous())
+        if self.decoder_weights == fmt.keyword and self.cfg.dec_arch == 0:
+            self.tensors[name + fmt.suffixes[0][0]], self.tensors[name + fmt.suffixes[1][0]] = codes, scales
         return dq
 
     @property
@@ -378,7 +382,7 @@ class DeviceWeights:
                   mlm_head: bool = False, decoder_weights: Optional[str] = None) -> "DeviceWeights":
         """Fill the fused tensors on the GPU with the deterministic synthetic model (synth.py twin); contact_head: also the
         synthetic contact regression (synth.contact_head); mlm_head: also the synthetic masked-LM head (synth.mlm_head);
-        decoder_weights: None, "fp8" or "fp8_dequantized" (_fp8), "mxfp4" or "mxfp4_dequantized" (_mxfp4)."""
+        decoder_weights: one of DECODER_WEIGHT_FORMATS (_quantize)."""
         self = cls(cfg, torch.device(device))
         self._set_decoder_weights(decoder_weights)
         lib = _cabi.lib()
@@ -419,8 +423,8 @@ class DeviceWeights:
                     _cabi.check(lib.opus_fill_synth(t.data_ptr(), _cabi.OPUS_F16 if f.f16 else _cabi.OPUS_F32,
                                                     p.rows, p.cols, synth.tensor_seed(p.canon, seed), std, mean,
                                                     p.rb, p.rs, p.ro, 1 if f.tiled else 0, fseed, fstd, fmean, stream))
-                if f.name in self._fp8_names:            # (filled panel-tiled: back to rows, quantise, tile the dequantised weights)
-                    self.tensors[f.name] = tile_weight(self._fp8(f.name, untile_weight(t)))
+                if f.name in self._quantized_names:      # (filled panel-tiled: back to rows, quantise, tile the dequantised weights)
+                    self.tensors[f.name] = tile_weight(self._quantize(f.name, untile_weight(t)))
             self._derive(fspec, unfolded, vector)
             if contact_head:
                 head = synth.contact_head(cfg, seed)
@@ -432,13 +436,12 @@ class DeviceWeights:
     # -- binding ---------------------------------------------------------------------------------
     def bind(self, ctx) -> None:
         lib = _cabi.lib()
-        codes = {torch.uint8: _cabi.OPUS_F8E4M3, torch.int8: _cabi.OPUS_I8}            # (the FP8 panels and their row exponents)
-        mx = {".q4": _cabi.OPUS_F4E2M1X2, ".s4": _cabi.OPUS_E8M0}                      # (the MXFP4 code and scale panels: uint8 both)
+        quantized = {sfx: code for f in WEIGHT_FORMATS for sfx, code in f.suffixes}     # (the code and scale tensors, by suffix)
         for name, t in list(self.tensors.items()) + list(self.extra.items()):
             shape = (C.c_int64 * t.dim())(*t.shape)
             _cabi.check(lib.opus_bind_weight(ctx, name.encode(), t.data_ptr(),
                                              _cabi.OPUS_F16 if t.dtype == _cabi.operand_dtype() else
-                                             mx[name[-3:]] if name[-3:] in mx else codes.get(t.dtype, _cabi.OPUS_F32),
+                                             quantized.get(name[-3:], _cabi.OPUS_F32),
                                              t.dim(), shape))
         _cabi.check(lib.opus_weights_ready(ctx))
 

@@ -203,12 +203,11 @@ def test_keywords_are_validated_and_load_4bit_is_untouched():
     import inspect
     import opus_pllm_amd as opa
     from opus_pllm_amd import builder, weights
-    assert weights.DECODER_WEIGHT_FORMATS == (None, "fp8", "fp8_dequantized")
-    assert weights.DECODER_WEIGHT_FORMATS_MX == ("mxfp4", "mxfp4_dequantized")
+    assert weights.DECODER_WEIGHT_FORMATS == (None, "fp8", "fp8_dequantized", "mxfp4", "mxfp4_dequantized")
     for fn in (weights.DeviceWeights.from_canonical, weights.DeviceWeights.synthetic):
         assert inspect.signature(fn).parameters["decoder_weights"].default is None
     w = weights.DeviceWeights(opa.micro(), torch.device("cpu"))
-    for fmt in weights.DECODER_WEIGHT_FORMATS + weights.DECODER_WEIGHT_FORMATS_MX:
+    for fmt in weights.DECODER_WEIGHT_FORMATS:
         w._set_decoder_weights(fmt)
         assert w.decoder_weights == fmt
     assert w.decoder_weight_format == "mxfp4_dequantized"

@@ -138,10 +138,10 @@ def test_header_has_the_new_symbols_at_abi_10():
 def test_keyword_is_validated_and_load_4bit_is_untouched():
     import inspect
     from opus_pllm_amd import builder, weights
-    assert weights.DECODER_WEIGHT_FORMATS == (None, "fp8", "fp8_dequantized")
+    assert weights.DECODER_WEIGHT_FORMATS == (None, "fp8", "fp8_dequantized", "mxfp4", "mxfp4_dequantized")
     for fn in (weights.DeviceWeights.from_canonical, weights.DeviceWeights.synthetic):
         assert inspect.signature(fn).parameters["decoder_weights"].default is None
     src = inspect.getsource(builder.load_pretrained_model)
     assert "decoder_weights" in src and "loading unquantised fp16" in src
     import opus_pllm_amd as opa
-    assert weights.fp8_names(opa.micro())[:4] == ["dec.0.wqkv", "dec.0.wo", "dec.0.wgu", "dec.0.wd"]
+    assert weights.quantized_names(opa.micro())[:4] == ["dec.0.wqkv", "dec.0.wo", "dec.0.wgu", "dec.0.wd"]
