@@ -292,6 +292,50 @@ int opus_trie_path_sums(opus_ctx *ctx, const float *d_node_lp, const int32_t *d_
 int opus_debug_attn_tree(opus_ctx *ctx, const void *d_qkv, const void *d_k_hist, const void *d_v_hist, const int32_t *d_kstart,
                          int32_t P, int32_t Tp, int32_t R, const int32_t *h_src, const int32_t *h_par, const int32_t *h_depth,
                          void *d_out, void *stream);
+/* Trie search (OpusLlamaForCausalLM.search_trie): beam search for the best members of a token trie behind a cached prefix.  The
+ * decoder runs P x K rows (row p K + k = beam k of prompt p) through opus_llama_prefill_behind / opus_llama_decode_step; between
+ * two passes opus_trie_search_level expands every prompt's beams on the device (trie_beam_expand_kernel, one workgroup per
+ * prompt), its `parent` array is what opus_kv_reorder takes and its `tok` array what the next step takes.
+ *
+ * opus_set_trie_search uploads the table (host arrays, copied to a device allocation the context owns; returns after the stream
+ * has finished): the tries' children in CSR form - state s owns edges edge_off[s] .. edge_off[s + 1), ids ascending and inside the
+ * vocabulary, edge_next the child states; member[s] >= 0: the member index of a state that completes a member (-1 otherwise);
+ * stop_set[s] in [0, n_sets): the id set of the state's trie, ids stop_ids[stop_off[set] .. stop_off[set + 1]) (at least one id per
+ * set).  State 0 is the dead state: no edges, no member.  Every array is checked (OPUS_EBADARG); n_edges < 2^27. */
+int opus_set_trie_search(opus_ctx *ctx, int32_t n_states, const int32_t *edge_off, const int32_t *edge_tok, const int32_t *edge_next,
+                         int32_t n_edges, const int32_t *member, const int32_t *stop_set, int32_t n_sets, const int32_t *stop_off,
+                         const int32_t *stop_ids, void *stream);
+/* One level's device arrays, P prompts x K beams (1 <= top <= K <= 16).  Beam k of prompt p stands in state state[p K + k] with
+ * the running score score[p K + k] (-inf or state 0: dead).  The call replaces both by the K best continuations (score descending,
+ * ties to the lower (beam, id); dead: state 0, -inf), writes their ids to tok (dead: a valid id), the ROW p K + k' each continues to
+ * parent (dead: its own row) and, optionally, the edge's log-prob to edge_lp and each old beam's stop term to beam_stop.  The
+ * pool (pool_member -1 / pool_lp -inf / pool_stop -inf = empty) keeps the best `top` members by pool_lp + pool_stop, ties to the
+ * lower member index.  flags [P, 3]: {live, exhaustive, some beam changes its row}; set {1, 1, 0} before the first level.  A
+ * prompt whose best beam is strictly below its top-th pool entry, or that has no beam left, stops: live = 0, all beams dead.
+ * d_words [2] receives {prompts still live, prompts whose beams change rows}; d_lse [rows] is scratch for the rows' log-sum-exp. */
+typedef struct opus_trie_search_io {
+    int32_t P, K, top, include_stop;
+    int32_t *d_state;
+    float *d_score;
+    int32_t *d_tok, *d_parent;
+    int32_t *d_pool_member;
+    float *d_pool_lp, *d_pool_stop;
+    int32_t *d_flags;
+    int32_t *d_words;
+    float *d_lse;
+    float *d_edge_lp, *d_beam_stop;   /* optional (NULL: off) */
+} opus_trie_search_io;
+/* The first level's logits: final norm + lm_head of d_last_rows fp32 [P, H] (opus_llama_prefix's last rows) into the context's
+ * logits, one row per prompt.  The context is left without a prefill (opus_llama_prefill_behind follows). */
+int opus_trie_search_begin(opus_ctx *ctx, const float *d_last_rows, int32_t P, void *stream);
+/* One level on the context's logits: first != 0: the P rows opus_trie_search_begin left (only beam 0 of a prompt is read);
+ * otherwise the P K rows of the last prefill / decode step (OPUS_ESHAPE when that had another row count).  Needs
+ * opus_set_trie_search (OPUS_ESTATE).  Reads the logits, never writes them; fixed orders, bitwise repeatable.  Phase "decode". */
+int opus_trie_search_level(opus_ctx *ctx, const opus_trie_search_io *io, int32_t first, void *stream);
+/* Diagnostic: the same launch on caller logits fp32 [rows, V] (rows = P when first != 0, else P K; P K <= max_batch); the table's ids
+ * must lie below V.  d_lse of `io` receives the rows' log-sum-exp as the kernel used it. */
+int opus_debug_trie_beam_expand(opus_ctx *ctx, const float *d_logits, int32_t V, const opus_trie_search_io *io, int32_t first,
+                                void *stream);
 /* ESM-2 contact maps (EsmContactPredictionHead / fair-esm return_contacts=True) beside the per-residue states, on the token-packed
  * encoder: the same arguments and pooled output as opus_esm2_encode_packed, then d_contacts fp32 receives protein b's [n_b, n_b]
  * map (n_b = cu[b + 1] - cu[b] - 2 residues, row-major) at element offset sum_{b' < b} n_{b'}^2.  Needs the optional weights
@@ -769,8 +813,8 @@ int64_t opus_stat(opus_ctx *ctx, const char *name);
  * belongs to, and its ALGORITHMIC bytes and FLOPs.  opus_timing_get sums the records since the last reset that match
  * kernel_class and phase ("*" = any); opus_timing_names returns "class,class,...;phase,phase,..." .  Classes and phases are
  * addressed by name, never by position.  Order of the lists: phases are append-only ("score" last); among the classes "xent"
- * stays the last entry, as published since opus_llama_forward, and a class added later ("contact", "constraint", "guidance", "mlm", "logitproc") is
- * listed in front of it ("logitproc" keeps its place next to "xent"). */
+ * stays the last entry, as published since opus_llama_forward, and a class added later ("contact", "trie_search", "constraint", "guidance", "mlm", "logitproc") is
+ * listed in front of it ("constraint", "guidance", "mlm", "logitproc" keep their places next to "xent"). */
 int opus_timing_enable(opus_ctx *ctx, int32_t on);
 int opus_timing_reset(opus_ctx *ctx);
 int opus_timing_get(opus_ctx *ctx, const char *kernel_class, const char *phase, double *ms, int64_t *launches, double *bytes,

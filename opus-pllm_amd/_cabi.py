@@ -64,6 +64,16 @@ class CPrefixSnap(C.Structure):
 
 
 _SNAP = C.POINTER(CPrefixSnap)
+
+
+class CTrieSearchIO(C.Structure):
+    """struct opus_trie_search_io (include/opus_pllm.h): one level's device arrays of search_trie()."""
+    _fields_ = [("P", C.c_int32), ("K", C.c_int32), ("top", C.c_int32), ("include_stop", C.c_int32),
+                ("d_state", _P), ("d_score", _P), ("d_tok", _P), ("d_parent", _P), ("d_pool_member", _P), ("d_pool_lp", _P),
+                ("d_pool_stop", _P), ("d_flags", _P), ("d_words", _P), ("d_lse", _P), ("d_edge_lp", _P), ("d_beam_stop", _P)]
+
+
+_TSIO = C.POINTER(CTrieSearchIO)
 _I32P = C.POINTER(C.c_int32)
 # name -> (restype, argtypes): every symbol include/opus_pllm.h declares
 SIGNATURES = {
@@ -164,6 +174,10 @@ SIGNATURES = {
     "opus_llama_dec_rows_cap": (C.c_int64, [C.POINTER(CConfig)]),
     "opus_llama_tree_max_depth": (C.c_int32, []),
     "opus_trie_path_sums": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "opus_set_trie_search": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
+    "opus_trie_search_begin": (C.c_int, [_P, _P, C.c_int32, _P]),
+    "opus_trie_search_level": (C.c_int, [_P, _TSIO, C.c_int32, _P]),
+    "opus_debug_trie_beam_expand": (C.c_int, [_P, _P, C.c_int32, _TSIO, C.c_int32, _P]),
     "opus_debug_attn_tree": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     "opus_debug_xent": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "opus_esm2_contacts_packed": (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.c_int32, _P, _P, _P, C.c_int64, _P]),

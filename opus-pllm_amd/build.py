@@ -18,7 +18,7 @@ SRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "lib", "libopus_pllm.so")
 LIB_BF16 = os.path.join(HERE, "lib", "libopus_pllm_bf16.so")      # the same sources with -DOPUS_BF16 (csrc/common.h)
-SOURCES = ["gemm.hip", "gemm_stream.hip", "norm.hip", "elementwise.hip", "attn_prefill.hip", "attn_prefix.hip", "kv_place.hip", "stream.hip", "attn_decode.hip", "beam.hip", "score.hip", "contact.hip", "mlm.hip", "logits_proc.hip", "constraint.hip", "guidance.hip", "quant.hip", "lookup.hip", "api.cpp"]
+SOURCES = ["gemm.hip", "gemm_stream.hip", "norm.hip", "elementwise.hip", "attn_prefill.hip", "attn_prefix.hip", "kv_place.hip", "stream.hip", "attn_decode.hip", "beam.hip", "score.hip", "contact.hip", "mlm.hip", "logits_proc.hip", "constraint.hip", "guidance.hip", "quant.hip", "lookup.hip", "trie_search.hip", "api.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
@@ -36,7 +36,8 @@ EXTRA = {"attn_prefill.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-na
 # one more fusion will not fit): checked from the compiler's own resource remarks on every build, a hard failure.
 NO_SCRATCH = ("gemm_pp_kernel", "gemm_stream_kernel", "gemm_wide_kernel", "gemm_skinny_kernel", "attn_prefill_kernel",
               "attn_decode_kernel", "attn_prefix_kernel", "tree_path_sums_kernel", "beam_", "kv_export_kernel", "kv_place_kernel",
-              "kv_append_kernel", "guidance_", "stream_finish_kernel", "stream_refill_kernel", "stream_reset_kernel")
+              "kv_append_kernel", "guidance_", "stream_finish_kernel", "stream_refill_kernel", "stream_reset_kernel", "trie_beam_expand_kernel",
+              "trie_search_summary_kernel")
 RU_FLAG = "-Rpass-analysis=kernel-resource-usage"
 
 

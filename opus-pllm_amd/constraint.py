@@ -471,5 +471,61 @@ def plan_trie_score(tries: Sequence[TokenTrie], include_stop: bool, rows_cap: in
     return plan
 
 
+# ---------------------------------------------------------------------------------------------------- search_trie(): the table
+TRIE_SEARCH_MAX_BEAMS = 16    # beams per prompt search_trie() takes (the expand kernel's register lists)
+
+
+class TrieSearchTable:
+    """What search_trie() uploads (opus_set_trie_search): the children of the distinct tries in CSR form.  State 0 is the dead state;
+    node n of distinct trie k is state root[k] + n, so a state minus its root is score_trie()'s node number.  edge_off / edge_tok
+    (ascending within a state) / edge_next; member [states]: the member index of a node that completes a member, -1 otherwise;
+    stop_set [states]: the trie's entry in stop_off / stop_ids (TokenTrie.stop_ids(): what score_trie's stop term sums);
+    start [P]: the root of prompt p's trie.  The separator's edges are not part of it: the search ends at one member."""
+
+    def __init__(self, tries: Sequence[TokenTrie]):
+        tries = list(tries)
+        if not tries or any(not isinstance(t, TokenTrie) for t in tries):
+            raise TypeError("TrieSearchTable takes a non-empty list of TokenTrie objects")
+        distinct, index = [], {}
+        for t in tries:
+            if id(t) not in index:
+                index[id(t)] = len(distinct)
+                distinct.append(t)
+        counts, toks, nxts, member, sset, roots, soff, sids = [0], [], [], [-1], [0], [], [0], []
+        for k, t in enumerate(distinct):
+            base = len(counts)
+            roots.append(base)
+            of_node = {n: m for m, n in enumerate(t.member_nodes)}
+            for n, kids in enumerate(t.children):
+                counts.append(len(kids))
+                for tok in sorted(kids):
+                    toks.append(tok)
+                    nxts.append(base + kids[tok])
+                member.append(of_node.get(n, -1))
+                sset.append(k)
+            sids += t.stop_ids()
+            soff.append(len(sids))
+        off = np.zeros(len(counts) + 1, dtype=np.int64)
+        np.cumsum(np.asarray(counts, dtype=np.int64), out=off[1:])
+        if off[-1] >= 2 ** 27 or len(counts) >= 2 ** 31:
+            raise ValueError("the trie's table does not fit the search kernel's 27-bit edge numbers")
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)                           # noqa: E731
+        self.tries = distinct
+        self.edge_off, self.edge_tok, self.edge_next = i32(off), i32(toks), i32(nxts)
+        self.member, self.stop_set, self.stop_off, self.stop_ids = i32(member), i32(sset), i32(soff), i32(sids)
+        self.root = i32(roots)
+        self.trie_of_row = i32([index[id(t)] for t in tries])
+        self.start = self.root[self.trie_of_row]
+        self.max_depth = max(t.max_depth for t in distinct)
+
+    @property
+    def n_states(self) -> int:
+        return len(self.member)
+
+    @property
+    def n_edges(self) -> int:
+        return len(self.edge_tok)
+
+
 def is_constraint(obj) -> bool:
     return isinstance(obj, (TokenTrie, PerRowTokenTrie))

@@ -197,6 +197,11 @@ struct opus_ctx {
     char *proj_big = nullptr;
     // beam search (opus_beam_topk / opus_kv_reorder): one layer's K and V cache rows while they are permuted (first use allocates)
     half_t *kv_tmp = nullptr;
+    // trie search (opus_set_trie_search): the table in an allocation of its own, grown on use; ts.edge_off == nullptr: none set
+    char *ts_tab = nullptr;
+    size_t ts_tab_bytes = 0;
+    TrieSearchTable ts{};
+    int32_t ts_max_id = -1;
     // cache epoch: a new value (process-wide unique, so that a handle of another context never matches) whenever a call prefills or
     // permutes the KV cache; opus_llama_prefix hands it out, opus_llama_score_continuations checks it.  h_kstart: the first real
     // slot of every row of the last opus_llama_prefix (host copy for the continuation rows' positions).
@@ -474,6 +479,7 @@ extern "C" int opus_ctx_destroy(opus_ctx *c) {
     if (c->gen_mem) (void)hipFree(c->gen_mem);
     if (c->lproc_mem) (void)hipFree(c->lproc_mem);
     if (c->cons_tab) (void)hipFree(c->cons_tab);
+    if (c->ts_tab) (void)hipFree(c->ts_tab);
     if (c->cons_mem) (void)hipFree(c->cons_mem);
     if (c->guid_mem) (void)hipFree(c->guid_mem);
     if (c->guid_keep) (void)hipFree(c->guid_keep);
@@ -3792,6 +3798,129 @@ extern "C" int opus_kv_reorder(opus_ctx *c, const int32_t *d_src_rows, int32_t R
     return OPUS_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ trie search
+extern "C" int opus_set_trie_search(opus_ctx *c, int32_t n_states, const int32_t *edge_off, const int32_t *edge_tok,
+                                    const int32_t *edge_next, int32_t n_edges, const int32_t *member, const int32_t *stop_set,
+                                    int32_t n_sets, const int32_t *stop_off, const int32_t *stop_ids, void *stream) {
+    const char *who = "set_trie_search";
+    if (!c) return fail(OPUS_EBADARG, "ctx is null");
+    if (n_states < 2 || n_edges < 1 || n_sets < 1 || !edge_off || !edge_tok || !edge_next || !member || !stop_set || !stop_off || !stop_ids)
+        return fail(OPUS_EBADARG, "%s: null table or empty trie", who);
+    if (n_edges >= (1 << 27)) return fail(OPUS_EBADARG, "%s: %d edges (below 2^27)", who, n_edges);
+    const int V = c->cfg.dec_vocab;
+    if (edge_off[0] != 0 || edge_off[1] != 0 || edge_off[n_states] != n_edges || member[0] >= 0)
+        return fail(OPUS_EBADARG, "%s: edge_off must run from 0 to n_edges and state 0 is the dead state (no edges, no member)", who);
+    if (stop_off[0] != 0) return fail(OPUS_EBADARG, "%s: stop_off must start at 0", who);
+    for (int k = 0; k < n_sets; ++k)
+        if (stop_off[k + 1] <= stop_off[k] || stop_off[k + 1] - stop_off[k] > TC_MAX_END + 1)
+            return fail(OPUS_EBADARG, "%s: stop set %d holds %d ids (1 to %d)", who, k, stop_off[k + 1] - stop_off[k], TC_MAX_END + 1);
+    const int n_ids = stop_off[n_sets];
+    int32_t max_id = -1;
+    for (int k = 0; k < n_ids; ++k) {
+        if (stop_ids[k] < 0 || stop_ids[k] >= V) return fail(OPUS_EBADARG, "%s: stop id %d outside [0, %d)", who, stop_ids[k], V);
+        if (stop_ids[k] > max_id) max_id = stop_ids[k];
+    }
+    for (int s = 0; s < n_states; ++s) {
+        const int e0 = edge_off[s], e1 = edge_off[s + 1];
+        if (e1 < e0 || e1 > n_edges) return fail(OPUS_EBADARG, "%s: edge_off not monotone at state %d", who, s);
+        for (int e = e0; e < e1; ++e) {
+            if (edge_tok[e] < 0 || edge_tok[e] >= V) return fail(OPUS_EBADARG, "%s: id %d outside [0, %d)", who, edge_tok[e], V);
+            if (e > e0 && edge_tok[e] <= edge_tok[e - 1]) return fail(OPUS_EBADARG, "%s: ids of state %d not ascending", who, s);
+            if (edge_next[e] < 1 || edge_next[e] >= n_states) return fail(OPUS_EBADARG, "%s: target %d outside [1, %d)", who, edge_next[e], n_states);
+        }
+        if (e1 > e0 && edge_tok[e1 - 1] > max_id) max_id = edge_tok[e1 - 1];
+        if (stop_set[s] < 0 || stop_set[s] >= n_sets) return fail(OPUS_EBADARG, "%s: stop set %d of state %d outside [0, %d)", who, stop_set[s], s, n_sets);
+    }
+    HIPC(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t o_tok = align_up((size_t)(n_states + 1) * 4), o_nxt = o_tok + align_up((size_t)n_edges * 4),
+                 o_mem = o_nxt + align_up((size_t)n_edges * 4), o_set = o_mem + align_up((size_t)n_states * 4),
+                 o_off = o_set + align_up((size_t)n_states * 4), o_ids = o_off + align_up((size_t)(n_sets + 1) * 4),
+                 total = o_ids + align_up((size_t)n_ids * 4);
+    HIPC(hipStreamSynchronize(s));           // a call in flight may still read the table that is replaced
+    c->ts.edge_off = nullptr;
+    if (total > c->ts_tab_bytes) {
+        if (c->ts_tab) HIPC(hipFree(c->ts_tab));
+        c->ts_tab = nullptr;
+        c->ts_tab_bytes = 0;
+        HIPC(hipMalloc((void **)&c->ts_tab, total));
+        c->ts_tab_bytes = total;
+    }
+    char *t = c->ts_tab;
+    HIPC(hipMemcpyAsync(t, edge_off, (size_t)(n_states + 1) * 4, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(t + o_tok, edge_tok, (size_t)n_edges * 4, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(t + o_nxt, edge_next, (size_t)n_edges * 4, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(t + o_mem, member, (size_t)n_states * 4, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(t + o_set, stop_set, (size_t)n_states * 4, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(t + o_off, stop_off, (size_t)(n_sets + 1) * 4, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(t + o_ids, stop_ids, (size_t)n_ids * 4, hipMemcpyHostToDevice, s));
+    HIPC(hipStreamSynchronize(s));           // the host arrays are the caller's again
+    auto at = [&](size_t o) { return reinterpret_cast<const int32_t *>(t + o); };
+    c->ts = TrieSearchTable{at(0), at(o_tok), at(o_nxt), at(o_mem), at(o_set), at(o_off), at(o_ids), n_states, n_edges};
+    c->ts_max_id = max_id;
+    return OPUS_OK;
+}
+
+extern "C" int opus_trie_search_begin(opus_ctx *c, const float *d_last_rows, int32_t P, void *stream) {
+    OPC(need_ready(c));
+    if (!d_last_rows) return fail(OPUS_EBADARG, "trie_search_begin: null pointer");
+    if (P < 1 || P > c->cfg.max_batch) return fail(OPUS_ESHAPE, "trie_search_begin: P=%d prompts, the context holds max_batch=%d", P, c->cfg.max_batch);
+    hipStream_t s = (hipStream_t)stream;
+    new_epoch(c);                            // (d_xl and the logits are the decode state's)
+    c->prefilled = false;
+    c->cur_B = 0;
+    c->phase = PH_DECODE;
+    HIPC(hipMemcpyAsync(c->d_xl, d_last_rows, (size_t)P * c->cfg.dec_dim * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (c->cfg.dec_arch == 1) return lm_head_opt(c, s, P);
+    ResidShadow none;
+    return lm_head(c, s, none, P);
+}
+
+// the level on `logits` (rows of V floats): the rows' log-sum-exp (the arg-max pass of opus_debug_argmax_lse; its indices land in
+// d_tok, which the level overwrites), then trie_beam_expand_kernel
+static int trie_search_level(opus_ctx *c, const char *who, const float *logits, int V, const opus_trie_search_io *io, bool first, hipStream_t s) {
+    if (!c->ts.edge_off) return fail(OPUS_ESTATE, "%s: no table set (opus_set_trie_search)", who);
+    if (!io || !io->d_state || !io->d_score || !io->d_tok || !io->d_parent || !io->d_pool_member || !io->d_pool_lp || !io->d_pool_stop ||
+        !io->d_flags || !io->d_words || !io->d_lse)
+        return fail(OPUS_EBADARG, "%s: null pointer", who);
+    if (io->P < 1 || io->K < 1 || io->K > TS_MAXK || io->top < 1 || io->top > io->K || (int64_t)io->P * io->K > c->cfg.max_batch)
+        return fail(OPUS_ESHAPE, "%s: P=%d K=%d top=%d (1 <= top <= K <= %d, P x K <= max_batch=%d)", who, io->P, io->K, io->top, TS_MAXK, c->cfg.max_batch);
+    if (c->ts_max_id >= V) return fail(OPUS_ESHAPE, "%s: the table holds id %d, V=%d", who, c->ts_max_id, V);
+    OPC(ensure_gen_mem(c));
+    const int rows = first ? io->P : io->P * io->K;
+    KL(KC_OTHER, 4.0 * rows * V, launch_argmax_lse_partial(logits, rows, V, c->d_pval, c->d_pidx, c->d_gpsum, s));
+    KL(KC_OTHER, 512.0 * rows, launch_argmax_lse_final(c->d_pval, c->d_pidx, c->d_gpsum, rows, io->d_tok, io->d_lse, s));
+    TrieSearchLevel a{};
+    a.logits = logits; a.lse = io->d_lse; a.ld = V;
+    a.K = io->K; a.top = io->top; a.include_stop = io->include_stop ? 1 : 0; a.rows_per_prompt = first ? 1 : io->K;
+    a.state_in = io->d_state; a.score_in = io->d_score;
+    a.tok = io->d_tok; a.parent = io->d_parent; a.state_out = io->d_state; a.score_out = io->d_score;
+    a.pool_member = io->d_pool_member; a.pool_lp = io->d_pool_lp; a.pool_stop = io->d_pool_stop;
+    a.flags = io->d_flags; a.edge_lp = io->d_edge_lp; a.beam_stop = io->d_beam_stop;
+    // (bytes: per beam a few hundred edges' ids, targets, member words and logits; counted for the widest case the table allows)
+    KL(KC_TRIE_SEARCH, 16.0 * io->P * io->K * (double)c->ts.n_edges / (double)c->ts.n_states, launch_trie_beam_expand(c->ts, a, io->P, io->d_words, s));
+    return OPUS_OK;
+}
+
+extern "C" int opus_trie_search_level(opus_ctx *c, const opus_trie_search_io *io, int32_t first, void *stream) {
+    if (!c) return fail(OPUS_EBADARG, "ctx is null");
+    HIPC(hipSetDevice(c->device));
+    if (!first && !c->prefilled) return fail(OPUS_ESTATE, "trie_search_level before the beams' prefill");
+    if (io && !first && io->P * io->K != c->cur_B)
+        return fail(OPUS_ESHAPE, "trie_search_level: P=%d x K=%d rows, the last step had %d", io->P, io->K, c->cur_B);
+    c->phase = PH_DECODE;
+    return trie_search_level(c, "trie_search_level", c->d_logits, c->cfg.dec_vocab, io, first != 0, (hipStream_t)stream);
+}
+
+extern "C" int opus_debug_trie_beam_expand(opus_ctx *c, const float *d_logits, int32_t V, const opus_trie_search_io *io, int32_t first,
+                                           void *stream) {
+    if (!c || !d_logits) return fail(OPUS_EBADARG, "debug_trie_beam_expand: null pointer");
+    if (V < 1) return fail(OPUS_ESHAPE, "debug_trie_beam_expand: V=%d", V);
+    HIPC(hipSetDevice(c->device));
+    c->phase = PH_OTHER;
+    return trie_search_level(c, "debug_trie_beam_expand", d_logits, V, io, first != 0, (hipStream_t)stream);
+}
+
 // fp32 logits [B, dec_vocab] of the most recent prefill / decode step of this context (the optional logits gather of
 // SURVEY 8e; also what a caller needs to apply its own logits processors).
 extern "C" int opus_last_logits(opus_ctx *c, float *d_out, int32_t B, void *stream) {
@@ -4015,7 +4144,7 @@ extern "C" int opus_timing_reset(opus_ctx *c) {
     return OPUS_OK;
 }
 static const char *kclass_names[KC_COUNT] = {"gemm_skinny", "gemm_mid", "gemm_wide", "gemm_ring", "gemm_pp", "gemm_tile", "splitk_reduce",
-                                            "attn_prefill", "attn_decode", "norm", "other", "gemm_stream", "contact", "constraint", "guidance", "mlm", "logitproc",
+                                            "attn_prefill", "attn_decode", "norm", "other", "gemm_stream", "contact", "trie_search", "constraint", "guidance", "mlm", "logitproc",
                                             "xent"};
 static const char *phase_names[PH_COUNT] = {"encode", "project", "splice", "prefill", "decode", "other", "score"};
 

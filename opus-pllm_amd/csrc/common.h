@@ -52,7 +52,7 @@ int skinny_max_m();   // rows up to which the skinny kernel is used (default 4, 
 constexpr int MID_MAX_M = 64;   // (65..128 rows measured faster on the split-K tile kernel)
 // kernel classes of the per-launch timing (opus_timing_get): one per kernel family
 enum KClass { KC_SKINNY = 0, KC_MID, KC_WIDE, KC_RING, KC_PP, KC_TILE, KC_REDUCE, KC_ATTN_PREFILL, KC_ATTN_DECODE, KC_NORM,
-              KC_OTHER, KC_STREAM, KC_CONTACT, KC_CONSTRAINT, KC_GUIDANCE, KC_MLM, KC_LOGITPROC, KC_XENT, KC_COUNT };
+              KC_OTHER, KC_STREAM, KC_CONTACT, KC_TRIE_SEARCH, KC_CONSTRAINT, KC_GUIDANCE, KC_MLM, KC_LOGITPROC, KC_XENT, KC_COUNT };
 // Ordering rule of the published class list (opus_timing_names, include/opus_pllm.h): "xent" stays its last entry, as published
 // since opus_llama_forward, and a class added later goes in front of it.  Classes are looked up by name, never by index.
 // phases of the path a launch belongs to (set by the entry points of api.cpp)
@@ -630,6 +630,34 @@ hipError_t launch_beam_sample(const float *logits, const float *run, int B, int 
 hipError_t launch_kv_gather_rows(half_t *cache, half_t *tmp, const int32_t *idx, int R, int64_t row_halfs, int nsub, int64_t sub_halfs,
                                  const int32_t *step, int T0, int hd, int back, hipStream_t s);
 hipError_t launch_upload_i32(const int32_t *h, int n, int32_t *dst, hipStream_t s);   // host ints -> device through kernel arguments
+// trie_search.hip: one level of search_trie()'s beam search per launch, one workgroup per prompt (opus_trie_search_level)
+constexpr int TS_MAXK = 16;            // beams per prompt, and pool entries, at most
+struct TrieSearchTable {               // opus_set_trie_search: the tries' children in CSR form; state 0 is the dead state
+    const int32_t *edge_off;           // [n_states + 1]
+    const int32_t *edge_tok;           // [n_edges] ids, ascending within a state
+    const int32_t *edge_next;          // [n_edges] child states
+    const int32_t *member;             // [n_states] member index of a state that completes a member, -1 otherwise
+    const int32_t *stop_set;           // [n_states] the stop id set of the state's trie
+    const int32_t *stop_off;           // [n_sets + 1]
+    const int32_t *stop_ids;           // [stop_off[n_sets]]
+    int32_t n_states, n_edges;
+};
+struct TrieSearchLevel {               // == struct opus_trie_search_io behind the logits (include/opus_pllm.h)
+    const float *logits;               // rows of `ld` floats: row p K + k of beam k (rows_per_prompt == 1: row p, the first level)
+    const float *lse;                  // the rows' log-sum-exp
+    int64_t ld;
+    int32_t K, top, include_stop, rows_per_prompt;
+    const int32_t *state_in;           // [P, K] (in and out may be the same memory)
+    const float *score_in;             // [P, K] running scores, -inf = dead
+    int32_t *tok, *parent, *state_out; // [P, K] next id, parent ROW (p K + k'), next state; dead: a valid id, the own row, 0
+    float *score_out;                  // [P, K] descending, -inf = dead
+    int32_t *pool_member;              // [P, top] in / out: best first, -1 = empty
+    float *pool_lp, *pool_stop;        // [P, top] member log-prob and stop term (0 without include_stop; -inf where empty)
+    int32_t *flags;                    // [P, 3] in / out: live, exhaustive; out: some beam changes its row
+    float *edge_lp;                    // [P, K] optional: log-prob of the edge each new beam took
+    float *beam_stop;                  // [P, K] optional: stop term of each beam as it stood (-inf: none)
+};
+hipError_t launch_trie_beam_expand(const TrieSearchTable &t, const TrieSearchLevel &a, int P, int32_t *words, hipStream_t s);
 hipError_t launch_mask_to_kstart(const uint8_t *mask, int B, int T, int32_t *kstart, hipStream_t s);
 
 // lookup.hip : prompt-lookup decoding - the n-gram draft, the verify pass's input rows, acceptance and commit in lockstep

@@ -16,6 +16,10 @@ Differences, all deliberate: the gather moves token ids
 once (cache_prefix), the trie of the allowed terms is scored behind them in one tree pass (score_trie) and every saved item carries
 `"ranked_terms": [[term, logprob], ...]`, its K most probable terms (`generated` is the first of them): the per-term scores that
 function prediction is evaluated with.  --rank_with_stop adds the log-probability of ending the answer right behind the term.
+`--allowed_terms FILE --search_terms K [--search_top N] [--rank_with_stop]` writes the same `ranked_terms` from a beam search over
+the terms (search_trie, K beams per prompt, the N <= K best kept): approximate - a term whose first ids fall out of the beam is
+missed - and much cheaper on a vocabulary of tens of thousands of terms; on a small one --rank_terms is exact and about as fast.
+The two flags exclude each other.
 
 `--num_return_sequences N` (the reference's eval/eval_total_ablation.sh samples every dataset five times, one whole run per repeat):
 N answers per item from ONE run - a call takes batch_size // N prompts, encodes and prefills them once and decodes batch_size rows
@@ -245,11 +249,15 @@ def build_result(qs, texts, num_return_sequences: int = 1):
     return result
 
 
-def rank_terms(model, tokenizer, items, input_path, batch_size, trie, k, with_stop=False, device=None):
+def rank_terms(model, tokenizer, items, input_path, batch_size, trie, k, with_stop=False, device=None, beams=0):
     """--rank_terms: per item the K best members of `trie` behind its prompt -> (log-probs fp32 [n, K] descending, member indices
-    [n, K]).  One cache_prefix + one score_trie per batch; nothing is generated."""
+    [n, K]).  One cache_prefix + one score_trie per batch; nothing is generated.  beams > 0 (--search_terms): search_trie with that
+    many beams instead - approximate wherever a prompt's search was not exhaustive; member index -1 / -inf where fewer than K
+    members were found."""
     dev = device or model.device
     k = min(int(k), len(trie.member_ids))
+    if beams:
+        k = min(k, int(beams))
     vals, idx = [], []
     for i in range(0, len(items), batch_size):
         batch = items[i:i + batch_size]
@@ -259,7 +267,11 @@ def rank_terms(model, tokenizer, items, input_path, batch_size, trie, k, with_st
         mask = ids != tokenizer.pad_token_id
         with torch.inference_mode():
             prefix = model.cache_prefix(ids, seq=[q["input"] for q in batch], attention_mask=mask)
-            v, j = model.score_trie(prefix, trie, include_stop=with_stop).topk(k)
+            if beams:
+                res = model.search_trie(prefix, trie, num_beams=int(beams), top=k, include_stop=with_stop)
+                v, j = res.logprob, res.member_index
+            else:
+                v, j = model.score_trie(prefix, trie, include_stop=with_stop).topk(k)
         vals.append(v)
         idx.append(j)
     if not vals:
@@ -295,11 +307,16 @@ def eval_model(args):
     model_name = opa.get_model_name_from_path(args.model_base_path)
     cstp_path = return_cstp_path(args.opus_pllm_weights_path, "modality_encoder/modality_encoding_adapter.ckpt")
     n_rank = int(getattr(args, "rank_terms", 0) or 0)
+    n_beams = int(getattr(args, "search_terms", 0) or 0)          # --search_terms K: beam search instead of the exact tree pass
+    if n_rank and n_beams:
+        raise ValueError("--search_terms and --rank_terms exclude each other")
+    if n_beams:
+        n_rank = int(getattr(args, "search_top", 0) or 0) or n_beams
     if n_rank and not getattr(args, "allowed_terms", None):
-        raise ValueError("--rank_terms needs --allowed_terms (the vocabulary to rank)")
+        raise ValueError("--rank_terms / --search_terms need --allowed_terms (the vocabulary to rank)")
     held = {}
     continuous = bool(getattr(args, "continuous", False))
-    ctx_new, ctx_batch = max_new, args.batch_size * max(1, args.num_beams)
+    ctx_new, ctx_batch = max_new, args.batch_size * max(1, args.num_beams, n_beams)
     if continuous:
         bad = continuous_refusals(args)
         if bad:
@@ -320,7 +337,8 @@ def eval_model(args):
         if n_rank:                                    # the terms' positions sit behind the prompt: room for the longest of them
             held["trie"] = token_constraint(args, tok)
             need += held["trie"].max_depth
-        return dict(max_prompt=max(args.max_prompt or 0, need))
+        extra = dict(max_new_tokens=max(ctx_new, held["trie"].max_depth)) if n_beams else {}   # (the beams decode the members)
+        return dict(max_prompt=max(args.max_prompt or 0, need), **extra)
     # capacity of the context: the reference has no cap; here the KV cache is sized once, from what this run will really ask for
     tokenizer, model, _ = load_pretrained_model(args.model_base_path, args.opus_pllm_weights_path, model_name,
                                                 args.load_8bit, args.load_4bit, switch_projector_type=args.switch_projector_type,
@@ -331,7 +349,7 @@ def eval_model(args):
     dev = torch.device("cuda", local)
     t0 = time.time()
     if n_rank:
-        return _eval_ranked_terms(args, qs, mine, tokenizer, model, held["trie"], n_rank, dev, rank, world, t0)
+        return _eval_ranked_terms(args, qs, mine, tokenizer, model, held["trie"], n_rank, dev, rank, world, t0, n_beams)
     logits = [] if args.dump_logits else None
     proc_kw = logits_processor_kwargs(args)
     proc_kw.update(lookup_kw)
@@ -379,9 +397,9 @@ def eval_model(args):
         torch.distributed.destroy_process_group()
 
 
-def _eval_ranked_terms(args, qs, mine, tokenizer, model, trie, k, dev, rank, world, t0):
+def _eval_ranked_terms(args, qs, mine, tokenizer, model, trie, k, dev, rank, world, t0, beams=0):
     vals, idx = rank_terms(model, tokenizer, mine, args.input_path, args.batch_size, trie, k,
-                           bool(getattr(args, "rank_with_stop", False)), dev)
+                           bool(getattr(args, "rank_with_stop", False)), dev, beams)
     all_vals = odist.all_gather_logits(vals.contiguous()).cpu()
     all_idx = odist.all_gather_ids(idx.contiguous(), 0).cpu()
     if rank == 0:
@@ -389,7 +407,7 @@ def _eval_ranked_terms(args, qs, mine, tokenizer, model, trie, k, dev, rank, wor
         names = trie.member_strings
         result = []
         for q, v, j in zip(qs, all_vals.tolist(), all_idx.tolist()):
-            ranked = [[names[m], lp] for m, lp in zip(j, v)]
+            ranked = [[names[m], lp] for m, lp in zip(j, v) if m >= 0]            # (--search_terms may find fewer than K)
             result.append({"ground_truth": q["output"], "generated": ranked[0][0], "ranked_terms": ranked})
         print(f"entries/sec: {len(qs) / dt}, time elapsed: {dt}")
         with open(args.save_path, "w") as f:
@@ -452,11 +470,18 @@ def build_parser() -> argparse.ArgumentParser:
                         "(greedy or sampling; computed on the GPU in the decode loop)")
     p.add_argument("--dump_logits", type=str, default=None,
                    help="parity dump: save the fp32 last-step logits of every item ([n, V], input order) to this .pt file")
-    p.add_argument("--rank_terms", type=int, default=0, metavar="K",
+    how = p.add_mutually_exclusive_group()
+    how.add_argument("--search_terms", type=int, default=0, metavar="K",
+                     help="with --allowed_terms: no generation; beam search over the allowed terms with K beams per prompt "
+                          "(search_trie) and save the best ones as `ranked_terms`, in --rank_terms' format.  Approximate: a term "
+                          "whose first ids fall out of the beam is missed; --rank_terms is exact and about as fast on small "
+                          "vocabularies")
+    p.add_argument("--search_top", type=int, default=0, metavar="N", help="with --search_terms: terms saved per item (default K)")
+    how.add_argument("--rank_terms", type=int, default=0, metavar="K",
                    help="with --allowed_terms: no generation; score every allowed term behind each prompt in one tree pass and save "
                         "the K most probable ones with their log-probabilities as `ranked_terms`")
     p.add_argument("--rank_with_stop", action="store_true",
-                   help="with --rank_terms: add the log-probability of ending the answer right behind the term")
+                   help="with --rank_terms / --search_terms: add the log-probability of ending the answer right behind the term")
     add_logits_processor_args(p)
     add_lookup_args(p)
     add_constraint_args(p)

@@ -1580,6 +1580,146 @@ class OpusLlamaForCausalLM:
         self._leave()
         return TrieScores(member_lp, stop_lp, node_lp, torch.from_numpy(plan.n_members).to(dev), plan.rows_evaluated)
 
+    # ------------------------------------------------------------------ trie search
+    def _set_trie_search(self, trie):
+        """The search table of `trie` (constraint.TrieSearchTable, kept on the trie object), uploaded to this context unless it
+        is the one the context holds."""
+        from .constraint import TrieSearchTable
+        tab = getattr(trie, "_search_table", None)
+        if tab is None:
+            tab = trie._search_table = TrieSearchTable(trie.tries if hasattr(trie, "tries") else [trie])
+        if getattr(self, "_trie_search", None) is not tab:
+            p = lambda a: a.ctypes.data                                                      # noqa: E731
+            s = self._enter()
+            try:
+                _cabi.check(self._lib.opus_set_trie_search(self._ctx, tab.n_states, p(tab.edge_off), p(tab.edge_tok), p(tab.edge_next),
+                                                           tab.n_edges, p(tab.member), p(tab.stop_set), len(tab.stop_off) - 1,
+                                                           p(tab.stop_off), p(tab.stop_ids), s))
+            finally:
+                self._leave()
+            self._trie_search = tab
+        return tab
+
+    @torch.no_grad()
+    def search_trie(self, prefix: "OpusPrefix", trie, num_beams: int = 8, top: int = 5, include_stop: bool = False,
+                    return_trace: bool = False) -> "TrieSearchResult":
+        """The `top` best members of a TokenTrie behind a cached prefix, by beam search over the trie with `num_beams` beams per
+        prompt: score_trie()'s scores and member numbering at num_beams x depth decoder rows per prompt instead of one row per
+        trie node.  `trie`: a TokenTrie (every prefix row searches it) or TokenTrie.per_row([...]).  Returns TrieSearchResult.
+
+        Scores are score_trie()'s: a member's log-prob is the sum of its edge log-probs behind prompt p, added in fp32 from the
+        root; include_stop adds the log of the mass on TokenTrie.stop_ids() at the member's node.
+
+        The search is level-synchronous, per prompt.  The frontier starts as {root, 0}; the prefix's last-position logits serve
+        level 1 without a decoder pass.  At each level every live beam (node s, score a) offers its children with a + logp(id).
+        Without include_stop a child that is a member goes to the pool of finished members at once and only children that have a
+        child compete for the num_beams slots (a leaf is never run through the decoder); with it every child competes and a beam
+        standing on a member node adds score + stop term to the pool at the next level, from its own logits.  Beams are chosen
+        by score descending, ties to the lower (beam, id); the pool keeps the best `top`, ties to the lower member index.  A
+        prompt stops when it has no live beam or when its best beam is STRICTLY below its top-th pool entry (every term is
+        <= 0: exact).  `exhaustive[p]` says that no candidate of prompt p ever went without a slot: the row then equals
+        score_trie(...).topk(top) up to the two launch shapes' rounding; otherwise it is approximate - a member whose prefix fell
+        out of the beam is missed.
+
+        Each level is one launch (trie_beam_expand_kernel) that leaves ids, parent rows, states, scores and the pool on the
+        device; the host reads two words per level.  P x num_beams decoder rows above max_batch run as groups of
+        max_batch // num_beams prompts.  The call overwrites the context's decode rows and KV cache as generate(prefix=...) does:
+        a live handle is detached first, other live handles go stale.
+
+        ValueError: 1 <= top <= num_beams <= 16 violated; a trie deeper than the context's max_new_tokens or
+        constraint.TRIE_MAX_DEPTH; num_beams > max_batch; a prefix as wide as max_prompt (the beams' first pass needs one slot)."""
+        from .constraint import PerRowTokenTrie, TokenTrie, TRIE_MAX_DEPTH, TRIE_SEARCH_MAX_BEAMS
+        cfg = self.cfg
+        if not isinstance(prefix, OpusPrefix):
+            raise TypeError("search_trie() needs the OpusPrefix that cache_prefix() returned")
+        if isinstance(trie, TokenTrie):
+            tries = [trie] * prefix.rows
+        elif isinstance(trie, PerRowTokenTrie):
+            if trie.n_rows() != prefix.rows:
+                raise ValueError(f"TokenTrie.per_row of {trie.n_rows()} tries for {prefix.rows} prefix rows")
+            tries = list(trie.tries)
+        else:
+            raise TypeError("search_trie() needs a TokenTrie or TokenTrie.per_row(...)")
+        K, top = int(num_beams), int(top)
+        if not 1 <= top <= K <= TRIE_SEARCH_MAX_BEAMS:
+            raise ValueError(f"search_trie: 1 <= top <= num_beams <= {TRIE_SEARCH_MAX_BEAMS} (got top={top}, num_beams={K})")
+        deepest = max(t.max_depth for t in tries)
+        if deepest > TRIE_MAX_DEPTH:
+            raise ValueError(f"search_trie: a member of {deepest} ids, the depth limit is TRIE_MAX_DEPTH={TRIE_MAX_DEPTH}")
+        if deepest > cfg.max_new_tokens:
+            raise ValueError(f"search_trie: a member of {deepest} ids, the context decodes max_new_tokens={cfg.max_new_tokens}")
+        if K > cfg.max_batch:
+            raise ValueError(f"search_trie: num_beams={K} decoder rows per prompt need max_batch>={K} (the context holds {cfg.max_batch})")
+        if prefix.slots + 1 > cfg.max_prompt:
+            raise ValueError(f"search_trie: a prefix of {prefix.slots} slots + the beams' first id exceed max_prompt={cfg.max_prompt}")
+        for t in tries:
+            if max(max(t.node_tok), max(t.stop_ids())) >= cfg.dec_vocab:
+                raise ValueError(f"trie ids must lie in [0, {cfg.dec_vocab})")
+        prefix = self._usable_prefix(prefix, detach=True)
+        tab = self._set_trie_search(trie)
+        P, dev, H = prefix.rows, self.device, cfg.dec_dim
+        per = cfg.max_batch // K                                            # prompts per group
+        i32 = dict(dtype=torch.int32, device=dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        pool_m = torch.full((P, top), -1, **i32)
+        pool_lp = torch.full((P, top), float("-inf"), **f32)
+        pool_st = torch.full((P, top), float("-inf"), **f32)
+        flags = torch.tensor([1, 1, 0], **i32).repeat(P, 1).contiguous()
+        start = torch.from_numpy(tab.start).to(dev).expand(P).contiguous()  # (one trie for every row: one start state)
+        snap = prefix._snap()
+        levels, rows_decoded, trace = 0, 0, []
+        s = self._enter()
+        with torch.cuda.stream(self._stream):
+            for p0 in range(0, P, per):
+                g = min(per, P - p0)
+                R = g * K
+                state = torch.zeros((g, K), **i32)
+                state[:, 0] = start[p0: p0 + g]
+                score = torch.full((g, K), float("-inf"), **f32)
+                score[:, 0] = 0.0
+                tok, parent, words = torch.zeros((R,), **i32), torch.zeros((R,), **i32), torch.zeros((2,), **i32)
+                lse = torch.empty((R,), **f32)
+                edge_lp = torch.empty((g, K), **f32) if return_trace else None
+                beam_stop = torch.empty((g, K), **f32) if return_trace else None
+                ptr = lambda x: None if x is None else x.data_ptr()                          # noqa: E731
+                io = _cabi.CTrieSearchIO(g, K, top, 1 if include_stop else 0, state.data_ptr(), score.data_ptr(), tok.data_ptr(),
+                                         parent.data_ptr(), pool_m[p0:].data_ptr(), pool_lp[p0:].data_ptr(), pool_st[p0:].data_ptr(),
+                                         flags[p0:].data_ptr(), words.data_ptr(), lse.data_ptr(), ptr(edge_lp), ptr(beam_stop))
+                h_lens = (C.c_int32 * R)(*([1] * R))
+                h_src = (C.c_int32 * R)(*[p0 + r // K for r in range(R)])
+                _cabi.check(self._lib.opus_trie_search_begin(self._ctx, prefix._last_rows[p0: p0 + g].contiguous().data_ptr(), g, s))
+                n = 0
+                while True:
+                    before = state.clone() if return_trace else None
+                    _cabi.check(self._lib.opus_trie_search_level(self._ctx, C.byref(io), 1 if n == 0 else 0, s))
+                    n += 1
+                    live, moved = words.cpu().tolist()                                       # (synchronises this stream)
+                    if return_trace:
+                        trace.append(dict(group=p0, level=n, prompt=p0 + torch.arange(g).repeat_interleave(K),
+                                          node=(state - start[p0: p0 + g, None]).clamp(min=0).cpu().reshape(-1), alive=(state > 0).cpu().reshape(-1),
+                                          edge_logprob=edge_lp.cpu().reshape(-1), score=score.cpu().reshape(-1),
+                                          from_node=(before - start[p0: p0 + g, None]).clamp(min=0).cpu().reshape(-1),
+                                          from_alive=(before > 0).cpu().reshape(-1), from_stop=beam_stop.cpu().reshape(-1)))
+                    if not live:
+                        break
+                    if n > deepest:                                                          # (level depth + 1 offers stop terms only)
+                        raise _cabi.OpusError(-1, "search_trie: the search ran past the trie's depth")
+                    if n == 1:
+                        emb = self.model.embed_tokens(tok.long()).to(_cabi.operand_dtype()).view(R, 1, H).contiguous()
+                        _cabi.check(self._lib.opus_llama_prefill_behind(self._ctx, C.byref(snap), emb.data_ptr(), R, 1, h_lens, h_src,
+                                                                        None, None, s))
+                    else:
+                        if moved:
+                            _cabi.check(self._lib.opus_kv_reorder(self._ctx, parent.data_ptr(), R, s))
+                        _cabi.check(self._lib.opus_llama_decode_step(self._ctx, tok.data_ptr(), None, s))
+                    rows_decoded += R
+                levels = max(levels, n)
+            torch.cuda.current_stream().synchronize()
+        self._leave()
+        n_members = torch.as_tensor([len(t.member_ids) for t in tries], device=dev)
+        return TrieSearchResult(pool_m.long(), pool_lp, pool_st if include_stop else None, levels, rows_decoded, flags[:, 1].bool(),
+                                n_members, trace if return_trace else None)
+
     # ------------------------------------------------------------------ parity taps (tests / bench)
     def prefill_logits(self, embeds: torch.Tensor, mask: torch.Tensor, num_return_sequences: int = 1) -> torch.Tensor:
         """Last-position logits fp32 [B, V].  num_return_sequences = N > 1: the fanned-out prefill (opus_llama_prefill_fanout) -
@@ -1877,6 +2017,21 @@ class TrieScores:
             raise ValueError(f"topk: k={k} for {self.logprob.shape[1]} members")
         vals, idx = torch.sort(self.logprob, dim=1, descending=True, stable=True)
         return vals[:, :k], idx[:, :k]
+
+
+class TrieSearchResult:
+    """What search_trie() returns.  member_index int64 [P, top]: indices into trie.member_ids / member_strings (per_row: of that
+    row's trie), best first, -1 where fewer members were found; logprob fp32 [P, top] descending (-inf at -1) = member_logprob
+    (+ stop_logprob with include_stop; None without) - TrieScores' definitions.  levels: levels run (the most of any group);
+    rows_decoded: decoder rows run through the layers; exhaustive bool [P]: no candidate of the prompt ever went without a beam
+    slot - the row is then score_trie(...).topk(top); n_members [P].  trace (return_trace=True): per group and level a dict of
+    flat [prompts x num_beams] CPU tensors - prompt, the new beams' node / alive / edge_logprob / score, and the beams they came
+    from: from_node / from_alive / from_stop (the stop term of a beam on a member node, -inf otherwise)."""
+
+    def __init__(self, member_index, member_logprob, stop_logprob, levels: int, rows_decoded: int, exhaustive, n_members, trace=None):
+        self.member_index, self.member_logprob, self.stop_logprob = member_index, member_logprob, stop_logprob
+        self.logprob = member_logprob if stop_logprob is None else member_logprob + stop_logprob
+        self.levels, self.rows_decoded, self.exhaustive, self.n_members, self.trace = int(levels), int(rows_decoded), exhaustive, n_members, trace
 
 
 # capacities of the processor kernel (include/opus_pllm.h, opus_set_logits_processors)
