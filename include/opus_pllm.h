@@ -760,6 +760,23 @@ int opus_beam_sample_topk(opus_ctx *ctx, const float *d_logits, const float *d_r
  * context) = off.  transformers 4.46.3 - requirements.txt:20 of the reference - defaults GenerationConfig.top_k to 50 when it
  * samples (transformers >= 5: None); the Python mirror's generate(top_k=...) defaults to 50 accordingly. */
 int opus_set_sampling_top_k(opus_ctx *ctx, int32_t k);
+/* The truncation warpers of this context's sampling paths (opus_generate_sample, opus_generate_scored and its forms,
+ * opus_debug_sample, the continuous-batching session), behind the temperature, top-k and top-p in transformers' order - MinP,
+ * Typical, Epsilon, Eta, each with min_tokens_to_keep = 1 and each seeing the softmax over what the earlier ones kept.  With
+ * p = exp(l / T - max / T) over the set K0 that top-k / top-p keep:
+ *   min_p m:          keeps p >= m (m times the largest p, 1).
+ *   typical_p t < 1:  q = p / Z, H = -sum q log q, d = |-log q - H|; keeps the smallest prefix in ascending d whose mass reaches t
+ *                     (the token that crosses t stays, ties in d stay together): a band p_lo <= p <= p_hi around Z e^-H that can
+ *                     leave the arg-max token out.
+ *   epsilon_cutoff e: removes q < e (q over the survivors); every token at the survivors' maximum stays.
+ *   eta_cutoff e':    the same with min(e', sqrt(e') e^-H), H over the survivors at that point.
+ * The draw is the CDF inversion of opus_generate_sample over the band that is left, with the same (seed, row, step) uniform;
+ * output_scores hold l / T on the band and -inf elsewhere.  Off values (a new context's state): 0, 1, 0, 0; with all four off every
+ * launch and draw is what it was without this entry point.  The captured decode step reads the values from device memory: changing
+ * them instantiates no graph.  OPUS_EBADARG outside min_p in [0, 1], typical_p in (0, 1], both cutoffs in [0, 1), and for a null
+ * context (before the device is touched).  opus_beam_sample_topk returns OPUS_EUNSUPPORTED while any warper is on.  (Added within
+ * ABI 10.) */
+int opus_set_sampling_warpers(opus_ctx *ctx, float min_p, float typical_p, float epsilon_cutoff, float eta_cutoff);
 
 /* Continuous batching (no reference counterpart; added within ABI 10): one live decode batch - a session - whose done rows are handed
  * to new prompts while the other rows keep decoding.  Step t of a session writes every row's token to column t of d_ids int32

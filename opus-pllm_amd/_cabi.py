@@ -152,6 +152,7 @@ SIGNATURES = {
     "opus_beam_sample_topk": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_uint64, C.c_int32,
                                         _P, _P, _P]),
     "opus_set_sampling_top_k": (C.c_int, [_P, C.c_int32]),
+    "opus_set_sampling_warpers": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_float]),
     "opus_set_stop_sequence": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int32]),
     "opus_debug_gemm_slabs": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _P]),
     "opus_debug_gemm_plan": (C.c_int, [_P, C.POINTER(C.c_int32)]),

@@ -80,13 +80,14 @@ struct StepPlan {
     int outs = 0;                        // GEN_* flags of opus_generate_scored (the addresses come from the descriptors)
     bool lproc = false;                  // logits processors on (their values come from the descriptor d_lproc)
     bool cons = false;                   // token constraint on (its table comes from the descriptor d_cons)
+    bool warp = false;                   // sampling warpers on (their values come from the descriptor d_warp)
     int budget = -1;                     // a session's token budget per row (the finish launch); -1: not a session
 };
 // "the same captured step": the key of the graph cache and of the session's slot
 static bool same_step(const StepPlan &a, const StepPlan &b) {
     return a.rows == b.rows && a.guided == b.guided && a.stride == b.stride && a.ids == b.ids && a.n_eos == b.n_eos && a.pad == b.pad &&
            a.temp == b.temp && a.top_p == b.top_p && a.top_k == b.top_k && a.n_stop == b.n_stop && a.outs == b.outs &&
-           a.lproc == b.lproc && a.cons == b.cons && a.budget == b.budget;
+           a.lproc == b.lproc && a.cons == b.cons && a.warp == b.warp && a.budget == b.budget;
 }
 
 struct opus_ctx {
@@ -116,6 +117,13 @@ struct opus_ctx {
     int32_t *d_chosen;
     int samp_top_k = 0;                       // opus_set_sampling_top_k (0 = no TopKLogitsWarper)
     float *d_bthr = nullptr, *d_blse = nullptr;   // beam-sample: keep threshold and log-sum-exp per decoder row
+    // sampling warpers (opus_set_sampling_warpers): the host setting, uploaded in stream order by every call that samples with one
+    // on, and a small allocation made on first use - the device descriptor and the band's bounds per row [2, max_batch]
+    SamplingWarpers h_warp{0.f, 1.f, 0.f, 0.f};
+    char *warp_mem = nullptr;
+    SamplingWarpers *d_warp = nullptr;
+    float *d_wlo = nullptr, *d_whi = nullptr;
+    bool warp_on() const { return h_warp.min_p > 0.f || h_warp.typical_p < 1.f || h_warp.epsilon > 0.f || h_warp.eta > 0.f; }
     int64_t gemm_ws_bytes = 0;
     half_t *d_xn, *d_qkv, *d_ctx, *d_act, *d_xln, *kc, *vc;
     float *cs_enc, *cs_dec, *cs_row;
@@ -478,6 +486,7 @@ extern "C" int opus_ctx_destroy(opus_ctx *c) {
     if (c->kv_tmp) (void)hipFree(c->kv_tmp);
     if (c->gen_mem) (void)hipFree(c->gen_mem);
     if (c->lproc_mem) (void)hipFree(c->lproc_mem);
+    if (c->warp_mem) (void)hipFree(c->warp_mem);
     if (c->cons_tab) (void)hipFree(c->cons_tab);
     if (c->ts_tab) (void)hipFree(c->ts_tab);
     if (c->cons_mem) (void)hipFree(c->cons_mem);
@@ -2440,6 +2449,20 @@ static int ensure_gen_mem(opus_ctx *c) {
     return OPUS_OK;
 }
 
+// sampling warpers on: the descriptor and the rows' band bounds exist, and the descriptor holds the host setting (stream order)
+static int upload_warpers(opus_ctx *c, hipStream_t s) {
+    if (!c->warp_mem) {
+        const size_t B = c->cfg.max_batch, o_lo = align_up(sizeof(SamplingWarpers)), rows = align_up(B * sizeof(float));
+        HIPC(hipMalloc((void **)&c->warp_mem, o_lo + 2 * rows));
+        c->d_warp = reinterpret_cast<SamplingWarpers *>(c->warp_mem);
+        c->d_wlo = reinterpret_cast<float *>(c->warp_mem + o_lo);
+        c->d_whi = reinterpret_cast<float *>(c->warp_mem + o_lo + rows);
+    }
+    HIPC(launch_upload_i32(reinterpret_cast<const int32_t *>(&c->h_warp), (int)(sizeof(SamplingWarpers) / sizeof(int32_t)),
+                           reinterpret_cast<int32_t *>(c->d_warp), s));
+    return OPUS_OK;
+}
+
 static int ensure_lproc_mem(opus_ctx *c) {
     if (c->lproc_mem) return OPUS_OK;
     const size_t B = c->cfg.max_batch, N = c->cfg.max_new_tokens;
@@ -2529,7 +2552,7 @@ static int select_next(opus_ctx *c, hipStream_t s, const StepPlan &p) {
     if (proc) {
         if (p.outs & GEN_LOGITS)
             KL(KC_OTHER, 8.0 * BV, launch_gen_scores(c->d_logits, HB, g.dec_vocab, c->d_gen_raw, c->d_step, max_new, 0.f, 1.f,
-                                                     nullptr, nullptr, s));
+                                                     nullptr, nullptr, nullptr, s));
         if (guid) {
             KL(KC_GUIDANCE, 8.0 * BV, launch_guidance_lse_partial(c->d_logits, 2 * HB, g.dec_vocab, c->d_pval, c->d_gdpsum, s));
             KL(KC_GUIDANCE, 1024.0 * HB, launch_guidance_lse_final(c->d_pval, c->d_gdpsum, 2 * HB, c->d_gmax, c->d_glog, c->d_glse, s));
@@ -2548,7 +2571,17 @@ static int select_next(opus_ctx *c, hipStream_t s, const StepPlan &p) {
             KL(KC_CONSTRAINT, 4.0 * BV,
                launch_token_constraint(c->d_logits, HB, g.dec_vocab, d_out, max_new, c->d_step, max_new, c->d_cons, s));
     }
-    if (p.temp > 0.f) {
+    const bool warp = p.warp && p.temp > 0.f;       // the warpers narrow stage 2's threshold to a band and make the draw
+    if (warp) {
+        KL(KC_OTHER, 4.0 * 4 * HB * g.dec_vocab,
+           launch_sample_select(c->d_logits, HB, g.dec_vocab, p.temp, p.top_p, p.top_k, nullptr, nullptr,
+                                c->d_pval, c->d_pidx, c->d_probs, c->d_cand_i, c->d_cand_n, c->d_zpart, c->d_spart, nullptr, c->d_wlo,
+                                lp && !proc ? c->d_gpsum : nullptr, nullptr, s));
+        KL(KC_OTHER, 8.0 * HB * g.dec_vocab,
+           launch_sample_warp_draw(HB, g.dec_vocab, c->d_warp, c->d_seed, c->d_step, c->d_probs, c->d_cand_i, c->d_cand_n, c->d_chosen,
+                                   c->d_wlo, c->d_whi, s));
+        chosen = c->d_chosen;
+    } else if (p.temp > 0.f) {
         KL(KC_OTHER, 4.0 * 4 * HB * g.dec_vocab,
            launch_sample_select(c->d_logits, HB, g.dec_vocab, p.temp, p.top_p, p.top_k, c->d_seed, c->d_step,
                                 c->d_pval, c->d_pidx, c->d_probs, c->d_cand_i, c->d_cand_n, c->d_zpart, c->d_spart, c->d_chosen, nullptr,
@@ -2563,7 +2596,7 @@ static int select_next(opus_ctx *c, hipStream_t s, const StepPlan &p) {
     if (proc ? (p.outs & GEN_SCORES) != 0 : sc)
         KL(KC_OTHER, 4.0 * HB * g.dec_vocab * (1 + ((p.outs & GEN_SCORES) ? 1 : 0) + ((p.outs & GEN_LOGITS) && !proc ? 1 : 0)),
            launch_gen_scores(c->d_logits, HB, g.dec_vocab, proc ? c->d_gen_proc : c->d_gen, c->d_step, max_new, p.temp,
-                             p.top_p, c->d_pval, p.temp > 0.f ? c->d_gthr : nullptr, s));
+                             p.top_p, c->d_pval, warp ? c->d_wlo : p.temp > 0.f ? c->d_gthr : nullptr, warp ? c->d_whi : nullptr, s));
     if (lp && proc)
         KL(KC_OTHER, 512.0 * HB + 8.0 * HB * max_new,
            launch_argmax_rawlp_step(c->d_pval, c->d_pidx, guid ? c->d_glse : c->d_rlse, p.lproc && !guid ? c->d_rawh : nullptr, chosen, HB, c->d_eos, n_eos, pad_id, c->d_fin, d_out,
@@ -2647,7 +2680,8 @@ static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mas
     StepPlan plan;
     plan.rows = BN; plan.guided = guidance != nullptr; plan.stride = max_new; plan.ids = d_out_ids; plan.n_eos = n_eos; plan.pad = pad_id;
     plan.temp = temperature; plan.top_p = top_p; plan.top_k = c->samp_top_k; plan.n_stop = c->n_stop;
-    plan.lproc = c->lproc_on; plan.cons = c->cons_on;
+    plan.lproc = c->lproc_on; plan.cons = c->cons_on; plan.warp = temperature > 0.f && c->warp_on();
+    if (plan.warp) OPC(upload_warpers(c, s));
     if (outs) plan.outs = (outs->token_lp ? GEN_LOGPROBS : 0) | (outs->scores ? GEN_SCORES : 0) | (outs->logits ? GEN_LOGITS : 0);
     if (plan.outs) {
         OPC(ensure_gen_mem(c));
@@ -2802,6 +2836,8 @@ extern "C" int opus_stream_begin(opus_ctx *c, const void *d_embeds, const uint8_
     st.plan.rows = B; st.plan.stride = g.max_new_tokens; st.plan.ids = d_ids; st.plan.n_eos = n_eos; st.plan.pad = pad_id;
     st.plan.temp = temperature; st.plan.top_p = top_p; st.plan.top_k = c->samp_top_k; st.plan.n_stop = c->n_stop;
     st.plan.budget = max_new;
+    st.plan.warp = temperature > 0.f && c->warp_on();
+    if (st.plan.warp) OPC(upload_warpers(c, s));
     st.start.assign(B, 0);
     st.on = true;
     return OPUS_OK;
@@ -3511,8 +3547,16 @@ extern "C" int opus_debug_sample(opus_ctx *c, const float *d_logits, int32_t B, 
     hipStream_t s = (hipStream_t)stream;
     HIPC(hipMemcpyAsync(c->d_seed, &seed, sizeof(seed), hipMemcpyHostToDevice, s));
     HIPC(hipMemcpyAsync(c->d_plan, &step, sizeof(step), hipMemcpyHostToDevice, s));
-    HIPC(launch_sample_select(d_logits, B, c->cfg.dec_vocab, temperature, top_p, c->samp_top_k, c->d_seed, c->d_plan, c->d_pval, c->d_pidx,
-                              c->d_probs, c->d_cand_i, c->d_cand_n, c->d_zpart, c->d_spart, d_tokens, nullptr, nullptr, nullptr, s));
+    if (c->warp_on()) {
+        OPC(upload_warpers(c, s));
+        HIPC(launch_sample_select(d_logits, B, c->cfg.dec_vocab, temperature, top_p, c->samp_top_k, nullptr, nullptr, c->d_pval, c->d_pidx,
+                                  c->d_probs, c->d_cand_i, c->d_cand_n, c->d_zpart, c->d_spart, nullptr, c->d_wlo, nullptr, nullptr, s));
+        HIPC(launch_sample_warp_draw(B, c->cfg.dec_vocab, c->d_warp, c->d_seed, c->d_plan, c->d_probs, c->d_cand_i, c->d_cand_n, d_tokens,
+                                     c->d_wlo, c->d_whi, s));
+    } else {
+        HIPC(launch_sample_select(d_logits, B, c->cfg.dec_vocab, temperature, top_p, c->samp_top_k, c->d_seed, c->d_plan, c->d_pval, c->d_pidx,
+                                  c->d_probs, c->d_cand_i, c->d_cand_n, c->d_zpart, c->d_spart, d_tokens, nullptr, nullptr, nullptr, s));
+    }
     HIPC(hipStreamSynchronize(s));   // seed / step are host temporaries
     return OPUS_OK;
 }
@@ -3744,6 +3788,9 @@ extern "C" int opus_beam_sample_topk(opus_ctx *c, const float *d_logits, const f
         return fail(OPUS_ESHAPE, "beam_sample_topk: B=%d x K=%d rows (the last step had %d, the context holds %d)", B, K, c->cur_B, c->cfg.max_batch);
     if (M < 1 || M > 16) return fail(OPUS_ESHAPE, "beam_sample_topk: 1 <= M <= 16 candidates per row (got %d)", M);
     if (!(temperature > 0.f) || top_p <= 0.f || top_p > 1.f) return fail(OPUS_EBADARG, "beam_sample_topk: temperature > 0, 0 < top_p <= 1");
+    if (c->warp_on())
+        return fail(OPUS_EUNSUPPORTED, "beam_sample_topk: sampling warpers (opus_set_sampling_warpers) are set on this context; beam-sample "
+                                       "needs min_tokens_to_keep = #eos + 1, i.e. M / K, and joint draws");
     HIPC(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const float *lg = d_logits ? d_logits : c->d_logits;
@@ -3770,6 +3817,20 @@ extern "C" int opus_set_sampling_top_k(opus_ctx *c, int32_t k) {
     if (!c || k < 0) return fail(OPUS_EBADARG, "set_sampling_top_k: k >= 0");
     if (k != c->samp_top_k) drop_graphs(c);                                      // the captured step holds k
     c->samp_top_k = k;
+    return OPUS_OK;
+}
+
+// The truncation warpers of this context's sampling paths (opus_generate_sample, opus_generate_scored, opus_debug_sample, the
+// continuous-batching session) behind top-k / top-p, in transformers' order: MinPLogitsWarper, TypicalLogitsWarper,
+// EpsilonLogitsWarper, EtaLogitsWarper, min_tokens_to_keep = 1.  Off: 0, 1, 0, 0.  The captured step reads the values from device
+// memory and holds only whether any warper is on.
+extern "C" int opus_set_sampling_warpers(opus_ctx *c, float min_p, float typical_p, float epsilon_cutoff, float eta_cutoff) {
+    if (!c) return fail(OPUS_EBADARG, "set_sampling_warpers: null context");
+    if (!(min_p >= 0.f && min_p <= 1.f) || !(typical_p > 0.f && typical_p <= 1.f) || !(epsilon_cutoff >= 0.f && epsilon_cutoff < 1.f) ||
+        !(eta_cutoff >= 0.f && eta_cutoff < 1.f))
+        return fail(OPUS_EBADARG, "set_sampling_warpers: min_p in [0, 1], typical_p in (0, 1], epsilon_cutoff and eta_cutoff in [0, 1) "
+                                  "(got %g, %g, %g, %g)", (double)min_p, (double)typical_p, (double)epsilon_cutoff, (double)eta_cutoff);
+    c->h_warp = SamplingWarpers{min_p, typical_p, epsilon_cutoff, eta_cutoff};
     return OPUS_OK;
 }
 

@@ -538,6 +538,15 @@ hipError_t launch_sample_select(const float *logits, int B, int V, float tempera
                                 const int32_t *step, float *pmax, int32_t *pidx, float *cand_p, int32_t *cand_i,
                                 int32_t *cand_n, float *zpart, float *spart, int32_t *chosen, float *thr_out, float *psum,
                                 float *thr_keep, hipStream_t s);
+// The sampling warpers behind top-k / top-p (opus_set_sampling_warpers), read by the captured step from device memory.  Off: 0, 1, 0, 0.
+struct SamplingWarpers {
+    float min_p, typical_p, epsilon, eta;
+};
+// Behind launch_sample_select(chosen = nullptr, thr_out = thr_lo): the warpers narrow the kept set to the band thr_lo[b] < p <=
+// thr_hi[b] (both written back), then the draw over it into chosen.
+hipError_t launch_sample_warp_draw(int B, int V, const SamplingWarpers *warp, const uint64_t *seed, const int32_t *step,
+                                   const float *cand_p, const int32_t *cand_i, const int32_t *cand_n, int32_t *chosen, float *thr_lo,
+                                   float *thr_hi, hipStream_t s);
 constexpr int APART = 64;     // parts a logits row is cut into by argmax_partial / sample_stage1 (pmax[row * APART + part])
 __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
     x += 0x9E3779B97F4A7C15ull;
@@ -574,9 +583,10 @@ hipError_t launch_argmax_rawlp_step(const float *pval, const int32_t *pidx, cons
                                     int32_t *out_ids, int max_new, const int32_t *step, int32_t *next_tok, int32_t *n_unfinished,
                                     const int32_t *stop, int n_stop, const float *logits, int V, const GenOutDesc *out,
                                     hipStream_t s);
-// out->scores / out->logits at the step (thr != nullptr: sampling - l / T where the draw kept the token, -inf elsewhere)
+// out->scores / out->logits at the step (thr != nullptr: sampling - l / T where the draw kept the token, -inf elsewhere; thr_hi !=
+// nullptr: the kept set is the band thr[b] < p <= thr_hi[b] of launch_sample_warp_draw)
 hipError_t launch_gen_scores(const float *logits, int B, int V, const GenOutDesc *out, const int32_t *step, int max_new,
-                             float temperature, float top_p, const float *pmax, const float *thr, hipStream_t s);
+                             float temperature, float top_p, const float *pmax, const float *thr, const float *thr_hi, hipStream_t s);
 // logits_proc.hip: generate()'s logits processors (opus_set_logits_processors), read by the captured step from device memory.
 // Capacities (include/opus_pllm.h): LP_MAX_BAD bad-word entries of at most LP_MAX_BAD_LEN ids, LP_MAX_BAD_IDS ids in all; a
 // history of at most LP_MAX_HIST ids.

@@ -791,29 +791,33 @@ hipError_t launch_argmax_lse_final(const float *pval, const int32_t *pidx, const
 // [max_new, B, V]; a null pointer is skipped).  thr != nullptr (sampling): scores hold HF's processed scores, l / T where the draw
 // kept the token and -inf elsewhere.  "Kept" is the draw's own test, not a second filter: stage 1's p = exp(l / T - max / T) (the
 // same fma and exponential as sample_stage1_kernel), above stage 1's candidate bound (1 - top_p) / V and above the threshold
-// sample_stage2 exported (thr[b]).  Grid (chunks of GS_CHUNK values, B); float4 when every row is 16-byte aligned.
+// sample_stage2 exported (thr[b]).  thr_hi != nullptr (sampling warpers on: sample_warp_draw_kernel's band): and at most thr_hi[b] -
+// typical_p can drop the most probable tokens, the arg-max included.  Grid (chunks of GS_CHUNK values, B); float4 when every row is
+// 16-byte aligned.
 constexpr int GS_CHUNK = 4096;
 __global__ __launch_bounds__(256) void gen_scores_kernel(const float *__restrict__ logits, int V, const GenOutDesc *__restrict__ out,
                                                          const int32_t *__restrict__ step, int max_new, float inv_temp, float top_p,
-                                                         const float *__restrict__ pmax, const float *__restrict__ thr) {
+                                                         const float *__restrict__ pmax, const float *__restrict__ thr,
+                                                         const float *__restrict__ thr_hi) {
     const int b = blockIdx.y, B = gridDim.y;
     const int st = *step;
     if (st >= max_new) return;
     float *sc = out->scores, *lg = out->logits;
     const int64_t o = ((int64_t)st * B + b) * V;
     const float *row = logits + (int64_t)b * V;
-    float gmax = 0.f, t = 0.f, cand = 0.f;
+    float gmax = 0.f, t = 0.f, cand = 0.f, t_hi = INFINITY;
     if (thr) {
         gmax = pmax[b * APART];
         for (int k = 1; k < APART; ++k) gmax = fmaxf(gmax, pmax[b * APART + k]);
         gmax *= inv_temp;
         t = thr[b];
+        if (thr_hi) t_hi = thr_hi[b];
         cand = (1.0f - top_p) / (float)V;
     }
     auto proc = [&](float l) -> float {
         if (!thr) return l;
         const float p = __expf(__builtin_fmaf(l, inv_temp, -gmax));
-        return (p > cand && p > t) ? l * inv_temp : -INFINITY;
+        return (p > cand && p > t && p <= t_hi) ? l * inv_temp : -INFINITY;
     };
     const int lo = blockIdx.x * GS_CHUNK, hi = (lo + GS_CHUNK < V ? lo + GS_CHUNK : V);
     const bool vec = (V & 3) == 0 && ((((uintptr_t)logits) | (uintptr_t)sc | (uintptr_t)lg) & 15) == 0;
@@ -832,9 +836,9 @@ __global__ __launch_bounds__(256) void gen_scores_kernel(const float *__restrict
     }
 }
 hipError_t launch_gen_scores(const float *logits, int B, int V, const GenOutDesc *out, const int32_t *step, int max_new,
-                             float temperature, float top_p, const float *pmax, const float *thr, hipStream_t s) {
+                             float temperature, float top_p, const float *pmax, const float *thr, const float *thr_hi, hipStream_t s) {
     hipLaunchKernelGGL(gen_scores_kernel, dim3((V + GS_CHUNK - 1) / GS_CHUNK, B), dim3(256), 0, s, logits, V, out, step, max_new,
-                       thr ? 1.0f / temperature : 1.0f, top_p, pmax, thr);
+                       thr ? 1.0f / temperature : 1.0f, top_p, pmax, thr, thr ? thr_hi : nullptr);
     return hipGetLastError();
 }
 
@@ -977,6 +981,77 @@ __global__ __launch_bounds__(256) void sample_stage1_kernel(const float *__restr
 
 // Stage 2 (one workgroup per row): nucleus threshold by bisection over the candidates, then the draw.
 constexpr int SAMPLE_LDS_CAP = 6144;
+constexpr int EXACT_CAP = 1024;       // at most so many candidates: thresholds exactly, by rank (see sample_stage2_kernel)
+// the candidate counts of a row's APART parts -> their offsets s_off[0 .. APART] (one wave scans; ends in a barrier)
+__device__ __forceinline__ void row_cand_offsets(const int32_t *__restrict__ cand_n, int b, int *s_off) {
+    const int tid = threadIdx.x;
+    if (tid < 64) {                                   // (APART = 64 parts: one wave scans their candidate counts)
+        static_assert(APART == 64, "one wave scans the parts");
+        int x = cand_n[b * APART + tid];
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int y = __shfl_up(x, o, 64);
+            if (tid >= o) x += y;
+        }
+        s_off[tid + 1] = x;
+        if (tid == 0) s_off[0] = 0;
+    }
+    __syncthreads();
+}
+// candidate c of a row (global order = index order) lives at part k, slot c - off[k]
+struct RowCands {
+    const float *p;
+    const int32_t *i;
+    const int *off;
+    int64_t part0;                    // row * APART
+    int per;
+    __device__ __forceinline__ float operator()(int c, int &idx) const {
+        int k = 0;
+        while (c >= off[k + 1]) ++k;
+        const int64_t o = (part0 + k) * per + (c - off[k]);
+        idx = i[o];
+        return p[o];
+    }
+};
+// The draw.  kept = candidates with lo < p <= hi (hi = +inf: the one-sided threshold of top-k / top-p; a finite hi: the band the
+// sampling warpers leave); CDF inversion in index order over contiguous chunks of the candidate list.
+__device__ __forceinline__ void sample_draw(float lo, float hi, int nc, bool in_lds, const float *s_p, const RowCands &cand,
+                                            float *s_wtot, float *s_pref, const uint64_t *__restrict__ seed_p,
+                                            const int32_t *__restrict__ step, int32_t *__restrict__ chosen, int b) {
+    const int tid = threadIdx.x;
+    int dummy_id;
+    const int cper = (nc + 255) / 256;
+    const int c0 = tid * cper, c1 = (c0 + cper < nc ? c0 + cper : nc);
+    float mine = 0.f;
+    for (int c = c0; c < c1; ++c) {
+        const float p = in_lds ? s_p[c] : cand(c, dummy_id);
+        mine += (p > lo && p <= hi) ? p : 0.f;
+    }
+    const float incl = block_incl_scan256<float>(mine, s_wtot);
+    // the fp32 scan is not monotone (see there): the interval bounds are the running MAXIMUM of the scan over the threads that
+    // hold kept mass, so a thread without kept mass owns an empty interval and the intervals [s_pref[t], s_pref[t + 1])
+    // partition [0, total) - exactly one thread owns the target (u < 1: u * total rounds below total)
+    s_pref[tid + 1] = block_incl_max256(mine > 0.f ? incl : 0.f, s_wtot);
+    if (tid == 0) s_pref[0] = 0.f;
+    __syncthreads();
+    const float total = s_pref[256];
+    const uint64_t h = splitmix64(*seed_p ^ (0x9E3779B97F4A7C15ull * (uint64_t)(b + 1)) ^ ((uint64_t)(*step + 1) << 32));
+    const float target = (float)(h >> 40) * (1.0f / 16777216.0f) * total;          // u in [0,1)
+    if (s_pref[tid] <= target && target < s_pref[tid + 1]) {
+        float run = s_pref[tid];
+        int pick = -1, last_kept = -1;
+        for (int c = c0; c < c1; ++c) {
+            int id;
+            const float p = cand(c, id);
+            if (p > lo && p <= hi) {
+                last_kept = id;
+                run += p;
+                if (target < run) { pick = id; break; }
+            }
+        }
+        if (last_kept >= 0) chosen[b] = pick >= 0 ? pick : last_kept;   // (the walk's own rounding may end short of target)
+    }
+}
 // thr_out != nullptr: no draw - the row's keep threshold (a token is kept iff its p = exp(l / T - max / T) exceeds it) is written
 // there instead (beam-sample: beam.hip draws M continuations per batch row from the K filtered rows jointly).
 // thr_keep != nullptr: the draw's threshold is exported there as well (generate()'s output_scores: gen_scores_kernel).
@@ -993,65 +1068,12 @@ __global__ __launch_bounds__(256) void sample_stage2_kernel(int V, float top_p, 
     __shared__ float s_p[SAMPLE_LDS_CAP];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int per = ((V + APART - 1) / APART + 3) & ~3;
-    if (tid < 64) {                                   // (APART = 64 parts: one wave scans their candidate counts)
-        static_assert(APART == 64, "one wave scans the parts");
-        int x = cand_n[b * APART + tid];
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int y = __shfl_up(x, o, 64);
-            if (tid >= o) x += y;
-        }
-        s_off[tid + 1] = x;
-        if (tid == 0) s_off[0] = 0;
-    }
-    __syncthreads();
+    row_cand_offsets(cand_n, b, s_off);
     const int nc = s_off[APART];
     float Z = 0.f, S0 = 0.f;
     for (int k = 0; k < APART; ++k) { Z += zpart[b * APART + k]; S0 += spart[b * APART + k]; }   // fixed order
-    // candidate c (global order = index order) lives at part k, slot c - s_off[k]
-    auto cand = [&](int c, int &idx) -> float {
-        int k = 0;
-        while (c >= s_off[k + 1]) ++k;
-        const int64_t o = ((int64_t)b * APART + k) * per + (c - s_off[k]);
-        idx = cand_i[o];
-        return cand_p[o];
-    };
+    const RowCands cand{cand_p, cand_i, s_off, (int64_t)b * APART, per};
     const bool in_lds = nc <= SAMPLE_LDS_CAP;
-    int dummy_id;
-    // kept = candidates with p > lo; CDF inversion in index order over contiguous chunks of the candidate list
-    auto draw = [&](float lo) {
-        const int cper = (nc + 255) / 256;
-        const int c0 = tid * cper, c1 = (c0 + cper < nc ? c0 + cper : nc);
-        float mine = 0.f;
-        for (int c = c0; c < c1; ++c) {
-            const float p = in_lds ? s_p[c] : cand(c, dummy_id);
-            mine += p > lo ? p : 0.f;
-        }
-        const float incl = block_incl_scan256<float>(mine, s_wtot);
-        // the fp32 scan is not monotone (see there): the interval bounds are the running MAXIMUM of the scan over the threads that
-        // hold kept mass, so a thread without kept mass owns an empty interval and the intervals [s_pref[t], s_pref[t + 1])
-        // partition [0, total) - exactly one thread owns the target (u < 1: u * total rounds below total)
-        s_pref[tid + 1] = block_incl_max256(mine > 0.f ? incl : 0.f, s_wtot);
-        if (tid == 0) s_pref[0] = 0.f;
-        __syncthreads();
-        const float total = s_pref[256];
-        const uint64_t h = splitmix64(*seed_p ^ (0x9E3779B97F4A7C15ull * (uint64_t)(b + 1)) ^ ((uint64_t)(*step + 1) << 32));
-        const float target = (float)(h >> 40) * (1.0f / 16777216.0f) * total;          // u in [0,1)
-        if (s_pref[tid] <= target && target < s_pref[tid + 1]) {
-            float run = s_pref[tid];
-            int pick = -1, last_kept = -1;
-            for (int c = c0; c < c1; ++c) {
-                int id;
-                const float p = cand(c, id);
-                if (p > lo) {
-                    last_kept = id;
-                    run += p;
-                    if (target < run) { pick = id; break; }
-                }
-            }
-            if (last_kept >= 0) chosen[b] = pick >= 0 ? pick : last_kept;   // (the walk's own rounding may end short of target)
-        }
-    };
     if (in_lds)
         for (int c = tid; c < nc; c += 256) { int id; s_p[c] = cand(c, id); }
     __syncthreads();
@@ -1063,7 +1085,6 @@ __global__ __launch_bounds__(256) void sample_stage2_kernel(int V, float top_p, 
     // rank - one O(nc^2 / 256) pass instead of two bisections of 40 block reductions each (round 5: 31.6 -> ~8 us per step at
     // batch 64).  The same kept sets: a token survives top-k iff fewer than k tokens are more probable (ties with the k-th stay),
     // and the nucleus iff the ascending cumulative mass up to and including its ties exceeds (1 - top_p) Z.
-    constexpr int EXACT_CAP = 1024;
     if (in_lds && nc <= EXACT_CAP) {
         float lok = 0.f;
         const bool use_k = top_k > 0 && top_k < V && nc > top_k;
@@ -1105,7 +1126,7 @@ __global__ __launch_bounds__(256) void sample_stage2_kernel(int V, float top_p, 
             return;
         }
         if (thr_keep && tid == 0) thr_keep[b] = lo_e;
-        draw(lo_e);
+        sample_draw(lo_e, INFINITY, nc, in_lds, s_p, cand, s_wtot, s_pref, seed_p, step, chosen, b);
         return;
     }
     float lo_k = 0.f;
@@ -1147,7 +1168,136 @@ __global__ __launch_bounds__(256) void sample_stage2_kernel(int V, float top_p, 
         return;
     }
     if (thr_keep && tid == 0) thr_keep[b] = lo;
-    draw(lo);
+    sample_draw(lo, INFINITY, nc, in_lds, s_p, cand, s_wtot, s_pref, seed_p, step, chosen, b);
+}
+
+// The sampling warpers behind top-k / top-p (opus_set_sampling_warpers; transformers' order: min_p, typical_p, epsilon_cutoff,
+// eta_cutoff, min_tokens_to_keep = 1), then the draw.  One workgroup per row, behind sample_stage2_kernel run WITHOUT a draw: its
+// threshold thr_lo[b] says what top-k / top-p keep, K0 = {candidates with p > thr_lo[b]} (the arg-max has p = 1).  Every warper
+// sees the softmax over what the earlier ones kept and only removes, so the kept set stays a band lo < p <= hi of candidates:
+//   min_p m:      p >= m (m times the largest p, which is 1).
+//   typical_p t:  Z = sum p, A = sum p log p over the band; q = p / Z, H = log Z - A / Z, d_i = |-log q_i - H| = |A / Z - log p_i|.
+//                 Kept: d_i <= d*, the smallest d_j whose mass {d <= d_j} reaches t Z (the token that crosses t stays, ties in d
+//                 stay together) - a band around e^(A / Z) that can leave the arg-max out.  By rank when nc <= EXACT_CAP; else a
+//                 bisection on d whose every probe is the p-interval [e^(c - d), e^(c + d)], c = A / Z (no logarithm per token).
+//   epsilon e:    q >= e, i.e. p >= e Z; every token at the band's maximum stays.
+//   eta e':       the same with min(e', sqrt(e') e^-H), H over the band at that point.
+// Every sum is a fixed-order block reduction, so a (seed, row, step) triple always gives the same token.  The final band goes to
+// thr_lo[b] / thr_hi[b] (gen_scores_kernel's kept test), then the draw of sample_stage2_kernel over it.
+__global__ __launch_bounds__(256) void sample_warp_draw_kernel(int V, const SamplingWarpers *__restrict__ wd,
+                                                               const uint64_t *__restrict__ seed_p, const int32_t *__restrict__ step,
+                                                               const float *__restrict__ cand_p, const int32_t *__restrict__ cand_i,
+                                                               const int32_t *__restrict__ cand_n, int32_t *__restrict__ chosen,
+                                                               float *__restrict__ thr_lo, float *__restrict__ thr_hi) {
+    __shared__ float scratch[4];
+    __shared__ float s_pref[257];
+    __shared__ float s_wtot[4];
+    __shared__ int s_off[APART + 1];
+    __shared__ float s_p[SAMPLE_LDS_CAP];
+    __shared__ float s_d[EXACT_CAP];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int per = ((V + APART - 1) / APART + 3) & ~3;
+    row_cand_offsets(cand_n, b, s_off);
+    const int nc = s_off[APART];
+    const RowCands cand{cand_p, cand_i, s_off, (int64_t)b * APART, per};
+    const bool in_lds = nc <= SAMPLE_LDS_CAP;
+    if (in_lds)
+        for (int c = tid; c < nc; c += 256) { int id; s_p[c] = cand(c, id); }
+    const SamplingWarpers w = *wd;
+    float lo = thr_lo[b], hi = INFINITY;
+    __syncthreads();
+    // f(p) for every candidate of the row: a thread sees a fixed subset in a fixed order - from LDS, or part by part from global
+    // memory (coalesced, and without the draw's search for a candidate's part)
+    auto each = [&](auto &&f) {
+        if (in_lds) {
+            for (int c = tid; c < nc; c += 256) f(s_p[c]);
+        } else {
+            for (int k = 0; k < APART; ++k) {
+                const float *pp = cand_p + ((int64_t)b * APART + k) * per;
+                const int n = s_off[k + 1] - s_off[k];
+                for (int j = tid; j < n; j += 256) f(pp[j]);
+            }
+        }
+    };
+    // reductions over the current band (a thread's terms in that order, then the fixed tree of the block reduction)
+    auto band_sum = [&](bool plogp) -> float {          // sum of p, or of p log p (a subnormal p adds nothing)
+        float a = 0.f;
+        each([&](float p) { if (p > lo && p <= hi) a += plogp ? (p >= 1.17549435e-38f ? p * logf(p) : 0.f) : p; });
+        return block_sum256(a, scratch);
+    };
+    auto band_max = [&]() -> float {
+        float a = 0.f;
+        each([&](float p) { if (p > lo && p <= hi) a = fmaxf(a, p); });
+        return block_max256(a, scratch);
+    };
+    auto band_min = [&]() -> float {
+        float a = -INFINITY;
+        each([&](float p) { if (p > lo && p <= hi) a = fmaxf(a, -p); });
+        return -block_max256(a, scratch);
+    };
+    // keep p >= x: the new lower bound is the largest member of the band below x (kept is p > lo)
+    auto keep_from = [&](float x) {
+        float a = lo;
+        each([&](float p) { if (p > lo && p <= hi && p < x) a = fmaxf(a, p); });
+        lo = block_max256(a, scratch);
+    };
+    if (w.min_p > 0.f) keep_from(w.min_p);
+    if (w.typical_p < 1.f) {
+        const float Z = band_sum(false), A = band_sum(true);
+        const float ctr = A / Z, need = w.typical_p * Z;
+        if (nc <= EXACT_CAP) {
+            for (int c = tid; c < nc; c += 256) {
+                const float p = s_p[c];
+                s_d[c] = (p > lo && p <= hi) ? fabsf(ctr - logf(p)) : INFINITY;
+            }
+            __syncthreads();
+            float dstar = INFINITY;                     // smallest d whose mass {d <= it} reaches t Z
+            for (int q = tid; q < nc; q += 256) {
+                const float dq = s_d[q];
+                if (dq == INFINITY) continue;
+                float m = 0.f;
+                for (int j = 0; j < nc; ++j) m += s_d[j] <= dq ? s_p[j] : 0.f;         // (fixed order; d = inf: outside the band)
+                if (m >= need) dstar = fminf(dstar, dq);
+            }
+            dstar = -block_max256(-dstar, scratch);     // (inf: rounding kept every sum below t Z - everything stays)
+            float pl = INFINITY, ph = 0.f;
+            for (int c = tid; c < nc; c += 256)
+                if (s_d[c] != INFINITY && s_d[c] <= dstar) { pl = fminf(pl, s_p[c]); ph = fmaxf(ph, s_p[c]); }
+            pl = -block_max256(-pl, scratch);
+            ph = block_max256(ph, scratch);
+            hi = ph;
+            keep_from(pl);
+        } else {
+            // M(x) = mass of the band inside [e^(ctr - x), e^(ctr + x)]; invariant M(dl) < t Z <= M(dh).  dh starts wide enough
+            // for the whole band (M = Z, summed in this very order), dl below 0 (an empty interval)
+            const float pmn = band_min(), pmx = band_max();
+            float dl = -1e-3f, dh = fmaxf(ctr - logf(pmn), logf(pmx) - ctr) * 1.001f + 1e-3f;
+            for (int it = 0; it < 40; ++it) {
+                const float mid = 0.5f * (dl + dh);
+                const float a = expf(ctr - mid), z = expf(ctr + mid);
+                float m = 0.f;
+                each([&](float p) { m += (p > lo && p <= hi && p >= a && p <= z) ? p : 0.f; });
+                m = block_sum256(m, scratch);
+                if (m >= need) dh = mid; else dl = mid;
+            }
+            hi = fminf(hi, expf(ctr + dh));
+            keep_from(expf(ctr - dh));
+        }
+    }
+    if (w.epsilon > 0.f) {
+        const float Z = band_sum(false), pm = band_max();
+        keep_from(fminf(w.epsilon * Z, pm));
+    }
+    if (w.eta > 0.f) {
+        const float Z = band_sum(false), A = band_sum(true), pm = band_max();
+        const float H = logf(Z) - A / Z;
+        keep_from(fminf(fminf(w.eta, sqrtf(w.eta) * expf(-H)) * Z, pm));
+    }
+    if (tid == 0) {                                     // (every thread read thr_lo[b] in front of the barriers above)
+        thr_lo[b] = lo;
+        thr_hi[b] = hi;
+    }
+    sample_draw(lo, hi, nc, in_lds, s_p, cand, s_wtot, s_pref, seed_p, step, chosen, b);
 }
 
 hipError_t launch_sample_select(const float *logits, int B, int V, float temperature, float top_p, int top_k, const uint64_t *seed,
@@ -1160,6 +1310,14 @@ hipError_t launch_sample_select(const float *logits, int B, int V, float tempera
                        cand_i, cand_n, zpart, spart);
     hipLaunchKernelGGL(sample_stage2_kernel, dim3(B), dim3(256), 0, s, V, top_p, top_k, seed, step, cand_p, cand_i, cand_n, zpart,
                        spart, chosen, thr_out, thr_keep);
+    return hipGetLastError();
+}
+
+hipError_t launch_sample_warp_draw(int B, int V, const SamplingWarpers *warp, const uint64_t *seed, const int32_t *step,
+                                   const float *cand_p, const int32_t *cand_i, const int32_t *cand_n, int32_t *chosen, float *thr_lo,
+                                   float *thr_hi, hipStream_t s) {
+    hipLaunchKernelGGL(sample_warp_draw_kernel, dim3(B), dim3(256), 0, s, V, warp, seed, step, cand_p, cand_i, cand_n, chosen, thr_lo,
+                       thr_hi);
     return hipGetLastError();
 }
 

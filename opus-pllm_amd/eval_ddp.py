@@ -41,7 +41,8 @@ import opus_pllm_amd as opa                                                    #
 from opus_pllm_amd import dist as odist                                        # noqa: E402
 from opus_pllm_amd.builder import load_pretrained_model, return_cstp_path      # noqa: E402
 from opus_pllm_amd.prompt import (add_constraint_args, add_logits_processor_args, add_lookup_args, after_process_output,  # noqa: E402
-                                  build_prompt, logits_processor_kwargs, lookup_kwargs, max_new_tokens_for, token_constraint)
+                                  build_prompt, logits_processor_kwargs, lookup_kwargs, max_new_tokens_for, token_constraint, add_warper_args,
+                                  warper_kwargs)
 
 
 def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperature=0.0, top_p=0.7, num_beams=1,
@@ -165,7 +166,7 @@ def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperatu
 
 
 def annotate_continuous(model, tokenizer, items, input_path, max_new, temperature=0.0, top_p=1.0, use_input_embed=False,
-                        device=None, stop_sequence=None, slots=None, refill_min=None, stats_out=None):
+                        device=None, stop_sequence=None, slots=None, refill_min=None, stats_out=None, warpers=None):
     """--continuous: the whole shard through ONE generate_continuous() call - a decode batch of `slots` rows whose finished rows
     are handed to the next prompts - instead of a sequence of batches that each wait for their longest answer.  Returns what
     annotate() returns, [n, max_new] padded with the EOS id; stats_out (a dict) receives the call's statistics."""
@@ -174,7 +175,7 @@ def annotate_continuous(model, tokenizer, items, input_path, max_new, temperatur
         return torch.empty((0, max_new), dtype=torch.long, device=dev)
     prompts = [opa.tokenizer_seq_token(build_prompt(q["instruction"], input_path), tokenizer, opa.DEFAULT_SEQ_TOKEN_INDEX,
                                        return_tensors="pt") for q in items]
-    extra = {}
+    extra = dict(warpers or {})                  # --min_p / --typical_p / --epsilon_cutoff / --eta_cutoff
     if use_input_embed:
         extra["protein_tokens"] = model.project_dataset(torch.tensor([q["input_embed"] for q in items], dtype=torch.float32, device=dev))
     with torch.inference_mode():
@@ -353,6 +354,7 @@ def eval_model(args):
     logits = [] if args.dump_logits else None
     proc_kw = logits_processor_kwargs(args)
     proc_kw.update(lookup_kw)
+    proc_kw.update(warper_kwargs(args))
     trie = token_constraint(args, tokenizer)          # --allowed_terms: built once, uploaded once per context
     if trie is not None:
         proc_kw["prefix_allowed_tokens_fn"] = trie
@@ -362,7 +364,8 @@ def eval_model(args):
     if continuous:              # the rank's whole shard in one call; the same fields are saved
         cstats = {}
         local_ids = annotate_continuous(model, tokenizer, mine, args.input_path, max_new, args.temperature, args.top_p,
-                                        args.use_input_embed, dev, stop_ids, slots=ctx_batch, refill_min=args.refill_min, stats_out=cstats)
+                                        args.use_input_embed, dev, stop_ids, slots=ctx_batch, refill_min=args.refill_min, stats_out=cstats,
+                                        warpers=warper_kwargs(args))
         if cstats:
             print(f"rank {rank}: continuous {cstats}, occupancy {cstats['live_row_steps'] / max(cstats['slot_steps'], 1):.3f}")
     else:
@@ -483,6 +486,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--rank_with_stop", action="store_true",
                    help="with --rank_terms / --search_terms: add the log-probability of ending the answer right behind the term")
     add_logits_processor_args(p)
+    add_warper_args(p)
     add_lookup_args(p)
     add_constraint_args(p)
     return p

@@ -19,8 +19,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import opus_pllm_amd as opa                                                    # noqa: E402
 from opus_pllm_amd.builder import load_pretrained_model, return_cstp_path      # noqa: E402
 from opus_pllm_amd.conversation import conv_vicuna_v0                          # noqa: E402
-from opus_pllm_amd.prompt import (add_constraint_args, add_logits_processor_args, add_lookup_args, is_protein_sequence,  # noqa: E402
-                                  logits_processor_kwargs, lookup_kwargs, online_cut, online_prompt, token_constraint)
+from opus_pllm_amd.prompt import (add_constraint_args, add_logits_processor_args, add_lookup_args, add_warper_args,  # noqa: E402
+                                  is_protein_sequence, logits_processor_kwargs, lookup_kwargs, online_cut, online_prompt,
+                                  token_constraint, warper_kwargs)
 
 
 def answer_once(model, tokenizer, instruction: str, seq: str, args, conv=conv_vicuna_v0, constraint=None):
@@ -36,7 +37,7 @@ def answer_once(model, tokenizer, instruction: str, seq: str, args, conv=conv_vi
         out = model.generate(input_ids, seq, attention_mask=None, pad_token_id=tokenizer.eos_token_id, seq_embedding=None,
                              do_sample=args.temperature > 0, temperature=args.temperature, top_p=args.top_p,
                              num_beams=args.num_beams, max_new_tokens=args.max_new_tokens, use_cache=True,
-                             **logits_processor_kwargs(args), **lookup_kwargs(args),
+                             **logits_processor_kwargs(args), **lookup_kwargs(args), **warper_kwargs(args),
                              **({} if getattr(args, "guidance_scale", None) is None else dict(guidance_scale=args.guidance_scale)),
                              **({} if constraint is None else dict(prefix_allowed_tokens_fn=constraint)))
     text = tokenizer.batch_decode(out, skip_special_tokens=True)[0]
@@ -93,6 +94,7 @@ if __name__ == "__main__":
     p.add_argument("--max_residues", type=int, default=1024)
     p.add_argument("--max_prompt", type=int, default=256)
     add_logits_processor_args(p)
+    add_warper_args(p)
     add_lookup_args(p)
     add_constraint_args(p)
     eval_model(p.parse_args())

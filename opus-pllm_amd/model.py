@@ -524,6 +524,11 @@ class OpusLlamaForCausalLM:
         repetition_penalty, no_repeat_ngram_size, bad_words_ids, min_length / min_new_tokens (see _logits_processors).  They see
         only the ids generated so far, never the prompt, as the reference's generate from inputs_embeds does.  With any of them on,
         `scores` hold the processed scores while `logits` and `token_logprobs` stay raw; num_beams > 1 raises.
+        Sampling warpers (do_sample=True; ignored otherwise, as in transformers): min_p, typical_p, epsilon_cutoff, eta_cutoff, in
+        transformers' order behind temperature / top_k / top_p, min_tokens_to_keep = 1, on the GPU inside the captured step (see
+        _sampling_warpers; off: None, and 0 / 1.0 / 0 / 0).  typical_p keeps a band of probabilities and can drop the most probable
+        token; `scores` hold l / T on the kept set, `logits` and `token_logprobs` stay raw.  Bad values raise transformers'
+        ValueErrors, num_beams > 1 with one of them on NotImplementedError.
         Constrained decoding (greedy and sampling): prefix_allowed_tokens_fn=TokenTrie(...) / TokenTrie.per_row([...])
         (constraint.py) - transformers' PrefixConstrainedLogitsProcessor as a device automaton, behind min_new_tokens and in front
         of the warpers; `scores` are -inf outside the allowed set, `logits` and `token_logprobs` stay raw.  Any other callable
@@ -619,6 +624,12 @@ class OpusLlamaForCausalLM:
         eos = [] if eos is None else ([int(eos)] if isinstance(eos, int) else [int(e) for e in eos])
         vocab = getattr(getattr(self, "cfg", None), "dec_vocab", None)
         lproc = _logits_processors(kwargs, eos, vocab)
+        warpers = _sampling_warpers(kwargs)
+        if not do_sample:
+            warpers = None                                     # (transformers: the warpers exist only when it samples)
+        if num_beams > 1 and warpers is not None:
+            raise NotImplementedError("min_p / typical_p / epsilon_cutoff / eta_cutoff are built for sampling one sequence per row, "
+                                      "not for num_beams > 1 (beam-sample needs min_tokens_to_keep = #eos + 1, i.e. M / K, and joint draws)")
         if num_beams > 1 and lproc is not None:
             raise NotImplementedError("repetition_penalty / no_repeat_ngram_size / bad_words_ids / min_length / min_new_tokens are "
                                       "built for greedy and sampling, not for num_beams > 1 (transformers applies them to the "
@@ -699,6 +710,7 @@ class OpusLlamaForCausalLM:
                 lproc = (pen, ngram, min_new, bad)
             self._set_logits_processors(lproc)
             self._set_token_constraint(constraint)
+            self._set_warpers(warpers)
             outs = (want["output_token_logprobs"], want["output_scores"], want["output_logits"]) if return_dict else None
             return self._greedy(embeds, None, max_new, eos, int(pad_id), sampler, outputs=outs, behind=behind)
         if num_beams <= 1 and nret > 1 and inputs.shape[0] * nret > self.cfg.max_batch:
@@ -725,6 +737,7 @@ class OpusLlamaForCausalLM:
                 embeds, mask = pad_left_common(embeds, mask.to(torch.uint8), n_embeds, n_mask)
         self._set_logits_processors(lproc)
         self._set_token_constraint(constraint)
+        self._set_warpers(warpers)
         if lookup_k:
             ids, stats = self._lookup(embeds, mask, max_new, eos, int(pad_id), lookup_k, lookup_m, lookup_hist)
             if not return_dict:
@@ -854,6 +867,14 @@ class OpusLlamaForCausalLM:
         arr = (C.c_int32 * max(1, len(ids)))(*ids)
         _cabi.check(self._lib.opus_set_stop_sequence(self._ctx, arr, len(ids)))
         self._stop_ids = ids
+
+    def _set_warpers(self, setting) -> None:
+        """setting = (min_p, typical_p, epsilon_cutoff, eta_cutoff) or None (off: 0, 1, 0, 0), applied to this context's following
+        sampling calls; an unchanged setting costs nothing.  The captured decode step reads the values from device memory."""
+        setting = tuple(float(x) for x in setting) if setting is not None else _WARPERS_OFF
+        if setting != getattr(self, "_warpers", _WARPERS_OFF):
+            _cabi.check(self._lib.opus_set_sampling_warpers(self._ctx, *setting))
+            self._warpers = setting
 
     def _set_logits_processors(self, setting) -> None:
         """setting = (repetition_penalty, no_repeat_ngram_size, min_new_tokens, bad_words_ids tuple) or None (off), applied to
@@ -1035,7 +1056,7 @@ class OpusLlamaForCausalLM:
         create the context with a few times the token budget (continuous.py holds the schedule).  New prompts are prefilled in
         a helper context (new_context(), created on first use and kept) and their K / V placed under the free rows.
 
-        Greedy and sampling, EOS ids and the stop sequence.  Draws are keyed by (seed, decode row, session step), so the same
+        Greedy and sampling (with generate()'s min_p / typical_p / epsilon_cutoff / eta_cutoff), EOS ids and the stop sequence.  Draws are keyed by (seed, decode row, session step), so the same
         call twice gives the same ids, but a sampled run is NOT the generate() run of the same seed (a prompt's row and step
         differ).  Greedy ids are generate()'s wherever the top-1 margin is decisive: a refilled row's K / V come from the same
         prefill kernels, at other cache slots.  num_beams > 1, num_return_sequences > 1, guidance_scale, prefix=,
@@ -1055,6 +1076,9 @@ class OpusLlamaForCausalLM:
                 raise NotImplementedError(f"generate_continuous({k}={int(v)}) is not built: one decode row per prompt")
         for k in ("use_cache", "position_ids", "attention_mask"):
             kwargs.pop(k, None)
+        warpers = _sampling_warpers(kwargs)
+        if not do_sample:
+            warpers = None
         if kwargs:
             raise TypeError(f"generate_continuous() got unexpected arguments {sorted(kwargs)}")
         if prompts is None or len(prompts) == 0:
@@ -1094,6 +1118,7 @@ class OpusLlamaForCausalLM:
         self.set_stop_sequence(stop_sequence)
         self._set_logits_processors(None)
         self._set_token_constraint(None)
+        self._set_warpers(warpers)
         if sampler is not None:
             self._set_top_k(sampler[3])
         backend = _StreamBackend(self, prompts, lens, seqs, seq_embedding, protein_tokens, max_new, eos, pad_id, sampler, slots)
@@ -1117,6 +1142,7 @@ class OpusLlamaForCausalLM:
         B = input_ids.shape[0]
         self._set_logits_processors(None)       # (a previous generate()'s processors do not carry over; no-op when off)
         self._set_token_constraint(None)
+        self._set_warpers(None)
         if bucket_rows == "packed":      # d_tokens: packed int32 [M] on the device; d_lens: the HOST row offsets cu [B + 1]
             s = self._enter()
             with torch.cuda.stream(self._stream):
@@ -2192,6 +2218,30 @@ def pad_left_common(a: torch.Tensor, a_mask: torch.Tensor, b: torch.Tensor, b_ma
     mask[:P, T - a.shape[1]:] = a_mask
     mask[P:, T - b.shape[1]:] = b_mask.to(a_mask.dtype)
     return out, mask
+
+
+_WARPER_NAMES = ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff")
+_WARPERS_OFF = (0.0, 1.0, 0.0, 0.0)
+
+
+def _sampling_warpers(kwargs: dict):
+    """Pops generate()'s truncation warpers from kwargs and checks them with transformers' messages (ValueError).  Returns None when
+    all are off, else (min_p, typical_p, epsilon_cutoff, eta_cutoff) with the off value in an unused place.  Off: min_p None / 0,
+    typical_p None / 1.0, epsilon_cutoff and eta_cutoff None / 0 (transformers' defaults)."""
+    vals = [kwargs.pop(k, None) for k in _WARPER_NAMES]
+    for name, v in zip(_WARPER_NAMES, vals):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer))):
+            raise ValueError(f"`{name}` has to be a float, but is {v!r}")
+    min_p, typical, eps, eta = (None if v is None else float(v) for v in vals)
+    if min_p is not None and not 0.0 <= min_p <= 1.0:
+        raise ValueError(f"`min_p` has to be a float in the [0, 1] interval, but is {min_p}")
+    if typical is not None and typical != 1.0 and not 0.0 < typical < 1.0:
+        raise ValueError(f"`typical_p` has to be a float > 0 and < 1, but is {typical}")
+    for name, v in (("epsilon_cutoff", eps), ("eta_cutoff", eta)):
+        if v is not None and v != 0.0 and not 0.0 < v < 1.0:
+            raise ValueError(f"`{name}` has to be a float > 0 and < 1, but is {v}")
+    out = (min_p or 0.0, 1.0 if typical is None else typical, eps or 0.0, eta or 0.0)
+    return None if out == _WARPERS_OFF else out
 
 
 def _logits_processors(kwargs: dict, eos: Sequence[int], vocab: Optional[int]):

@@ -126,6 +126,20 @@ def add_logits_processor_args(p) -> None:
                    help="EOS is banned until this many ids have been generated; unset: off")
 
 
+def add_warper_args(p) -> None:
+    """The drivers' truncation warpers of generate(do_sample=True) (transformers' options, behind top-k / top-p; all off by default)."""
+    p.add_argument("--min_p", type=float, default=None, help="keep tokens with at least min_p times the top token's probability")
+    p.add_argument("--typical_p", type=float, default=None, help="locally typical sampling: the mass kept around the entropy; 1.0 / unset: off")
+    p.add_argument("--epsilon_cutoff", type=float, default=None, help="drop tokens whose probability is below this; 0 / unset: off")
+    p.add_argument("--eta_cutoff", type=float, default=None, help="the same with min(eta, sqrt(eta) exp(-entropy)); 0 / unset: off")
+
+
+def warper_kwargs(args) -> dict:
+    """generate() keywords of add_warper_args' options (unset ones are left out)."""
+    names = ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff")
+    return {k: getattr(args, k) for k in names if getattr(args, k, None) is not None}
+
+
 def logits_processor_kwargs(args) -> dict:
     """generate() keywords of add_logits_processor_args' options (unset ones are left out)."""
     names = ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens")
