@@ -478,6 +478,27 @@ int opus_llama_prefix_export(opus_ctx *ctx, int64_t epoch, int32_t R, int32_t T,
  * R n <= max_batch max_prompt and 1 <= n_r <= n; OPUS_EBADARG for a row of h_src outside the snapshot. */
 int opus_llama_prefill_behind(opus_ctx *ctx, const opus_prefix_snap *snap, const void *d_embeds, int32_t R, int32_t n,
                               const int32_t *h_lens, const int32_t *h_src, float *d_last_logits, int64_t *epoch, void *stream);
+/* opus_llama_prefill_behind that also leaves a LIVE prefix on the context, as opus_llama_prefix does for a plain prefill: the final
+ * residual rows of the R rows' last positions -> d_last_rows fp32 [R, H] (required), the rows' kstart' is kept on the host, *epoch
+ * (required) is the new cache epoch.  Afterwards opus_llama_score_continuations / opus_llama_score_tree / opus_llama_prefix_export
+ * take (P = R, *epoch) with Tp + n slots per row.  Everything else - arguments, checks, launches, the decode state - is
+ * opus_llama_prefill_behind's.  Added within ABI 10 (a new symbol only). */
+int opus_llama_prefix_behind(opus_ctx *ctx, const opus_prefix_snap *snap, const void *d_embeds, int32_t R, int32_t n,
+                             const int32_t *h_lens, const int32_t *h_src, float *d_last_logits, float *d_last_rows, int64_t *epoch,
+                             void *stream);
+/* Ragged copy-out of the cache a decode loop leaves behind (kv_export_rows_kernel: K and V of all layers in one launch, bits
+ * unchanged).  T0 = the slot count of the context's last prefill (plain, fanned out or behind a prefix), kstart = the context's own.
+ * Row r's window is slots kstart[r] .. T0 + h_keep[r] - 1 (h_keep HOST [R]: how many of the slots the decode steps appended belong
+ * to the row), L_r = T0 - kstart[r] + h_keep[r] of them.  It is written to d_k / d_v [dec_layers][R][dec_kv_heads][Tp_out]
+ * [dec_head_dim] at slots Tp_out - L_r .. Tp_out - 1 - every row ends at the last slot, as opus_llama_prefill_behind expects of a
+ * snapshot - with zeros in every slot below, and d_kstart_out[r] = Tp_out - L_r (device int32 [R], required).  The whole snapshot is
+ * written: two exports of one state are bit-identical.  OPUS_ESTATE when the context holds no prefill (or a continuous session is
+ * open); OPUS_ESHAPE when R is not the row count of the last step, an h_keep[r] is negative or above the number of decode steps
+ * that ran since the prefill, Tp_out < max L_r or Tp_out > max_prompt + max_new_tokens (opus_llama_prefix_bytes' range).  Reads the
+ * step word and kstart back (synchronises the stream once); changes nothing in the context, the epoch included.  Added within
+ * ABI 10 (a new symbol only). */
+int opus_llama_prefix_export_rows(opus_ctx *ctx, int32_t R, const int32_t *h_keep, int32_t Tp_out, void *d_k, void *d_v,
+                                  int32_t *d_kstart_out, void *stream);
 /* opus_generate_scored with its prefill replaced by opus_llama_prefill_behind (greedy: temperature == 0; outputs optional, all NULL:
  * the plain loop).  Everything behind the prefill is that of an R-row batch: the captured step and its cache key, EOS ids, stop
  * sequence, logits processors, token constraint, the draws keyed by (seed, row, step). */
@@ -821,7 +842,9 @@ int opus_last_logits(opus_ctx *ctx, float *d_out, int32_t B, void *stream);
  * launched from a graph.  "graphs_cached".  "decode_steps": decode steps the generate loops enqueued - with an EOS id or a stop
  * sequence the loop polls the rows' state with a bounded run-ahead and stops at most 2 steps after the last row finished (HF stops
  * at once; the extra steps emit pad ids only, the returned ids and n_out are exact).  "w8_gemms": GEMMs issued on this context
- * (eagerly or while a graph was captured; replays are not counted) whose kernel streamed the FP8 panels.  "w4_gemms": the same for the MXFP4 panels. */
+ * (eagerly or while a graph was captured; replays are not counted) whose kernel streamed the FP8 panels.  "w4_gemms": the same for the MXFP4 panels.
+ * "cache_epoch": the current cache epoch - what opus_llama_prefix_export takes, also behind an opus_generate_* call, which hands
+ * none out. */
 int64_t opus_stat(opus_ctx *ctx, const char *name);
 
 /* Measurement support (bench.py).  With timing enabled (off by default; decode runs eagerly instead of from the

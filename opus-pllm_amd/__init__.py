@@ -13,6 +13,7 @@ from .config import (OpusConfig, PRESETS, llama3_8b, vicuna_13b, c1_tiny, micro,
                      galactica_1_3b, opt_1_3b, galactica_6_7b, qwen2_7b)
 from .mm_utils import tokenizer_seq_token, left_pad_sequence, get_model_name_from_path  # noqa: F401
 from .constraint import TokenTrie  # noqa: F401
+from .chat import ChatSession  # noqa: F401
 
 __all__ = ["IGNORE_INDEX", "DEFAULT_SEQ_TOKEN_INDEX", "DEFAULT_SEQ_TOKEN", "OpusConfig", "PRESETS",
-           "tokenizer_seq_token", "left_pad_sequence", "get_model_name_from_path", "TokenTrie"]
+           "tokenizer_seq_token", "left_pad_sequence", "get_model_name_from_path", "TokenTrie", "ChatSession"]

@@ -80,6 +80,8 @@ SIGNATURES = {
     "opus_llama_prefix_bytes": (C.c_int64, [C.POINTER(CConfig), C.c_int32, C.c_int32]),
     "opus_llama_prefix_export": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "opus_llama_prefill_behind": (C.c_int, [_P, _SNAP, _P, C.c_int32, C.c_int32, _I32P, _I32P, _P, C.POINTER(C.c_int64), _P]),
+    "opus_llama_prefix_behind": (C.c_int, [_P, _SNAP, _P, C.c_int32, C.c_int32, _I32P, _I32P, _P, _P, C.POINTER(C.c_int64), _P]),
+    "opus_llama_prefix_export_rows": (C.c_int, [_P, C.c_int32, _I32P, C.c_int32, _P, _P, _P, _P]),
     "opus_generate_scored_behind": (C.c_int, [_P, _SNAP, _P, C.c_int32, C.c_int32, _I32P, _I32P, C.c_int32, _I32P, C.c_int32, C.c_int32,
                                               C.c_float, C.c_float, C.c_uint64, _P, _I32P, _P, _P, _P, _P]),
     "opus_llama_score_continuations_detached": (C.c_int, [_P, _SNAP, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),

@@ -35,7 +35,7 @@ EXTRA = {"attn_prefill.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-na
 # Kernels that must not touch scratch memory (a spilled register in a kernel at its register ceiling is the first sign that
 # one more fusion will not fit): checked from the compiler's own resource remarks on every build, a hard failure.
 NO_SCRATCH = ("gemm_pp_kernel", "gemm_stream_kernel", "gemm_wide_kernel", "gemm_skinny_kernel", "attn_prefill_kernel",
-              "attn_decode_kernel", "attn_prefix_kernel", "tree_path_sums_kernel", "beam_", "kv_export_kernel", "kv_place_kernel",
+              "attn_decode_kernel", "attn_prefix_kernel", "tree_path_sums_kernel", "beam_", "kv_export_kernel", "kv_export_rows_kernel", "kv_place_kernel",
               "kv_append_kernel", "guidance_", "stream_finish_kernel", "stream_refill_kernel", "stream_reset_kernel", "trie_beam_expand_kernel",
               "trie_search_summary_kernel")
 RU_FLAG = "-Rpass-analysis=kernel-resource-usage"

@@ -118,6 +118,62 @@ class Conversation:
             raise NotImplementedError("get_prompt_eval needs a tokenizer with a chat template")
         return self._templated(True)
 
+    # ------------------------------------------------------------------ multi-turn: what one more turn adds to the rendered text
+    # A chat session (chat.ChatSession) keeps the KV cache of everything rendered so far, so a follow-up question must be fed as
+    # the text it ADDS, not as the whole conversation again.  With P1 = get_prompt() of [user 1, empty assistant message] (it ends
+    # in the assistant cue), the rendering of the whole conversation up to the next cue is
+    #     P1 + answer_segment(a1) + turn_delta(u2) + answer_segment(a2) + turn_delta(u3) + ...
+    # as strings.  Call turn_delta(u) when `messages` ends with the assistant's answer, before appending u.
+    def _uses_template(self) -> bool:
+        return self.tokenizer is not None and hasattr(self.tokenizer, "apply_chat_template")
+
+    def answer_segment(self, answer: str) -> str:
+        """The answer as it stands behind the assistant cue in the rendered conversation (SINGLE, TWO and LLAMA_2 put a blank
+        between the cue and the text; the others and the chat templates nothing)."""
+        if not self._uses_template() and self.sep_style in (SeparatorStyle.SINGLE, SeparatorStyle.TWO, SeparatorStyle.LLAMA_2):
+            return f" {answer}"
+        if not self._uses_template() and self.sep_style not in _RENDERERS:
+            raise ValueError(f"Invalid style: {self.sep_style}")
+        return answer
+
+    def turn_delta(self, message: str) -> str:
+        """What a new user message adds behind the last answer: the separator that closes the answer, the user's role and
+        message, and the assistant cue.  `messages` must end with the assistant's (non-empty) answer; nothing is appended.
+        Separator styles are rendered directly; with a chat template both states are rendered and the suffix is taken -
+        ValueError when the earlier rendering (the prompt up to the cue + the answer) is not a prefix of the later one, i.e.
+        when the template rewrites history and a cached conversation cannot be continued."""
+        if not message:
+            raise ValueError("turn_delta() needs a non-empty user message")
+        if not self.messages or not self.messages[-1]["content"]:
+            raise ValueError("turn_delta() continues a conversation whose last message is the assistant's answer")
+        i = len(self.messages)                                         # index of the new user message
+        if self._uses_template():
+            answer = self.messages[-1]
+            earlier = self.tokenizer.apply_chat_template(self.messages[:-1], tokenize=False, add_generation_prompt=True)
+            earlier += answer["content"]
+            later = self.tokenizer.apply_chat_template(self.messages + [{"role": self.roles[0], "content": message}],
+                                                       tokenize=False, add_generation_prompt=True)
+            if not later.startswith(earlier):
+                raise ValueError("the chat template does not render the conversation so far as a prefix of the next turn's "
+                                 "prompt: a cached conversation cannot be continued with it")
+            return later[len(earlier):]
+        user, cue = self.roles[0], self.roles[1]
+        seps = (self.sep, self.sep2)
+        st = self.sep_style
+        if st == SeparatorStyle.SINGLE:
+            return f"{self.sep}{user}: {message}{self.sep}{cue}:"
+        if st == SeparatorStyle.TWO:
+            return f"{seps[(i - 1) % 2]}{user}: {message}{seps[i % 2]}{cue}:"
+        if st == SeparatorStyle.MPT:
+            return f"{self.sep}{user}{message}{self.sep}{cue}"
+        if st == SeparatorStyle.LLAMA_2:
+            return f" {self.sep2}{self.sep}[INST] {message} [/INST]"
+        if st == SeparatorStyle.PLAIN:
+            return f"{seps[(i - 1) % 2]}{message}{seps[i % 2]}"
+        if st in _RENDERERS:
+            _unrendered(self)
+        raise ValueError(f"Invalid style: {self.sep_style}")
+
     def append_message(self, role: str, message: Optional[str]) -> None:
         self.messages.append({"role": role, "content": message})
 

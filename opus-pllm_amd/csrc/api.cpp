@@ -2318,7 +2318,8 @@ struct BehindArgs {
     const opus_prefix_snap *snap;
     const int32_t *h_lens, *h_src;
 };
-static int prefill_behind(opus_ctx *c, hipStream_t s, const BehindArgs &b, const half_t *embeds, int R, int n) {
+static int prefill_behind(opus_ctx *c, hipStream_t s, const BehindArgs &b, const half_t *embeds, int R, int n,
+                          std::vector<int32_t> *nks_out = nullptr) {
     const opus_config &g = c->cfg;
     if (!b.snap || !b.h_lens || !b.h_src || !embeds) return fail(OPUS_EBADARG, "prefill_behind: null pointer");
     PrefixSrc ps;
@@ -2392,6 +2393,7 @@ static int prefill_behind(opus_ctx *c, hipStream_t s, const BehindArgs &b, const
     c->cur_T = Tp + n;
     c->prefilled = true;
     ++c->prefills_behind;
+    if (nks_out) nks_out->swap(nks);                                          // (opus_llama_prefix_behind: the rows' kstart on the host)
     return OPUS_OK;
 }
 
@@ -2404,6 +2406,75 @@ extern "C" int opus_llama_prefill_behind(opus_ctx *c, const opus_prefix_snap *sn
     if (d_last_logits)
         HIPC(hipMemcpyAsync(d_last_logits, c->d_logits, (size_t)R * c->cfg.dec_vocab * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (epoch) *epoch = c->epoch;
+    return OPUS_OK;
+}
+
+// opus_llama_prefill_behind that also hands out the rows' final residual (taken where opus_llama_prefix takes it) and keeps the
+// rows' kstart on the host: the context then holds a live prefix of R rows x Tp + n slots, as after opus_llama_prefix on the
+// concatenated prompts.
+extern "C" int opus_llama_prefix_behind(opus_ctx *c, const opus_prefix_snap *snap, const void *d_embeds, int32_t R, int32_t n,
+                                        const int32_t *h_lens, const int32_t *h_src, float *d_last_logits, float *d_last_rows,
+                                        int64_t *epoch, void *stream) {
+    OPC(need_ready(c));
+    if (!d_last_rows || !epoch) return fail(OPUS_EBADARG, "prefix_behind: null last rows / epoch");
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int32_t> nks;
+    OPC(prefill_behind(c, s, BehindArgs{snap, h_lens, h_src}, (const half_t *)d_embeds, R, n, &nks));
+    const opus_config &g = c->cfg;
+    HIPC(hipMemcpyAsync(d_last_rows, c->d_xl, (size_t)R * g.dec_dim * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (d_last_logits)
+        HIPC(hipMemcpyAsync(d_last_logits, c->d_logits, (size_t)R * g.dec_vocab * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPC(hipStreamSynchronize(s));
+    c->h_kstart = nks;
+    *epoch = c->epoch;
+    return OPUS_OK;
+}
+
+// Ragged copy-out of the cache a decode loop left: row r's window kstart[r] .. T0 + h_keep[r] - 1, right-aligned in a snapshot of
+// Tp_out slots (kv_export_rows_kernel).  Reads the step word and kstart back (one synchronisation); changes nothing in the context.
+extern "C" int opus_llama_prefix_export_rows(opus_ctx *c, int32_t R, const int32_t *h_keep, int32_t Tp_out, void *d_k, void *d_v,
+                                             int32_t *d_kstart_out, void *stream) {
+    OPC(need_ready(c));
+    if (!h_keep || !d_k || !d_v || !d_kstart_out) return fail(OPUS_EBADARG, "prefix_export_rows: null pointer");
+    const opus_config &g = c->cfg;
+    if (!c->prefilled) return fail(OPUS_ESTATE, "prefix_export_rows: the context holds no prefill");
+    if (c->st.on) return fail(OPUS_ESTATE, "prefix_export_rows: a continuous session is open on this context");
+    if (R != c->cur_B) return fail(OPUS_ESHAPE, "prefix_export_rows: R=%d, the last step ran %d rows", R, c->cur_B);
+    hipStream_t s = (hipStream_t)stream;
+    int32_t steps = 0;
+    std::vector<int32_t> kst(R), nks(R);
+    HIPC(hipMemcpyAsync(&steps, c->d_step, sizeof(steps), hipMemcpyDeviceToHost, s));
+    HIPC(hipMemcpyAsync(kst.data(), c->d_kstart, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    const int T0 = c->cur_T;
+    if (steps < 0 || steps > g.max_new_tokens || T0 < 1 || T0 > g.max_prompt)
+        return fail(OPUS_ESTATE, "prefix_export_rows: step word %d / %d prompt slots outside the cache", steps, T0);
+    int maxL = 0;
+    for (int r = 0; r < R; ++r) {
+        if (h_keep[r] < 0 || h_keep[r] > steps)
+            return fail(OPUS_ESHAPE, "prefix_export_rows: h_keep[%d]=%d outside [0, %d decode steps]", r, h_keep[r], steps);
+        if (kst[r] < 0 || kst[r] >= T0) return fail(OPUS_ESTATE, "prefix_export_rows: kstart[%d]=%d outside [0, %d)", r, kst[r], T0);
+        maxL = std::max(maxL, T0 - kst[r] + h_keep[r]);
+    }
+    if (Tp_out < maxL || Tp_out > g.max_prompt + g.max_new_tokens)
+        return fail(OPUS_ESHAPE, "prefix_export_rows: Tp_out=%d (the longest window holds %d slots; at most %d)", Tp_out, maxL,
+                    g.max_prompt + g.max_new_tokens);
+    double slots = 0.0;
+    for (int r = 0; r < R; ++r) {
+        nks[r] = Tp_out - (T0 - kst[r] + h_keep[r]);
+        slots += Tp_out - nks[r];
+    }
+    HIPC(launch_upload_i32(nks.data(), R, d_kstart_out, s));
+    KvExportRowsParams p;
+    p.kc = c->kc; p.vc = c->vc; p.cache_sl = c->cache_sl; p.cache_sb = c->cache_sb; p.cache_sh = c->cache_sh;
+    p.kstart = c->d_kstart; p.nks = d_kstart_out; p.R = R; p.Tp = Tp_out;
+    p.snap_k = (half_t *)d_k; p.snap_v = (half_t *)d_v; p.layers = g.dec_layers; p.nkv = g.dec_kv_heads; p.hd = g.dec_head_dim;
+    const int phase = c->phase;
+    c->phase = PH_OTHER;
+    // bytes: the windows read, the whole snapshot written
+    const double per_slot = 2.0 * g.dec_layers * g.dec_kv_heads * g.dec_head_dim * sizeof(half_t);
+    KL(KC_OTHER, (slots + (double)R * Tp_out) * per_slot, launch_kv_export_rows(p, s));
+    c->phase = phase;
     return OPUS_OK;
 }
 
@@ -4189,6 +4260,7 @@ extern "C" int64_t opus_stat(opus_ctx *c, const char *name) {
     if (!strcmp(name, "stream_refills")) return c->stream_refills;
     if (!strcmp(name, "stream_graph")) return c->stream_graph.exec ? 1 : 0;
     if (!strcmp(name, "lookup_passes")) return c->lookup_passes;
+    if (!strcmp(name, "cache_epoch")) return c->epoch;       // (what opus_llama_prefix_export takes, also behind a generate call)
     return -1;
 }
 

@@ -400,6 +400,19 @@ hipError_t launch_attn_prefix(const AttnPrefixParams &p, int nblocks, hipStream_
 // export: snapshot <- rows 0 .. R - 1, slots 0 .. T - 1 of every layer of the cache (one launch, K and V)
 hipError_t launch_kv_export(const half_t *kc, const half_t *vc, int64_t cache_sl, int64_t cache_sb, int64_t cache_sh, int layers, int R,
                             int nkv, int T, int hd, half_t *snap_k, half_t *snap_v, hipStream_t s);
+// export rows (the inverse of place, for the ragged cache a decode loop leaves): the window kstart[r] .. kstart[r] + Tp - nks[r] - 1
+// of cache row r -> slots nks[r] .. Tp - 1 of snapshot row r, zeros below nks[r]; all layers, K and V, one launch.  Every row then
+// ends at the snapshot's last slot, as launch_kv_place expects.  The caller has checked every window against the cache's slots.
+struct KvExportRowsParams {
+    const half_t *kc, *vc;
+    int64_t cache_sl, cache_sb, cache_sh;
+    const int32_t *kstart;          // [R] device: first slot of every row's window in the cache
+    const int32_t *nks;             // [R] device: first visible slot of every snapshot row (Tp - window length)
+    int R, Tp;
+    half_t *snap_k, *snap_v;
+    int layers, nkv, hd;
+};
+hipError_t launch_kv_export_rows(const KvExportRowsParams &p, hipStream_t s);
 // place: the visible slots kstart[p] .. Tp - 1 of snapshot row p -> every decode row r of list[off[p] .. off[p + 1]) at slots
 // new_kstart[r] .. new_kstart[r] + Tp - kstart[p] - 1, all layers, K and V, one launch; each 16-byte piece is read once and stored
 // to all the rows of its prefix row.  Nothing else of the cache is written.

@@ -575,7 +575,18 @@ class OpusLlamaForCausalLM:
         a retrieved annotation, an earlier answer, a term list).  batch x (k + 1) <= max_batch, else ValueError.  With
         return_dict_in_generate the result carries `stats` (LookupStats: passes, plain_steps, drafted, accepted).  do_sample,
         num_beams > 1, num_return_sequences > 1, guidance_scale, prefix=, the logits processors, a TokenTrie and the output_*
-        flags raise NotImplementedError.  k None or 0 is the call without the argument."""
+        flags raise NotImplementedError.  k None or 0 is the call without the argument.
+        return_prefix=True (extension; needs return_dict_in_generate=True, else ValueError): the output's `prefix` is a DETACHED
+        OpusPrefix of every row's prompt + answer, cut out of the cache the decode loop leaves (opus_llama_prefix_export_rows, one
+        launch) - the next turn of a conversation is generate(follow_up_ids, prefix=out.prefix) and prefills the follow-up only.
+        Row b emitted n_b ids (counted_tokens: up to and including its EOS id / the stop sequence's last id, else all); the
+        handle holds K / V of the prompt and ids[b, : n_b - 1], `lengths` the rows' slot counts, `slots` their maximum, and
+        `pending` (int64 [B]) ids[b, n_b - 1] - chosen but never fed.  generate(prefix=) and cache_prefix(prefix=) feed the
+        pending id in front of the suffix (an empty suffix row is legal then); score_continuations / score_trie / search_trie
+        want a sealed handle: cache_prefix(empty_rows, prefix=handle).  Works for greedy and sampling, with EOS ids, the stop
+        sequence, the processors, a TokenTrie, the warpers and the output_* flags, behind plain generate() and generate(prefix=).
+        num_beams > 1, num_return_sequences > 1, guidance_scale and prompt_lookup_num_tokens raise NotImplementedError.  The
+        conversation has to fit max_prompt (prefix.slots + suffix <= max_prompt), else OpusError -2 naming the max_prompt needed."""
         return_dict = bool(kwargs.pop("return_dict_in_generate", False))
         want = {k: bool(kwargs.pop(k, False)) for k in ("output_scores", "output_logits", "output_token_logprobs",
                                                          "output_attentions", "output_hidden_states")}
@@ -588,6 +599,7 @@ class OpusLlamaForCausalLM:
         attention_mask = kwargs.pop("attention_mask", None)
         prefix = kwargs.pop("prefix", None)
         prefix_rows = kwargs.pop("prefix_rows", None)
+        return_prefix = bool(kwargs.pop("return_prefix", False))
         guidance = _guidance_scale(kwargs.pop("guidance_scale", None))
         neg_ids = kwargs.pop("negative_prompt_ids", None)
         neg_mask = kwargs.pop("negative_prompt_attention_mask", None)
@@ -666,6 +678,15 @@ class OpusLlamaForCausalLM:
             pad_id = eos[0] if eos else 0
         if inputs is None:
             raise ValueError("generate() needs input ids")
+        if return_prefix:                      # every check before the device is touched
+            if not return_dict:
+                raise ValueError("generate(return_prefix=True) needs return_dict_in_generate=True: the handle is a field of the output")
+            for on, what in ((num_beams > 1, "num_beams > 1 (the beams' cache rows are permuted hypotheses, not answers)"),
+                             (nret > 1, "num_return_sequences > 1"), (guidance is not None, "guidance_scale"),
+                             (bool(lookup_k), "prompt_lookup_num_tokens")):
+                if on:
+                    raise NotImplementedError(f"generate(return_prefix=True) is built for greedy search and sampling of one answer "
+                                              f"per row, not for {what}")
         if lookup_k:                           # every check before the device is touched
             lookup_m = _check_lookup(lookup_k, lookup_m, int(inputs.shape[0]), self.cfg.max_batch, do_sample=do_sample,
                                      num_beams=num_beams, nret=nret, guidance=guidance, prefix=prefix, lproc=lproc,
@@ -712,7 +733,10 @@ class OpusLlamaForCausalLM:
             self._set_token_constraint(constraint)
             self._set_warpers(warpers)
             outs = (want["output_token_logprobs"], want["output_scores"], want["output_logits"]) if return_dict else None
-            return self._greedy(embeds, None, max_new, eos, int(pad_id), sampler, outputs=outs, behind=behind)
+            res = self._greedy(embeds, None, max_new, eos, int(pad_id), sampler, outputs=outs, behind=behind)
+            if return_prefix:                  # right behind the loop: nothing else has touched the context
+                res.prefix = self._export_answer(res.sequences, eos, behind.new_kstart, behind.Tp + int(embeds.shape[1]))
+            return res
         if num_beams <= 1 and nret > 1 and inputs.shape[0] * nret > self.cfg.max_batch:
             raise _cabi.OpusError(-2, f"num_return_sequences runs batch x num_return_sequences = {inputs.shape[0]} x {nret} decoder "
                                       f"rows: the context holds max_batch={self.cfg.max_batch}")
@@ -755,8 +779,12 @@ class OpusLlamaForCausalLM:
             return GenerateBeamDecoderOnlyOutput(sequences=ids, sequences_scores=self.last_beam_scores.to(self.device))
         if not return_dict:
             return self._greedy(embeds, mask, max_new, eos, int(pad_id), sampler, nret=nret)
-        return self._greedy(embeds, mask, max_new, eos, int(pad_id), sampler,
-                            outputs=(want["output_token_logprobs"], want["output_scores"], want["output_logits"]), nret=nret)
+        res = self._greedy(embeds, mask, max_new, eos, int(pad_id), sampler,
+                           outputs=(want["output_token_logprobs"], want["output_scores"], want["output_logits"]), nret=nret)
+        if return_prefix:                      # right behind the loop: nothing else has touched the context
+            first = mask.to(torch.int32).argmax(dim=1).cpu().numpy()      # (a row's first real slot: its kstart)
+            res.prefix = self._export_answer(res.sequences, eos, first, int(embeds.shape[1]))
+        return res
 
     def compute_transition_scores(self, sequences: torch.Tensor, scores, beam_indices: Optional[torch.Tensor] = None,
                                   normalize_logits: bool = False) -> torch.Tensor:
@@ -1300,14 +1328,35 @@ class OpusLlamaForCausalLM:
     @torch.no_grad()
     def cache_prefix(self, input_ids: torch.Tensor, seq=None, attention_mask: Optional[torch.Tensor] = None,
                      seq_embedding=None, protein_tokens: Optional[torch.Tensor] = None, detach: bool = False,
-                     last_logits: bool = False) -> "OpusPrefix":
+                     last_logits: bool = False, prefix: Optional["OpusPrefix"] = None, prefix_rows=None) -> "OpusPrefix":
         """Prefills a prompt batch once and returns a handle that score_continuations() ranks continuations against.  The inputs
         are prepared exactly as generate() prepares them (inference-mode splice with `seq` / `seq_embedding` / `protein_tokens`;
         left-padded or unpadded rows): it IS a prefill, decode_logits() continues it as after prefill_logits().  The last slot of
         every row must be a real token (ValueError otherwise).  The handle is valid until the next call on this context that
-        prefills or permutes the cache (cache_prefix, generate, forward, prefill_logits, beam search); decode steps keep it."""
+        prefills or permutes the cache (cache_prefix, generate, forward, prefill_logits, beam search); decode steps keep it.
+        prefix=OpusPrefix (+ prefix_rows, as in generate(prefix=...)): `input_ids` are SUFFIX rows behind that handle, teacher-
+        forced without generating (opus_llama_prefix_behind: the handle's K / V placed, only the suffix prefilled).  The result is
+        a LIVE handle on this context of prefix.slots + n slots, with the rows' total lengths and last rows; detach() and the
+        scoring calls work on it unchanged.  A handle with `pending` ids (generate(return_prefix=True)) gets each row's pending id
+        in front of its suffix, so empty suffix rows ([R, 0] ids or an all-zero mask) are legal there: that "seals" the handle."""
         if input_ids is None:
             raise ValueError("cache_prefix() needs input ids")
+        if prefix is not None:
+            embeds, call = self._suffix_behind(prefix, prefix_rows, input_ids, attention_mask, seq, seq_embedding, protein_tokens, 1)
+            R, n, H = embeds.shape
+            s = self._enter()
+            with torch.cuda.stream(self._stream):
+                last = torch.empty((R, H), dtype=torch.float32, device=self.device)
+                logits = torch.empty((R, self.cfg.dec_vocab), dtype=torch.float32, device=self.device) if last_logits else None
+                epoch = C.c_int64(0)
+                _cabi.check(self._lib.opus_llama_prefix_behind(self._ctx, call.snap, embeds.data_ptr(), R, n, call.lens, call.src,
+                                                               None if logits is None else logits.data_ptr(), last.data_ptr(),
+                                                               C.byref(epoch), s))
+            self._leave()
+            lengths = torch.from_numpy(np.asarray(call.prefix_len, dtype=np.int64) + np.asarray(call.lens[:], dtype=np.int64))
+            handle = OpusPrefix(self, epoch.value, last, lengths, slots=call.Tp + n)
+            handle.last_logits = logits
+            return handle.detach() if detach else handle
         if attention_mask is not None and not bool(attention_mask.detach().bool()[:, -1].all()):
             raise ValueError("cache_prefix(): the last slot of every row must be a real token (left-pad the prompts)")
         if seq is not None or seq_embedding is not None or protein_tokens is not None:
@@ -1353,6 +1402,46 @@ class OpusLlamaForCausalLM:
         torch.cuda.current_stream(self.device).synchronize()
         return k, v, kst
 
+    def export_cache_rows(self, keep, slots: int):
+        """Ragged copy-out of the cache a decode loop left (opus_llama_prefix_export_rows): row r's window kstart[r] .. T0 +
+        keep[r] - 1, right-aligned in `slots` slots, zeros in front.  (k, v, kstart) = ([layers, rows, kv heads, slots, head_dim]
+        x 2 in the operand dtype, int32 [rows] = slots - window length).  OpusError -6 without a prefill, -2 for a bad keep / slots."""
+        cfg = self.cfg
+        keep = [int(x) for x in keep]
+        rows = len(keep)
+        if rows < 1 or int(slots) < 1:
+            raise _cabi.OpusError(-2, f"export_cache_rows: {rows} rows x {slots} slots")
+        s = self._enter()
+        try:
+            with torch.cuda.stream(self._stream):
+                shape = (cfg.dec_layers, rows, cfg.dec_kv_heads, int(slots), cfg.dec_head_dim)
+                k = torch.empty(shape, dtype=_cabi.operand_dtype(), device=self.device)
+                v = torch.empty(shape, dtype=_cabi.operand_dtype(), device=self.device)
+                kst = torch.empty((rows,), dtype=torch.int32, device=self.device)
+                _cabi.check(self._lib.opus_llama_prefix_export_rows(self._ctx, rows, (C.c_int32 * rows)(*keep), int(slots),
+                                                                    k.data_ptr(), v.data_ptr(), kst.data_ptr(), s))
+        finally:
+            self._leave()
+        torch.cuda.current_stream(self.device).synchronize()
+        return k, v, kst
+
+    def _export_answer(self, ids: torch.Tensor, eos, kstart, T0: int) -> "OpusPrefix":
+        """generate(return_prefix=True): the detached handle of prompt + answer.  Row b emitted n_b ids (counted_tokens); the
+        cache holds the prompt and ids 0 .. n_b - 2 (the last id was chosen, never fed), so the export keeps n_b - 1 decode
+        slots per row and the last id goes into `pending`.  kstart [B], T0: the prefill the loop ran behind."""
+        from .prefix import plan_export_rows
+        n_b = counted_tokens(ids, eos, getattr(self, "_stop_ids", [])).cpu()
+        if ids.shape[1] < 1:
+            raise ValueError("generate(return_prefix=True) needs at least one generated id")
+        keep = (n_b - 1).numpy()
+        lengths, Tp_out, nks = plan_export_rows(kstart, T0, keep)
+        k, v, kst = self.export_cache_rows(keep, Tp_out)
+        h = kst.cpu().numpy().astype(np.int32)
+        if not np.array_equal(h, nks):
+            raise RuntimeError(f"return_prefix: the context's row windows {h.tolist()} are not the planned ones {nks.tolist()}")
+        pending = ids.cpu().gather(1, (n_b - 1).view(-1, 1)).view(-1)
+        return OpusPrefix._snapshot(self, k, v, kst, h, torch.from_numpy(lengths), Tp_out, pending)
+
     def _usable_prefix(self, prefix: "OpusPrefix", detach: bool) -> "OpusPrefix":
         """The handle a call behind `prefix` works with: a detached one as it is (any context of the same weights), a live one
         detached on the fly when the call is going to overwrite the cache (detach)."""
@@ -1374,15 +1463,8 @@ class OpusLlamaForCausalLM:
         from .prefix import CapacityError, plan_prefill_behind
         cfg = self.cfg
         prefix = self._usable_prefix(prefix, detach=True)
-        ids = inputs.detach().cpu().long()
-        if ids.dim() != 2:
-            raise ValueError("generate(prefix=...) takes suffix ids [R, n]")
-        m = torch.ones_like(ids, dtype=torch.bool) if attention_mask is None else attention_mask.detach().cpu().bool()
-        rows = [ids[r][m[r]] for r in range(ids.shape[0])]
+        rows, src = _suffix_rows(prefix, prefix_rows, inputs, attention_mask)
         R = len(rows)
-        for r, row in enumerate(rows):
-            if row.numel() == 0:
-                raise ValueError(f"suffix row {r} is empty: every row needs at least one token behind the prefix")
         if R * nret > cfg.max_batch:
             raise _cabi.OpusError(-2, f"generate(prefix=...): {R * nret} decoder rows, the context holds max_batch={cfg.max_batch}")
         width = max(int(row.numel()) for row in rows)
@@ -1391,14 +1473,6 @@ class OpusLlamaForCausalLM:
         for r, row in enumerate(rows):
             rp[r, : row.numel()] = row
             rm[r, : row.numel()] = True
-        if prefix_rows is None:
-            if R != prefix.rows:
-                raise ValueError(f"{R} suffix rows for {prefix.rows} prefix rows: pass prefix_rows")
-            src = np.arange(R, dtype=np.int64)
-        else:
-            src = np.asarray(torch.as_tensor(prefix_rows).cpu(), dtype=np.int64).reshape(-1)
-            if src.shape[0] != R:
-                raise ValueError(f"prefix_rows has {src.shape[0]} entries for {R} suffix rows")
         has_seq = bool((rp == DEFAULT_SEQ_TOKEN_INDEX).any())
         if has_seq and width == 1:             # (the multimodal preparation passes one-token rows through unspliced)
             raise ValueError("a suffix that is the <seq> placeholder alone is not supported: put the protein into the prefix")
@@ -1419,9 +1493,13 @@ class OpusLlamaForCausalLM:
             plan = plan_prefill_behind(prefix._kstart.cpu().numpy(), prefix.slots, src, lens, int(embeds.shape[1]), cfg.max_batch,
                                        cfg.max_prompt, cap)
         except CapacityError as e:
-            raise _cabi.OpusError(-2, str(e)) from None
+            need = prefix.slots + int(embeds.shape[1])
+            hint = f"; a context created with max_prompt >= {need} would hold it" if need > cfg.max_prompt else ""
+            raise _cabi.OpusError(-2, str(e) + hint) from None
         embeds = embeds.to(self.device, _cabi.operand_dtype()).contiguous()
-        return embeds, _BehindCall(prefix, plan.lens, plan.src)
+        call = _BehindCall(prefix, plan.lens, plan.src)
+        call.new_kstart, call.prefix_len = plan.new_kstart, plan.prefix_len
+        return embeds, call
 
     def prefill_logits_behind(self, prefix: "OpusPrefix", embeds: torch.Tensor, lens, prefix_rows=None):
         """prefill_logits() behind a prefix (opus_llama_prefill_behind): embeds [R, n, H] right-padded suffix rows with `lens`
@@ -1453,6 +1531,7 @@ class OpusLlamaForCausalLM:
         cfg = self.cfg
         if not isinstance(prefix, OpusPrefix):
             raise TypeError("score_continuations() needs the OpusPrefix that cache_prefix() returned")
+        _refuse_pending(prefix, "score_continuations()")
         prefix = self._usable_prefix(prefix, detach=False)     # (a detached handle: read from its snapshot, never stale)
         if isinstance(continuations, torch.Tensor):
             ids = continuations.detach().cpu().long()
@@ -1537,6 +1616,7 @@ class OpusLlamaForCausalLM:
         cfg = self.cfg
         if not isinstance(prefix, OpusPrefix):
             raise TypeError("score_trie() needs the OpusPrefix that cache_prefix() returned")
+        _refuse_pending(prefix, "score_trie()")
         prefix = self._usable_prefix(prefix, detach=False)     # (a detached handle: read from its snapshot, never stale)
         if isinstance(trie, TokenTrie):
             tries = [trie] * prefix.rows
@@ -1658,6 +1738,7 @@ class OpusLlamaForCausalLM:
         cfg = self.cfg
         if not isinstance(prefix, OpusPrefix):
             raise TypeError("search_trie() needs the OpusPrefix that cache_prefix() returned")
+        _refuse_pending(prefix, "search_trie()")
         if isinstance(trie, TokenTrie):
             tries = [trie] * prefix.rows
         elif isinstance(trie, PerRowTokenTrie):
@@ -1875,10 +1956,27 @@ class OpusPrefix:
 
     def __init__(self, owner, epoch: int, last_rows: torch.Tensor, lengths: torch.Tensor, slots: int = 0):
         self._owner, self._epoch, self._last_rows = owner, int(epoch), last_rows
-        self.rows = int(last_rows.shape[0])
+        self.rows = int(last_rows.shape[0]) if last_rows is not None else int(lengths.shape[0])
         self.lengths = lengths
         self.slots = int(slots)          # Tp: cache slots per row (the padded prompt width)
         self._k = self._v = self._kstart = self._h_kstart = None
+        # generate(return_prefix=True): int64 [rows], the last id every row emitted - chosen, never fed, so its K / V is not in
+        # the snapshot and the handle has no last rows.  generate(prefix=) and cache_prefix(prefix=) feed it in front of the
+        # suffix; the scoring calls need a sealed handle (cache_prefix(prefix=handle)).  None on every other handle.
+        self.pending = None
+
+    @classmethod
+    def _snapshot(cls, owner, k, v, kstart, h_kstart, lengths, slots: int, pending) -> "OpusPrefix":
+        """A detached handle around an export of the live cache (generate(return_prefix=True))."""
+        self = cls(owner, -1, None, lengths, slots)
+        self._k, self._v, self._kstart = k, v, kstart
+        self._h_kstart = (C.c_int32 * self.rows)(*[int(x) for x in h_kstart])
+        self.pending = pending
+        return self
+
+    def nbytes(self) -> int:
+        """Device bytes a detached handle holds in K and V (prefix.snapshot_bytes); 0 for a live one."""
+        return 0 if self._k is None else int(self._k.numel() * self._k.element_size() * 2)
 
     @property
     def detached(self) -> bool:
@@ -1901,11 +1999,49 @@ class OpusPrefix:
         return _cabi.CPrefixSnap(self._k.data_ptr(), self._v.data_ptr(), self._kstart.data_ptr(), self._h_kstart, self.rows, self.slots)
 
 
+def _refuse_pending(prefix: OpusPrefix, who: str) -> None:
+    if prefix.pending is not None:
+        raise ValueError(f"{who}: the handle holds pending ids (the last id of every answer was chosen but never fed, so it has no "
+                         f"last rows to score from): seal it with cache_prefix(prefix=handle)")
+
+
+def _suffix_rows(prefix, prefix_rows, inputs, attention_mask):
+    """The unpadded suffix rows of a call behind `prefix` (1-D int64 tensors) and the prefix row of each (int64 [R]).  A handle
+    with `pending` ids (generate(return_prefix=True)) gets the pending id of row prefix_rows[r] in front of suffix row r, so an
+    empty suffix row is legal there; behind any other handle it is a ValueError."""
+    ids = inputs.detach().cpu().long()
+    if ids.dim() != 2:
+        raise ValueError("generate(prefix=...) takes suffix ids [R, n]")
+    m = torch.ones_like(ids, dtype=torch.bool) if attention_mask is None else attention_mask.detach().cpu().bool()
+    rows = [ids[r][m[r]] for r in range(ids.shape[0])]
+    R = len(rows)
+    pending = getattr(prefix, "pending", None)
+    if pending is None:
+        for r, row in enumerate(rows):
+            if row.numel() == 0:
+                raise ValueError(f"suffix row {r} is empty: every row needs at least one token behind the prefix")
+    if prefix_rows is None:
+        if R != prefix.rows:
+            raise ValueError(f"{R} suffix rows for {prefix.rows} prefix rows: pass prefix_rows")
+        src = np.arange(R, dtype=np.int64)
+    else:
+        src = np.asarray(torch.as_tensor(prefix_rows).cpu(), dtype=np.int64).reshape(-1)
+        if src.shape[0] != R:
+            raise ValueError(f"prefix_rows has {src.shape[0]} entries for {R} suffix rows")
+    if pending is not None:
+        if src.size and (src.min() < 0 or src.max() >= prefix.rows):
+            raise ValueError(f"prefix_rows must lie in [0, {prefix.rows})")
+        pend = pending.detach().cpu().long()
+        rows = [torch.cat([pend[int(p)].view(1), row]) for row, p in zip(rows, src)]
+    return rows, src
+
+
 class _BehindCall:
     """Arguments of one opus_*_behind call (kept alive for its duration): the snapshot, the rows' lengths and prefix rows."""
 
     def __init__(self, prefix: OpusPrefix, lens: np.ndarray, src: np.ndarray):
         self.prefix, self.Tp = prefix, prefix.slots
+        self.new_kstart = None           # (set by _suffix_behind: the decode rows' first real slots, prefix.plan_prefill_behind)
         self._struct = prefix._snap()
         self.snap = C.byref(self._struct)
         self.lens = (C.c_int32 * len(lens))(*[int(x) for x in lens])
@@ -2346,6 +2482,7 @@ class GenerateDecoderOnlyOutput(_FieldsOutput):
         self.sequences, self.scores, self.logits = sequences, scores, logits
         self.attentions, self.hidden_states, self.past_key_values = attentions, hidden_states, past_key_values
         self.token_logprobs, self.logprob, self.n_tokens = token_logprobs, logprob, n_tokens
+        self.prefix = None               # return_prefix=True (extension; attribute only): the detached OpusPrefix of prompt + answer
 
 
 class GenerateBeamDecoderOnlyOutput(_FieldsOutput):

@@ -11,6 +11,10 @@ prefix the context looks like a left-padded prefill of the concatenated prompts 
     decode step i        : slot T' + i, position Lp + n_r + i  (the decode step's slot - kstart' rule)
 
 `off` / `list` group the decode rows by prefix row (the native PrefixTables): rows list[off[p] .. off[p + 1]) continue row p.
+
+The way back (generate(return_prefix=True) / opus_llama_prefix_export_rows): after s decode steps behind a prefill of T0 slots, row
+r keeps h_keep[r] <= s of the appended slots; its window kstart[r] .. T0 + h_keep[r] - 1 (L_r slots) lands right-aligned in a
+snapshot of Tp_out = max L_r slots, new kstart Tp_out - L_r (plan_export_rows).
 """
 from __future__ import annotations
 
@@ -34,6 +38,24 @@ class BehindPlan:
 def snapshot_bytes(layers: int, kv_heads: int, head_dim: int, P: int, Tp: int, itemsize: int = 2) -> int:
     """Bytes of a snapshot's K plus V: [layers][P][kv heads][Tp][head_dim] each (opus_llama_prefix_bytes)."""
     return 2 * layers * P * kv_heads * Tp * head_dim * itemsize
+
+
+def plan_export_rows(kstart: Sequence[int], T0: int, keep: Sequence[int]):
+    """Host mirror of opus_llama_prefix_export_rows.  kstart [R], T0: the live cache after a prefill of T0 slots; keep [R]: how many
+    of the slots the decode steps appended belong to row r.  Row r's window is slots kstart[r] .. T0 + keep[r] - 1, L_r = T0 -
+    kstart[r] + keep[r] of them; in a snapshot of Tp_out = max L_r slots it sits at slots Tp_out - L_r .. Tp_out - 1.  Returns
+    (lengths int64 [R], Tp_out, new_kstart int32 [R]) with new_kstart + lengths == Tp_out."""
+    kst = np.asarray(kstart, dtype=np.int64).reshape(-1)
+    kp = np.asarray(keep, dtype=np.int64).reshape(-1)
+    if kst.shape[0] < 1 or kp.shape[0] != kst.shape[0]:
+        raise ValueError(f"{kp.shape[0]} keep counts for {kst.shape[0]} rows")
+    if T0 < 1 or (kst < 0).any() or (kst >= T0).any():
+        raise ValueError(f"a cache of {T0} prompt slots needs 0 <= kstart < T0 for every row")
+    if (kp < 0).any():
+        raise ValueError("keep counts must not be negative")
+    lengths = T0 - kst + kp
+    Tp_out = int(lengths.max())
+    return lengths, Tp_out, np.ascontiguousarray(Tp_out - lengths, dtype=np.int32)
 
 
 def plan_prefill_behind(kstart: Sequence[int], Tp: int, src: Sequence[int], lens: Sequence[int], n: int, max_batch: int,

@@ -109,6 +109,16 @@ def online_prompt(instruction: str, has_sequence: bool, conv=conv_vicuna_v0):
     return f"{conv.system}\n\n### {conv.roles[0]}: {instruction}\n### Professor:", instruction
 
 
+def online_followup(instruction: str, has_sequence: bool, conv=conv_vicuna_v0, after_separator: bool = False):
+    """(text, instruction as shown) a follow-up turn of eval_online.py --multi_turn adds behind the previous answer, in
+    online_prompt's own format: the separator line that closes the answer (left out when the answer already ended with the
+    separator: after_separator), the student's turn, the answer cue."""
+    if has_sequence and DEFAULT_SEQ_TOKEN not in instruction:
+        instruction = DEFAULT_SEQ_TOKEN + "\n" + instruction
+    head = " " if after_separator else "\n### "
+    return f"{head}{conv.roles[0]}: {instruction}\n### Professor:", instruction
+
+
 def online_cut(outputs: str, sep: str = "###") -> str:
     """Text up to the first separator found from offset 2 (run_opus_online.py:86-92)."""
     outputs = outputs.strip()
