@@ -566,6 +566,27 @@ int opus_debug_lookup_accept(opus_ctx *ctx, const int32_t *d_argmax, const int32
 /* Diagnostic: opus_generate_scored's fused arg-max / log-sum-exp pass on fp32 logits [B, V] (B <= max_batch, any V >= 1; rows
  * need no alignment): d_idx [B] the arg-max (lowest index among ties, bitwise what the greedy step picks), d_lse [B]. */
 int opus_debug_argmax_lse(opus_ctx *ctx, const float *d_logits, int32_t B, int32_t V, int32_t *d_idx, float *d_lse, void *stream);
+/* Top log-probs: the k likeliest tokens of a raw logits row l[0..V) and their log-probabilities.  Entries are ordered by value
+ * descending, then index ascending - np.argsort(-l, kind="stable")[:k], an exact comparison of the stored values (-0 == +0); -inf
+ * entries order like any value and give -inf; a row without a finite entry, and NaNs, are undefined.  top_lp[j] = l[top_ids[j]] -
+ * lse(l) in fp32, the lse being the one d_token_logprobs uses.
+ * opus_set_gen_top_logprobs(ctx, k, d_top_ids, d_top_lp), 1 <= k <= min(20, dec_vocab), applies to every later
+ * opus_generate_scored / _fanout / _guided / _behind call of the context AND to opus_llama_forward, until cleared with k = 0 (the
+ * buffers are then ignored); the setter launches nothing.
+ *   generate: d_top_ids int32 / d_top_lp fp32 [rows, max_new, k], rows as the call's other outputs (B nret; P under guidance).  The
+ *   row is the raw one: before guidance (the conditional row), the logits processors, the token constraint, temperature and the
+ *   warpers.  A row that had finished before a step gets ids -1 and log-probs 0 at it (the step that emits the EOS id or the last
+ *   stop-sequence id still counts); steps past *n_out are not written.  "On" is part of the captured step's identity, k and the
+ *   addresses are not (they travel in the device descriptor): another k or fresh buffers instantiate no graph.  Off: every launch,
+ *   graph and id is what it was.
+ *   forward: [R, k] in the order of d_rows, from each lm_head chunk's 16-bit logits and the log-sum-exp of its NLL pass.
+ * OPUS_EBADARG: k outside 0..20 or above dec_vocab, a NULL buffer with k > 0.  Added within ABI 10 (new symbols only). */
+int opus_set_gen_top_logprobs(opus_ctx *ctx, int32_t k, int32_t *d_top_ids, float *d_top_lp);
+/* Diagnostic: the two top-k launches alone on caller rows d_logits [R, ld] (dtype OPUS_F32, or OPUS_F16 = the build's 16-bit type;
+ * V <= ld values a row; any R >= 1; rows need no alignment), 1 <= k <= min(20, V): d_ids int32 / d_lp fp32 [R, k].  d_lse fp32 [R],
+ * or NULL: the rows' log-sum-exp is computed here (contiguous fp32 rows: by the decode step's fused arg-max / log-sum-exp pass). */
+int opus_debug_top_logprobs(opus_ctx *ctx, const void *d_logits, int32_t dtype, int64_t ld, int32_t R, int32_t V, int32_t k,
+                            const float *d_lse, int32_t *d_ids, float *d_lp, void *stream);
 /* Diagnostic: the guidance launches of opus_generate_scored_guided alone on caller memory - fp32 logits [2 P, V] (any P >= 1, any
  * V >= 1; rows need no alignment): rows [0, P) become g (lsm(l_b) - lsm(l_{P+b})) + lsm(l_{P+b}) with lsm(x) = (x - max x) -
  * log(sum exp(x - max x)) in fp32 (g = 0 returns the partner rows' log-softmax as the kernel takes it); rows [P, 2 P) are not
@@ -853,7 +874,7 @@ int64_t opus_stat(opus_ctx *ctx, const char *name);
  * belongs to, and its ALGORITHMIC bytes and FLOPs.  opus_timing_get sums the records since the last reset that match
  * kernel_class and phase ("*" = any); opus_timing_names returns "class,class,...;phase,phase,..." .  Classes and phases are
  * addressed by name, never by position.  Order of the lists: phases are append-only ("score" last); among the classes "xent"
- * stays the last entry, as published since opus_llama_forward, and a class added later ("contact", "trie_search", "constraint", "guidance", "mlm", "logitproc") is
+ * stays the last entry, as published since opus_llama_forward, and a class added later ("contact", "trie_search", "topk", "constraint", "guidance", "mlm", "logitproc") is
  * listed in front of it ("constraint", "guidance", "mlm", "logitproc" keep their places next to "xent"). */
 int opus_timing_enable(opus_ctx *ctx, int32_t on);
 int opus_timing_reset(opus_ctx *ctx);

@@ -195,6 +195,8 @@ SIGNATURES = {
     "opus_generate_scored_fanout": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
                                               C.c_int32, C.c_float, C.c_float, C.c_uint64, _P, C.POINTER(C.c_int32), _P, _P, _P, _P]),
     "opus_debug_argmax_lse": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    "opus_set_gen_top_logprobs": (C.c_int, [_P, C.c_int32, _P, _P]),
+    "opus_debug_top_logprobs": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "opus_generate_scored_guided": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
                                               C.c_int32, C.c_float, C.c_float, C.c_uint64, _P, C.POINTER(C.c_int32), _P, _P, _P, _P]),
     "opus_debug_guidance": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, _P]),

@@ -18,7 +18,7 @@ SRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "lib", "libopus_pllm.so")
 LIB_BF16 = os.path.join(HERE, "lib", "libopus_pllm_bf16.so")      # the same sources with -DOPUS_BF16 (csrc/common.h)
-SOURCES = ["gemm.hip", "gemm_stream.hip", "norm.hip", "elementwise.hip", "attn_prefill.hip", "attn_prefix.hip", "kv_place.hip", "stream.hip", "attn_decode.hip", "beam.hip", "score.hip", "contact.hip", "mlm.hip", "logits_proc.hip", "constraint.hip", "guidance.hip", "quant.hip", "lookup.hip", "trie_search.hip", "api.cpp"]
+SOURCES = ["gemm.hip", "gemm_stream.hip", "norm.hip", "elementwise.hip", "attn_prefill.hip", "attn_prefix.hip", "kv_place.hip", "stream.hip", "attn_decode.hip", "beam.hip", "score.hip", "contact.hip", "mlm.hip", "logits_proc.hip", "constraint.hip", "guidance.hip", "quant.hip", "lookup.hip", "trie_search.hip", "topk.hip", "api.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
@@ -37,7 +37,7 @@ EXTRA = {"attn_prefill.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-na
 NO_SCRATCH = ("gemm_pp_kernel", "gemm_stream_kernel", "gemm_wide_kernel", "gemm_skinny_kernel", "attn_prefill_kernel",
               "attn_decode_kernel", "attn_prefix_kernel", "tree_path_sums_kernel", "beam_", "kv_export_kernel", "kv_export_rows_kernel", "kv_place_kernel",
               "kv_append_kernel", "guidance_", "stream_finish_kernel", "stream_refill_kernel", "stream_reset_kernel", "trie_beam_expand_kernel",
-              "trie_search_summary_kernel")
+              "trie_search_summary_kernel", "topk_part_kernel", "topk_merge_kernel", "topk_row_lse_kernel")
 RU_FLAG = "-Rpass-analysis=kernel-resource-usage"
 
 

@@ -160,6 +160,17 @@ struct opus_ctx {
     GenOutDesc *d_gen = nullptr;
     GenOutDesc h_gen{};
     float *d_gpsum = nullptr, *d_gthr = nullptr;
+    // top log-probs (opus_set_gen_top_logprobs; 0: off): the caller's buffers, and an allocation made on first use - the parts'
+    // candidate keys [topk_rows(), APART, TOPK_MAX] and (opus_debug_top_logprobs) the rows' log-sum-exp
+    int top_k = 0;
+    int32_t *top_ids = nullptr;
+    float *top_lp = nullptr;
+    char *topk_mem = nullptr;
+    uint64_t *d_tcand = nullptr;
+    float *d_tlse = nullptr;
+    float *fwd_lse = nullptr;            // opus_llama_forward with top log-probs on: a chunk's log-sum-exp rows (grown on use)
+    int64_t fwd_lse_cap = 0;
+    int topk_rows() const { return cfg.max_batch > 64 ? cfg.max_batch : 64; }
     // logits processors (opus_set_logits_processors): the host setting, uploaded in stream order by every generate call, and a
     // separate allocation made on first use - the device descriptor, the step word of opus_debug_logits_process, the output
     // descriptors split into raw (before the processors) and processed (after), the raw rows' log-sum-exp and the raw logits of the
@@ -485,6 +496,8 @@ extern "C" int opus_ctx_destroy(opus_ctx *c) {
     if (c->proj_big) (void)hipFree(c->proj_big);
     if (c->kv_tmp) (void)hipFree(c->kv_tmp);
     if (c->gen_mem) (void)hipFree(c->gen_mem);
+    if (c->topk_mem) (void)hipFree(c->topk_mem);
+    if (c->fwd_lse) (void)hipFree(c->fwd_lse);
     if (c->lproc_mem) (void)hipFree(c->lproc_mem);
     if (c->warp_mem) (void)hipFree(c->warp_mem);
     if (c->cons_tab) (void)hipFree(c->cons_tab);
@@ -1734,6 +1747,8 @@ static int64_t score_chunk_rows(const opus_config &g, int64_t R, bool loss_only,
     return n;
 }
 
+static int ensure_topk_mem(opus_ctx *c);
+
 // final norm + lm_head over the n fp32 rows in X -> operand-dtype logits [n, V] (row stride V), then the NLL of every row
 static int score_rows(opus_ctx *c, hipStream_t s, const float *X, int n, half_t *logits, const int32_t *targets, float *logprob,
                       float *lse) {
@@ -1763,6 +1778,16 @@ extern "C" int opus_llama_forward(opus_ctx *c, const void *d_embeds, const uint8
     if (R > 0 && chunk < 1)
         return fail(OPUS_EBADARG, "forward: scratch of %lld bytes holds no row (opus_llama_forward_scratch_bytes)", (long long)scratch_bytes);
     hipStream_t s = (hipStream_t)stream;
+    if (c->top_k > 0 && R > 0) {             // the chunk's log-sum-exp rows (grown on use; the stream is idle between forward calls)
+        OPC(ensure_topk_mem(c));
+        if (chunk > c->fwd_lse_cap) {
+            HIPC(hipStreamSynchronize(s));
+            if (c->fwd_lse) (void)hipFree(c->fwd_lse);
+            c->fwd_lse = nullptr; c->fwd_lse_cap = 0;
+            HIPC(hipMalloc((void **)&c->fwd_lse, align_up((size_t)chunk * sizeof(float))));
+            c->fwd_lse_cap = chunk;
+        }
+    }
     OPC(prefill(c, s, (const half_t *)d_embeds, d_mask, B, T, true));
     c->phase = PH_SCORE;
     const int H = g.dec_dim, V = g.dec_vocab;
@@ -1772,7 +1797,15 @@ extern "C" int opus_llama_forward(opus_ctx *c, const void *d_embeds, const uint8
         const int n = (int)std::min<int64_t>(chunk, R - r0);
         KL(KC_OTHER, 8.0 * n * H + 4.0 * n, launch_gather_rows(c->d_x, d_rows + r0, n, (int64_t)B * T, H, rows_f, s));
         half_t *out = loss_only ? slab : reinterpret_cast<half_t *>(d_logits) + r0 * V;
-        OPC(score_rows(c, s, rows_f, n, out, d_targets + r0, d_logprob + r0, nullptr));
+        OPC(score_rows(c, s, rows_f, n, out, d_targets + r0, d_logprob + r0, c->top_k > 0 ? c->fwd_lse : nullptr));
+        // opus_set_gen_top_logprobs: the k likeliest ids of every scored row, [R, k], from the chunk's 16-bit logits and xent's lse
+        for (int q0 = 0; c->top_k > 0 && q0 < n; q0 += c->topk_rows()) {
+            const int m = std::min(n - q0, c->topk_rows());
+            TopkArgs ta;
+            ta.cand = c->d_tcand; ta.lse = c->fwd_lse + q0; ta.k = c->top_k;
+            ta.ids = c->top_ids + (r0 + q0) * c->top_k; ta.lp = c->top_lp + (r0 + q0) * c->top_k;
+            KL(KC_TOPK, 2.0 * m * V, launch_topk_h16(out + (int64_t)q0 * V, V, m, V, ta, s));
+        }
     }
     return OPUS_OK;
 }
@@ -2507,7 +2540,7 @@ extern "C" int opus_debug_attn_tree(opus_ctx *c, const void *d_qkv, const void *
 }
 
 // opus_generate_scored's outputs (StepPlan::outs)
-enum { GEN_LOGPROBS = 1, GEN_SCORES = 2, GEN_LOGITS = 4 };
+enum { GEN_LOGPROBS = 1, GEN_SCORES = 2, GEN_LOGITS = 4, GEN_TOPLP = 8 };
 
 static int ensure_gen_mem(opus_ctx *c) {
     if (c->gen_mem) return OPUS_OK;
@@ -2517,6 +2550,15 @@ static int ensure_gen_mem(opus_ctx *c) {
     c->d_gen = reinterpret_cast<GenOutDesc *>(c->gen_mem);
     c->d_gpsum = reinterpret_cast<float *>(c->gen_mem + o_ps);
     c->d_gthr = reinterpret_cast<float *>(c->gen_mem + o_thr);
+    return OPUS_OK;
+}
+
+static int ensure_topk_mem(opus_ctx *c) {
+    if (c->topk_mem) return OPUS_OK;
+    const size_t R = c->topk_rows(), o_lse = align_up(R * APART * TOPK_MAX * sizeof(uint64_t));
+    HIPC(hipMalloc((void **)&c->topk_mem, o_lse + align_up(R * sizeof(float))));
+    c->d_tcand = reinterpret_cast<uint64_t *>(c->topk_mem);
+    c->d_tlse = reinterpret_cast<float *>(c->topk_mem + o_lse);
     return OPUS_OK;
 }
 
@@ -2619,7 +2661,11 @@ static int select_next(opus_ctx *c, hipStream_t s, const StepPlan &p) {
     const int HB = guid ? p.rows / 2 : p.rows;      // rows the head works on
     const bool proc = p.lproc || p.cons || guid;    // the logits are edited in place: raw outputs first
     const bool lp = p.outs & GEN_LOGPROBS, sc = p.outs & (GEN_SCORES | GEN_LOGITS);
+    const bool tl = p.outs & GEN_TOPLP;             // the k likeliest ids of the raw rows (topk.hip), k and the addresses from the descriptor
+    const bool lse = lp || tl;                      // the raw rows' log-sum-exp is needed
     const size_t BV = (size_t)HB * g.dec_vocab;
+    TopkArgs ta;
+    ta.cand = c->d_tcand; ta.finished = c->d_fin; ta.step = c->d_step; ta.max_new = max_new;
     if (proc) {
         if (p.outs & GEN_LOGITS)
             KL(KC_OTHER, 8.0 * BV, launch_gen_scores(c->d_logits, HB, g.dec_vocab, c->d_gen_raw, c->d_step, max_new, 0.f, 1.f,
@@ -2627,12 +2673,20 @@ static int select_next(opus_ctx *c, hipStream_t s, const StepPlan &p) {
         if (guid) {
             KL(KC_GUIDANCE, 8.0 * BV, launch_guidance_lse_partial(c->d_logits, 2 * HB, g.dec_vocab, c->d_pval, c->d_gdpsum, s));
             KL(KC_GUIDANCE, 1024.0 * HB, launch_guidance_lse_final(c->d_pval, c->d_gdpsum, 2 * HB, c->d_gmax, c->d_glog, c->d_glse, s));
+            if (tl) {
+                ta.lse = c->d_glse; ta.desc = c->d_gen_raw;
+                KL(KC_TOPK, 4.0 * BV, launch_topk_f32(c->d_logits, g.dec_vocab, HB, g.dec_vocab, ta, s));
+            }
             KL(KC_GUIDANCE, (lp ? 16.0 : 12.0) * BV,
                launch_guidance_combine(c->d_logits, c->d_logits + BV, HB, g.dec_vocab, c->d_gmax, c->d_glog, c->d_gmax + HB,
                                        c->d_glog + HB, c->d_gscale, lp ? c->guid_keep : nullptr, s));
-        } else if (lp) {
+        } else if (lse) {
             KL(KC_OTHER, 4.0 * BV, launch_argmax_lse_partial(c->d_logits, HB, g.dec_vocab, c->d_pval, c->d_pidx, c->d_gpsum, s));
             KL(KC_OTHER, 512.0 * HB, launch_argmax_lse_final(c->d_pval, c->d_pidx, c->d_gpsum, HB, c->d_ridx, c->d_rlse, s));
+            if (tl) {
+                ta.lse = c->d_rlse; ta.desc = c->d_gen_raw;
+                KL(KC_TOPK, 4.0 * BV, launch_topk_f32(c->d_logits, g.dec_vocab, HB, g.dec_vocab, ta, s));
+            }
         }
         if (p.lproc)
             KL(KC_LOGITPROC, 12.0 * HB * max_new,
@@ -2647,7 +2701,7 @@ static int select_next(opus_ctx *c, hipStream_t s, const StepPlan &p) {
         KL(KC_OTHER, 4.0 * 4 * HB * g.dec_vocab,
            launch_sample_select(c->d_logits, HB, g.dec_vocab, p.temp, p.top_p, p.top_k, nullptr, nullptr,
                                 c->d_pval, c->d_pidx, c->d_probs, c->d_cand_i, c->d_cand_n, c->d_zpart, c->d_spart, nullptr, c->d_wlo,
-                                lp && !proc ? c->d_gpsum : nullptr, nullptr, s));
+                                lse && !proc ? c->d_gpsum : nullptr, nullptr, s));
         KL(KC_OTHER, 8.0 * HB * g.dec_vocab,
            launch_sample_warp_draw(HB, g.dec_vocab, c->d_warp, c->d_seed, c->d_step, c->d_probs, c->d_cand_i, c->d_cand_n, c->d_chosen,
                                    c->d_wlo, c->d_whi, s));
@@ -2656,13 +2710,17 @@ static int select_next(opus_ctx *c, hipStream_t s, const StepPlan &p) {
         KL(KC_OTHER, 4.0 * 4 * HB * g.dec_vocab,
            launch_sample_select(c->d_logits, HB, g.dec_vocab, p.temp, p.top_p, p.top_k, c->d_seed, c->d_step,
                                 c->d_pval, c->d_pidx, c->d_probs, c->d_cand_i, c->d_cand_n, c->d_zpart, c->d_spart, c->d_chosen, nullptr,
-                                lp && !proc ? c->d_gpsum : nullptr, sc ? c->d_gthr : nullptr, s));
+                                lse && !proc ? c->d_gpsum : nullptr, sc ? c->d_gthr : nullptr, s));
         chosen = c->d_chosen;
-    } else if (lp && !proc) {
+    } else if (lse && !proc) {
         KL(KC_OTHER, 4.0 * HB * g.dec_vocab,
            launch_argmax_lse_partial(c->d_logits, HB, g.dec_vocab, c->d_pval, c->d_pidx, c->d_gpsum, s));
     } else {
         KL(KC_OTHER, 4.0 * HB * g.dec_vocab, launch_argmax_partial(c->d_logits, HB, g.dec_vocab, c->d_pval, c->d_pidx, s));
+    }
+    if (tl && !proc) {                              // the plain path: the parts of the pass above give the lse, as in the step kernel
+        ta.pval = c->d_pval; ta.psum = c->d_gpsum; ta.desc = c->d_gen;
+        KL(KC_TOPK, 4.0 * BV, launch_topk_f32(c->d_logits, g.dec_vocab, HB, g.dec_vocab, ta, s));
     }
     if (proc ? (p.outs & GEN_SCORES) != 0 : sc)
         KL(KC_OTHER, 4.0 * HB * g.dec_vocab * (1 + ((p.outs & GEN_SCORES) ? 1 : 0) + ((p.outs & GEN_LOGITS) && !proc ? 1 : 0)),
@@ -2737,6 +2795,12 @@ static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mas
                          const int32_t *eos_ids, int32_t n_eos, int32_t pad_id, float temperature, float top_p, uint64_t seed,
                          int32_t *d_out_ids, int32_t *n_out, void *stream, const GenOutDesc *outs = nullptr, int32_t nret = 1,
                          const BehindArgs *behind = nullptr, const float *guidance = nullptr) {
+    GenOutDesc with_top{};                   // the scored calls under opus_set_gen_top_logprobs: their outputs + the setter's
+    if (outs && c && c->top_k > 0) {
+        with_top = *outs;
+        with_top.top_lp = c->top_lp; with_top.top_ids = c->top_ids; with_top.top_k = c->top_k;
+        outs = &with_top;
+    }
     // guidance (opus_generate_scored_guided; nret 1, no behind): B = 2 P rows, the head of every step works on the first P
     // behind (opus_generate_scored_behind): the B rows are suffixes of T right-padded positions behind a detached prefix (no mask)
     OPC(need_ready(c));
@@ -2753,7 +2817,9 @@ static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mas
     plan.temp = temperature; plan.top_p = top_p; plan.top_k = c->samp_top_k; plan.n_stop = c->n_stop;
     plan.lproc = c->lproc_on; plan.cons = c->cons_on; plan.warp = temperature > 0.f && c->warp_on();
     if (plan.warp) OPC(upload_warpers(c, s));
-    if (outs) plan.outs = (outs->token_lp ? GEN_LOGPROBS : 0) | (outs->scores ? GEN_SCORES : 0) | (outs->logits ? GEN_LOGITS : 0);
+    if (outs) plan.outs = (outs->token_lp ? GEN_LOGPROBS : 0) | (outs->scores ? GEN_SCORES : 0) | (outs->logits ? GEN_LOGITS : 0) |
+                          (outs->top_k > 0 ? GEN_TOPLP : 0);
+    if (plan.outs & GEN_TOPLP) OPC(ensure_topk_mem(c));
     if (plan.outs) {
         OPC(ensure_gen_mem(c));
         c->h_gen = *outs;                    // (a member: the source outlives the asynchronous copy)
@@ -2764,7 +2830,7 @@ static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mas
         return fail(OPUS_ESHAPE, "generate: the token constraint has %d per-row start states, the batch %d rows", c->cons_n_start, HB);
     if (c->cons_on) OPC(set_cons_start_div(c, nret, s));    // one start state per prompt: decoder row r starts at start[r / nret]
     if (guidance) {
-        OPC(ensure_guid_mem(c, plan.outs & GEN_LOGPROBS));
+        OPC(ensure_guid_mem(c, (plan.outs & GEN_LOGPROBS) != 0));
         OPC(upload_guidance_scale(c, *guidance, s));
     }
     if (c->lproc_on || c->cons_on || guidance) {
@@ -2773,7 +2839,7 @@ static int generate_impl(opus_ctx *c, const void *d_embeds, const uint8_t *d_mas
         OPC(ensure_lproc_mem(c));
         if (c->lproc_on) OPC(upload_lproc(c, c->h_lproc, s));
         if (plan.outs) {                     // raw logits before the processors, the rest after them
-            OPC(upload_gen_desc(GenOutDesc{nullptr, nullptr, outs->logits, nullptr}, c->d_gen_raw, s));
+            OPC(upload_gen_desc(GenOutDesc{nullptr, nullptr, outs->logits, outs->top_lp, outs->top_ids, outs->top_k, 0}, c->d_gen_raw, s));
             OPC(upload_gen_desc(GenOutDesc{outs->token_lp, outs->scores, nullptr, nullptr}, c->d_gen_proc, s));
         }
     }
@@ -3609,6 +3675,58 @@ extern "C" int opus_debug_argmax_lse(opus_ctx *c, const float *d_logits, int32_t
     return OPUS_OK;
 }
 
+/* The k likeliest tokens of every step's raw row (topk.hip) for the opus_generate_scored* calls of this context, and of every scored
+   row for opus_llama_forward, until cleared with k = 0.  generate: d_top_ids int32 / d_top_lp fp32 [rows, max_new, k], rows those of
+   the call's other outputs; a row that had finished before a step gets ids -1 and log-probs 0.  forward: [R, k] in the order of
+   d_rows.  The raw row is the one d_token_logprobs describes (before guidance, processors, constraint, temperature, warpers; the
+   conditional row under guidance).  Only "on" enters the captured step's identity: k and the addresses travel in the descriptor. */
+extern "C" int opus_set_gen_top_logprobs(opus_ctx *c, int32_t k, int32_t *d_top_ids, float *d_top_lp) {
+    if (!c) return fail(OPUS_EBADARG, "ctx is null");
+    if (k < 0 || k > TOPK_MAX || k > c->cfg.dec_vocab)
+        return fail(OPUS_EBADARG, "set_gen_top_logprobs: k=%d outside 0..%d (dec_vocab %d)", k, TOPK_MAX, c->cfg.dec_vocab);
+    if (k > 0 && (!d_top_ids || !d_top_lp)) return fail(OPUS_EBADARG, "set_gen_top_logprobs: null buffer");
+    c->top_k = k;
+    c->top_ids = k ? d_top_ids : nullptr;
+    c->top_lp = k ? d_top_lp : nullptr;
+    return OPUS_OK;
+}
+
+/* Diagnostic: the two top-k stages alone on caller rows - d_logits [R, ld] of dtype OPUS_F32 or OPUS_F16 (the build's 16-bit type),
+   V <= ld values a row, any R >= 1, 1 <= k <= min(20, V); d_ids int32 / d_lp fp32 [R, k].  d_lse [R] or NULL: the rows'
+   log-sum-exp is computed here (contiguous fp32 rows: the fused arg-max / log-sum-exp pass of the decode step). */
+extern "C" int opus_debug_top_logprobs(opus_ctx *c, const void *d_logits, int32_t dtype, int64_t ld, int32_t R, int32_t V, int32_t k,
+                                       const float *d_lse, int32_t *d_ids, float *d_lp, void *stream) {
+    if (!c || !d_logits || !d_ids || !d_lp) return fail(OPUS_EBADARG, "debug_top_logprobs: null pointer");
+    if (dtype != OPUS_F32 && dtype != OPUS_F16) return fail(OPUS_EBADARG, "debug_top_logprobs: dtype %d (OPUS_F32 or OPUS_F16)", dtype);
+    if (R < 1 || V < 1 || ld < V) return fail(OPUS_ESHAPE, "debug_top_logprobs: R=%d V=%d ld=%lld", R, V, (long long)ld);
+    if (k < 1 || k > TOPK_MAX || k > V) return fail(OPUS_EBADARG, "debug_top_logprobs: k=%d outside 1..min(%d, V=%d)", k, TOPK_MAX, V);
+    HIPC(hipSetDevice(c->device));
+    OPC(ensure_gen_mem(c));
+    OPC(ensure_topk_mem(c));
+    hipStream_t s = (hipStream_t)stream;
+    c->phase = PH_OTHER;
+    const bool f32 = dtype == OPUS_F32;
+    const int Bm = c->cfg.max_batch;                                   // (d_pval / d_gpsum hold max_batch rows)
+    for (int r0 = 0; r0 < R; r0 += Bm) {
+        const int n = R - r0 < Bm ? R - r0 : Bm;
+        const char *rows = (const char *)d_logits + (size_t)r0 * ld * (f32 ? sizeof(float) : sizeof(half_t));
+        TopkArgs ta;
+        ta.cand = c->d_tcand; ta.k = k; ta.ids = d_ids + (size_t)r0 * k; ta.lp = d_lp + (size_t)r0 * k;
+        if (d_lse) {
+            ta.lse = d_lse + r0;
+        } else if (f32 && ld == V) {
+            KL(KC_OTHER, 4.0 * n * V, launch_argmax_lse_partial((const float *)rows, n, V, c->d_pval, c->d_pidx, c->d_gpsum, s));
+            ta.pval = c->d_pval; ta.psum = c->d_gpsum;
+        } else {
+            KL(KC_OTHER, (f32 ? 8.0 : 4.0) * n * V, launch_topk_row_lse(rows, f32, ld, n, V, c->d_tlse, s));
+            ta.lse = c->d_tlse;
+        }
+        if (f32) KL(KC_TOPK, 4.0 * n * V, launch_topk_f32((const float *)rows, ld, n, V, ta, s));
+        else KL(KC_TOPK, 2.0 * n * V, launch_topk_h16((const half_t *)rows, ld, n, V, ta, s));
+    }
+    return OPUS_OK;
+}
+
 /* Diagnostic: one draw per row from fp32 logits [B,V] with the sampling head (step counter = `step`). */
 extern "C" int opus_debug_sample(opus_ctx *c, const float *d_logits, int32_t B, float temperature, float top_p, uint64_t seed,
                                  int32_t step, int32_t *d_tokens, void *stream) {
@@ -4277,7 +4395,7 @@ extern "C" int opus_timing_reset(opus_ctx *c) {
     return OPUS_OK;
 }
 static const char *kclass_names[KC_COUNT] = {"gemm_skinny", "gemm_mid", "gemm_wide", "gemm_ring", "gemm_pp", "gemm_tile", "splitk_reduce",
-                                            "attn_prefill", "attn_decode", "norm", "other", "gemm_stream", "contact", "trie_search", "constraint", "guidance", "mlm", "logitproc",
+                                            "attn_prefill", "attn_decode", "norm", "other", "gemm_stream", "contact", "trie_search", "topk", "constraint", "guidance", "mlm", "logitproc",
                                             "xent"};
 static const char *phase_names[PH_COUNT] = {"encode", "project", "splice", "prefill", "decode", "other", "score"};
 

@@ -52,7 +52,7 @@ int skinny_max_m();   // rows up to which the skinny kernel is used (default 4, 
 constexpr int MID_MAX_M = 64;   // (65..128 rows measured faster on the split-K tile kernel)
 // kernel classes of the per-launch timing (opus_timing_get): one per kernel family
 enum KClass { KC_SKINNY = 0, KC_MID, KC_WIDE, KC_RING, KC_PP, KC_TILE, KC_REDUCE, KC_ATTN_PREFILL, KC_ATTN_DECODE, KC_NORM,
-              KC_OTHER, KC_STREAM, KC_CONTACT, KC_TRIE_SEARCH, KC_CONSTRAINT, KC_GUIDANCE, KC_MLM, KC_LOGITPROC, KC_XENT, KC_COUNT };
+              KC_OTHER, KC_STREAM, KC_CONTACT, KC_TRIE_SEARCH, KC_TOPK, KC_CONSTRAINT, KC_GUIDANCE, KC_MLM, KC_LOGITPROC, KC_XENT, KC_COUNT };
 // Ordering rule of the published class list (opus_timing_names, include/opus_pllm.h): "xent" stays its last entry, as published
 // since opus_llama_forward, and a class added later goes in front of it.  Classes are looked up by name, never by index.
 // phases of the path a launch belongs to (set by the entry points of api.cpp)
@@ -572,13 +572,38 @@ hipError_t launch_argmax_step(const float *pval, const int32_t *pidx, const int3
                               int32_t *next_tok, int32_t *n_unfinished, const int32_t *stop, int n_stop, hipStream_t s);
 hipError_t launch_step_advance(int32_t *step, hipStream_t s);
 // generate()'s optional outputs, read by the captured step from device memory (opus_generate_scored writes the descriptor before
-// its loop): token_lp [B, max_new], scores / logits [max_new, B, V], fp32, rows and steps indexed by the device step word; null = off
+// its loop): token_lp [B, max_new], scores / logits [max_new, B, V], fp32, rows and steps indexed by the device step word; null = off.
+// top_lp / top_ids [B, max_new, top_k] (opus_set_gen_top_logprobs): the k likeliest tokens of the raw row and their log-probabilities
 struct GenOutDesc {
     float *token_lp;
     float *scores;
     float *logits;
-    float *unused;
+    float *top_lp;
+    int32_t *top_ids;
+    int32_t top_k;
+    int32_t pad_;
 };
+// topk.hip: the k <= TOPK_MAX likeliest entries of each of R logits rows (value descending, then index ascending) and their
+// log-probabilities l[id] - lse, in two launches: the k best of every one of the row's APART parts into cand [R, APART, TOPK_MAX]
+// (64-bit keys), then a wave per row merges them.  The lse: lse[row], or (lse == nullptr) parts_lse over pval / psum [R, APART] of
+// argmax_lse_partial on the same rows.  Where to: desc != nullptr (the captured step) - desc->top_ids / top_lp / top_k, read on the
+// device; else ids / lp / k.  step != nullptr: [row, *step, :] of a [R, max_new, k] array, nothing when *step >= max_new; else [row, :].
+// finished != nullptr: a row whose word is set gets ids -1 and log-probs 0.
+constexpr int TOPK_MAX = 20;
+struct TopkArgs {
+    uint64_t *cand = nullptr;
+    const float *lse = nullptr, *pval = nullptr, *psum = nullptr;
+    const int32_t *finished = nullptr, *step = nullptr;
+    int max_new = 1;
+    const GenOutDesc *desc = nullptr;
+    int k = 0;
+    int32_t *ids = nullptr;
+    float *lp = nullptr;
+};
+hipError_t launch_topk_f32(const float *logits, int64_t ld, int R, int V, const TopkArgs &a, hipStream_t s);
+hipError_t launch_topk_h16(const half_t *logits, int64_t ld, int R, int V, const TopkArgs &a, hipStream_t s);
+// lse [R] of rows of either type with a leading dimension (opus_debug_top_logprobs)
+hipError_t launch_topk_row_lse(const void *logits, bool f32, int64_t ld, int R, int V, float *lse, hipStream_t s);
 // argmax_partial + each part's sum of exp(l - part max) (psum [B, APART])
 hipError_t launch_argmax_lse_partial(const float *logits, int B, int V, float *pval, int32_t *pidx, float *psum, hipStream_t s);
 // argmax_step + out->token_lp[b, step] = logits[b, tok] - logsumexp(logits[b]) (0 for rows finished before the step)

@@ -47,7 +47,8 @@ from opus_pllm_amd.prompt import (add_constraint_args, add_logits_processor_args
 
 def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperature=0.0, top_p=0.7, num_beams=1,
              use_input_embed=False, device=None, logits_out=None, stop_sequence=None, inflight=1, logprobs_out=None,
-             processors=None, num_return_sequences=1, share_prompt_head=False, guidance_scale=None):
+             processors=None, num_return_sequences=1, share_prompt_head=False, guidance_scale=None, top_logprobs_out=None,
+             top_k=0):
     """The batch loop of run_opus_ddp.py:88-134 over this rank's items -> [n, max_new] new ids (rows padded with eos).
 
     use_input_embed (two-stage pipeline): the `input_embed` vectors of the WHOLE shard go through the modality
@@ -56,6 +57,9 @@ def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperatu
     logits_out (a list, --dump_logits): receives the fp32 [b, V] logits of each batch's last decode step (model.last_logits).
     logprobs_out (a list, --save_logprobs): receives ([n, max_new] fp32 token log-probabilities, 0 after a row's end, [n] counted
     positions) - generate(return_dict_in_generate=True, output_token_logprobs=True).
+    top_logprobs_out (a list, --save_top_logprobs K = top_k): receives ([n, max_new, K] int64 ids, -1 after a row's end,
+    [n, max_new, K] fp32 log-probabilities, [n] counted positions): the K likeliest tokens of every step's raw distribution -
+    generate(top_logprobs=K).
     inflight (--inflight): batches in flight on this GPU.  The reference's loop is strictly sequential; with n > 1, n contexts
     that share the model's weights (model.new_context()) take the batches round-robin from n host threads - batches are
     independent, results come back in input order and are the same ids as with one context: greedy ids because the kernels are
@@ -96,6 +100,8 @@ def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperatu
     outs = [None] * len(starts)
     last = [None] * len(starts)
     lps = [None] * len(starts)
+    tops = [None] * len(starts)
+    want_dict = logprobs_out is not None or top_logprobs_out is not None
     # one sampler seed per batch, drawn in input order before any worker thread starts (generate() would otherwise draw it from
     # the global generator at call time: with two threads racing, which batch got which seed depended on thread scheduling)
     seeds = [int(torch.randint(0, 2 ** 62, (1,)).item()) for _ in starts] if temperature > 0 else [None] * len(starts)
@@ -115,17 +121,26 @@ def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperatu
             extra["num_return_sequences"] = nret
         if guided:
             extra["guidance_scale"] = float(guidance_scale)
-        if logprobs_out is not None:
+        if want_dict:                                    # (the counted positions come with the token log-probabilities)
             extra.update(return_dict_in_generate=True, output_token_logprobs=True)
+        if top_logprobs_out is not None:
+            extra["top_logprobs"] = int(top_k)
         with torch.inference_mode():
             out = m.generate(ids, [q["input"] for q in batch], attention_mask=mask, pad_token_id=tokenizer.eos_token_id,
                              do_sample=temperature > 0, temperature=temperature, top_p=top_p,
                              num_beams=num_beams, max_new_tokens=max_new, use_cache=True, stop_sequence=stop_sequence,
                              seed=seeds[j], **extra)
+        if top_logprobs_out is not None:
+            n = out.top_ids.shape[1]
+            tid = torch.full((out.sequences.shape[0], max_new, int(top_k)), -1, dtype=torch.long, device=dev)
+            tlp = torch.zeros((out.sequences.shape[0], max_new, int(top_k)), dtype=torch.float32, device=dev)
+            tid[:, :n], tlp[:, :n] = out.top_ids, out.top_logprobs
+            tops[j] = (tid, tlp, out.n_tokens)
         if logprobs_out is not None:
             lp = torch.zeros((out.sequences.shape[0], max_new), dtype=torch.float32, device=dev)
             lp[:, : out.token_logprobs.shape[1]] = out.token_logprobs
             lps[j] = (lp, out.n_tokens)
+        if want_dict:
             out = out.sequences
         if logits_out is not None:
             last[j] = m.last_logits(len(batch) * nret)
@@ -162,6 +177,8 @@ def annotate(model, tokenizer, items, input_path, batch_size, max_new, temperatu
         logits_out.extend(last)
     if logprobs_out is not None:
         logprobs_out.extend(lps)
+    if top_logprobs_out is not None:
+        top_logprobs_out.extend(tops)
     return torch.cat(outs) if outs else torch.empty((0, max_new), dtype=torch.long, device=dev)
 
 
@@ -201,7 +218,7 @@ def continuous_refusals(args):
     g = getattr(args, "guidance_scale", None)
     if g is not None and float(g) != 1.0:
         bad.append("--guidance_scale")
-    for flag in ("share_prompt_head", "save_logprobs", "dump_logits", "rank_terms", "allowed_terms"):
+    for flag in ("share_prompt_head", "save_logprobs", "save_top_logprobs", "dump_logits", "rank_terms", "allowed_terms"):
         if getattr(args, flag, None):
             bad.append("--" + flag)
     if logits_processor_kwargs(args):
@@ -359,6 +376,8 @@ def eval_model(args):
     if trie is not None:
         proc_kw["prefix_allowed_tokens_fn"] = trie
     lps = [] if args.save_logprobs else None
+    top_K = int(getattr(args, "save_top_logprobs", 0) or 0)
+    tops = [] if top_K else None
     N = int(getattr(args, "num_return_sequences", 1) or 1)
     stop_ids = tokenizer.encode("###", add_special_tokens=False) if args.stop_at_hashes else None
     if continuous:              # the rank's whole shard in one call; the same fields are saved
@@ -373,8 +392,15 @@ def eval_model(args):
                              args.num_beams, args.use_input_embed, dev, logits, stop_ids, inflight=args.inflight,
                              logprobs_out=lps, processors=proc_kw, num_return_sequences=N,
                              share_prompt_head=bool(getattr(args, "share_prompt_head", False)),
-                             guidance_scale=getattr(args, "guidance_scale", None))
+                             guidance_scale=getattr(args, "guidance_scale", None), top_logprobs_out=tops, top_k=top_K)
     all_ids = odist.all_gather_ids(local_ids, tokenizer.eos_token_id)
+    if tops is not None:        # [n, max_new K] ids and log-probabilities and [n] counted positions, in rank order
+        loc_ti = torch.cat([x[0] for x in tops]).view(-1, max_new * top_K) if tops else torch.empty((0, max_new * top_K), dtype=torch.long, device=dev)
+        loc_tl = torch.cat([x[1] for x in tops]).view(-1, max_new * top_K) if tops else torch.empty((0, max_new * top_K), dtype=torch.float32, device=dev)
+        loc_tn = torch.cat([x[2] for x in tops]).view(-1, 1) if tops else torch.empty((0, 1), dtype=torch.long, device=dev)
+        all_ti = odist.all_gather_ids(loc_ti.contiguous(), -1).view(-1, max_new, top_K).cpu()
+        all_tl = odist.all_gather_logits(loc_tl.contiguous()).view(-1, max_new, top_K).cpu()
+        all_tn = odist.all_gather_ids(loc_tn, 0).view(-1).cpu()
     if lps is not None:         # [n, max_new] log-probabilities and [n] counted positions, in rank order
         loc_lp = torch.cat([x[0] for x in lps]) if lps else torch.empty((0, max_new), dtype=torch.float32, device=dev)
         loc_n = torch.cat([x[1] for x in lps]).view(-1, 1) if lps else torch.empty((0, 1), dtype=torch.long, device=dev)
@@ -393,6 +419,11 @@ def eval_model(args):
                 row = all_lp[k * N, : int(all_n[k * N])]
                 r["logprob"] = float(row.double().sum())
                 r["token_logprobs"] = [float(v) for v in row]
+        if tops is not None:    # the K alternatives of every counted step; N > 1: of the item's first answer
+            for k, r in enumerate(result):
+                steps = int(all_tn[k * N])
+                r["top_logprobs"] = [{"ids": [int(i) for i in all_ti[k * N, t]], "logprobs": [float(v) for v in all_tl[k * N, t]],
+                                      "tokens": [tokenizer.decode([int(i)]) for i in all_ti[k * N, t]]} for t in range(steps)]
         print(f"entries/sec: {n / dt}, time elapsed: {dt}")
         with open(args.save_path, "w") as f:
             json.dump(result, f)
@@ -468,6 +499,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--share_prompt_head", action="store_true",
                    help="opt-in: prefill the id run that all prompts of the shard share in front of the protein once (a detached "
                         "prefix) and generate every batch behind it; not with --num_beams > 1")
+    p.add_argument("--save_top_logprobs", type=int, default=0, metavar="K",
+                   help="each saved item also gets `top_logprobs`: per counted step the K (1..20) likeliest tokens of the model's raw "
+                        "distribution as `ids`, `logprobs` and decoded `tokens` (generate(top_logprobs=K)); works beside --save_logprobs")
     p.add_argument("--save_logprobs", action="store_true",
                    help="each saved item also gets `logprob` and `token_logprobs`: the log-probabilities of its generated tokens "
                         "(greedy or sampling; computed on the GPU in the decode loop)")

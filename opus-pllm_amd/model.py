@@ -22,6 +22,8 @@ from .config import OpusConfig
 from .constants import DEFAULT_SEQ_TOKEN_INDEX, IGNORE_INDEX
 from .weights import DeviceWeights
 
+TOP_LOGPROBS_MAX = 20          # generate() / forward()'s top_logprobs (csrc/common.h: TOPK_MAX)
+
 
 class _ProteinEncoderHandle:
     """What get_protein_encoder() returns: exposes get_protein_seq_embeddings like
@@ -590,6 +592,9 @@ class OpusLlamaForCausalLM:
         return_dict = bool(kwargs.pop("return_dict_in_generate", False))
         want = {k: bool(kwargs.pop(k, False)) for k in ("output_scores", "output_logits", "output_token_logprobs",
                                                          "output_attentions", "output_hidden_states")}
+        top_lp = _top_logprobs_arg(kwargs.pop("top_logprobs", None), getattr(getattr(self, "cfg", None), "dec_vocab", None))
+        if not return_dict:
+            top_lp = 0                                         # (ignored without the output object, as the output_* flags are)
         if return_dict:
             for k in ("output_attentions", "output_hidden_states"):
                 if want[k]:
@@ -616,9 +621,9 @@ class OpusLlamaForCausalLM:
         seed = kwargs.pop("seed", None)
         num_beams = kwargs.pop("num_beams", 1)
         num_beams = 1 if num_beams is None else int(num_beams)
-        if return_dict and num_beams > 1 and (want["output_scores"] or want["output_logits"] or want["output_token_logprobs"]):
+        if return_dict and num_beams > 1 and (want["output_scores"] or want["output_logits"] or want["output_token_logprobs"] or top_lp):
             raise NotImplementedError("with num_beams > 1, return_dict_in_generate returns `sequences` and `sequences_scores` only: "
-                                      "output_scores / output_logits / output_token_logprobs are built for greedy and sampling")
+                                      "output_scores / output_logits / output_token_logprobs / top_logprobs are built for greedy and sampling")
         nret = kwargs.pop("num_return_sequences", 1)
         nret = 1 if nret is None else int(nret)
         if nret < 1:
@@ -690,8 +695,8 @@ class OpusLlamaForCausalLM:
         if lookup_k:                           # every check before the device is touched
             lookup_m = _check_lookup(lookup_k, lookup_m, int(inputs.shape[0]), self.cfg.max_batch, do_sample=do_sample,
                                      num_beams=num_beams, nret=nret, guidance=guidance, prefix=prefix, lproc=lproc,
-                                     constraint=constraint, outputs=return_dict and any(
-                                         want[k] for k in ("output_scores", "output_logits", "output_token_logprobs")))
+                                     constraint=constraint, outputs=return_dict and (bool(top_lp) or any(
+                                         want[k] for k in ("output_scores", "output_logits", "output_token_logprobs"))))
             lookup_hist = lookup_history(inputs, attention_mask, lookup_ids, self.cfg.n_prot_tokens)
         if guidance is not None:               # every check before the device is touched
             if num_beams > 1:
@@ -732,7 +737,7 @@ class OpusLlamaForCausalLM:
             self._set_logits_processors(lproc)
             self._set_token_constraint(constraint)
             self._set_warpers(warpers)
-            outs = (want["output_token_logprobs"], want["output_scores"], want["output_logits"]) if return_dict else None
+            outs = (want["output_token_logprobs"], want["output_scores"], want["output_logits"], top_lp) if return_dict else None
             res = self._greedy(embeds, None, max_new, eos, int(pad_id), sampler, outputs=outs, behind=behind)
             if return_prefix:                  # right behind the loop: nothing else has touched the context
                 res.prefix = self._export_answer(res.sequences, eos, behind.new_kstart, behind.Tp + int(embeds.shape[1]))
@@ -770,7 +775,7 @@ class OpusLlamaForCausalLM:
             res.stats = stats
             return res
         if guidance is not None:
-            outs = (want["output_token_logprobs"], want["output_scores"], want["output_logits"]) if return_dict else None
+            outs = (want["output_token_logprobs"], want["output_scores"], want["output_logits"], top_lp) if return_dict else None
             return self._greedy(embeds, mask, max_new, eos, int(pad_id), sampler, outputs=outs, guidance=guidance)
         if num_beams > 1:
             ids = self._beam_search(embeds, mask, max_new, eos, beam_pad, num_beams, sampler, nret)
@@ -780,7 +785,7 @@ class OpusLlamaForCausalLM:
         if not return_dict:
             return self._greedy(embeds, mask, max_new, eos, int(pad_id), sampler, nret=nret)
         res = self._greedy(embeds, mask, max_new, eos, int(pad_id), sampler,
-                           outputs=(want["output_token_logprobs"], want["output_scores"], want["output_logits"]), nret=nret)
+                           outputs=(want["output_token_logprobs"], want["output_scores"], want["output_logits"], top_lp), nret=nret)
         if return_prefix:                      # right behind the loop: nothing else has touched the context
             first = mask.to(torch.int32).argmax(dim=1).cpu().numpy()      # (a row's first real slot: its kstart)
             res.prefix = self._export_answer(res.sequences, eos, first, int(embeds.shape[1]))
@@ -943,7 +948,7 @@ class OpusLlamaForCausalLM:
 
     def _greedy(self, embeds, mask, max_new, eos, pad_id, sampler=None, outputs=None, nret: int = 1, behind=None,
                 guidance: Optional[float] = None):
-        """outputs = (token_logprobs, scores, logits) flags: a GenerateDecoderOnlyOutput instead of the ids.
+        """outputs = (token_logprobs, scores, logits) flags (+ top_logprobs' k, 0 = off): a GenerateDecoderOnlyOutput instead of the ids.
         nret > 1: the B prompts are prefilled once and decoded as B nret rows (opus_generate_scored_fanout); every result has
         B nret rows.
         behind (a _BehindCall; mask unused, nret 1): embeds are right-padded suffix rows behind a detached prefix
@@ -971,8 +976,10 @@ class OpusLlamaForCausalLM:
             if sampler is not None:
                 self._set_top_k(sampler[3] if len(sampler) > 3 else self.default_top_k)
             lp = sc = lg = None
+            top_k = 0
             if outputs is not None:
-                want_lp, want_sc, want_lg = outputs
+                want_lp, want_sc, want_lg = outputs[:3]
+                top_k = int(outputs[3]) if len(outputs) > 3 else 0
                 # fresh caller-owned tensors every call: their addresses reach the captured step through a device descriptor
                 lp = torch.zeros((B, max_new), dtype=torch.float32, device=self.device) if want_lp else None
                 sc = torch.empty((max_new, B, V), dtype=torch.float32, device=self.device) if want_sc else None
@@ -991,8 +998,16 @@ class OpusLlamaForCausalLM:
                 entry, head = self._lib.opus_generate_scored, (embeds.data_ptr(), mask.data_ptr(), B, T)
             t, p, sd = (sampler[0], sampler[1], sampler[2]) if sampler is not None else (0.0, 1.0, 0)
             ptr = lambda x: None if x is None else x.data_ptr()                              # noqa: E731
-            _cabi.check(entry(self._ctx, *head, max_new, eos_arr, len(eos), pad_id, t, p, sd, out.data_ptr(), C.byref(n_out),
-                              ptr(lp), ptr(sc), ptr(lg), s))
+            if top_k:                                    # (steps the loop never ran keep the finished row's values)
+                top_ids = torch.full((B, max_new, top_k), -1, dtype=torch.int32, device=self.device)
+                top_val = torch.zeros((B, max_new, top_k), dtype=torch.float32, device=self.device)
+                _cabi.check(self._lib.opus_set_gen_top_logprobs(self._ctx, top_k, top_ids.data_ptr(), top_val.data_ptr()))
+            try:
+                _cabi.check(entry(self._ctx, *head, max_new, eos_arr, len(eos), pad_id, t, p, sd, out.data_ptr(), C.byref(n_out),
+                                  ptr(lp), ptr(sc), ptr(lg), s))
+            finally:
+                if top_k:
+                    self._lib.opus_set_gen_top_logprobs(self._ctx, 0, None, None)
         self._leave()
         n = n_out.value
         ids = out[:, :n].long()                          # (a copy: the id buffer is reused by the next call)
@@ -1007,6 +1022,9 @@ class OpusLlamaForCausalLM:
             res.token_logprobs = lp[:, :n]
             res.logprob = res.token_logprobs.sum(dim=1)
             res.n_tokens = counted_tokens(ids, eos, getattr(self, "_stop_ids", []))
+        if top_k:
+            res.top_logprobs = top_val[:, :n]
+            res.top_ids = top_ids[:, :n].long()
         return res
 
     # ------------------------------------------------------------------ prompt-lookup decoding
@@ -1060,7 +1078,8 @@ class OpusLlamaForCausalLM:
     # ------------------------------------------------------------------ continuous batching
     _CONTINUOUS_UNSUPPORTED = ("guidance_scale", "negative_prompt_ids", "negative_prompt_attention_mask", "prefix", "prefix_rows",
                                "prefix_allowed_tokens_fn", "repetition_penalty", "no_repeat_ngram_size", "bad_words_ids",
-                               "min_length", "min_new_tokens", "output_scores", "output_logits", "output_token_logprobs")
+                               "min_length", "min_new_tokens", "output_scores", "output_logits", "output_token_logprobs",
+                               "top_logprobs")
 
     @torch.no_grad()
     def generate_continuous(self, prompts, seqs=None, max_new_tokens: int = 32, eos_token_id=None, pad_token_id=None,
@@ -1205,14 +1224,18 @@ class OpusLlamaForCausalLM:
                 use_cache: Optional[bool] = None, output_attentions: Optional[bool] = None,
                 output_hidden_states: Optional[bool] = None, seq=None, input_embed: Optional[torch.Tensor] = None,
                 return_dict: Optional[bool] = None, protein_tokens: Optional[torch.Tensor] = None, return_logits: bool = True,
-                **kwargs):
+                top_logprobs: Optional[int] = None, **kwargs):
         """opus_llama.py:41-92 (+ LlamaForCausalLM.forward): with `seq` (or `input_embed` pooled embeddings / `protein_tokens`
         projected blocks) the proteins are spliced into the prompt in training mode (right padding, IGNORE_INDEX labels on the
         protein slots); otherwise `input_ids` are embedded (or `inputs_embeds` taken as they are).  Returns a CausalLMOutput:
         `loss` = HF's causal-LM loss (target of position t is labels[b, t + 1]; -100 ignored; fp32 mean over the counted targets,
         NaN when none is counted), `logits` [B, T, V] in the operand dtype (None with return_logits=False; values at masked
         positions are unspecified), `past_key_values` = None; extensions `token_logprobs` fp32 [B, T] (log p(labels[b, t]) at
-        counted targets, 0 elsewhere) and `n_tokens`.
+        counted targets, 0 elsewhere) and `n_tokens`.  top_logprobs=k (an int in 1..20, with labels): `top_logprobs` fp32 / `top_ids`
+        int64 [B, T, k], at every counted target labels[b, t] the k likeliest ids of the distribution that predicts it (value
+        descending, then id ascending, on the 16-bit logits) and their log-probabilities; 0 / -1 elsewhere.  With
+        return_logits=False it still runs the lm_head on all positions of a group of max_batch rows, into one group's buffer that is
+        dropped at the end of the call: both values of return_logits then give identical lists and token_logprobs.
         Rows are right-padded or unpadded; left-padded rows only with position_ids == cumsum(mask) - 1 on their real slots (what
         the kernels compute; HF would use arange positions).  Overwrites this context's KV cache: decode_step fails until the next
         prefill / generate.  Batches above max_batch run in groups of max_batch rows (one loss over all of them)."""
@@ -1226,6 +1249,9 @@ class OpusLlamaForCausalLM:
         if kwargs:
             raise TypeError(f"forward() got unexpected keyword arguments {sorted(kwargs)}")
         cfg = self.cfg
+        top_k = _top_logprobs_arg(top_logprobs, cfg.dec_vocab)
+        if top_k and labels is None:
+            raise ValueError("forward(top_logprobs=k) needs labels: the alternatives are those of the counted targets")
         embeds = None
         if seq is not None or input_embed is not None or protein_tokens is not None:
             if input_ids is None:
@@ -1279,20 +1305,27 @@ class OpusLlamaForCausalLM:
         mask_u8 = torch.from_numpy(m.astype(np.uint8)).to(dev)
         token_lp = torch.zeros((B, T), dtype=torch.float32, device=dev)
         logits = torch.empty((B, T, cfg.dec_vocab), dtype=dt, device=dev) if return_logits else None
+        top_val = torch.zeros((B, T, top_k), dtype=torch.float32, device=dev) if top_k else None
+        top_ids = torch.full((B, T, top_k), -1, dtype=torch.int64, device=dev) if top_k else None
         G = cfg.max_batch
+        # top log-probs without returned logits: the lm_head still runs on all rows of a group, as with return_logits=True, into
+        # one group's buffer that lives for the call - the two paths then share their GEMM launches and give identical lists
+        # (the loss-only lm_head runs at another row count through other kernels, whose 16-bit logits differ in the last bit)
+        full = return_logits or bool(top_k)
+        group_logits = torch.empty((min(B, G), T, cfg.dec_vocab), dtype=dt, device=dev) if full and not return_logits else None
         tgt_all = np.full((B, T), -1, dtype=np.int32)
         if lab is not None:
             tgt_all[:, :-1] = np.where(src[:, :-1], lab[:, 1:], -1)
         cc = _cabi.CConfig.from_config(cfg)
-        R_max = min(B, G) * T if return_logits else max(int(src[g0:g0 + G].sum()) for g0 in range(0, B, G))
-        n_scratch = int(self._lib.opus_llama_forward_scratch_bytes(C.byref(cc), R_max, 1 if return_logits else 0))
+        R_max = min(B, G) * T if full else max(int(src[g0:g0 + G].sum()) for g0 in range(0, B, G))
+        n_scratch = int(self._lib.opus_llama_forward_scratch_bytes(C.byref(cc), R_max, 1 if full else 0))
         s = self._enter()
         with torch.cuda.stream(self._stream):
             scratch = torch.empty((max(n_scratch, 1),), dtype=torch.uint8, device=dev)
             keep = []
             for g0 in range(0, B, G):
                 Bg = min(G, B - g0)
-                if return_logits:
+                if full:
                     rows = np.arange(Bg * T, dtype=np.int32)
                     tg = tgt_all[g0:g0 + Bg].reshape(-1)
                 else:
@@ -1302,11 +1335,24 @@ class OpusLlamaForCausalLM:
                 d_rows = torch.from_numpy(rows).to(dev, non_blocking=True) if R else None
                 d_tg = torch.from_numpy(np.ascontiguousarray(tg)).to(dev, non_blocking=True) if R else None
                 lp = torch.empty((max(R, 1),), dtype=torch.float32, device=dev)
-                _cabi.check(self._lib.opus_llama_forward(
-                    self._ctx, embeds[g0:].data_ptr(), mask_u8[g0:].data_ptr(), Bg, T,
-                    None if d_rows is None else d_rows.data_ptr(), R, None if d_tg is None else d_tg.data_ptr(), lp.data_ptr(),
-                    None if logits is None else logits[g0:].data_ptr(), scratch.data_ptr(), n_scratch, s))
-                if return_logits:
+                if top_k:                                               # [R, k] in the order of rows (opus_set_gen_top_logprobs)
+                    r_ids = torch.full((max(R, 1), top_k), -1, dtype=torch.int32, device=dev)
+                    r_val = torch.zeros((max(R, 1), top_k), dtype=torch.float32, device=dev)
+                    _cabi.check(self._lib.opus_set_gen_top_logprobs(self._ctx, top_k, r_ids.data_ptr(), r_val.data_ptr()))
+                try:
+                    _cabi.check(self._lib.opus_llama_forward(
+                        self._ctx, embeds[g0:].data_ptr(), mask_u8[g0:].data_ptr(), Bg, T,
+                        None if d_rows is None else d_rows.data_ptr(), R, None if d_tg is None else d_tg.data_ptr(), lp.data_ptr(),
+                        (logits[g0:] if return_logits else group_logits).data_ptr() if full else None, scratch.data_ptr(), n_scratch, s))
+                finally:
+                    if top_k:
+                        self._lib.opus_set_gen_top_logprobs(self._ctx, 0, None, None)
+                if top_k and R:                                         # position t predicts the label at t + 1
+                    counted = torch.from_numpy(np.flatnonzero(src[g0:g0 + Bg].reshape(-1)).astype(np.int64)).to(dev)
+                    top_val[g0:g0 + Bg].view(-1, top_k)[counted + 1] = r_val[counted]
+                    top_ids[g0:g0 + Bg].view(-1, top_k)[counted + 1] = r_ids[counted].long()
+                    keep.append((r_ids, r_val))
+                if full:
                     token_lp[g0:g0 + Bg, 1:] = lp.view(Bg, T)[:, :-1]
                 elif R:
                     flat = token_lp[g0:g0 + Bg].view(-1)                # position t scores the label at t + 1
@@ -1318,6 +1364,8 @@ class OpusLlamaForCausalLM:
                 loss = -token_lp.sum() / n_tokens if n_tokens else torch.tensor(float("nan"), device=dev)
         self._leave()
         out = CausalLMOutput(loss=loss, logits=logits, token_logprobs=token_lp, n_tokens=n_tokens)
+        if top_k:
+            out.top_logprobs, out.top_ids = top_val, top_ids
         if return_dict is False:
             return out.to_tuple()
         return out
@@ -2278,6 +2326,17 @@ def lookup_history(input_ids, attention_mask=None, lookup_ids=None, n_prot_token
     for b, h in enumerate(rows):
         out[b, :len(h)] = h
     return out, np.asarray([len(h) for h in rows], dtype=np.int32)
+
+
+def _top_logprobs_arg(k, vocab: Optional[int]) -> int:
+    """generate() / forward()'s top_logprobs: None -> 0 (off); an int in 1..min(20, vocabulary), else ValueError."""
+    if k is None:
+        return 0
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= TOP_LOGPROBS_MAX:
+        raise ValueError(f"`top_logprobs` has to be an integer from 1 to {TOP_LOGPROBS_MAX} (got {k!r})")
+    if vocab is not None and int(k) > vocab:
+        raise ValueError(f"`top_logprobs` ({int(k)}) exceeds the vocabulary ({vocab})")
+    return int(k)
 
 
 def _guidance_scale(g) -> Optional[float]:
